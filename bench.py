@@ -21,15 +21,18 @@ in HBM), episode length 100 with device-side auto-reset.  Environments are
 independent, so N GPUs run N disjoint slices with no collective (weak scaling:
 B per GPU fixed); the only communication is the timing barrier.
 
-Timing.  A timed BLOCK is exactly --steps steps.  After the warm-up a series of
-R consecutive blocks is timed (the rollout simply continues; R sized so that at
-least --min-timed-ms are timed: a short `--steps 20` command is ONE 0.3 ms
-launch per block and would otherwise be a single noisy sample), the series
-bracketed by a barrier + torch.cuda.synchronize() on both sides, every block
-delimited by HIP events on the launch stream, MAX over ranks per block.  ONE
-clock feeds `value`, `ms_per_step` and `roofline.achieved`: the MEDIAN block on
-the GPU's own timeline (gaps between launches included); min / max / count and
-the host wall clock of the same series are reported beside it (`timing`).
+Timing.  The headline times exactly --steps steps: after the untimed prewarm
+(--prewarm-ms of stepping to bring the clocks up; the env state is then put
+back to where it was before it, so the timed inputs never depend on the clock)
+and the --warmup steps, ONE series of --steps steps is delimited by a HIP event
+pair on the launch stream and bracketed by a barrier + torch.cuda.synchronize()
+on both sides, MAX over ranks.  ONE clock feeds `value`, `ms_per_step` (= that
+series / --steps) and `roofline.achieved`; the host wall clock of the same
+series is reported beside it (`timing`).  The measurements beside the headline
+repeat their blocks until --min-timed-ms have been timed and report the MEDIAN
+block.  With the same arguments the timed steps see the same inputs from run to
+run; `--dump-outputs DIR` writes what the last of them computed (see
+last_step_outputs).
 
 `roofline.traffic` (HBM bytes per launch from the PMC counters) is measured in the same run on the same box at N = 1:
 before this process touches the GPU, two short child runs of the workload under `rocprofv3 --pmc WRITE_SIZE` and
@@ -52,6 +55,26 @@ for _p in (ROOT, PKG):
 
 HBM_PEAK_GBPS = 8000.0          # MI355X spec peak (MI355X_MICROARCH.md); 6290 measured copy
 INFINITY_CACHE_BYTES = 256 << 20
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together
+
+
+def last_step_outputs(arrays, seed=0):
+    """--dump-outputs: the [B, ...] device tensors of one step as float32 host arrays.  Where all B envs would exceed
+    DUMP_BYTES, every array keeps the same fixed, seeded sample of envs (ascending).  Returns (arrays, sample or None)."""
+    import numpy as np
+    import torch
+    B = next(iter(arrays.values())).shape[0]
+    per_env = sum(4 * v[0].numel() for v in arrays.values())
+    keep = min(B, (DUMP_BYTES - 4096) // per_env)              # 4 KB for the .npy headers
+    sample = None
+    if keep < B:
+        sample = np.sort(np.random.RandomState(seed).choice(B, keep, replace=False))
+    out = {}
+    for k, v in arrays.items():
+        if sample is not None:
+            v = v.index_select(0, torch.as_tensor(sample, device=v.device))
+        out[k] = v.float().cpu().numpy()
+    return out, sample
 
 
 def hbm_bytes_per_launch(n, envs, steps_per_launch):
@@ -318,7 +341,11 @@ def main():
                     help="step: one fg_step_hd launch per step; rollout: fg_rollout_hd, --chunk steps per launch")
     ap.add_argument("--chunk", type=int, default=20)
     ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="repeat the timed block of --steps steps until this much GPU time has been timed")
+                    help="measurements beside the headline: repeat their timed block until this much GPU time has been "
+                         "timed (the headline times exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (observation, rewards, done flags, "
+                         "the state after it) as DIR/<name>.npy in float32, at most 64 MB (rank 0's envs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-auto-reset", action="store_true", help="tuning aid: episodes never reset")
     ap.add_argument("--obs-every", type=int, default=1,
@@ -351,6 +378,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the timing barrier (gloo: ranks may share a GPU, test only)")
     a = ap.parse_args()
+    if a.dump_outputs and a.obs_every != 1:
+        ap.error("--dump-outputs needs every observation written (--obs-every 1)")
     if a.quick:
         a.no_extra = a.no_cpu_baseline = a.no_live_traffic = True
 
@@ -455,10 +484,12 @@ def main():
     gate_failed = [False]
     solo = [False]            # a measurement rank 0 takes ALONE (the others wait at a barrier): no collective inside
 
-    def measure(N, B, mode, steps, warmup, chunk_req, other_steps=0, global_envs=None, policy=False):
+    def measure(N, B, mode, steps, warmup, chunk_req, other_steps=0, global_envs=None, policy=False, exact=False, dump=False):
         """Times blocks of `steps` env steps of N agents x B envs on this GPU in `mode` (and, if other_steps > 0,
         the other launch mode beside it).  global_envs: this rank owns its slice of a GLOBAL batch of that many envs
-        (default: B per GPU, weak scaling).  policy: closed loop with the built-in controller (rollout_policy)."""
+        (default: B per GPU, weak scaling).  policy: closed loop with the built-in controller (rollout_policy).
+        exact: ONE series of exactly `steps` steps from a clock-independent state (the headline, `timed_exact`).
+        dump: also return what the last timed step computed (`last_step_outputs`) under r["dump"]."""
         # initial states: this rank owns the contiguous slice [lo, hi) of the global env range;
         # global env g is seeded 1 + 1000 g, so results do not depend on the GPU count
         ws = 1 if solo[0] else world_size
@@ -495,6 +526,8 @@ def main():
             for t in range(start, start + n):
                 launchers[t % P](t)
 
+        last_k = [0]                                           # steps of the latest rollout launch
+
         def run_rollout(n, start):
             t = start
             while t < start + n:
@@ -505,6 +538,7 @@ def main():
                 env.rollout(act_pool[lo_:lo_ + k], out={k2: v[:k // (a.obs_every if k2 == "obs" else 1)] for k2, v in seq.items()
                                                         if torch.is_tensor(v)},
                             obs_every=a.obs_every)
+                last_k[0] = k
                 t += k
 
         def run_policy_rollout(n, start):
@@ -589,6 +623,38 @@ def main():
                     break
             return dev_blocks, wall_blocks, local_blocks
 
+        def timed_exact(fn, n, w):
+            """The headline: the untimed prewarm, then the env put back to its state before it (the prewarm runs for a
+            wall-clock time, so the number of steps it takes varies), the W warm-up steps, and ONE series of exactly n
+            timed steps delimited by a HIP event pair, bracketed by barrier + device synchronize.  The warm-up steps are
+            queued after the barrier, so that the series starts on a busy stream (as the blocks of `timed_once` do)."""
+            snap = env._snapshot()
+            cursor = 0
+            t_end = time.perf_counter() + a.prewarm_ms * 1e-3
+            while time.perf_counter() < t_end:
+                fn(chunk, cursor)
+                cursor += chunk
+                if cursor % (8 * chunk) == 0:
+                    torch.cuda.synchronize()
+            env._restore(snap)
+            last_group[0] = 1
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            barrier()
+            fn(w, 0)
+            cursor = -(-w // chunk) * chunk                    # a launch boundary, as in timed_once
+            t0 = time.perf_counter()
+            ev0.record()
+            fn(n, cursor)
+            ev1.record()
+            while not ev1.query():                             # completion seen by polling the closing event
+                pass
+            wall = time.perf_counter() - t0
+            torch.cuda.synchronize()
+            barrier()
+            local = ev0.elapsed_time(ev1)
+            wall_ms = (wall if solo[0] else sharding.max_over_ranks(wall, red_dev, sync_group)) * 1e3
+            return max_vec([local]), [wall_ms], [local]
+
         seq = None
         if mode == "rollout" or other_steps > 0:
             f = dict(dtype=torch.float32, device=dev)
@@ -610,8 +676,17 @@ def main():
             fns = {"step": run_policy_steps, "rollout": run_policy_rollout}
         else:
             fns = {"step": run_steps, "rollout": run_rollout}
-        dev_blocks, wall_blocks, local_blocks = timed(fns[mode], steps, warmup)
+        dev_blocks, wall_blocks, local_blocks = (timed_exact if exact else timed)(fns[mode], steps, warmup)
         blocks_per_event = last_group[0]
+        dumped = None
+        if dump:
+            # the arrays env.step / env.rollout hand back for the last timed step, and the env state after it
+            if mode == "rollout":
+                last = {k2: seq[k2][last_k[0] - 1] for k2 in ("obs", "reward", "indiv", "done")}
+            else:
+                last = {k2: out[k2] for k2 in ("obs", "reward", "indiv", "done")}
+            last["pos"], last["vel"] = env.world.get_state()
+            dumped = last_step_outputs(last)
         side = {}
         if mode == "rollout" and not policy and a.obs_every == 1 and placed.get("rollout", {}).get("probed") and chunk <= P:
             # beside the timed series (never `value`): the same launch (a) into an ORDINARY allocation - what the round-3
@@ -643,7 +718,7 @@ def main():
         bytes_per_env_step = _native.step_hd_bytes(N)
         med = median(dev_blocks)                                     # every block is already the MAX over ranks
         r = {"ms": med, "blocks": dev_blocks, "blocks_per_event": blocks_per_event, "wall_blocks": wall_blocks, "local_ms": median(local_blocks),
-             "chunk": chunk, "B": B, "placement": placed, "side": side,
+             "chunk": chunk, "B": B, "placement": placed, "side": side, "dump": dumped,
              "bytes_per_env_step": bytes_per_env_step, "extra": None,
              "GBps": bytes_per_env_step * B * steps / (med * 1e-3) / 1e9}
         if other_steps > 0:
@@ -719,8 +794,18 @@ def main():
 
     N, B = a.agents, a.envs
     headline = (N, B) == (27, 4096)
-    m = measure(N, B, a.mode, a.steps, a.warmup, a.chunk, 0 if a.no_extra else min(a.steps, 400))
+    m = measure(N, B, a.mode, a.steps, a.warmup, a.chunk, 0 if a.no_extra else min(a.steps, 400), exact=True,
+                dump=bool(a.dump_outputs) and rank == 0)
     chunk, extra, finite = m["chunk"], m["extra"], m["finite"]
+    dump_info = None
+    if m["dump"] is not None:
+        arrays, sample = m["dump"]
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        dump_info = {"dir": a.dump_outputs, "arrays": {k: list(v.shape) for k, v in arrays.items()},
+                     "envs": "all %d" % m["B"] if sample is None else
+                             "%d of %d, np.random.RandomState(0).choice without replacement, ascending" % (len(sample), m["B"])}
     if profiled and a.placement_candidates > 1 and not a.no_extra:
         # under rocprofv3 the memory an arena hands back never returns to the driver (profiles/r03_place/
         # arena_memory_check_rocprofv3.txt): only the headline buffers are placed in a profiled process
@@ -851,19 +936,18 @@ def main():
                        "steps_per_launch": spl,
                        "kernel": ("fg::step_kernel<%d> T=%d E=%d" % (N, cfg["threads"], cfg["envs_per_wg"]))
                        if a.mode == "step" else "fg::rollout_kernel<%d> (producer/writer pipelined)" % N},
-            "timing": {"clock": "HIP events on the launch stream delimiting consecutive blocks of --steps steps (the series "
-                                "bracketed by barrier + device synchronize, MAX over ranks per block); blocks shorter than "
-                                "5 ms share an event pair (blocks_per_event consecutive blocks, sample = pair / that: an event "
-                                "after every launch costs the stream ~5 us); value, ms_per_step and roofline.achieved all "
-                                "come from the MEDIAN sample",
+            "timing": {"clock": "a HIP event pair on the launch stream delimiting ONE series of exactly --steps steps after the "
+                                "prewarm and the --warmup steps (bracketed by barrier + device synchronize, MAX over ranks); "
+                                "value, ms_per_step (= series / --steps) and roofline.achieved all come from it",
+                       "timed_steps": a.steps,
                        "blocks": len(blocks) * m.get("blocks_per_event", 1), "blocks_per_event": m.get("blocks_per_event", 1),
                        "timed_ms_total": round(sum(blocks) * m.get("blocks_per_event", 1), 3),
                        "block_ms_median": round(ms_block, 5), "block_ms_min": round(min(blocks), 5),
                        "block_ms_max": round(max(blocks), 5),
                        "wall_block_ms_median": round(median(walls), 5),
                        "wall_env_steps_per_s_median": round(world_size * B * a.steps / (median(walls) * 1e-3), 1),
-                       "note": "wall = host clock over the whole series / blocks (first launch latency and the completion "
-                                "poll included once)"},
+                       "note": "wall = host clock from queueing the series to seeing its closing event complete (what is "
+                                "left of the queued warm-up steps and the completion poll included)"},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBPS, 4),
                          "traffic": traffic, "traffic_source": traffic_src,
@@ -902,6 +986,8 @@ def main():
             res["roofline"]["frac_counter_bytes"] = round(achieved * ratio / HBM_PEAK_GBPS, 4)
         if a.obs_every != 1:
             res["INVALID"] = "observations written only every %d-th step (tuning run)" % a.obs_every
+        if dump_info:
+            res["dump_outputs"] = dump_info
         if extra:
             res["other_mode"] = extra
         if small:

@@ -534,10 +534,10 @@ def test_bench_json_contract_single_and_two_ranks():
         assert 0.5 < r["traffic"] / r["algorithmic_bytes_per_launch"] < 1.5, r
     else:
         assert "traffic_live_error" in r, r
-    # ONE clock: value, ms_per_step and roofline.achieved all come from the median HIP-event block, and a short
-    # --steps block is repeated until >= 50 ms have been timed
+    # ONE clock: value, ms_per_step and roofline.achieved all come from ONE HIP-event series of exactly --steps steps
     t = d["timing"]
-    assert t["blocks"] >= 3 and t["timed_ms_total"] >= 35.0 and t["block_ms_min"] <= t["block_ms_median"] <= t["block_ms_max"]
+    assert t["timed_steps"] == 30 and t["blocks"] == 1 and t["block_ms_min"] == t["block_ms_median"] == t["block_ms_max"]
+    assert abs(t["timed_ms_total"] - t["block_ms_median"]) < 1e-3
     assert abs(d["ms_per_step"] * 30 - t["block_ms_median"]) < 1e-3 * t["block_ms_median"] + 1e-5
     assert abs(d["value"] - 512 * 30 / (t["block_ms_median"] * 1e-3)) < 1e-3 * d["value"]
     alg = d["roofline"]["algorithmic_bytes_per_launch"] / d["config"]["steps_per_launch"] * 30
@@ -575,6 +575,33 @@ def test_bench_json_contract_single_and_two_ranks():
                 "--backend", "gloo", "--no-extra", "--min-timed-ms", "5"])
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1 and json.loads(line[0])["n_gpus"] == 2
+
+
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` at the headline shape: what the last of the --steps timed steps computed, float32, a
+    seeded sample of envs under 64 MB, bit for bit the same in two runs whose wall-clock prewarm differs (the env is put
+    back to its state before the prewarm, so the timed steps never depend on the clock)."""
+    import json
+    import os
+    dumps = []
+    for prewarm in ("0", "300"):
+        out = str(tmp_path / ("prewarm_" + prewarm))
+        line = [l for l in _run(["bench.py", "--steps", "50", "--warmup", "10", "--no-extra", "--prewarm-ms", prewarm,
+                                 "--dump-outputs", out]).splitlines() if l.startswith("{")]
+        assert len(line) == 1
+        d = json.loads(line[0])
+        assert d["steps"] == 50 and d["timing"]["timed_steps"] == 50 and d["dump_outputs"]["dir"] == out
+        files = sorted(os.listdir(out))
+        assert files == sorted(k + ".npy" for k in ("obs", "reward", "indiv", "done", "pos", "vel"))
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 * 10 ** 6
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in files})
+    a, b = dumps
+    n = a["obs"].shape[0]
+    assert 0 < n < 4096 and a["obs"].shape == (n, 27, 162) and a["done"].shape == a["reward"].shape == (n, 27)
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape[0] == n
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert np.isfinite(a["obs"]).all() and np.isfinite(a["pos"]).all() and (a["obs"] != 0).any()
 
 
 def test_bench_many_ranks_share_the_gpu():
