@@ -20,6 +20,7 @@
 // producer and writer waves (fg_rollout_kernels.hpp).
 // Observation bytes (24 N^2 per env) dominate traffic; everything else is 53 N + 16.
 // There is no dense contraction here, hence no MFMA: the kernel is HBM-store bound.
+// (The one exception: the caller's MLP actor inside the closed-loop rollout, fg_actor_rollout_kernel.hpp, on fp32 MFMA.)
 //
 // Source layout: fg_common.hpp (arguments, LDS layout, reductions, RNG, World options),
 // fg_pair_loops.hpp, fg_obs_writers.hpp, fg_step_kernel.hpp, fg_rollout_kernels.hpp,
@@ -40,6 +41,7 @@
 #include "fg_scn_lane_kernel.hpp"
 #include "fg_hd_lane_kernel.hpp"
 #include "fg_policy_kernels.hpp"
+#include "fg_actor_rollout_kernel.hpp"
 
 namespace fg {
 
@@ -1446,6 +1448,97 @@ int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void*
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(FG_ERR_HIP, "decode launch failed: %s", hipGetErrorString(err));
     return FG_OK;
+}
+
+}  // extern "C"
+
+// ---- closed loop with the caller's MLP actor (fg_actor_rollout_kernel.hpp) ----
+static bool actor_n_supported(int N) {
+    return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
+}
+template <int NC, int H>
+static int launch_actor_v(const Args& a, const ActorW& w, hipStream_t st) {
+    constexpr int E = actor_envs(NC), lds = actor_lds_bytes<NC, H>();
+    static_assert(lds <= 160 * 1024, "actor rollout LDS");
+    const int grid = (a.B + E - 1) / E;
+    if (describe("actor_rollout_kernel<%d,%d> grid %d block %d envs/wg %d lds %d; ", NC, H, grid, FG_ACTOR_THREADS, E, lds))
+        return FG_OK;
+    static std::atomic<unsigned long long> raised{0};
+    hipError_t err = raise_lds_limit((const void*)&actor_rollout_kernel<NC, H>, lds, &raised);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL((actor_rollout_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w);
+        err = hipGetLastError();
+    }
+    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor rollout launch failed: %s", hipGetErrorString(err));
+    return FG_OK;
+}
+// the checks every actor entry shares (no device touched): FG_OK, or the status of the first one that fails
+static int actor_check(const FgParams* params, const FgActor* actor, int B, int N, int K) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: B >= 0 and K >= 1 required%s");
+    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    if (!actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: actor is NULL%s");
+    if (actor->hidden != 32 && actor->hidden != 64 && actor->hidden != 128)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: hidden must be 32, 64 or 128%s");
+    if (!actor->w1 || !actor->w2 || !actor->w3) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a weight pointer is NULL%s");
+    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
+         (uintptr_t)actor->b3) & 3u)
+        return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor: weights must be 4-byte aligned%s");
+    if (world_options_set(*params))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
+    return FG_OK;
+}
+static int actor_dispatch(const Args& a, const FgActor& actor, hipStream_t st) {
+    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+#define FG_ACTOR(NN) \
+    if (a.N == NN) return actor.hidden == 32 ? launch_actor_v<NN, 32>(a, w, st) : actor.hidden == 64 ? launch_actor_v<NN, 64>(a, w, st) \
+                                                                                    : launch_actor_v<NN, 128>(a, w, st);
+    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
+#undef FG_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+}
+
+extern "C" {
+
+int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int N, int K,
+                        float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                        float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                        float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                        int obs_every, void* stream) {
+    int rc = actor_check(params, actor, B, N, K);
+    if (rc) return rc;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
+    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
+    if (B == 0) return FG_OK;
+    const DeviceGuard device_guard(stream, pos_x);
+    Args a; memset(&a, 0, sizeof(a));
+    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
+    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
+    a.do_phys = 1; a.do_post = 1;
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
+    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
+    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
+    a.act_out = act_seq;
+    return actor_dispatch(a, *actor, (hipStream_t)stream);
+}
+
+int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
+                             char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: out buffer required%s");
+    out[0] = 0;
+    int rc = actor_check(params, actor, B, N, K);
+    if (rc) return rc;
+    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
+    Args a; memset(&a, 0, sizeof(a));
+    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
+    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
+    g_describe = out; g_describe_cap = out_len;
+    rc = actor_dispatch(a, *actor, nullptr);
+    g_describe = nullptr; g_describe_cap = 0;
+    return rc;
 }
 
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,

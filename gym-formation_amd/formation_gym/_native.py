@@ -84,6 +84,17 @@ class FgScenario(ctypes.Structure):
     ]
 
 
+class FgActor(ctypes.Structure):
+    """Mirror of `struct FgActor` (include/formation_hip.h): the caller's MLP actor for fg_rollout_hd_actor."""
+    _fields_ = [
+        ("hidden", ctypes.c_int32),
+        ("out_tanh", ctypes.c_int32),
+        ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p),
+        ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+        ("w3", ctypes.c_void_p), ("b3", ctypes.c_void_p),
+    ]
+
+
 class FormationHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libformation_hip: status %d: %s" % (code, msg))
@@ -131,6 +142,8 @@ SIGNATURES = {
     "fg_policy_bfs": (_I, [_I, _I, _I, _P, ctypes.c_int64, _P, _P]),
     "fg_policy_bfs_state": (_I, [_I, _I, _I] + [_P] * 6),
     "fg_rollout_hd_policy": (_I, [_PP, _I, _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_rollout_hd_actor": (_I, [_PP, ctypes.POINTER(FgActor), _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_describe_actor_launch": (_I, [_PP, ctypes.POINTER(FgActor), _I, _I, _I, _I, ctypes.c_char_p, _I]),
 }
 
 _lib = None

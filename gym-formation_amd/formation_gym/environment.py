@@ -22,7 +22,7 @@ N observation / 2N reward / N done callbacks of environment.py:113-142.
 import numpy as np
 import torch
 
-from . import _native, spaces
+from . import _native, actor_rollout, spaces
 
 cam_range = 2
 
@@ -349,6 +349,101 @@ class MultiAgentEnv(object):
         rew = out["reward"] if self.shared_reward else out["indiv"]
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), \
             {"individual_reward": out["indiv"], "actions": out["act"]}
+
+    def actor_path(self, actor):
+        """'fused' when `rollout_actor(K, actor)` runs as ONE launch with the actor inside the rollout kernel
+        (`fg_rollout_hd_actor`), 'host' when it runs the host-paced loop.  The rules: formation_gym/actor_rollout.py."""
+        sc = self.scenario
+        fused = getattr(sc, "bind_rollout_actor", None) is not None
+        world_options = False
+        if fused:
+            try:
+                p = sc.params(self.world)
+            except NotImplementedError:                    # scripted agents: only the World API drives them
+                fused = False
+            else:
+                world_options = bool(p.num_walls > 0 or p.u_noise > 0 or p.max_speed > 0 or p.accel > 0 or p.agent_props
+                                     or p.comm_state)
+        return actor_rollout.actor_path(actor, self.num_agents, self.world.device, fused_scenario=fused,
+                                        continuous=not self._action_mode(), silent=not self.world.any_non_silent(),
+                                        world_options=world_options, callback=self.post_step_callback is not None)
+
+    def rollout_actor(self, K, actor, out=None, obs_every=1):
+        """The loop of a learned actor for K steps in one call:
+            act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
+        from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
+        after the device auto-reset, when `auto_reset` is set); each agent's observation row [6N] is one row of the actor's
+        input batch.  Results come back like `rollout_policy`'s, with the actions taken under info['actions'] [K, B, N, 2],
+        and with its aliasing rules for `out`.
+        `actor_path(actor)` tells which loop runs.  'fused': ONE launch (`fg_rollout_hd_actor`) with the actor - one
+        Sequential(Linear(6N, H), ReLU, Linear(H, H), ReLU, Linear(H, 2) [, Tanh]) shared by all agents, H in {32, 64, 128} -
+        evaluated inside the rollout kernel on its parameters in place (an optimizer step between two calls is seen by the
+        next one); replaying info['actions'] through `rollout` gives the same bits.  'host': any other callable, the same loop
+        in Python under torch.no_grad(), one `step` per action."""
+        if self._action_mode():
+            raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
+        K, obs_every = int(K), int(obs_every)
+        if K < 1 or obs_every < 1:
+            raise ValueError("need K >= 1 steps and obs_every >= 1")
+        if self.actor_path(actor) == "host":
+            return self._rollout_actor_by_steps(K, actor, obs_every)
+        hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device)
+        B, N = self.num_envs, self.num_agents
+        D = self._out["obs"].shape[-1]
+        f = dict(dtype=torch.float32, device=self._act.device)
+        want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
+        if out is None:
+            out = self._default_out(K, obs_every, True) if self.default_placed else False
+        own_buffers = out is not False
+        if out is False:
+            out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
+                       else torch.empty(shp, **f)) for k, shp in want.items()}
+        # bound once per (buffers, weights, stream, constants), like rollout_policy: the binding holds the parameter tensors'
+        # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
+        key = None
+        if own_buffers and all(k in out for k in want):
+            key = ("actor", K, hidden, bool(out_tanh), tuple(0 if t is None else t.data_ptr() for t in weights),
+                   tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
+                   self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
+                   getattr(self.scenario, "_seed", 0))
+        launch = self._roll_launchers.get(key) if key is not None else None
+        if launch is None:
+            for k, shp in want.items():
+                if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
+                    raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
+            launch = self.scenario.bind_rollout_actor(self.world, K, (hidden, out_tanh, weights), out, obs_every=obs_every,
+                                                      auto_reset=self.auto_reset)
+            if key is not None:
+                if len(self._roll_launchers) >= 8:
+                    self._roll_launchers.clear()
+                self._roll_launchers[key] = launch
+        launch(self._launch_rng_offset())
+        self.scenario._cache = None
+        self._advance_rng(K)
+        self.current_step += K
+        self.world.world_step += K
+        rew = out["reward"] if self.shared_reward else out["indiv"]
+        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), \
+            {"individual_reward": out["indiv"], "actions": out["act"]}
+
+    def _rollout_actor_by_steps(self, K, actor, obs_every):
+        """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
+        launch's (fresh tensors)."""
+        observe = getattr(self.scenario, "observe_batch", None)
+        if observe is not None:                            # the observation of the current state (a multi-step launch
+            observe(self.world, {"obs": self._out["obs"]})  # leaves the env's own step buffer behind)
+        obs = self._out["obs"]
+        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act")}
+        with torch.no_grad():
+            for k in range(K):
+                act = actor(obs)
+                res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
+                obs, r, d, info = self.step(act)
+                if (k + 1) % obs_every == 0:
+                    res["obs"].append(obs.clone())
+                res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
+        return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
+                torch.stack(res["done"]), {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])})
 
     # ------------------------------------------------------------ buffers
     def _default_out(self, K, obs_every, policy):

@@ -262,6 +262,32 @@ class Scenario(BaseScenario):
             return keep
         return launch
 
+    def bind_rollout_actor(self, world, K, spec, out, obs_every=1, auto_reset=False):
+        """K closed-loop steps with the caller's MLP actor (`fg_rollout_hd_actor`), every pointer and the FgParams struct
+        resolved once: returns `launch(rng_offset)`.  spec = (hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) from
+        `actor_rollout.actor_spec`; the kernel reads those tensors in place at every launch, and the launcher keeps them
+        alive.  out["act"] [K,B,N,2] receives the actions taken, the other tensors are those of `rollout_batch`."""
+        lib = _native.load()
+        hidden, out_tanh, weights = spec
+        fa = _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in weights])
+        p = self.params(world, auto_reset, 0, out.get("obs"))
+        args = (world.num_envs, len(world.agents), int(K),
+                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
+                world.step_count.data_ptr(),
+                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
+                _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
+        fn = lib.fg_rollout_hd_actor
+        keep = (out, tuple(weights), fa)
+
+        def launch(rng_offset=0):
+            p.rng_offset = rng_offset
+            rc = fn(p, fa, *args)
+            if rc:
+                _native.check(rc)
+            return keep
+        return launch
+
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the
         simulator state (`fg_policy_bfs_state`): raw actions [B, N, 2]."""

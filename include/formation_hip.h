@@ -434,6 +434,40 @@ int fg_rollout_hd_policy(const FgParams* params, int B, int N, int K, int per_la
                          float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
                          int obs_every, void* stream);
 
+/* The caller's MLP actor for fg_rollout_hd_actor: Linear(6N, hidden) - ReLU - Linear(hidden, hidden) - ReLU -
+ * Linear(hidden, 2) [- tanh], one actor shared by every agent.  Weights in the torch Linear layout [out][in], fp32, in
+ * DEVICE memory, read in place by every launch (an optimizer step between two launches is seen by the next one); a NULL
+ * bias counts as zero.  hidden: 32, 64 or 128. */
+typedef struct FgActor {
+    int32_t hidden;
+    int32_t out_tanh;        /* 1: tanh on the two outputs */
+    const float* w1;         /* [hidden][6N] */
+    const float* b1;         /* [hidden] or NULL */
+    const float* w2;         /* [hidden][hidden] */
+    const float* b2;         /* [hidden] or NULL */
+    const float* w3;         /* [2][hidden] */
+    const float* b3;         /* [2] or NULL */
+} FgActor;
+
+/* Closed-loop rollout with the caller's actor: the loop of a learned policy
+ *     act_n = actor(obs_n); obs_n, ... = env.step(act_n)
+ * for K >= 1 steps and all B envs of formation_hd_env, in ONE launch (actor_rollout_kernel): step 0 acts on the
+ * observation of the current state, step k on the observation step k-1 returned (after the device auto-reset, when
+ * params->auto_reset is set).  Arguments as fg_rollout_hd_policy's - act_seq [K][B][N][2] is an OUTPUT (the actions taken,
+ * required), obs_env_pitch, obs_placed, auto-reset and rng_offset / rng_offset_dev as documented above - and the results
+ * equal fg_rollout_hd driven by the recorded act_seq bit for bit.  N in {3, 4, 8, 9, 16, 25, 27, 32}, silent agents and no
+ * World options (walls, accel, max_speed, u_noise, agent_props, comm_state): anything else returns FG_ERR_UNSUPPORTED_N
+ * (N) or FG_ERR_BAD_ARG; there is no fall-back inside the library. */
+int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int N, int K,
+                        float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                        float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                        float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                        int obs_every, void* stream);
+/* Dry run of fg_rollout_hd_actor: the kernel instantiation and launch geometry it would use, written to `out` as text,
+ * after the same checks (same status codes).  Touches no device. */
+int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
+                             char* out, int out_len);
+
 #ifdef __cplusplus
 }
 #endif
