@@ -1,0 +1,298 @@
+// fg_actor_rollout_body.inc - the one body of actor_rollout_kernel and actor_sample_kernel (fg_actor_rollout_kernel.hpp).
+// Included inside each kernel, whose scope provides the kernel arguments `a` (Args) and `w` (ActorW), the template
+// parameters NC and H, `constexpr bool SAMPLE` and `log_std` / `logp` (SAMPLE = false: nullptr).  Not a header: no guard.
+//
+// Why a textual include and not a force-inlined __device__ function: behind a function boundary the kernel arguments reach
+// the body through a by-value copy, and even inlined early the copy changes how the arguments are loaded and the order in
+// which the address arithmetic is canonicalised - the deterministic kernel's ISA changed (kernarg loads split and sunk into
+// branches, different registers).  Expanded in place, `if constexpr (SAMPLE)` leaves actor_rollout_kernel exactly the code
+// it was before the sampling kernel existed.
+    static_assert(!FG_F64, "the actor rollout is an fp32 kernel");
+    constexpr int N = NC, NP = npad(NC), G = actor_lanes(NC), E = actor_envs(NC);
+    constexpr int NPS = NP <= 16 ? NP : 0;
+    constexpr int D = 6 * N;                           // actor input width
+    constexpr int HS = actor_hstride(H), CB = H / 16, RT = FG_ACTOR_ROWS / 16, NW = FG_ACTOR_THREADS / 64;
+    constexpr int TILES = (E * N + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
+    static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float* const smemf = reinterpret_cast<float*>(smem);
+    float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
+    float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
+    float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
+    float* const hbuf = wsm + 4 * H + 4;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int e = tid / G, i = tid % G;
+    const int b0 = (int)blockIdx.x * E;
+    const int b = b0 + e;
+    const bool env_ok = b < a.B;
+    const bool valid = env_ok && i < N;
+    const int El = min(E, a.B - b0);
+    float* const blk = smemf + e * env_block_floats(N);
+    float2* const A = reinterpret_cast<float2*>(blk);                    // A[3N] | V[N] | NV[N]
+    float* const QX = blk + 10 * N;
+    float* const QY = QX + NP; float* const PX = QY + NP; float* const PY = PX + NP;
+    float* const SX = PY + NP; float* const SY = SX + NP;
+
+    for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
+        wsm[q] = w.b1 ? w.b1[q] : 0.f;
+        wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
+        wsm[2 * H + q] = w.w3[q];
+        wsm[3 * H + q] = w.w3[H + q];
+    }
+    if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
+    if constexpr (SAMPLE) {
+        if (tid < 2) wsm[4 * H + 2 + tid] = log_std[tid];
+    }
+
+    const float one_minus_damp = 1.0f - a.p.damping;
+    const float dt = a.p.dt;
+    const float cutoff = a.p.dist_min + 18.0f * a.p.contact_margin;
+    const float cutoff2 = cutoff * cutoff;
+    const float thr2 = (float)((double)a.p.collide_thresh * (double)a.p.collide_thresh);
+    const float invN = 1.0f / (float)N;
+    const uint64_t rbase = rng_base(a.p);
+
+    float2 p = make_float2(0.f, 0.f), v = p, s = p, iv = p;
+    int t_step = 0;
+    const size_t sidx = (size_t)b * N + i;
+    if (valid) {
+        p = make_float2(a.px[sidx], a.py[sidx]);
+        v = make_float2(a.vx[sidx], a.vy[sidx]);
+        s = reinterpret_cast<const float2*>(a.shape)[sidx];
+        QX[i] = p.x; QY[i] = p.y; SX[i] = s.x; SY[i] = s.y;
+        if (i < N - 1) A[N + i] = make_float2(0.f, 0.f);                  // the communication block of silent agents
+    } else if (env_ok && i < NP) {
+        QX[i] = FAR_AWAY; QY[i] = FAR_AWAY; PX[i] = FAR_AWAY; PY[i] = FAR_AWAY; SX[i] = FAR_AWAY; SY[i] = FAR_AWAY;
+    }
+    if (env_ok) { iv = reinterpret_cast<const float2*>(a.ivel)[b]; if (a.step) t_step = a.step[b]; }
+    auto publish = [&]() {                             // the observation tables of the state in registers
+        if (valid) {
+            A[i] = p; A[3 * N + i] = v; A[4 * N + i] = make_float2(-v.x, -v.y);
+            A[2 * N - 1 + i] = s;
+            if (i == 0) A[3 * N - 1] = iv;
+            QX[i] = p.x; QY[i] = p.y;
+        }
+    };
+
+    // ---- the actor on the published tables: act_lds[e N + i] = actor(observation row i of env e) ----
+    // (SAMPLE: plus exp(log_std) eps, eps drawn at counter offset `off`, and logp_lds[e N + i] = its log-density)
+    const int M = El * N;                              // rows that are agents of this workgroup
+    auto actor = [&](uint64_t off) {
+        float* const hb = hbuf + wave * FG_ACTOR_ROWS * HS;
+        const int col = lane & 15, kq = lane >> 4;     // MFMA operand lane map: row / column lane & 15, k = lane >> 4
+        for (int t = wave; t < TILES; t += NW) {
+            const int q0 = t * FG_ACTOR_ROWS;
+            // this lane's A-operand row in each 16-row tile: env, agent, its position (unit r of its own table)
+            const float2* AT[RT];
+            int r_of[RT];
+            float2 pr[RT];
+            bool row_ok[RT];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const int q = q0 + rt * 16 + col;
+                row_ok[rt] = q < M;
+                const int qq = row_ok[rt] ? q : 0;
+                const int ee = qq / N;
+                r_of[rt] = qq - ee * N;
+                AT[rt] = reinterpret_cast<const float2*>(smemf + ee * env_block_floats(N));
+                pr[rt] = AT[rt][r_of[rt]];
+            }
+            // observation unit u of row r (as write_obs_rows stores it): 0 velocity, 1 .. N-1 p_j - p_r (j skips r),
+            // N .. 2N-2 communication (zeros), 2N-1 .. 3N-2 ideal shape, 3N-1 ideal velocity
+            auto x_in = [&](int rt, int k) -> float {
+                const int u = k >> 1;
+                const int r = r_of[rt];
+                const bool rel = u >= 1 && u < N;
+                const int idx = u == 0 ? 3 * N + r : (rel ? ((u - 1 >= r) ? u : u - 1) : u);
+                const float2 val = AT[rt][u < 3 * N ? idx : 0];
+                const float2 sub = rel ? pr[rt] : make_float2(0.f, 0.f);
+                const float x = (k & 1) ? val.y - sub.y : val.x - sub.x;
+                return (row_ok[rt] && k < D) ? x : 0.f;
+            };
+            f32x4 acc[RT][CB];
+            // ---- layer 1: relative positions and velocity (k < 2N), then ideal shape and velocity (k >= 4N - 2) ----
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                const float bias = wsm[cb * 16 + col];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
+            }
+            // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would all
+            // be held in registers)
+            const float* w1row = w.w1 + (size_t)col * D;
+            asm volatile("" : "+v"(w1row));
+            auto l1_chunk = [&](int ks) {
+                const int k = ks * 4 + kq;
+                float xa[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) xa[rt] = x_in(rt, k);
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) {
+                    const float wb = k < D ? w1row[cb * 16 * D + k] : 0.f;
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt)
+                        acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
+                }
+            };
+            constexpr int KA = (2 * N + 3) / 4, KB0 = (4 * N - 2) / 4, KB1 = (D + 3) / 4;
+            static_assert(KB0 >= KA, "the two input blocks overlap");
+#pragma unroll 2
+            for (int ks = 0; ks < KA; ++ks) l1_chunk(ks);
+#pragma unroll 2
+            for (int ks = KB0; ks < KB1; ++ks) l1_chunk(ks);
+            // ReLU -> activation tile: accumulator register j of lane l is row 4 (l >> 4) + j, column l & 15
+            auto store_tile = [&]() {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            hb[(rt * 16 + kq * 4 + j) * HS + cb * 16 + col] = fmaxf(acc[rt][cb][j], 0.f);
+            };
+            store_tile();
+            WaveSync()();
+            // ---- layer 2 ----
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                const float bias = wsm[H + cb * 16 + col];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
+            }
+            const float* w2row = w.w2 + (size_t)col * H;
+            asm volatile("" : "+v"(w2row));
+#pragma unroll 2
+            for (int ks = 0; ks < H / 4; ++ks) {
+                const int k = ks * 4 + kq;
+                float xa[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) {
+                    const float wb = w2row[cb * 16 * H + k];
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt)
+                        acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
+                }
+            }
+            WaveSync()();                              // every read of the layer-1 tile before it is overwritten
+            store_tile();
+            WaveSync()();
+            // ---- layer 3 on the VALU: lane = (row, output) ----
+            {
+                const int row = lane >> 1, o = lane & 1;
+                const float* const hr = hb + row * HS;
+                const float* const w3 = wsm + 2 * H + o * H;
+                float y = wsm[4 * H + o];
+#pragma unroll 8
+                for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
+                if (w.out_tanh) y = tanhf(y);
+                const int q = q0 + row;
+                if constexpr (SAMPLE) {
+                    // both lanes of a row draw the row's pair: lane o adds component o and lane 0 keeps the log-density
+                    const int ee = q / N;
+                    const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
+                    const float ls0 = wsm[4 * H + 2], ls1 = wsm[4 * H + 3];
+                    y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
+                    if (q < M && o == 0) logp_lds[q] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
+                }
+                if (q < M) reinterpret_cast<float*>(act_lds)[2 * q + o] = y;
+            }
+            WaveSync()();                              // the tile is free for the next pass
+        }
+    };
+
+    publish();
+    __syncthreads();
+    actor(rbase);                                      // the action of step 0: the observation of the current state
+    __syncthreads();
+
+    for (int k = 0; k < a.K; ++k) {
+        // ---- physics: World.step + reward + done + auto-reset of step k (rollout_kernel's producer step) ----
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (valid) {
+            const float2 u_act = act_lds[e * N + i];
+            reinterpret_cast<float2*>(a.act_out)[((size_t)k * a.B + b) * N + i] = u_act;
+            if constexpr (SAMPLE) {
+                if (logp) logp[((size_t)k * a.B + b) * N + i] = logp_lds[e * N + i];
+            }
+            float2 f = contact_force_packed<NPS>(QX, QY, NP, i, p, a.p.contact_force, a.p.contact_margin,
+                                                 a.p.dist_min, cutoff2);
+            f.x += a.p.mass * (a.p.sensitivity * u_act.x);
+            f.y += a.p.mass * (a.p.sensitivity * u_act.y);
+            v.x = v.x * one_minus_damp + (f.x / a.p.mass) * dt;
+            v.y = v.y * one_minus_damp + (f.y / a.p.mass) * dt;
+            p.x += v.x * dt;
+            p.y += v.y * dt;
+            PX[i] = p.x; PY[i] = p.y;
+        }
+        t_step += 1;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        float sums[4] = {valid ? p.x : 0.f, valid ? p.y : 0.f, valid ? v.x : 0.f, valid ? v.y : 0.f};
+        env_reduce<G, G, 4, R_SUM, R_SUM, R_SUM, R_SUM>(sums, nullptr);
+        const float mx = sums[0] * invN, my = sums[1] * invN;
+        const float mvx = sums[2] * invN, mvy = sums[3] * invN;
+        float rowmin = INFINITY, colmin = INFINITY;
+        int cnt = 0, arg_lm = 0, arg_ag = 0;
+        if (valid)
+            reward_pass_packed<false, NPS>(PX, PY, SX, SY, NP, p, p.x - mx, p.y - my, s.x + mx, s.y + my, thr2,
+                                           rowmin, colmin, cnt, arg_lm, arg_ag);
+        float red[3] = {valid ? rowmin : -INFINITY, valid ? colmin : -INFINITY, (float)cnt};
+        env_reduce<G, G, 3, R_MAX, R_MAX, R_SUM, R_SUM>(red, nullptr);
+        const float Hd = rsqrt_(rmax(red[0], red[1]));
+        const float ex = iv.x - mvx, ey = iv.y - mvy;
+        const float velterm = rsqrt_(ex * ex + ey * ey);
+        const bool is_done = t_step >= a.p.world_length;
+        if (valid) {
+            const size_t o = ((size_t)k * a.B + b) * N + i;
+            a.rew[o] = (float)(-(double)N * ((double)Hd + (double)velterm) - (double)red[2]);
+            if (a.indiv) a.indiv[o] = (-Hd - velterm) - (float)cnt;
+            if (a.done) a.done[o] = is_done ? 1 : 0;
+        }
+        if (a.p.auto_reset) {
+            const bool mine = is_done && env_ok;
+            if (__any(mine) != 0) {
+                uint32_t c[4] = {(uint32_t)(b + a.p.env_index_base), (uint32_t)i, (uint32_t)(rbase + k),
+                                 (uint32_t)((rbase + k) >> 32)};
+                philox4x32(c, (uint32_t)a.p.seed, (uint32_t)(a.p.seed >> 32));
+                float raw[2] = {valid ? u_pm1(c[2]) : 0.f, valid ? u_pm1(c[3]) : 0.f};
+                const float rx = raw[0], ry = raw[1];
+                env_reduce<G, G, 2, R_SUM, R_SUM, R_SUM, R_SUM>(raw, nullptr);
+                uint32_t c2[4] = {(uint32_t)(b + a.p.env_index_base), 0xFFFFFFFFu, (uint32_t)(rbase + k),
+                                  (uint32_t)((rbase + k) >> 32)};
+                philox4x32(c2, (uint32_t)a.p.seed, (uint32_t)(a.p.seed >> 32));
+                if (mine) {
+                    iv = make_float2(u_pm1(c2[0]), u_pm1(c2[1]));
+                    t_step = 0;
+                    if (valid) {
+                        p = make_float2(u_pm1(c[0]), u_pm1(c[1]));
+                        v = make_float2(0.f, 0.f);
+                        s = make_float2(rfma(-raw[0], invN, rx), rfma(-raw[1], invN, ry));
+                        SX[i] = s.x; SY[i] = s.y;
+                        reinterpret_cast<float2*>(a.shape)[sidx] = s;
+                        if (i == 0) reinterpret_cast<float2*>(a.ivel)[b] = iv;
+                    }
+                }
+            }
+        }
+        publish();
+        __syncthreads();
+        // ---- the step's observations, then the actor for step k + 1 on the same tables ----
+        int slot = k;
+        bool want_obs = a.obs != nullptr;
+        if (a.obs_every > 1) { want_obs = want_obs && ((k + 1) % a.obs_every == 0); slot = k / a.obs_every; }
+        if (want_obs) {
+            const size_t unit0 = ((size_t)slot * a.B + b0) * (size_t)a.obs_pitch;
+            write_obs_rows<NC, NW, E>(reinterpret_cast<const float2*>(smemf), env_block_floats(N) / 2, wave,
+                                      reinterpret_cast<float2*>(a.obs) + unit0, (size_t)a.obs_pitch, El, 3);
+        }
+        if (k + 1 < a.K) actor(rbase + k + 1);         // step k + 1 draws at its own offset
+        __syncthreads();
+    }
+    if (valid) {
+        a.px[sidx] = p.x; a.py[sidx] = p.y; a.vx[sidx] = v.x; a.vy[sidx] = v.y;
+    }
+    if (a.step && env_ok && i == 0) a.step[b] = t_step;

@@ -1456,17 +1456,25 @@ int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void*
 static bool actor_n_supported(int N) {
     return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
 }
+// log_std == NULL: actor_rollout_kernel (the deterministic actor); else actor_sample_kernel (the Gaussian actor)
 template <int NC, int H>
-static int launch_actor_v(const Args& a, const ActorW& w, hipStream_t st) {
-    constexpr int E = actor_envs(NC), lds = actor_lds_bytes<NC, H>();
-    static_assert(lds <= 160 * 1024, "actor rollout LDS");
+static int launch_actor_v(const Args& a, const ActorW& w, const float* log_std, float* logp, hipStream_t st) {
+    const bool sample = log_std != nullptr;
+    constexpr int E = actor_envs(NC);
+    const int lds = sample ? actor_lds_bytes<NC, H, true>() : actor_lds_bytes<NC, H>();
+    static_assert(actor_lds_bytes<NC, H, true>() <= 160 * 1024, "actor rollout LDS");
     const int grid = (a.B + E - 1) / E;
-    if (describe("actor_rollout_kernel<%d,%d> grid %d block %d envs/wg %d lds %d; ", NC, H, grid, FG_ACTOR_THREADS, E, lds))
+    if (describe("%s<%d,%d> grid %d block %d envs/wg %d lds %d; ", sample ? "actor_sample_kernel" : "actor_rollout_kernel",
+                 NC, H, grid, FG_ACTOR_THREADS, E, lds))
         return FG_OK;
-    static std::atomic<unsigned long long> raised{0};
-    hipError_t err = raise_lds_limit((const void*)&actor_rollout_kernel<NC, H>, lds, &raised);
+    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
+    hipError_t err = sample ? raise_lds_limit((const void*)&actor_sample_kernel<NC, H>, lds, &raised_sample)
+                            : raise_lds_limit((const void*)&actor_rollout_kernel<NC, H>, lds, &raised);
     if (err == hipSuccess) {
-        hipLaunchKernelGGL((actor_rollout_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w);
+        if (sample)
+            hipLaunchKernelGGL((actor_sample_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w, log_std, logp);
+        else
+            hipLaunchKernelGGL((actor_rollout_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w);
         err = hipGetLastError();
     }
     if (err != hipSuccess) return fail(FG_ERR_HIP, "actor rollout launch failed: %s", hipGetErrorString(err));
@@ -1489,14 +1497,48 @@ static int actor_check(const FgParams* params, const FgActor* actor, int B, int 
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
     return FG_OK;
 }
-static int actor_dispatch(const Args& a, const FgActor& actor, hipStream_t st) {
+// the Gaussian actor's extra argument: FG_OK or the status of the first check that fails (no device touched)
+static int actor_sample_check(const float* log_std) {
+    if (!log_std) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
+    if ((uintptr_t)log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
+    return FG_OK;
+}
+static int actor_dispatch(const Args& a, const FgActor& actor, const float* log_std, float* logp, hipStream_t st) {
     const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
 #define FG_ACTOR(NN) \
-    if (a.N == NN) return actor.hidden == 32 ? launch_actor_v<NN, 32>(a, w, st) : actor.hidden == 64 ? launch_actor_v<NN, 64>(a, w, st) \
-                                                                                    : launch_actor_v<NN, 128>(a, w, st);
+    if (a.N == NN) return actor.hidden == 32 ? launch_actor_v<NN, 32>(a, w, log_std, logp, st) \
+                        : actor.hidden == 64 ? launch_actor_v<NN, 64>(a, w, log_std, logp, st)  \
+                                             : launch_actor_v<NN, 128>(a, w, log_std, logp, st);
     FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
 #undef FG_ACTOR
     return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+}
+
+extern "C" {
+
+}  // extern "C"
+
+static int rollout_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                              float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                              int obs_every, void* stream) {
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
+    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
+    if (B == 0) return FG_OK;
+    const DeviceGuard device_guard(stream, pos_x);
+    Args a; memset(&a, 0, sizeof(a));
+    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
+    int rc = set_obs_pitch(&a);
+    if (rc != FG_OK) return rc;
+    a.do_phys = 1; a.do_post = 1;
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
+    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
+    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
+    a.act_out = act_seq;
+    return actor_dispatch(a, *actor, log_std, logp_seq, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -1508,22 +1550,55 @@ int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int
                         int obs_every, void* stream) {
     int rc = actor_check(params, actor, B, N, K);
     if (rc) return rc;
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
-    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
+    return rollout_actor_impl(params, actor, nullptr, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
+                              step, obs_seq, reward_seq, indiv_seq, done_seq, nullptr, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                               int obs_every, void* stream) {
+    int rc = actor_check(params, actor, B, N, K);
+    if (rc) return rc;
+    if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
+    if ((uintptr_t)logp_seq & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: logp_seq must be 4-byte aligned%s");
+    return rollout_actor_impl(params, actor, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
+                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream);
+}
+
+int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || N < 1 || N >= (1 << 29)) return fail(FG_ERR_BAD_ARG, "fg_actor_noise: B >= 0 and 1 <= N < 2^29 required%s");
+    if (!eps) return fail(FG_ERR_BAD_ARG, "fg_actor_noise: eps is NULL%s");
+    if ((uintptr_t)eps & 7u) return fail(FG_ERR_ALIGNMENT, "fg_actor_noise: eps must be 8-byte aligned%s");
     if (B == 0) return FG_OK;
-    const DeviceGuard device_guard(stream, pos_x);
+    const DeviceGuard device_guard(stream, eps);
+    const long long count = (long long)B * N;
+    hipLaunchKernelGGL(actor_noise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       *params, B, N, reinterpret_cast<float2*>(eps));
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor noise launch failed: %s", hipGetErrorString(err));
+    return FG_OK;
+}
+
+}  // extern "C"
+
+static int describe_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                               int obs_every, char* out, int out_len) {
+    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
     Args a; memset(&a, 0, sizeof(a));
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    a.do_phys = 1; a.do_post = 1;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
-    a.act_out = act_seq;
-    return actor_dispatch(a, *actor, (hipStream_t)stream);
+    int rc = set_obs_pitch(&a);
+    if (rc != FG_OK) return rc;
+    g_describe = out; g_describe_cap = out_len;
+    rc = actor_dispatch(a, *actor, log_std, nullptr, nullptr);
+    g_describe = nullptr; g_describe_cap = 0;
+    return rc;
 }
+
+extern "C" {
 
 int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
                              char* out, int out_len) {
@@ -1531,14 +1606,17 @@ int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B
     out[0] = 0;
     int rc = actor_check(params, actor, B, N, K);
     if (rc) return rc;
-    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    g_describe = out; g_describe_cap = out_len;
-    rc = actor_dispatch(a, *actor, nullptr);
-    g_describe = nullptr; g_describe_cap = 0;
-    return rc;
+    return describe_actor_impl(params, actor, nullptr, B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                                    int obs_every, char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_sample_launch: out buffer required%s");
+    out[0] = 0;
+    int rc = actor_check(params, actor, B, N, K);
+    if (rc) return rc;
+    if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
+    return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,

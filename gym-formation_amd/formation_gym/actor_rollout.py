@@ -5,8 +5,15 @@ The fused kernel takes one actor shared by every agent, exactly
     torch.nn.Sequential(Linear(6N, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])
 with H in {32, 64, 128}, fp32 contiguous parameters on the env's device (a None bias counts as zero), for N in
 {3, 4, 8, 9, 16, 25, 27, 32} agents of formation_hd_env with continuous actions, silent agents, no World options and no
-post_step_callback.  Anything else runs host-paced: a shape or option the kernel cannot honour never runs fused."""
+post_step_callback.  Anything else runs host-paced: a shape or option the kernel cannot honour never runs fused.
+
+A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
+log_std is a contiguous fp32 [2] tensor on the env's device."""
+import math
+
 import torch
+
+LOG_2PI = math.log(2.0 * math.pi)
 
 FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)
 FUSED_HIDDEN = (32, 64, 128)
@@ -35,9 +42,64 @@ def actor_spec(actor, num_agents, device=None):
             continue
         if t.dtype != torch.float32 or not t.is_contiguous():
             return None
-        if dev is not None and (t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index)):
+        if not _on_device(t, dev):
             return None
     return H, len(mods) == 6, params
+
+
+class GaussianActor(torch.nn.Module):
+    """A diagonal Gaussian policy with a state-independent log-std (onpolicy's DiagGaussian): the action is
+    mean(obs) + exp(log_std) * eps, eps ~ N(0, I), with no clipping and no tanh after the noise.
+    `mean` maps observations [..., 6N] to [..., 2]; `log_std` is an nn.Parameter [2] (zeros when not given).
+    `forward` draws eps with torch.randn_like and is meant for use outside the env: inside `env.rollout_actor` the env's
+    counter stream supplies eps (`fg_actor_noise`), and the log-density of each action comes back in info['log_prob']."""
+
+    def __init__(self, mean, log_std=None):
+        super().__init__()
+        self.mean = mean
+        if log_std is None:
+            log_std = torch.zeros(2)
+        self.log_std = log_std if isinstance(log_std, torch.nn.Parameter) else torch.nn.Parameter(torch.as_tensor(log_std))
+
+    def forward(self, obs):
+        mu = self.mean(obs)
+        return mu + torch.exp(self.log_std) * torch.randn_like(mu)
+
+    def distribution(self, obs):
+        """torch.distributions.Normal(mean(obs), exp(log_std)) of the per-component actions."""
+        mu = self.mean(obs)
+        return torch.distributions.Normal(mu, torch.exp(self.log_std).expand_as(mu))
+
+    def log_prob(self, obs, act):
+        """Log-density of `act` [..., 2] under the policy at `obs`, summed over the last axis (the PPO ratio's input);
+        differentiable in the mean's parameters and in log_std."""
+        z = (act - self.mean(obs)) * torch.exp(-self.log_std)
+        return -0.5 * (z * z).sum(-1) - self.log_std.sum() - LOG_2PI
+
+    def entropy(self):
+        """Entropy of the action distribution (the same for every state): sum(log_std) + log(2 pi e)."""
+        return self.log_std.sum() + LOG_2PI + 1.0
+
+
+def _on_device(t, device):
+    if device is None:
+        return True
+    dev = torch.device(device)
+    return t.device.type == dev.type and (dev.index is None or t.device.index == dev.index)
+
+
+def sample_spec(actor, num_agents, device=None):
+    """(actor_spec(actor.mean, ...), log_std) when the fused kernel can sample from the GaussianActor `actor` for
+    `num_agents` agents, else None: its mean fuses (actor_spec) and log_std is a contiguous fp32 [2] tensor on `device`
+    (None: not checked).  log_std is the actor's own parameter, read in place by every launch."""
+    if not isinstance(actor, GaussianActor):
+        return None
+    spec = actor_spec(actor.mean, num_agents, device)
+    ls = actor.log_std
+    if spec is None or not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) \
+            or not ls.is_contiguous() or not _on_device(ls, device):
+        return None
+    return spec, ls
 
 
 def actor_path(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
@@ -47,4 +109,6 @@ def actor_path(actor, num_agents, device=None, fused_scenario=True, continuous=T
     accel, max_speed, u_noise, per-agent properties), no post_step_callback."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return "host"
+    if isinstance(actor, GaussianActor):
+        return "fused" if sample_spec(actor, num_agents, device) is not None else "host"
     return "fused" if actor_spec(actor, num_agents, device) is not None else "host"

@@ -379,30 +379,49 @@ class MultiAgentEnv(object):
         Sequential(Linear(6N, H), ReLU, Linear(H, H), ReLU, Linear(H, 2) [, Tanh]) shared by all agents, H in {32, 64, 128} -
         evaluated inside the rollout kernel on its parameters in place (an optimizer step between two calls is seen by the
         next one); replaying info['actions'] through `rollout` gives the same bits.  'host': any other callable, the same loop
-        in Python under torch.no_grad(), one `step` per action."""
+        in Python under torch.no_grad(), one `step` per action.
+        A `GaussianActor(mean, log_std)` explores: step k takes a = mean(o) + exp(log_std) * eps, where eps [B, N, 2] is the
+        env's own counter stream at step k's RNG offset (`fg_actor_noise`: seed, global env index, agent - the same draws on
+        either path and for a shard as for its slice of the full batch), and info['log_prob'] [K, B, N] holds
+        -(eps_0^2 + eps_1^2) / 2 - sum(log_std) - log(2 pi), the log-density of each action.  `out` may carry 'log_prob'.
+        It fuses (`fg_rollout_hd_actor_sample`) when its mean would and log_std is a contiguous fp32 [2] tensor on the env's
+        device, read in place like the weights."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
         if K < 1 or obs_every < 1:
             raise ValueError("need K >= 1 steps and obs_every >= 1")
+        gaussian = isinstance(actor, actor_rollout.GaussianActor)
         if self.actor_path(actor) == "host":
             return self._rollout_actor_by_steps(K, actor, obs_every)
-        hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device)
+        log_std = None
+        if gaussian:
+            (hidden, out_tanh, weights), log_std = actor_rollout.sample_spec(actor, self.num_agents, self.world.device)
+        else:
+            hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device)
         B, N = self.num_envs, self.num_agents
         D = self._out["obs"].shape[-1]
         f = dict(dtype=torch.float32, device=self._act.device)
         want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
+        if gaussian:
+            want["log_prob"] = (K, B, N)
         if out is None:
             out = self._default_out(K, obs_every, True) if self.default_placed else False
+            if gaussian and out is not False and "log_prob" not in out:
+                out["log_prob"] = torch.empty(want["log_prob"], **f)     # kept with this shape's buffers, same aliasing
         own_buffers = out is not False
         if out is False:
             out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
                        else torch.empty(shp, **f)) for k, shp in want.items()}
+        elif gaussian and "log_prob" not in out:                        # the caller's buffers without one: a fresh one
+            out = dict(out, log_prob=torch.empty(want["log_prob"], **f))
+            own_buffers = False
         # bound once per (buffers, weights, stream, constants), like rollout_policy: the binding holds the parameter tensors'
         # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
         key = None
         if own_buffers and all(k in out for k in want):
             key = ("actor", K, hidden, bool(out_tanh), tuple(0 if t is None else t.data_ptr() for t in weights),
+                   0 if log_std is None else log_std.data_ptr(),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))
@@ -412,7 +431,7 @@ class MultiAgentEnv(object):
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
             launch = self.scenario.bind_rollout_actor(self.world, K, (hidden, out_tanh, weights), out, obs_every=obs_every,
-                                                      auto_reset=self.auto_reset)
+                                                      auto_reset=self.auto_reset, log_std=log_std)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()
@@ -423,27 +442,53 @@ class MultiAgentEnv(object):
         self.current_step += K
         self.world.world_step += K
         rew = out["reward"] if self.shared_reward else out["indiv"]
-        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), \
-            {"individual_reward": out["indiv"], "actions": out["act"]}
+        info = {"individual_reward": out["indiv"], "actions": out["act"]}
+        if gaussian:
+            info["log_prob"] = out["log_prob"]
+        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
+
+    def actor_noise(self, out=None):
+        """The exploration noise eps [B, N, 2] that a GaussianActor's next step draws (`fg_actor_noise` at the offset of the
+        next launch): what `rollout_actor` adds, scaled by exp(log_std), to the mean action of that step."""
+        B, N = self.num_envs, self.num_agents
+        if out is None:
+            out = torch.empty((B, N, 2), dtype=torch.float32, device=self.world.device)
+        sc = self.scenario
+        p = self.world.native_params(seed=getattr(sc, "_seed", 0), rng_offset=self._launch_rng_offset(), scripted_ok=True)
+        p.env_index_base = int(getattr(sc, "env_base", 0))
+        _native.check(_native.load().fg_actor_noise(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
+        return out
 
     def _rollout_actor_by_steps(self, K, actor, obs_every):
         """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
-        launch's (fresh tensors)."""
+        launch's (fresh tensors).  A GaussianActor: mean(obs) + exp(log_std) * eps with eps from `actor_noise`, the draws
+        of the fused kernel, and the log-density from eps by the kernel's formula."""
+        gaussian = isinstance(actor, actor_rollout.GaussianActor)
         observe = getattr(self.scenario, "observe_batch", None)
         if observe is not None:                            # the observation of the current state (a multi-step launch
             observe(self.world, {"obs": self._out["obs"]})  # leaves the env's own step buffer behind)
         obs = self._out["obs"]
-        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act")}
+        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act", "logp")}
         with torch.no_grad():
             for k in range(K):
-                act = actor(obs)
+                if gaussian:
+                    eps = self.actor_noise()
+                    ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
+                    act = actor.mean(obs) + torch.exp(ls) * eps
+                    res["logp"].append(-0.5 * (eps[..., 0] * eps[..., 0] + eps[..., 1] * eps[..., 1]) - (ls[0] + ls[1])
+                                       - actor_rollout.LOG_2PI)
+                else:
+                    act = actor(obs)
                 res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
                 obs, r, d, info = self.step(act)
                 if (k + 1) % obs_every == 0:
                     res["obs"].append(obs.clone())
                 res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
+        info = {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])}
+        if gaussian:
+            info["log_prob"] = torch.stack(res["logp"])
         return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
-                torch.stack(res["done"]), {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])})
+                torch.stack(res["done"]), info)
 
     # ------------------------------------------------------------ buffers
     def _default_out(self, K, obs_every, policy):

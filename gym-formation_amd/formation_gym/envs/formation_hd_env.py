@@ -262,11 +262,13 @@ class Scenario(BaseScenario):
             return keep
         return launch
 
-    def bind_rollout_actor(self, world, K, spec, out, obs_every=1, auto_reset=False):
+    def bind_rollout_actor(self, world, K, spec, out, obs_every=1, auto_reset=False, log_std=None):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_hd_actor`), every pointer and the FgParams struct
         resolved once: returns `launch(rng_offset)`.  spec = (hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) from
         `actor_rollout.actor_spec`; the kernel reads those tensors in place at every launch, and the launcher keeps them
-        alive.  out["act"] [K,B,N,2] receives the actions taken, the other tensors are those of `rollout_batch`."""
+        alive.  out["act"] [K,B,N,2] receives the actions taken, the other tensors are those of `rollout_batch`.
+        log_std [2] (a GaussianActor's, read in place like the weights): the sampling launch
+        (`fg_rollout_hd_actor_sample`), with the actions' log-densities in out["log_prob"] [K,B,N]."""
         lib = _native.load()
         hidden, out_tanh, weights = spec
         fa = _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in weights])
@@ -279,6 +281,10 @@ class Scenario(BaseScenario):
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
         fn = lib.fg_rollout_hd_actor
         keep = (out, tuple(weights), fa)
+        if log_std is not None:
+            fn = lib.fg_rollout_hd_actor_sample
+            keep = keep + (log_std,)
+            args = (log_std.data_ptr(),) + args[:-2] + (out["log_prob"].data_ptr(),) + args[-2:]
 
         def launch(rng_offset=0):
             p.rng_offset = rng_offset

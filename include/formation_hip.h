@@ -468,6 +468,28 @@ int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int
 int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
                              char* out, int out_len);
 
+/* fg_rollout_hd_actor with a diagonal Gaussian on top of the actor (actor_sample_kernel): step k takes
+ *     a = actor(o) + exp(log_std) * eps,    log_prob = -(eps_0^2 + eps_1^2) / 2 - (log_std_0 + log_std_1) - log(2 pi)
+ * where log_std [2] is fp32 in DEVICE memory, state-independent and read in place by every launch, and eps [2] of agent i of
+ * env b is fg_actor_noise's draw at step k's counter offset (rng_base + k, the offset of step k's auto-reset): Philox4x32-10
+ * keyed by params->seed on the counter {b + env_index_base, i ^ 0xA0000000, lo32(offset), hi32(offset)}, then Box-Muller on
+ * words 0 and 1.  No clipping, no tanh after the noise.  logp_seq [K][B][N] receives log_prob (NULL: not written); every
+ * other argument, check and status code is fg_rollout_hd_actor's.  A NULL log_std returns FG_ERR_BAD_ARG. */
+int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                               int obs_every, void* stream);
+/* One step's exploration noise of fg_rollout_hd_actor_sample: eps [B][N][2] (8-byte aligned, device memory) at the counter
+ * offset rng_base(params) (rng_offset + *rng_offset_dev), from the same device function as the fused kernel - the
+ * host-paced loop of a Gaussian actor calls it once per step and draws the same numbers.  `params` passes the usual checks;
+ * the draw reads only its seed, env_index_base and offset.  N < 2^29 (the stream's counter word keeps three top bits). */
+int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream);
+/* Dry run of fg_rollout_hd_actor_sample (the twin of fg_describe_actor_launch): same checks and status codes, names the
+ * actor_sample_kernel<N,H> instantiation.  Touches no device; log_std is only checked for NULL and alignment. */
+int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+                                    int obs_every, char* out, int out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,262 @@
+"""GPU tests of the Gaussian actor rollout: `env.rollout_actor(K, GaussianActor(mean, log_std))`, fused
+(`fg_rollout_hd_actor_sample`, actor_sample_kernel) and host-paced (`fg_actor_noise` once per step).
+
+Noise reference bound.  eps = (r cos a, r sin a), r = sqrt(-2 ln u), u = ((c0 >> 8) + 1) / 2^24, a = 6.2831853f (c1 >> 8) / 2^24,
+c = Philox4x32-10 (below, in NumPy).  u is exact in fp32 and a carries one rounding (2^-24 relative), so the error is that of
+the fp32 transcendentals.  __logf is v_log_f32 (log2, ~1 ulp) times ln 2 (0.5 ulp): ln u to ~2^-22 relative; the square root
+halves that and adds 0.5 ulp: r to ~2.5e-7 relative.  __cosf / __sinf scale a by 1 / 2 pi (0.5 ulp of a revolution < 1) and
+take v_cos_f32 / v_sin_f32 (~2^-22 absolute): cos a, sin a to ~4e-7 absolute.  Per component
+    |eps - eps64| <= r (2.5e-7 |cos a| + 4e-7) + 0.5 ulp(eps) <= 7e-7 r + 1e-7,
+which is below 2e-6 for r <= 2.7 (97 % of the draws) and grows in the tail: at this test's ~1e5 draws r reaches ~4.8.  A flat
+2e-6 does not hold there - the measured maximum is 2.2-2.3e-6 - so the test enforces the per-draw bound.
+
+Log-prob fidelity bound.  The kernel's log_prob is -|eps|^2 / 2 - sum(log_std) - log(2 pi) of its own eps; the fp64 reference
+is Normal(mean64(o), std).log_prob(a).sum(-1) at the recorded fp32 action a.  With z = (a - mean64) / std the two differ by
+  sum_o |z_o| (|mean32 - mean64|_o / std_o + |a_o| 2^-24 / std_o + |eps_o| e_std) + fp32 rounding of the formula,
+where |mean32 - mean64| <= 1e-5 max(1, |mean|) is the existing actor bound (test_gpu_actor_rollout), 2^-24 |a| the rounding of
+the stored action and e_std ~ 3e-7 the relative error of __expf(log_std) for |log_std| <= 1.  The formula itself rounds to
+~1e-6 (1 + |log_prob|).
+"""
+import numpy as np
+import pytest
+import torch
+
+import formation_gym
+from formation_gym import GaussianActor, _native
+from formation_gym.actor_rollout import FUSED_N, LOG_2PI
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+B = 133                  # not a multiple of any workgroup's env count (8, 16, 32, 64)
+K = 24
+ACT_SCALE = 1.5
+CASES = [(n, 64) for n in FUSED_N] + [(9, 32), (9, 128), (27, 32), (27, 128)]
+
+
+def _mlp(N, H, tanh=False, seed=0, zero=False):
+    torch.manual_seed(seed)
+    mods = [torch.nn.Linear(6 * N, H), torch.nn.ReLU(), torch.nn.Linear(H, H), torch.nn.ReLU(), torch.nn.Linear(H, 2)]
+    if tanh:
+        mods.append(torch.nn.Tanh())
+    m = torch.nn.Sequential(*mods).to(DEV)
+    with torch.no_grad():
+        for p in m.parameters():
+            p.mul_(0.0 if zero else ACT_SCALE)
+    return m
+
+
+def _zero_actor(N, H=64):
+    return GaussianActor(_mlp(N, H, zero=True), torch.nn.Parameter(torch.zeros(2, device=DEV)))
+
+
+class _Wrap(torch.nn.Module):
+    """The same mean behind a module actor_spec does not accept: the host-paced path."""
+
+    def __init__(self, m):
+        super().__init__()
+        self.m = m
+
+    def forward(self, x):
+        return self.m(x)
+
+
+def _env(N, seed=3, num_envs=B):
+    env = formation_gym.make_env("formation_hd_env", False, N, num_envs=num_envs, device=DEV)
+    env.seed(seed)
+    env.reset()
+    env.auto_reset = True
+    wl = int(env.world.world_length)
+    step0 = np.random.RandomState(seed).randint(0, wl, num_envs)
+    step0[::3] = wl - 7                                  # an episode boundary inside the launch for a third of the envs
+    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
+    return env
+
+
+def _state(env):
+    w, sc = env.world, env.scenario
+    return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.step_count, sc.ideal_shape, sc.ideal_vel)]
+
+
+def _clone(res):
+    obs, rew, done, info = res
+    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
+
+
+def _noise_at(env, k):
+    """fg_actor_noise at the offset of step k of the next launch."""
+    sc = env.scenario
+    p = env.world.native_params(seed=sc._seed, rng_offset=env._launch_rng_offset() + k)
+    p.env_index_base = int(getattr(sc, "env_base", 0))
+    eps = torch.empty((env.num_envs, env.num_agents, 2), dtype=torch.float32, device=DEV)
+    _native.check(_native.load().fg_actor_noise(p, env.num_envs, env.num_agents, eps.data_ptr(),
+                                                _native.current_stream(DEV)))
+    return eps
+
+
+# ---- NumPy Philox4x32-10 and fp64 Box-Muller ----
+def _philox(c0, c1, c2, c3, seed):
+    M = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=np.uint64) & M for x in (c0, c1, c2, c3)]
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
+    for _ in range(10):
+        m0 = np.uint64(0xD2511F53) * c[0]
+        m1 = np.uint64(0xCD9E8D57) * c[2]
+        n0 = (m1 >> np.uint64(32)) ^ c[1] ^ k0
+        n2 = (m0 >> np.uint64(32)) ^ c[3] ^ k1
+        c = [n0 & M, m1 & M, n2 & M, m0 & M]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return c
+
+
+def _eps_ref(seed, Bn, N, offset, base=0):
+    g = np.arange(Bn, dtype=np.uint64)[:, None] + np.uint64(base)
+    i = np.arange(N, dtype=np.uint64)[None, :]
+    shape = (Bn, N)
+    c = _philox(np.broadcast_to(g, shape), np.broadcast_to(i ^ np.uint64(0xA0000000), shape),
+                np.full(shape, offset & 0xFFFFFFFF, np.uint64), np.full(shape, offset >> 32, np.uint64), int(seed))
+    u = ((c[0] >> np.uint64(8)).astype(np.float64) + 1.0) / 16777216.0
+    a = float(np.float32(6.2831853)) * ((c[1] >> np.uint64(8)).astype(np.float64) / 16777216.0)
+    r = np.sqrt(-2.0 * np.log(u))
+    return np.stack([r * np.cos(a), r * np.sin(a)], -1)
+
+
+def _logp_formula(eps, log_std):
+    return -0.5 * (eps[..., 0] * eps[..., 0] + eps[..., 1] * eps[..., 1]) - (log_std[0] + log_std[1]) - LOG_2PI
+
+
+@pytest.mark.parametrize("N", [9, 27])
+def test_exact_noise_over_two_launches(N):
+    env = _env(N)
+    actor = _zero_actor(N)
+    assert env.actor_path(actor) == "fused"
+    seen = []
+    for launch in range(2):
+        want = torch.stack([_noise_at(env, k) for k in range(K)])
+        off0 = env._launch_rng_offset()
+        _, _, done, info = _clone(env.rollout_actor(K, actor))
+        assert launch == 1 or bool(done.any()), "no episode boundary inside the launch"
+        acts, logp = info["actions"], info["log_prob"]
+        assert acts.shape == (K, B, N, 2) and logp.shape == (K, B, N)
+        assert torch.equal(acts, want), "launch %d: the actions are not fg_actor_noise at each step's offset" % launch
+        ref = np.stack([_eps_ref(env.scenario._seed, B, N, off0 + k) for k in range(K)])
+        r = np.sqrt((ref * ref).sum(-1, keepdims=True))
+        err = np.abs(acts.double().cpu().numpy() - ref)
+        assert (err <= 7e-7 * r + 1e-7).all(), "launch %d: max |eps - eps64| / (7e-7 r + 1e-7) = %.3g" % (
+            launch, (err / (7e-7 * r + 1e-7)).max())
+        small = (r <= 2.7)[..., 0]
+        assert err[small].max() <= 2e-6
+        lp = _logp_formula(acts, torch.zeros(2, device=DEV))
+        assert torch.allclose(logp, lp, rtol=1e-6, atol=0)
+        seen.append(acts)
+    assert not bool((seen[0] == seen[1]).all(-1).any()), "the second launch repeats draws of the first"
+
+
+@pytest.mark.parametrize("N", [9, 27])
+def test_host_and_fused_paths_match(N):
+    env = _env(N)
+    fused = _zero_actor(N)
+    host = GaussianActor(_Wrap(fused.mean), fused.log_std)
+    assert env.actor_path(fused) == "fused" and env.actor_path(host) == "host"
+    snap = env._snapshot()
+    f_obs, f_rew, f_done, f_info = _clone(env.rollout_actor(K, fused))
+    f_state = _state(env)
+    assert bool(f_done.any()), "no episode boundary inside the launch"
+    env._restore(snap)
+    h_obs, h_rew, h_done, h_info = env.rollout_actor(K, host)
+    assert torch.equal(f_info["actions"], h_info["actions"])
+    assert torch.equal(f_obs, h_obs) and torch.equal(f_rew, h_rew) and torch.equal(f_done, h_done)
+    for a, b in zip(f_state, _state(env)):
+        assert torch.equal(a, b)
+    assert torch.allclose(f_info["log_prob"], h_info["log_prob"], rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("N,H", CASES)
+def test_replay_and_log_prob_fidelity(N, H):
+    env = _env(N)
+    tanh = H != 128
+    actor = GaussianActor(_mlp(N, H, tanh=tanh), torch.nn.Parameter(torch.tensor([-0.5, 0.3], device=DEV)))
+    assert env.actor_path(actor) == "fused"
+    snap = env._snapshot()
+    obs0 = torch.empty_like(env._out["obs"])
+    env.scenario.observe_batch(env.world, {"obs": obs0})
+    obs, rew, done, info = _clone(env.rollout_actor(K, actor))
+    state = _state(env)
+    env._restore(snap)
+    r_obs, r_rew, r_done, r_info = env.rollout(info["actions"].clone())
+    assert torch.equal(obs, r_obs) and torch.equal(rew, r_rew) and torch.equal(done, r_done)
+    assert torch.equal(info["individual_reward"], r_info["individual_reward"])
+    for a, b in zip(state, _state(env)):
+        assert torch.equal(a, b)
+    # log-prob against fp64 Normal(mean64(o_k), std) at the recorded actions (bound: module docstring)
+    ref = GaussianActor(_mlp(N, H, tanh=tanh).double(), torch.nn.Parameter(actor.log_std.detach().double()))
+    ref.mean.load_state_dict(actor.mean.state_dict())
+    std = torch.exp(ref.log_std.detach())
+    for k in range(K):
+        o = (obs0 if k == 0 else obs[k - 1]).double()
+        a = info["actions"][k].double()
+        with torch.no_grad():
+            mu = ref.mean(o)
+            want = torch.distributions.Normal(mu, std).log_prob(a).sum(-1)
+        z = (a - mu) / std
+        d_mu = 1e-5 * torch.clamp(mu.abs(), min=1.0)
+        tol = (z.abs() * (d_mu / std + a.abs() * 2.0 ** -24 / std + z.abs() * 3e-7)).sum(-1) + 1e-6 * (1 + want.abs())
+        err = (info["log_prob"][k].double() - want).abs()
+        assert bool((err <= tol).all()), "step %d: max err %.3g" % (k, float(err.max()))
+
+
+def test_shard_draws_its_slice_of_the_full_batch():
+    from formation_gym import sharding
+    N, G = 9, B
+    full = formation_gym.make_env("formation_hd_env", False, N, num_envs=G, device=DEV)
+    full.seed(1)
+    full.reset()
+    shard, lo, hi = sharding.make_env_shard("formation_hd_env", N, G, seed=1, rank=1, world_size=2, local_rank=0)
+    shard.reset()
+    assert lo > 0 and hi == G
+    a_full = full.rollout_actor(8, _zero_actor(N))[3]["actions"].clone()
+    a_shard = shard.rollout_actor(8, _zero_actor(N))[3]["actions"].clone()
+    assert torch.equal(a_shard, a_full[:, lo:hi])
+
+
+@pytest.mark.parametrize("N", [9, 27])
+def test_determinism_and_log_std_read_in_place(N):
+    env = _env(N)
+    actor = _zero_actor(N)
+    snap = env._snapshot()
+    _, _, _, i1 = _clone(env.rollout_actor(K, actor))
+    env._restore(snap)
+    _, _, _, i2 = _clone(env.rollout_actor(K, actor))
+    assert torch.equal(i1["actions"], i2["actions"]) and torch.equal(i1["log_prob"], i2["log_prob"])
+    bound = dict(env._roll_launchers)
+    with torch.no_grad():
+        actor.log_std.add_(torch.tensor([0.5, -0.25], device=DEV))             # an optimizer step, in place
+    env._restore(snap)
+    _, _, _, i3 = _clone(env.rollout_actor(K, actor))
+    assert dict(env._roll_launchers) == bound, "the same buffers and parameters must reuse the bound launcher"
+    scale = torch.exp(torch.tensor([0.5, -0.25], device=DEV))
+    assert torch.allclose(i3["actions"], i1["actions"] * scale, rtol=1e-6, atol=1e-7)
+    assert torch.allclose(i3["log_prob"], i1["log_prob"] - 0.25, rtol=0, atol=1e-5)
+
+
+def test_noise_statistics():
+    N = 27
+    env = _env(N)
+    eps = env.rollout_actor(K, _zero_actor(N), out=False)[3]["actions"].double()       # [K, B, N, 2]
+    n = eps.numel()
+    x = eps.flatten()
+    assert abs(float(x.mean())) < 5.0 / n ** 0.5
+    assert abs(float(x.var()) - 1.0) < 5.0 * (2.0 / n) ** 0.5
+
+    def lag1(t, dim):
+        a, b = t.narrow(dim, 1, t.shape[dim] - 1).flatten(), t.narrow(dim, 0, t.shape[dim] - 1).flatten()
+        a, b = a - a.mean(), b - b.mean()
+        return float((a * b).sum() / (a.norm() * b.norm())), a.numel()
+    for dim in (0, 1, 2):                                    # step, env, agent
+        c, m = lag1(eps, dim)
+        assert abs(c) < 5.0 / m ** 0.5, (dim, c)
+    c, m = lag1(eps, 3)                                      # the two components of one draw
+    assert abs(c) < 5.0 / m ** 0.5, c
+    other = _env(N, seed=4)
+    eps2 = other.rollout_actor(K, _zero_actor(N), out=False)[3]["actions"].double()
+    assert not bool((eps2 == eps).any())
