@@ -2,7 +2,15 @@
 """Benchmark of the formation_gym hot path on MI355X.
 
     python bench.py --gpus 1 --steps 1000 --warmup 100
+    python bench.py --gpus 1 --steps 1000 --warmup 100 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: it sets up, warms up, times the --steps steps, writes --dump-outputs and
+prints the JSON line.  Everything beside the headline runs only with --full: the other launch mode, the side
+timings of the headline launch (`default_api`, `roofline.frac_unplaced`), the live `roofline.traffic` counter passes,
+the cache-resident buffer, the other shapes and GLOBAL batches, the closed loop, the landmark scenarios, config 1 and
+the CPU baselines.  --no-extra, --no-cpu-baseline, --no-live-traffic, --no-small-buffer, --no-other-configs and
+--quick take items off that list again.
 
 A "step" is one pass of the hot path (MultiAgentEnv.step: _set_action ->
 World.step -> observation/reward/done for every agent) over one batch of B
@@ -34,10 +42,11 @@ block.  With the same arguments the timed steps see the same inputs from run to
 run; `--dump-outputs DIR` writes what the last of them computed (see
 last_step_outputs).
 
-`roofline.traffic` (HBM bytes per launch from the PMC counters) is measured in the same run on the same box at N = 1:
-before this process touches the GPU, two short child runs of the workload under `rocprofv3 --pmc WRITE_SIZE` and
-`--pmc FETCH_SIZE` (`live_traffic`; ~40 s; `--no-live-traffic` or any failure falls back to the figure of the committed
-profile, `profiles/*_<N>x<B>*.json`, which is reported beside it either way).
+`roofline.traffic` (HBM bytes per launch from the PMC counters) is the figure of the committed profile,
+`profiles/*_<N>x<B>*.json`.  With --full it is measured in the same run on the same box at N = 1: before this process
+touches the GPU, two short child runs of the workload under `rocprofv3 --pmc WRITE_SIZE` and `--pmc FETCH_SIZE`
+(`live_traffic`; ~40 s; `--no-live-traffic` or any failure falls back to the committed figure, which is reported beside
+it either way).
 
 Prints ONE JSON line (rank 0).  `value` = env-steps/s over all GPUs.
 """
@@ -123,7 +132,7 @@ def live_traffic(a):
     tmp = tempfile.mkdtemp(prefix="fg_pmc_", dir="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--agents", str(a.agents), "--envs", str(a.envs), "--mode", a.mode,
              "--chunk", str(a.chunk), "--steps", str(2 * a.chunk), "--warmup", str(a.chunk), "--min-timed-ms", "1",
-             "--prewarm-ms", "0", "--no-cpu-baseline", "--no-extra", "--no-live-traffic",
+             "--prewarm-ms", "0", "--full", "--no-cpu-baseline", "--no-extra", "--no-live-traffic",
              "--placement-candidates", str(a.placement_candidates)]
     kib, launches = {}, 0
     try:
@@ -341,38 +350,45 @@ def main():
                     help="step: one fg_step_hd launch per step; rollout: fg_rollout_hd, --chunk steps per launch")
     ap.add_argument("--chunk", type=int, default=20)
     ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="measurements beside the headline: repeat their timed block until this much GPU time has been "
-                         "timed (the headline times exactly --steps steps)")
+                    help="measurements beside the headline (--full): repeat their timed block until this much GPU time has "
+                         "been timed (the headline times exactly --steps steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (observation, rewards, done flags, "
                          "the state after it) as DIR/<name>.npy in float32, at most 64 MB (rank 0's envs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (other mode, side timings of the headline launch, live "
+                         "counter passes, other shapes and GLOBAL batches, closed loop, scenarios, config 1, CPU baselines); "
+                         "the --no-* options below subtract from it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-auto-reset", action="store_true", help="tuning aid: episodes never reset")
     ap.add_argument("--obs-every", type=int, default=1,
                     help="tuning aid (rollout mode): write an observation only every n-th step; the JSON line is "
                          "then NOT a valid benchmark result")
-    ap.add_argument("--no-extra", action="store_true", help="headline workload only (no other mode / shapes / config 1)")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: headline workload only (no other mode / shapes / config 1)")
     ap.add_argument("--no-small-buffer", action="store_true",
-                    help="skip the extra 4-steps-per-launch (Infinity-Cache-sized buffer) measurement")
+                    help="with --full: skip the extra 4-steps-per-launch (Infinity-Cache-sized buffer) measurement")
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="untimed stepping before the W warm-up steps, so that short runs are not measured during the clock ramp")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of the other BASELINE shapes")
+                    help="with --full: skip the short runs of the other BASELINE shapes")
     ap.add_argument("--obs-pitch", type=int, default=0,
                     help="rollout mode: floats between consecutive envs' observation blocks in the rollout buffer "
                          "(0 = contiguous 6 N^2; -1 = 6 N^2 rounded up to 32 floats = whole 128-byte lines per env)")
     ap.add_argument("--global-div", type=int, default=1,
-                    help="test aid: run the GLOBAL-batch configs (BASELINE configs[3], [4]) with their batch sizes divided "
-                         "by this, whatever the headline shape is (the lines are marked)")
+                    help="test aid (with --full): run the GLOBAL-batch configs (BASELINE configs[3], [4]) with their batch sizes "
+                         "divided by this, whatever the headline shape is (the lines are marked)")
     ap.add_argument("--placement-candidates", type=int, default=8,
                     help="observation buffers beyond the Infinity Cache: allocate up to this many candidates, time the launch "
                          "on each, keep the fastest (formation_gym/placement.py); 1 = no probe")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed profile instead of two rocprofv3 --pmc child runs on this box "
-                         "(implied by --no-extra, by more than one rank, and when this process runs under a profiler)")
+                         "(implied without --full, by --no-extra, by more than one rank, and when this process runs under a "
+                         "profiler)")
     ap.add_argument("--quick", action="store_true",
-                    help="perf gate: the headline workload only (no other modes / shapes / scenarios, no CPU baseline, no counter "
-                         "passes), ~15 s; with --max-ms-per-step the exit code says whether the rate held")
+                    help="perf gate: the headline workload only, also with --full (no other modes / shapes / scenarios, no CPU "
+                         "baseline, no counter passes), ~15 s; with --max-ms-per-step the exit code says whether the rate "
+                         "held")
     ap.add_argument("--max-ms-per-step", type=float, default=0.0,
                     help="exit with status 3 (after printing the JSON line) when ms_per_step exceeds this")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -380,7 +396,7 @@ def main():
     a = ap.parse_args()
     if a.dump_outputs and a.obs_every != 1:
         ap.error("--dump-outputs needs every observation written (--obs-every 1)")
-    if a.quick:
+    if a.quick or not a.full:
         a.no_extra = a.no_cpu_baseline = a.no_live_traffic = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -688,7 +704,8 @@ def main():
             last["pos"], last["vel"] = env.world.get_state()
             dumped = last_step_outputs(last)
         side = {}
-        if mode == "rollout" and not policy and a.obs_every == 1 and placed.get("rollout", {}).get("probed") and chunk <= P:
+        if a.full and mode == "rollout" and not policy and a.obs_every == 1 and placed.get("rollout", {}).get("probed") \
+                and chunk <= P:
             # beside the timed series (never `value`): the same launch (a) into an ORDINARY allocation - what the round-3
             # default API gave - and (b) through the documented default API, env.rollout(action_seq) with no buffers passed,
             # which places its own buffer on first use
@@ -928,7 +945,7 @@ def main():
                                    "episode 100 with device auto-reset" % (N, B),
                        "baseline_config": "BASELINE.json configs[2] (27 agents x 4096 envs, the shape the north-star target "
                                           "is quoted on); configs[1] and the per-GPU shapes of configs[3], configs[4] are "
-                                          "under other_configs at N = 1, their GLOBAL batches under global_configs"
+                                          "under other_configs at N = 1, their GLOBAL batches under global_configs (--full)"
                                           if headline else "custom shape",
                        "agents": N, "envs_per_gpu": B, "global_envs": B * world_size, "mode": a.mode,
                        "parallelism": "env-batch sharded over %d GPU(s), no collective" % world_size,

@@ -2,7 +2,7 @@
 # A/B helper: ab.sh "<agents> <envs> <T,E> <steps> <chunk> <writer>" ...   (prints one line per config)
 for cfg in "$@"; do
   set -- $cfg
-  FG_FLAT=$6 FG_GEOM=$3 python bench.py --agents $1 --envs $2 --steps $4 --warmup 20 --chunk $5 --no-cpu-baseline 2>/dev/null | \
+  FG_FLAT=$6 FG_GEOM=$3 python bench.py --agents $1 --envs $2 --steps $4 --warmup 20 --chunk $5 --full --no-cpu-baseline 2>/dev/null | \
     python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())

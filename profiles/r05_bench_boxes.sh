@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # One short headline bench (placed buffer, probe with escalation) in a FRESH process on whatever box the call lands on; run several times
 # from the build container:  for i in 1 2 3 ...; do gpurun -- 'bash profiles/r05_bench_boxes.sh'; done  -> one line per box
-python3 bench.py --no-cpu-baseline --no-extra --no-live-traffic 2>/dev/null | python3 -c "
+python3 bench.py --full --no-cpu-baseline --no-extra --no-live-traffic 2>/dev/null | python3 -c "
 import json, sys, socket
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 p = d['placement']['rollout']

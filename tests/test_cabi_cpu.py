@@ -211,6 +211,17 @@ def test_bench_cli_and_cpp_example_build(tmp_path):
     assert os.path.getsize(exe) > 0
 
 
+def test_bench_lists_its_full_option():
+    """Everything beside the headline sits behind `bench.py --full` (a plain run is the headline alone)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0
+    assert "--full" in out.stdout and "--quick" in out.stdout
+
+
 def test_observation_pitch_detection_is_host_logic():
     """Scenario.obs_env_pitch: which observation tensors the kernels can be told about (contiguous -> 0, a uniform even
     env pitch >= 6 N^2 -> that pitch, anything else refused).  Pure stride arithmetic: runs on CPU tensors."""

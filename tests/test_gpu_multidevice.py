@@ -154,7 +154,7 @@ def test_two_rank_processes_on_distinct_devices_with_the_rccl_barrier(tmp_path):
     np.testing.assert_array_equal(r["pos_x"], whole.world.pos_x.cpu().numpy())
     line = [l for l in _run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                              "127.0.0.1", "--master-port", _free_port(), "bench.py", "--gpus", "2", "--steps", "20",
-                             "--warmup", "5", "--envs", "512", "--agents", "27", "--no-cpu-baseline", "--global-div", "32",
+                             "--warmup", "5", "--envs", "512", "--agents", "27", "--full", "--no-cpu-baseline", "--global-div", "32",
                              "--min-timed-ms", "5"], env_extra={"HSA_ENABLE_IPC_MODE_LEGACY": "0"},
                             timeout=600).splitlines() if l.startswith("{")]
     assert len(line) == 1

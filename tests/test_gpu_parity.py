@@ -516,7 +516,7 @@ def test_bench_json_contract_single_and_two_ranks():
     """bench.py prints ONE JSON line with the contract keys; the 2-rank path (barrier, MAX over
     ranks, sharded seeds, GLOBAL-batch configs) is exercised with two gloo ranks sharing this GPU."""
     import json
-    line = [l for l in _run(["bench.py", "--steps", "30", "--warmup", "5", "--envs", "512", "--agents", "9",
+    line = [l for l in _run(["bench.py", "--steps", "30", "--warmup", "5", "--envs", "512", "--agents", "9", "--full",
                              "--no-cpu-baseline", "--global-div", "64"]).splitlines() if l.startswith("{")]
     assert len(line) == 1
     d = json.loads(line[0])
@@ -544,7 +544,7 @@ def test_bench_json_contract_single_and_two_ranks():
     assert abs(d["roofline"]["achieved"] - alg / (t["block_ms_median"] * 1e-3) / 1e9) < 1e-3 * d["roofline"]["achieved"] + 0.1
     out = _run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", _free_port(), "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--envs", "256",
-                "--agents", "9", "--backend", "gloo", "--no-cpu-baseline", "--global-div", "64", "--min-timed-ms", "5"])
+                "--agents", "9", "--backend", "gloo", "--full", "--no-cpu-baseline", "--global-div", "64", "--min-timed-ms", "5"])
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
     d2 = json.loads(line[0])
@@ -604,6 +604,34 @@ def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
     assert np.isfinite(a["obs"]).all() and np.isfinite(a["pos"]).all() and (a["obs"] != 0).any()
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline workload timed as with --full (one series of
+    exactly N steps), and nothing beside it - no other mode, no side timings of the headline launch, no counter passes,
+    no other shapes, scenarios or CPU baselines."""
+    import json
+    import time
+    t0 = time.perf_counter()
+    line = [l for l in _run(["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]).splitlines() if l.startswith("{")]
+    elapsed = time.perf_counter() - t0
+    assert len(line) == 1
+    d = json.loads(line[0])
+    assert d["metric"] == "env-steps/sec" and d["unit"] == "env-steps/s" and d["higher_is_better"] and d["dtype"] == "f32"
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["state_finite"] and d["value"] > 0
+    t = d["timing"]
+    assert t["timed_steps"] == 20 and t["blocks"] == 1
+    assert abs(d["ms_per_step"] * 20 - t["block_ms_median"]) < 1e-3 * t["block_ms_median"] + 1e-5
+    assert d["config"]["agents"] == 27 and d["config"]["envs_per_gpu"] == 4096 and d["config"]["mode"] == "rollout"
+    for k in ("other_mode", "default_api", "rollout_cache_resident_buffer", "other_configs", "closed_loop_policy",
+              "global_configs", "config1", "other_scenarios", "cpu_baseline", "cpu_baseline_other_shapes"):
+        assert k not in d, k
+    r = d["roofline"]
+    assert "frac_unplaced" not in r and "traffic_live_error" not in r and "traffic_committed_profile" not in r
+    assert not str(r.get("traffic_source") or "").startswith("live")
+    # the --full run of the same arguments spends ~80 s beside its steps; the plain one a few seconds of set-up
+    print("plain bench run: %.1f s" % elapsed)
+    assert elapsed < 90, elapsed
+
+
 def test_bench_many_ranks_share_the_gpu():
     """A rehearsal of the multi-GPU launch with as many ranks as this pool lets one GPU carry (its process guard allows six
     GPU processes of ours at once: this test's own + 4 ranks; the 8-rank case is the driver's to run on an 8-GPU node):
@@ -613,7 +641,7 @@ def test_bench_many_ranks_share_the_gpu():
     import json
     out = _run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                 "--master-port", _free_port(), "bench.py", "--gpus", "4", "--steps", "20", "--warmup", "5", "--envs", "256",
-                "--agents", "27", "--backend", "gloo", "--no-cpu-baseline", "--global-div", "64", "--min-timed-ms", "5"],
+                "--agents", "27", "--backend", "gloo", "--full", "--no-cpu-baseline", "--global-div", "64", "--min-timed-ms", "5"],
                timeout=600)
     line = [l for l in out.splitlines() if l.startswith("{")]
     assert len(line) == 1
