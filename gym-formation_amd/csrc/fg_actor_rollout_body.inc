@@ -1,6 +1,8 @@
-// fg_actor_rollout_body.inc - the one body of actor_rollout_kernel and actor_sample_kernel (fg_actor_rollout_kernel.hpp).
-// Included inside each kernel, whose scope provides the kernel arguments `a` (Args) and `w` (ActorW), the template
-// parameters NC and H, `constexpr bool SAMPLE` and `log_std` / `logp` (SAMPLE = false: nullptr).  Not a header: no guard.
+// fg_actor_rollout_body.inc - the one body of actor_rollout_kernel, actor_sample_kernel, pa_actor_kernel and pa_sample_kernel
+// (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
+// (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
+// `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
+// (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  Not a header: no guard.
 //
 // Why a textual include and not a force-inlined __device__ function: behind a function boundary the kernel arguments reach
 // the body through a by-value copy, and even inlined early the copy changes how the arguments are loaded and the order in
@@ -12,14 +14,19 @@
     constexpr int NPS = NP <= 16 ? NP : 0;
     constexpr int D = 6 * N;                           // actor input width
     constexpr int HS = actor_hstride(H), CB = H / 16, RT = FG_ACTOR_ROWS / 16, NW = FG_ACTOR_THREADS / 64;
-    constexpr int TILES = (E * N + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
+    // PER_AGENT: the actor rows are agent-major - agent r owns rows r EP .. r EP + EP - 1, the workgroup's envs padded to
+    // EP >= 16 - so that every 16-row MFMA tile holds one agent and takes that agent's weights as its B operand
+    constexpr int EP = E >= 16 ? E : 16;
+    constexpr int TILES = ((PER_AGENT ? EP * N : E * N) + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
+    constexpr int WS = PER_AGENT ? 0 : 4 * H;           // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
+    static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
     float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
     float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + 4 * H + 4;
+    float* const hbuf = wsm + WS + 4;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -35,15 +42,17 @@
     float* const QY = QX + NP; float* const PX = QY + NP; float* const PY = PX + NP;
     float* const SX = PY + NP; float* const SY = SX + NP;
 
-    for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
-        wsm[q] = w.b1 ? w.b1[q] : 0.f;
-        wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
-        wsm[2 * H + q] = w.w3[q];
-        wsm[3 * H + q] = w.w3[H + q];
+    if constexpr (!PER_AGENT) {
+        for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
+            wsm[q] = w.b1 ? w.b1[q] : 0.f;
+            wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
+            wsm[2 * H + q] = w.w3[q];
+            wsm[3 * H + q] = w.w3[H + q];
+        }
+        if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
     }
-    if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
     if constexpr (SAMPLE) {
-        if (tid < 2) wsm[4 * H + 2 + tid] = log_std[tid];
+        if (tid < 2) wsm[WS + 2 + tid] = log_std[tid];
     }
 
     const float one_minus_damp = 1.0f - a.p.damping;
@@ -89,14 +98,26 @@
             int r_of[RT];
             float2 pr[RT];
             bool row_ok[RT];
+            int ra[RT];                                // PER_AGENT: the agent of each tile (wave-uniform)
+            // (the table's pointers reach the kernel as generic pointers: cast to the global address space, so that the loads
+            // are global_load with a scalar base instead of flat loads with a 64-bit address per lane)
+            using gfloat = const __attribute__((address_space(1))) float;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const int q = q0 + rt * 16 + col;
-                row_ok[rt] = q < M;
-                const int qq = row_ok[rt] ? q : 0;
-                const int ee = qq / N;
-                r_of[rt] = qq - ee * N;
-                AT[rt] = reinterpret_cast<const float2*>(smemf + ee * env_block_floats(N));
+                if constexpr (PER_AGENT) {
+                    ra[rt] = min((q0 + rt * 16) / EP, N - 1);
+                    const int ee = q % EP;
+                    row_ok[rt] = ee < El && q / EP < N;
+                    r_of[rt] = ra[rt];
+                    AT[rt] = reinterpret_cast<const float2*>(smemf + (row_ok[rt] ? ee : 0) * env_block_floats(N));
+                } else {
+                    row_ok[rt] = q < M;
+                    const int qq = row_ok[rt] ? q : 0;
+                    const int ee = qq / N;
+                    r_of[rt] = qq - ee * N;
+                    AT[rt] = reinterpret_cast<const float2*>(smemf + ee * env_block_floats(N));
+                }
                 pr[rt] = AT[rt][r_of[rt]];
             }
             // observation unit u of row r (as write_obs_rows stores it): 0 velocity, 1 .. N-1 p_j - p_r (j skips r),
@@ -113,27 +134,64 @@
             };
             f32x4 acc[RT][CB];
             // ---- layer 1: relative positions and velocity (k < 2N), then ideal shape and velocity (k >= 4N - 2) ----
+            // PER_AGENT: each tile its own agent's bias and weight rows (the same two agents for the whole pass)
+            auto bias_init = [&](int layer) {
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) {
+                        gfloat* const bv = (gfloat*)(layer == 1 ? tab.b1[ra[rt]] : tab.b2[ra[rt]]);
+                        const float bias = bv ? bv[cb * 16 + col] : 0.f;
+                        acc[rt][cb] = (f32x4){bias, bias, bias, bias};
+                    }
+            };
+            if constexpr (PER_AGENT) {
+                bias_init(1);
+            } else {
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
                 const float bias = wsm[cb * 16 + col];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
             }
+            }
             // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would all
             // be held in registers)
             const float* w1row = w.w1 + (size_t)col * D;
+            // PER_AGENT: each tile's agent's weights, scalar bases; the lane's row offset is made opaque per k chunk, so that
+            // the fragments of later chunks are not all loaded ahead into registers
+            gfloat* w1pa[RT];
+            if constexpr (PER_AGENT) {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) w1pa[rt] = (gfloat*)tab.w1[ra[rt]];
+            } else {
             asm volatile("" : "+v"(w1row));
+            }
             auto l1_chunk = [&](int ks) {
                 const int k = ks * 4 + kq;
+                int ro = 0;
+                if constexpr (PER_AGENT) {
+                    ro = col * D;
+                    asm volatile("" : "+v"(ro));
+                }
                 float xa[RT];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) xa[rt] = x_in(rt, k);
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
+                    if constexpr (PER_AGENT) {
+                        float wb[RT];
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt) wb[rt] = k < D ? w1pa[rt][ro + cb * 16 * D + k] : 0.f;
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt)
+                            acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb[rt], acc[rt][cb], 0, 0, 0);
+                    } else {
                     const float wb = k < D ? w1row[cb * 16 * D + k] : 0.f;
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt)
                         acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
+                    }
                 }
             };
             constexpr int KA = (2 * N + 3) / 4, KB0 = (4 * N - 2) / 4, KB1 = (D + 3) / 4;
@@ -155,26 +213,50 @@
             store_tile();
             WaveSync()();
             // ---- layer 2 ----
+            if constexpr (PER_AGENT) {
+                bias_init(2);
+            } else {
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {
                 const float bias = wsm[H + cb * 16 + col];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
             }
+            }
             const float* w2row = w.w2 + (size_t)col * H;
+            gfloat* w2pa[RT];
+            if constexpr (PER_AGENT) {
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) w2pa[rt] = (gfloat*)tab.w2[ra[rt]];
+            } else {
             asm volatile("" : "+v"(w2row));
+            }
 #pragma unroll 2
             for (int ks = 0; ks < H / 4; ++ks) {
                 const int k = ks * 4 + kq;
+                int ro = 0;
+                if constexpr (PER_AGENT) {
+                    ro = col * H;
+                    asm volatile("" : "+v"(ro));
+                }
                 float xa[RT];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
+                    if constexpr (PER_AGENT) {
+                        float wb[RT];
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt) wb[rt] = w2pa[rt][ro + cb * 16 * H + k];
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt)
+                            acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb[rt], acc[rt][cb], 0, 0, 0);
+                    } else {
                     const float wb = w2row[cb * 16 * H + k];
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt)
                         acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
+                    }
                 }
             }
             WaveSync()();                              // every read of the layer-1 tile before it is overwritten
@@ -184,12 +266,33 @@
             {
                 const int row = lane >> 1, o = lane & 1;
                 const float* const hr = hb + row * HS;
+                float y;
+                if constexpr (PER_AGENT) {             // the row's tile's agent, through L1
+                    gfloat* const b3 = (gfloat*)(row < 16 ? tab.b3[ra[0]] : tab.b3[ra[1]]);
+                    gfloat* const w3 = (gfloat*)(row < 16 ? tab.w3[ra[0]] : tab.w3[ra[1]]) + o * H;
+                    y = b3 ? b3[o] : 0.f;
+#pragma unroll 8
+                    for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
+                } else {
                 const float* const w3 = wsm + 2 * H + o * H;
-                float y = wsm[4 * H + o];
+                y = wsm[4 * H + o];
 #pragma unroll 8
                 for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
+                }
                 if (w.out_tanh) y = tanhf(y);
                 const int q = q0 + row;
+                if constexpr (PER_AGENT) {
+                    // the row's env and agent (agent-major rows), whether it is one of this workgroup's, its env-major slot
+                    const int ee = q % EP, r = q / EP, slot = ee * N + r;
+                    const bool ok = ee < El && r < N;
+                    if constexpr (SAMPLE) {            // actor_sample_kernel's draw of (env, agent)
+                        const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)r, off);
+                        const float ls0 = wsm[WS + 2], ls1 = wsm[WS + 3];
+                        y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
+                        if (ok && o == 0) logp_lds[slot] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
+                    }
+                    if (ok) reinterpret_cast<float*>(act_lds)[2 * slot + o] = y;
+                } else {
                 if constexpr (SAMPLE) {
                     // both lanes of a row draw the row's pair: lane o adds component o and lane 0 keeps the log-density
                     const int ee = q / N;
@@ -199,6 +302,7 @@
                     if (q < M && o == 0) logp_lds[q] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
                 }
                 if (q < M) reinterpret_cast<float*>(act_lds)[2 * q + o] = y;
+                }
             }
             WaveSync()();                              // the tile is free for the next pass
         }

@@ -23,6 +23,14 @@
 // actor_sample_kernel<N,H> (fg_rollout_hd_actor_sample) is the same body with a state-independent diagonal Gaussian on top of
 // the actor's output: each lane (row, o) of layer 3 adds exp(log_std[o]) * eps[o], eps = actor_eps(...) drawn from the
 // counter stream of the step that takes the action, and each row's log-density goes out with the action.
+//
+// pa_actor_kernel<N,H> / pa_sample_kernel<N,H> (fg_rollout_hd_actor_per_agent) are the same body with one actor per agent
+// (MADDPG-style): agent i's observation rows go through agent i's parameters.  The actor rows are taken agent-major - agent r
+// owns the rows r EP .. r EP + EP - 1, EP = max(E, 16), one per env of the workgroup - so that each 16-row MFMA tile belongs
+// to one agent, whose weight base pointers come from the by-value table `ActorTab` in the kernel arguments (wave-uniform
+// index: scalar loads).  Biases and W3 are read through L1 instead of LDS (4H + 2 floats per agent, 66 KB at 32 x 128).
+// At E = 8 (N > 16) the tiles are half full.  Same instructions in the same k order per output element as the shared
+// kernels: N identical members give their bits.
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -41,20 +49,29 @@ struct ActorW {
     int out_tanh;
 };
 
+// one actor per agent (pa_*_kernel): agent i's parameters; entries at i >= N are never read
+constexpr int FG_ACTOR_MAX_AGENTS = 32;
+struct ActorTab {
+    const float* w1[FG_ACTOR_MAX_AGENTS]; const float* b1[FG_ACTOR_MAX_AGENTS];
+    const float* w2[FG_ACTOR_MAX_AGENTS]; const float* b2[FG_ACTOR_MAX_AGENTS];
+    const float* w3[FG_ACTOR_MAX_AGENTS]; const float* b3[FG_ACTOR_MAX_AGENTS];
+    int out_tanh;
+};
+
 constexpr int FG_ACTOR_THREADS = 256;
 constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-row MFMA tiles
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
 __host__ __device__ constexpr int actor_envs(int n) { return FG_ACTOR_THREADS / actor_lanes(n); }
 __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // row pitch of the activation tile: 16 rows x 4 k conflict-free
 // LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
-//               b1 [H] b2 [H] W3 [2][H] b3 [2] (SAMPLE: log_std [2], else padding) | activations [4][32][H + 4]
+//               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) | activations [4][32][H + 4]
 // (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
-template <int NC, int H, bool SAMPLE = false> constexpr int actor_lds_floats() {
-    return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + 4 * H + 4 +
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false> constexpr int actor_lds_floats() {
+    return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
            (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H);
 }
-template <int NC, int H, bool SAMPLE = false> constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE>() * (int)sizeof(float);
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false> constexpr int actor_lds_bytes() {
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -78,7 +95,8 @@ __global__ __launch_bounds__(256) void actor_noise_kernel(const KParams p, int B
 // SAMPLE = false: the deterministic actor.
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const Args a, const ActorW w) {
-    constexpr bool SAMPLE = false;
+    constexpr bool SAMPLE = false, PER_AGENT = false;
+    constexpr ActorTab tab{};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
 #include "fg_actor_rollout_body.inc"
@@ -88,7 +106,27 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const A
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Args a, const ActorW w, const float* log_std,
                                                                          float* logp) {
-    constexpr bool SAMPLE = true;
+    constexpr bool SAMPLE = true, PER_AGENT = false;
+    constexpr ActorTab tab{};
+#include "fg_actor_rollout_body.inc"
+}
+
+// PER_AGENT = true: agent i evaluates tab's actor i (the deterministic actor).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_actor_kernel(const Args a, const ActorTab tab) {
+    constexpr bool SAMPLE = false, PER_AGENT = true;
+    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// PER_AGENT = true, SAMPLE = true: the per-agent means with actor_sample_kernel's Gaussian (one log_std [2] for all agents).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args a, const ActorTab tab, const float* log_std,
+                                                                      float* logp) {
+    constexpr bool SAMPLE = true, PER_AGENT = true;
+    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
 #include "fg_actor_rollout_body.inc"
 }
 

@@ -1514,15 +1514,78 @@ static int actor_dispatch(const Args& a, const FgActor& actor, const float* log_
     return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
 }
 
+// ---- one actor per agent (pa_actor_kernel / pa_sample_kernel) ----
+// log_std == NULL: pa_actor_kernel (deterministic); else pa_sample_kernel (the Gaussian on top of the per-agent means)
+template <int NC, int H>
+static int launch_pa_v(const Args& a, const ActorTab& tab, const float* log_std, float* logp, hipStream_t st) {
+    const bool sample = log_std != nullptr;
+    constexpr int E = actor_envs(NC);
+    const int lds = sample ? actor_lds_bytes<NC, H, true, true>() : actor_lds_bytes<NC, H, false, true>();
+    static_assert(actor_lds_bytes<NC, H, true, true>() <= 160 * 1024, "per-agent actor rollout LDS");
+    const int grid = (a.B + E - 1) / E;
+    if (describe("%s<%d,%d> grid %d block %d envs/wg %d lds %d; ", sample ? "pa_sample_kernel" : "pa_actor_kernel",
+                 NC, H, grid, FG_ACTOR_THREADS, E, lds))
+        return FG_OK;
+    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
+    hipError_t err = sample ? raise_lds_limit((const void*)&pa_sample_kernel<NC, H>, lds, &raised_sample)
+                            : raise_lds_limit((const void*)&pa_actor_kernel<NC, H>, lds, &raised);
+    if (err == hipSuccess) {
+        if (sample)
+            hipLaunchKernelGGL((pa_sample_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, tab, log_std, logp);
+        else
+            hipLaunchKernelGGL((pa_actor_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, tab);
+        err = hipGetLastError();
+    }
+    if (err != hipSuccess) return fail(FG_ERR_HIP, "per-agent actor rollout launch failed: %s", hipGetErrorString(err));
+    return FG_OK;
+}
+// actor_check on every member, then: every member has member 0's hidden width and tanh flag (no device touched)
+static int actor_per_agent_check(const FgParams* params, const FgActor* actors, int B, int N, int K) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: B >= 0 and K >= 1 required%s");
+    if (!actor_n_supported(N))
+        return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    if (!actors) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
+    char idx[16];
+    for (int i = 0; i < N; ++i) {
+        if ((rc = actor_check(params, &actors[i], B, N, K)) != FG_OK) return rc;
+        if (actors[i].hidden != actors[0].hidden || (actors[i].out_tanh != 0) != (actors[0].out_tanh != 0)) {
+            snprintf(idx, sizeof(idx), "%d", i);
+            return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
+                        idx);
+        }
+    }
+    return FG_OK;
+}
+static int actor_per_agent_dispatch(const Args& a, const FgActor* actors, const float* log_std, float* logp, hipStream_t st) {
+    ActorTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int i = 0; i < a.N; ++i) {
+        tab.w1[i] = actors[i].w1; tab.b1[i] = actors[i].b1; tab.w2[i] = actors[i].w2;
+        tab.b2[i] = actors[i].b2; tab.w3[i] = actors[i].w3; tab.b3[i] = actors[i].b3;
+    }
+    tab.out_tanh = actors[0].out_tanh ? 1 : 0;
+    const int hidden = actors[0].hidden;
+#define FG_ACTOR(NN) \
+    if (a.N == NN) return hidden == 32 ? launch_pa_v<NN, 32>(a, tab, log_std, logp, st) \
+                        : hidden == 64 ? launch_pa_v<NN, 64>(a, tab, log_std, logp, st)  \
+                                       : launch_pa_v<NN, 128>(a, tab, log_std, logp, st);
+    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
+#undef FG_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+}
+
 extern "C" {
 
 }  // extern "C"
 
+// per_agent: `actor` is a host array of N members (actor_per_agent_dispatch), else the one shared actor
 static int rollout_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
-                              int obs_every, void* stream) {
+                              int obs_every, void* stream, bool per_agent = false) {
     if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
     if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
@@ -1538,6 +1601,7 @@ static int rollout_actor_impl(const FgParams* params, const FgActor* actor, cons
     a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
     a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
     a.act_out = act_seq;
+    if (per_agent) return actor_per_agent_dispatch(a, actor, log_std, logp_seq, (hipStream_t)stream);
     return actor_dispatch(a, *actor, log_std, logp_seq, (hipStream_t)stream);
 }
 
@@ -1567,6 +1631,24 @@ int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, con
                               step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream);
 }
 
+int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N, int K,
+                                  float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                                  float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                  float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                  int obs_every, void* stream) {
+    int rc = actor_per_agent_check(params, actors, B, N, K);
+    if (rc) return rc;
+    if (log_std) {
+        if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
+        if ((uintptr_t)logp_seq & 3u)
+            return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_per_agent: logp_seq must be 4-byte aligned%s");
+    } else {
+        logp_seq = nullptr;
+    }
+    return rollout_actor_impl(params, actors, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
+                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream, true);
+}
+
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1586,14 +1668,15 @@ int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* strea
 }  // extern "C"
 
 static int describe_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
-                               int obs_every, char* out, int out_len) {
+                               int obs_every, char* out, int out_len, bool per_agent = false) {
     if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
     Args a; memset(&a, 0, sizeof(a));
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
     int rc = set_obs_pitch(&a);
     if (rc != FG_OK) return rc;
     g_describe = out; g_describe_cap = out_len;
-    rc = actor_dispatch(a, *actor, log_std, nullptr, nullptr);
+    rc = per_agent ? actor_per_agent_dispatch(a, actor, log_std, nullptr, nullptr)
+                   : actor_dispatch(a, *actor, log_std, nullptr, nullptr);
     g_describe = nullptr; g_describe_cap = 0;
     return rc;
 }
@@ -1617,6 +1700,16 @@ int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor
     if (rc) return rc;
     if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
     return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
+                                      int K, int obs_every, char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_per_agent_launch: out buffer required%s");
+    out[0] = 0;
+    int rc = actor_per_agent_check(params, actors, B, N, K);
+    if (rc) return rc;
+    if (log_std && (rc = actor_sample_check(log_std)) != FG_OK) return rc;
+    return describe_actor_impl(params, actors, log_std, B, N, K, obs_every, out, out_len, true);
 }
 
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,

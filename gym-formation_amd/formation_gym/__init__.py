@@ -18,7 +18,7 @@ import os.path as osp
 from .environment import MultiAgentEnv
 from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
-from .actor_rollout import GaussianActor  # noqa: F401
+from .actor_rollout import GaussianActor, PerAgentActor  # noqa: F401
 
 __all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor"]
 

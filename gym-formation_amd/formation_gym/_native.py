@@ -147,6 +147,8 @@ SIGNATURES = {
     "fg_rollout_hd_actor_sample": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),
     "fg_actor_noise": (_I, [_PP, _I, _I, _P, _P]),
     "fg_describe_actor_sample_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),
+    "fg_describe_actor_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
 }
 
 _lib = None

@@ -8,7 +8,10 @@ with H in {32, 64, 128}, fp32 contiguous parameters on the env's device (a None 
 post_step_callback.  Anything else runs host-paced: a shape or option the kernel cannot honour never runs fused.
 
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
-log_std is a contiguous fp32 [2] tensor on the env's device."""
+log_std is a contiguous fp32 [2] tensor on the env's device.
+
+A `PerAgentActor(actors)` gives every agent its own network (MADDPG-style): it fuses (`fg_rollout_hd_actor_per_agent`)
+when it holds N members that each fuse as above with one H and one tanh flag, alone or as the mean of a GaussianActor."""
 import math
 
 import torch
@@ -45,6 +48,32 @@ def actor_spec(actor, num_agents, device=None):
         if not _on_device(t, dev):
             return None
     return H, len(mods) == 6, params
+
+
+class PerAgentActor(torch.nn.Module):
+    """One actor per agent (no parameter sharing): `actors[i]` maps agent i's observation rows [..., 6N] to its actions
+    [..., 2].  `forward(obs [..., N, 6N])` returns [..., N, 2] with out[..., i, :] = actors[i](obs[..., i, :]), which is
+    what the host-paced loop runs and what the fused kernel computes."""
+
+    def __init__(self, actors):
+        super().__init__()
+        self.actors = torch.nn.ModuleList(actors)
+
+    def forward(self, obs):
+        if obs.shape[-2] != len(self.actors):
+            raise ValueError("obs has %d agents, the actor %d" % (obs.shape[-2], len(self.actors)))
+        return torch.stack([a(obs[..., i, :]) for i, a in enumerate(self.actors)], dim=-2)
+
+
+def per_agent_spec(actor, num_agents, device=None):
+    """(hidden, out_tanh, [[w1, b1, w2, b2, w3, b3] per agent]) when the fused kernel can evaluate the PerAgentActor `actor`
+    for `num_agents` agents, else None: N members, each passing actor_spec, all with the same H and tanh flag."""
+    if not isinstance(actor, PerAgentActor) or len(actor.actors) != int(num_agents):
+        return None
+    specs = [actor_spec(a, num_agents, device) for a in actor.actors]
+    if any(s is None for s in specs) or len({(s[0], s[1]) for s in specs}) != 1:
+        return None
+    return specs[0][0], specs[0][1], [s[2] for s in specs]
 
 
 class GaussianActor(torch.nn.Module):
@@ -90,11 +119,12 @@ def _on_device(t, device):
 
 def sample_spec(actor, num_agents, device=None):
     """(actor_spec(actor.mean, ...), log_std) when the fused kernel can sample from the GaussianActor `actor` for
-    `num_agents` agents, else None: its mean fuses (actor_spec) and log_std is a contiguous fp32 [2] tensor on `device`
+    `num_agents` agents, else None: its mean fuses (actor_spec; per_agent_spec for a PerAgentActor mean) and log_std is a contiguous fp32 [2] tensor on `device`
     (None: not checked).  log_std is the actor's own parameter, read in place by every launch."""
     if not isinstance(actor, GaussianActor):
         return None
-    spec = actor_spec(actor.mean, num_agents, device)
+    mean_spec = per_agent_spec if isinstance(actor.mean, PerAgentActor) else actor_spec
+    spec = mean_spec(actor.mean, num_agents, device)
     ls = actor.log_std
     if spec is None or not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) \
             or not ls.is_contiguous() or not _on_device(ls, device):
@@ -111,4 +141,6 @@ def actor_path(actor, num_agents, device=None, fused_scenario=True, continuous=T
         return "host"
     if isinstance(actor, GaussianActor):
         return "fused" if sample_spec(actor, num_agents, device) is not None else "host"
+    if isinstance(actor, PerAgentActor):
+        return "fused" if per_agent_spec(actor, num_agents, device) is not None else "host"
     return "fused" if actor_spec(actor, num_agents, device) is not None else "host"

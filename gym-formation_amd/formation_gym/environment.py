@@ -385,7 +385,9 @@ class MultiAgentEnv(object):
         either path and for a shard as for its slice of the full batch), and info['log_prob'] [K, B, N] holds
         -(eps_0^2 + eps_1^2) / 2 - sum(log_std) - log(2 pi), the log-density of each action.  `out` may carry 'log_prob'.
         It fuses (`fg_rollout_hd_actor_sample`) when its mean would and log_std is a contiguous fp32 [2] tensor on the env's
-        device, read in place like the weights."""
+        device, read in place like the weights.
+        A `PerAgentActor([actor_0, ..., actor_{N-1}])` gives agent i its own network, alone or as a GaussianActor's mean; it
+        fuses (`fg_rollout_hd_actor_per_agent`) when every member would, with one H and one tanh flag."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
@@ -397,8 +399,12 @@ class MultiAgentEnv(object):
         log_std = None
         if gaussian:
             (hidden, out_tanh, weights), log_std = actor_rollout.sample_spec(actor, self.num_agents, self.world.device)
+        elif isinstance(actor, actor_rollout.PerAgentActor):
+            hidden, out_tanh, weights = actor_rollout.per_agent_spec(actor, self.num_agents, self.world.device)
         else:
             hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device)
+        per_agent = bool(weights) and isinstance(weights[0], list)      # per_agent_spec: one weight list per agent
+        flat = [t for ws in weights for t in ws] if per_agent else weights
         B, N = self.num_envs, self.num_agents
         D = self._out["obs"].shape[-1]
         f = dict(dtype=torch.float32, device=self._act.device)
@@ -420,7 +426,7 @@ class MultiAgentEnv(object):
         # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
         key = None
         if own_buffers and all(k in out for k in want):
-            key = ("actor", K, hidden, bool(out_tanh), tuple(0 if t is None else t.data_ptr() for t in weights),
+            key = ("actor", K, hidden, bool(out_tanh), per_agent, tuple(0 if t is None else t.data_ptr() for t in flat),
                    0 if log_std is None else log_std.data_ptr(),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),

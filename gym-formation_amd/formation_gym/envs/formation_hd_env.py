@@ -268,9 +268,13 @@ class Scenario(BaseScenario):
         `actor_rollout.actor_spec`; the kernel reads those tensors in place at every launch, and the launcher keeps them
         alive.  out["act"] [K,B,N,2] receives the actions taken, the other tensors are those of `rollout_batch`.
         log_std [2] (a GaussianActor's, read in place like the weights): the sampling launch
-        (`fg_rollout_hd_actor_sample`), with the actions' log-densities in out["log_prob"] [K,B,N]."""
+        (`fg_rollout_hd_actor_sample`), with the actions' log-densities in out["log_prob"] [K,B,N].
+        spec from `actor_rollout.per_agent_spec` (one weight list per agent): `fg_rollout_hd_actor_per_agent`, agent i's rows
+        through agent i's weights, every member's tensors kept alive."""
         lib = _native.load()
         hidden, out_tanh, weights = spec
+        if weights and isinstance(weights[0], list):
+            return self._bind_rollout_actor_per_agent(lib, world, K, spec, out, obs_every, auto_reset, log_std)
         fa = _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in weights])
         p = self.params(world, auto_reset, 0, out.get("obs"))
         args = (world.num_envs, len(world.agents), int(K),
@@ -289,6 +293,30 @@ class Scenario(BaseScenario):
         def launch(rng_offset=0):
             p.rng_offset = rng_offset
             rc = fn(p, fa, *args)
+            if rc:
+                _native.check(rc)
+            return keep
+        return launch
+
+    def _bind_rollout_actor_per_agent(self, lib, world, K, spec, out, obs_every, auto_reset, log_std):
+        hidden, out_tanh, members = spec
+        fas = (_native.FgActor * len(members))(*[
+            _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in ws])
+            for ws in members])
+        p = self.params(world, auto_reset, 0, out.get("obs"))
+        args = (None if log_std is None else log_std.data_ptr(), world.num_envs, len(world.agents), int(K),
+                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
+                world.step_count.data_ptr(),
+                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
+                _native.ptr(out.get("done")), None if log_std is None else out["log_prob"].data_ptr(),
+                int(obs_every), _native.current_stream(world.device))
+        fn = lib.fg_rollout_hd_actor_per_agent
+        keep = (out, tuple(tuple(ws) for ws in members), fas, log_std)
+
+        def launch(rng_offset=0):
+            p.rng_offset = rng_offset
+            rc = fn(p, fas, *args)
             if rc:
                 _native.check(rc)
             return keep

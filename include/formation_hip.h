@@ -490,6 +490,23 @@ int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* strea
 int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
                                     int obs_every, char* out, int out_len);
 
+/* fg_rollout_hd_actor / fg_rollout_hd_actor_sample with one actor per agent (MADDPG-style, no parameter sharing): `actors`
+ * is a HOST array of N FgActor, agent i's observation rows go through actors[i] (pa_actor_kernel, or pa_sample_kernel when
+ * log_std is not NULL).  Every member passes fg_rollout_hd_actor's checks and has the hidden width and tanh flag of
+ * actors[0] (else FG_ERR_BAD_ARG, the message names the member's index); the table of pointers is copied into the launch,
+ * so `actors` may be freed when the call returns, while the weights it points at are read in place by the kernel.
+ * log_std == NULL: the deterministic actor, logp_seq ignored; else log_std [2] and logp_seq as in fg_rollout_hd_actor_sample
+ * (the same eps draws).  N identical members give the results of fg_rollout_hd_actor(_sample) with that member bit for bit. */
+int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N, int K,
+                                  float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                                  float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                  float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                  int obs_every, void* stream);
+/* Dry run of fg_rollout_hd_actor_per_agent: same checks and status codes, names the pa_actor_kernel<N,H> or
+ * pa_sample_kernel<N,H> instantiation.  Touches no device. */
+int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
+                                       int K, int obs_every, char* out, int out_len);
+
 #ifdef __cplusplus
 }
 #endif
