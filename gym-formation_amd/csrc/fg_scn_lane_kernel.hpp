@@ -25,6 +25,8 @@
 //   range     observation formation_hd_partial_range_env.py:38-52 (clipped), reward as partial
 //   obstacle  observation formation_hd_obs_env.py:44-58, reward :60-99 incl. the obstacle velocity override (:84-89)
 //   World.step core.py:206-277, 289-322 (all pairs of movable colliders)
+// The producer's step, its observation compose and the writer's block store are the textual includes fg_scn_lane_step.inc,
+// fg_scn_lane_compose.inc and fg_scn_lane_write.inc: scn_lane_actor (fg_scn_lane_actor_kernel.hpp) runs the same source text.
 #ifndef FG_SCN_LANE_KERNEL_HPP_
 #define FG_SCN_LANE_KERNEL_HPP_
 
@@ -96,76 +98,7 @@ FG_DEV void lane_writer_wave(const float2* smem_all, int KS, int B, int b0, int 
     for (int ks = 0; ks < KS; ++ks) {
         if (!DB) __syncthreads();                   // A: the block of step ks - 1 has been read (nothing to do for ks = 0)
         __syncthreads();                            // B: the block of step ks is complete
-        const float2* const smem = smem_all + (DB ? (ks & 1) * BLOCK_UNITS : 0);
-        const float* const s_rew = reinterpret_cast<const float*>(smem + ENVS * SU);
-        const float* const s_ind = s_rew + ENVS * N;
-        const uint32_t* const s_done = reinterpret_cast<const uint32_t*>(s_ind + ENVS * N);
-        const size_t kb = (size_t)ks * B;
-        const bool want_obs = obs != nullptr && (obs_every <= 1 || (ks + 1) % obs_every == 0);
-        if (want_obs) {
-            // unit q of the workgroup's span = unit (q mod U) of env (q div U); 64 units per instruction, lanes consecutive
-            const size_t ob = (size_t)(obs_every > 1 ? ks / obs_every : ks) * B;
-            float2* const out = reinterpret_cast<float2*>(obs + (ob + (size_t)b0) * N * D);
-            if (El == ENVS) {
-                // a full block: 32 U pairs of units, one 16-byte store per lane and instruction (1 KiB per wave instruction; the
-                // two units of a pair may sit in different rows of the LDS image.  8-byte stores: basic 3.2-3.45 -> 3.1 us/step,
-                // partial 6.8-7.5 -> 6.5, profiles/r04_lane_x4_ab.txt).  An odd U makes the image contiguous (pitch U | 1 = U):
-                // the pair is ONE 16-byte LDS read, lanes consecutive, no bank conflicts (the two 8-byte reads at a 16-byte lane
-                // stride met two-way: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.21 in profiles/r04_scn_pmc.txt).
-                constexpr int NP2 = ENVS / 2 * U, IT = (NP2 + 63) / 64;
-                constexpr int MINE = (IT + NWW - 1) / NWW;          // store instructions of one writer wave
-                f32x4* const out4 = reinterpret_cast<f32x4*>(out);
-                const f32x4* const img4 = reinterpret_cast<const f32x4*>(smem);
-#pragma unroll
-                for (int t0 = 0; t0 < MINE; t0 += 8) {
-                    f32x4 r[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        if (t0 + c < MINE) {
-                            const int pair = (w + NWW * (t0 + c)) * 64 + lane;
-                            const bool ok = pair < NP2;
-                            if constexpr (SU == U) {
-                                r[c] = img4[ok ? pair : 0];
-                            } else {
-                                const int q = 2 * pair;
-                                const int r0 = q / U, c0 = q - r0 * U;
-                                int r1 = r0, c1 = c0 + 1;
-                                if (c1 == U) { c1 = 0; r1 += 1; }
-                                const float2 x0 = smem[ok ? r0 * SU + c0 : 0], x1 = smem[ok ? r1 * SU + c1 : 0];
-                                r[c] = (f32x4){x0.x, x0.y, x1.x, x1.y};
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        const int pair = (w + NWW * (t0 + c)) * 64 + lane;
-                        if (t0 + c < MINE && pair < NP2) out4[pair] = r[c];
-                    }
-                }
-            } else {
-                const int units = El * U;
-                for (int q = w * 64 + lane; q < units; q += 64 * NWW) {
-                    const int row = q / U, col = q - row * U;
-                    out[q] = smem[row * SU + col];
-                }
-            }
-        }
-        // reward, individual reward, done of the 64 x N agents: [K][B][N], the workgroup's slice is contiguous; the 3 N store
-        // instructions are dealt over the writer waves
-        const int cnt = El * N;
-        const size_t o0 = (kb + b0) * N + lane;
-        if (rew) {                                  // (one uniform branch per array, not per store)
-#pragma unroll
-            for (int c = 0; c < N * PW; ++c) if (c % NWW == w && c * 64 + lane < cnt) rew[o0 + c * 64] = s_rew[c * 64 + lane];
-        }
-        if (indiv) {
-#pragma unroll
-            for (int c = 0; c < N * PW; ++c) if ((c + 1) % NWW == w && c * 64 + lane < cnt) indiv[o0 + c * 64] = s_ind[c * 64 + lane];
-        }
-        if (done) {
-#pragma unroll
-            for (int c = 0; c < N * PW; ++c) if ((c + 2) % NWW == w && c * 64 + lane < cnt) done[o0 + c * 64] = (uint8_t)s_done[c * 64 + lane];
-        }
+#include "fg_scn_lane_write.inc"
     }
 }
 
@@ -245,152 +178,7 @@ __global__ __launch_bounds__(64 * PW * (1 + scn_lane_writers(KIND))) void scn_la
 #pragma unroll
             for (int i = 0; i < N; ++i) u_next[i] = reinterpret_cast<const float2*>(a.act)[(kb + a.B + bl) * N + i];
         }
-        if (a.do_phys) {
-            // ---- World.step: every pair once, in lexicographic order - which is ascending j for each entity, the
-            // order core.py:240-262 (and scn_kernel) accumulates in; the pair's two forces are exact negatives
-            float fx[NE], fy[NE];
-#pragma unroll
-            for (int i = 0; i < NE; ++i) { fx[i] = 0.f; fy[i] = 0.f; }
-#pragma unroll
-            for (int i = 0; i < NE; ++i) {
-#pragma unroll
-                for (int j = i + 1; j < NE; ++j) {
-                    const float dmin = (i < N ? half_agent : half_obst) + (j < N ? half_agent : half_obst);
-                    const float cut = dmin + 18.0f * k_margin;
-                    const float dx = p[i].x - p[j].x, dy = p[i].y - p[j].y;
-                    const float d2 = dx * dx + dy * dy;
-                    if (d2 < cut * cut) {
-                        const float d = __builtin_amdgcn_sqrtf(d2);
-                        const float x = (dmin - d) / k_margin;
-                        const float pen = k_margin * (fmaxf(x, 0.0f) + __logf(1.0f + __expf(-fabsf(x))));
-                        const float c = a.p.contact_force * pen * __builtin_amdgcn_rcpf(d);
-                        fx[i] += dx * c; fy[i] += dy * c;
-                        const float ex = -dx, ey = -dy;                 // p_j - p_i, exactly
-                        fx[j] += ex * c; fy[j] += ey * c;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const float2 fa = action_force(a.p, agent_props_of(a.p, i, false), u_now[i], (uint32_t)(b + a.p.env_index_base),
-                                               (uint32_t)i, off);
-                fx[i] += fa.x; fy[i] += fa.y;
-            }
-            if (a.p.num_walls > 0) {                    // (one uniform branch around all entities)
-#pragma unroll
-                for (int i = 0; i < NE; ++i) wall_forces(a.p, p[i], i < N ? half_agent : half_obst, fx[i], fy[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < NE; ++i) {
-                v[i].x = v[i].x * (1.0f - a.p.damping) + (fx[i] / a.p.mass) * a.p.dt;
-                v[i].y = v[i].y * (1.0f - a.p.damping) + (fy[i] / a.p.mass) * a.p.dt;
-                if (i < N) v[i] = clamp_speed(a.p.max_speed, v[i]);
-                p[i].x += v[i].x * a.p.dt; p[i].y += v[i].y * a.p.dt;
-                if (i >= N) {                           // the reward callback re-arms the obstacle velocity every step (:84-89)
-                    const bool falling = p[i].y > a.sc.obstacle_floor;
-                    v[i] = make_float2(falling ? a.sc.obstacle_vx : 0.f, falling ? a.sc.obstacle_vy : 0.f);
-                }
-            }
-            t_step += 1;
-        }
-        // ---- formation term ----
-        float form;
-        if constexpr (BASIC) {
-            float slot[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) slot[g] = 0.f;
-#pragma unroll
-            for (int l = 0; l < L; ++l) {
-                float best = INFINITY; int barg = 0;
-#pragma unroll
-                for (int j = 0; j < N; ++j) {
-                    const float dx = p[j].x - lm[l].x, dy = p[j].y - lm[l].y, d2 = dx * dx + dy * dy;
-                    if (d2 < best) { best = d2; barg = j; }
-                }
-                slot[l % G] += sqrtf(best);
-                if (a.near_ag && live) a.near_ag[(kb + b) * L + l] = barg;
-            }
-            form = lane_group_sum<G>(slot);
-        } else {
-            float sx[G], sy[G], tx[G], ty[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                sx[g] = g < N ? p[g < N ? g : 0].x : 0.f; sy[g] = g < N ? p[g < N ? g : 0].y : 0.f;
-                tx[g] = 0.f; ty[g] = 0.f;
-            }
-#pragma unroll
-            for (int l = 0; l < L; ++l) { tx[l % G] += lm[l].x; ty[l % G] += lm[l].y; }
-            const float mx = lane_group_sum<G>(sx) * a.inv_n, my = lane_group_sum<G>(sy) * a.inv_n;
-            const float lx = lane_group_sum<G>(tx) * a.inv_l, ly = lane_group_sum<G>(ty) * a.inv_l;
-            float rowmax = -INFINITY, colmax = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {                       // min over landmarks for agent i
-                float rowmin = INFINITY;
-#pragma unroll
-                for (int l = 0; l < L; ++l) {
-                    const float dx = (p[i].x - mx) - (lm[l].x - lx), dy = (p[i].y - my) - (lm[l].y - ly);
-                    rowmin = fminf(rowmin, dx * dx + dy * dy);
-                }
-                rowmax = fmaxf(rowmax, rowmin);
-            }
-#pragma unroll
-            for (int l = 0; l < L; ++l) {                       // min over agents for landmark l
-                float cm = INFINITY;
-#pragma unroll
-                for (int j = 0; j < N; ++j) {
-                    const float dx = (p[j].x - mx) - (lm[l].x - lx), dy = (p[j].y - my) - (lm[l].y - ly);
-                    cm = fminf(cm, dx * dx + dy * dy);
-                }
-                colmax = fmaxf(colmax, cm);
-            }
-            form = sqrtf(fmaxf(rowmax, colmax));
-        }
-        // ---- collision counts (pairs shared: |p_j - p_i|^2 is the same number from either side) ----
-        int cnt[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) cnt[i] = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            if constexpr (BASIC) {                                      // the self pair (basic_formation_env.py:49-51): distance 0,
-                const float dx = p[i].x - p[i].x, dy = p[i].y - p[i].y; //   NaN for a NaN position, as scn_kernel computes it
-                cnt[i] += (dx * dx + dy * dy < thr2) ? 1 : 0;
-            }
-#pragma unroll
-            for (int j = i + 1; j < N; ++j) {
-                const float dx = p[j].x - p[i].x, dy = p[j].y - p[i].y;
-                const int hit = (dx * dx + dy * dy < thr2) ? 1 : 0;
-                cnt[i] += hit; cnt[j] += hit;
-            }
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-                const float dx = p[N + k].x - p[i].x, dy = p[N + k].y - p[i].y;
-                cnt[i] += (dx * dx + dy * dy < ot2) ? 1 : 0;
-            }
-        }
-        int total = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i) total += cnt[i];
-        const bool is_done = t_step >= a.p.world_length;
-        const float shared = (float)(-(double)N * (double)form - (double)a.sc.penalty * (double)(float)total);
-        float indiv[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) indiv[i] = -form - a.sc.penalty * (float)cnt[i];
-        const uint32_t done_flag = is_done ? 1u : 0u;       // the finished step's flag: the reset below does not change it
-        if (a.p.auto_reset && a.do_phys && is_done) {
-            // the vec-env worker's rule (env_wrappers.py:14-18): the env restarts at once, the RESET observation goes out
-            // with the finished step's reward / done.  The draws fg_reset_scenario makes.
-#pragma unroll
-            for (int i = 0; i < N; ++i) { p[i] = scn_fresh_pm1(a.p, b, (uint32_t)i, off); v[i] = make_float2(0.f, 0.f); }
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-                p[N + k] = scn_fresh_obstacle(a.p, b, k, a.sc.num_obstacles, off);
-                v[N + k] = make_float2(a.sc.obstacle_vx, a.sc.obstacle_vy);
-            }
-#pragma unroll
-            for (int l = 0; l < L; ++l) lm[l] = scn_fresh_pm1(a.p, b, SCN_LANDMARK_CODE | (uint32_t)l, off);
-            fresh_lm = true;
-            t_step = 0;
-        }
+#include "fg_scn_lane_step.inc"
         // ---- hand-over: the lane's [N][D] observation block and its rewards into LDS, for the writer wave ----
         const bool want_obs = a.obs_every <= 1 || (ks + 1) % a.obs_every == 0;      // uniform over the launch
         // one block: A - the writer has read the block of step ks - 1.  Two blocks: block (ks & 1) was last read for step
@@ -404,37 +192,7 @@ __global__ __launch_bounds__(64 * PW * (1 + scn_lane_writers(KIND))) void scn_la
         for (int i = 0; i < N; ++i) {
             s_rew[slot * N + i] = shared; s_ind[slot * N + i] = indiv[i]; s_done[slot * N + i] = done_flag;
         }
-        if (want_obs) {
-            float2* const mine = smem + slot * SU;
-            const float r = (KIND == FG_SCN_RANGE) ? a.sc.obs_range : INFINITY;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                float2* const o = mine + i * (D / 2);
-                int w = 0;
-                o[w++] = v[i];
-                if constexpr (BASIC) o[w++] = p[i];
-#pragma unroll
-                for (int l = 0; l < L; ++l) o[w++] = BASIC ? make_float2(lm[l].x - p[i].x, lm[l].y - p[i].y) : lm[l];
-#pragma unroll
-                for (int k = 0; k < M; ++k) o[w++] = make_float2(p[N + k].x - p[i].x, p[N + k].y - p[i].y);
-                if constexpr (KIND == FG_SCN_PARTIAL) {
-#pragma unroll
-                    for (int kk = 0; kk < NBR; ++kk) {
-                        int j = i + 1 + kk;                             // (i + 1 + kk) mod N
-                        while (j >= N) j -= N;
-                        o[w++] = make_float2(p[j].x - p[i].x, p[j].y - p[i].y);
-                    }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < N - 1; ++t) {
-                        const int j = t < i ? t : t + 1;                // the t-th OTHER agent, index order
-                        o[w++] = make_float2(fminf(fmaxf(p[j].x - p[i].x, -r), r), fminf(fmaxf(p[j].y - p[i].y, -r), r));
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < N - 1; ++t) o[w++] = make_float2(0.f, 0.f);
-            }
-        }
+#include "fg_scn_lane_compose.inc"
         __syncthreads();                                // B: published
     }   // steps
     if (live && a.do_phys) {

@@ -42,6 +42,7 @@
 #include "fg_hd_lane_kernel.hpp"
 #include "fg_policy_kernels.hpp"
 #include "fg_actor_rollout_kernel.hpp"
+#include "fg_scn_lane_actor_kernel.hpp"
 
 namespace fg {
 
@@ -1710,6 +1711,129 @@ int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* ac
     if (rc) return rc;
     if (log_std && (rc = actor_sample_check(log_std)) != FG_OK) return rc;
     return describe_actor_impl(params, actors, log_std, B, N, K, obs_every, out, out_len, true);
+}
+
+}  // extern "C"
+
+// ---- closed loop with the caller's MLP actor in the landmark scenarios (fg_scn_lane_actor_kernel.hpp) ----
+// log_std == NULL: scn_lane_actor (the deterministic actor); else scn_lane_actor_gauss (the Gaussian actor)
+template <int KIND, int NN, int LL, int MM, int NBR, int H>
+static int launch_scn_actor(const ScnArgs& a, const ActorW& w, float* act_out, const float* log_std, float* logp, hipStream_t st) {
+    const bool sample = log_std != nullptr;
+    const int lds = scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, sample);
+    static_assert(scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, true) <= 160 * 1024, "scenario actor rollout LDS");
+    const int grid = 8 * (((a.B + FG_SCN_ACTOR_ENVS - 1) / FG_SCN_ACTOR_ENVS + 7) / 8);
+    if (describe("%s<%d,%d,%d,%d,%d,%d> grid %d threads %d envs/wg %d lds %d; ", sample ? "scn_lane_actor_gauss" : "scn_lane_actor",
+                 KIND, NN, LL, MM, NBR, H, grid, FG_SCN_ACTOR_THREADS, FG_SCN_ACTOR_ENVS, lds)) return FG_OK;
+    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
+    hipError_t err = sample ? raise_lds_limit((const void*)&scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>, lds, &raised_sample)
+                            : raise_lds_limit((const void*)&scn_lane_actor<KIND, NN, LL, MM, NBR, H>, lds, &raised);
+    if (err == hipSuccess) {
+        if (sample)
+            hipLaunchKernelGGL((scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>), dim3(grid), dim3(FG_SCN_ACTOR_THREADS), lds, st,
+                               a, w, act_out, log_std, logp);
+        else
+            hipLaunchKernelGGL((scn_lane_actor<KIND, NN, LL, MM, NBR, H>), dim3(grid), dim3(FG_SCN_ACTOR_THREADS), lds, st,
+                               a, w, act_out);
+        err = hipGetLastError();
+    }
+    if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario actor rollout launch failed: %s", hipGetErrorString(err));
+    return FG_OK;
+}
+
+// the checks both scenario-actor entries share (no device touched): FG_OK, or the status of the first one that fails
+static int scn_actor_check(const FgParams* params, const FgScenario* sc, const FgActor* actor, const float* log_std,
+                           const float* logp, int B, int N, int K) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (!sc) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: scenario descriptor is NULL%s");
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: B >= 0 and K >= 1 required%s");
+    if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: unknown scenario kind%s");
+    if (!actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: actor is NULL%s");
+    if (actor->hidden != 32 && actor->hidden != 64)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: hidden must be 32 or 64%s");
+    if (!actor->w1 || !actor->w2 || !actor->w3) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: a weight pointer is NULL%s");
+    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
+         (uintptr_t)actor->b3 | (uintptr_t)log_std | (uintptr_t)logp) & 3u)
+        return fail(FG_ERR_ALIGNMENT, "fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned%s");
+    if (!log_std && logp) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: logp without log_std%s");
+    if (params->agent_props || params->comm_state || sc->variant == 1)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported%s");
+    return FG_OK;
+}
+
+static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act_out, const float* log_std, float* logp,
+                              hipStream_t st) {
+    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+    const int L = a.sc.num_landmarks, M = a.sc.num_obstacles;
+    const int nbr = a.sc.kind == FG_SCN_PARTIAL ? a.sc.num_obs : a.N - 1;
+    // the shapes of launch_scenario's FG_SCN_LANE list
+#define FG_SCN_ACTOR(KIND, NN, LL, MM, NBR)                                                                  \
+    if (a.sc.kind == KIND && a.N == NN && L == LL && M == MM && nbr == NBR)                                  \
+        return actor.hidden == 32 ? launch_scn_actor<KIND, NN, LL, MM, NBR, 32>(a, w, act_out, log_std, logp, st) \
+                                  : launch_scn_actor<KIND, NN, LL, MM, NBR, 64>(a, w, act_out, log_std, logp, st);
+    FG_SCN_ACTOR(FG_SCN_BASIC, 3, 3, 0, 2)
+    FG_SCN_ACTOR(FG_SCN_PARTIAL, 5, 5, 0, 3)
+    FG_SCN_ACTOR(FG_SCN_RANGE, 4, 4, 0, 3)
+    FG_SCN_ACTOR(FG_SCN_OBSTACLE, 4, 4, 3, 3)
+    FG_SCN_ACTOR(FG_SCN_PARTIAL, 3, 5, 0, 3)
+    FG_SCN_ACTOR(FG_SCN_RANGE, 3, 4, 0, 2)
+    FG_SCN_ACTOR(FG_SCN_OBSTACLE, 3, 4, 3, 2)
+#undef FG_SCN_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes%s");
+}
+
+static void scn_actor_args(ScnArgs* a, const FgParams* params, const FgScenario* sc, int B, int N, int K, int obs_every) {
+    memset(a, 0, sizeof(*a));
+    a->p = *params; a->sc = *sc; a->B = B; a->N = N; a->do_phys = 1; a->K = K; a->obs_every = obs_every < 1 ? 1 : obs_every;
+    a->inv_n = (float)(1.0 / (double)N); a->inv_l = (float)(1.0 / (double)(sc->num_landmarks > 0 ? sc->num_landmarks : 1));
+    a->coll_scale = (float)((double)params->collide_thresh / (double)params->dist_min);
+}
+
+extern "C" {
+
+int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario, const FgActor* actor, const float* log_std,
+                              int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                              float* landmarks, float* obst_pos, float* obst_vel, int32_t* step,
+                              float* obs, float* reward, float* indiv_reward, uint8_t* done, float* act_out, float* logp,
+                              int obs_every, void* stream) {
+    int rc = scn_actor_check(params, scenario, actor, log_std, logp, B, N, K);
+    if (rc) return rc;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !landmarks || !step || !reward || !act_out ||
+        (scenario->num_obstacles > 0 && (!obst_pos || !obst_vel)))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: a required pointer is NULL%s");
+    if (((uintptr_t)obs & 7u) || ((uintptr_t)landmarks & 7u) || ((uintptr_t)act_out & 7u) || ((uintptr_t)obst_pos & 7u) ||
+        ((uintptr_t)obst_vel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned%s");
+    ScnArgs a;
+    scn_actor_args(&a, params, scenario, B, N, K, obs_every);
+    if (B == 0) {                                      // nothing to launch; an unsupported shape is still reported
+        char dry[8];
+        g_describe = dry; g_describe_cap = (int)sizeof(dry); dry[0] = 0; a.B = 1;
+        rc = scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
+        g_describe = nullptr; g_describe_cap = 0;
+        return rc;
+    }
+    const DeviceGuard device_guard(stream, pos_x);
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.lm = landmarks; a.opos = obst_pos; a.ovel = obst_vel; a.step = step;
+    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
+    return scn_actor_dispatch(a, *actor, act_out, log_std, logp, (hipStream_t)stream);
+}
+
+int fg_describe_scenario_actor_launch(const FgParams* params, const FgScenario* scenario, const FgActor* actor,
+                                      const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_scenario_actor_launch: out buffer required%s");
+    out[0] = 0;
+    int rc = scn_actor_check(params, scenario, actor, log_std, nullptr, B, N, K);
+    if (rc) return rc;
+    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_scenario_actor_launch: B > 0 required%s");
+    ScnArgs a;
+    scn_actor_args(&a, params, scenario, B, N, K, obs_every);
+    g_describe = out; g_describe_cap = out_len;
+    rc = scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
+    g_describe = nullptr; g_describe_cap = 0;
+    return rc;
 }
 
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,

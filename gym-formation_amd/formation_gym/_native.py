@@ -149,6 +149,10 @@ SIGNATURES = {
     "fg_describe_actor_sample_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),
     "fg_describe_actor_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
+                                  + [_I, _P]),
+    "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,
+                                               ctypes.c_char_p, _I]),
 }
 
 _lib = None

@@ -11,7 +11,14 @@ A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample
 log_std is a contiguous fp32 [2] tensor on the env's device.
 
 A `PerAgentActor(actors)` gives every agent its own network (MADDPG-style): it fuses (`fg_rollout_hd_actor_per_agent`)
-when it holds N members that each fuse as above with one H and one tanh flag, alone or as the mean of a GaussianActor."""
+when it holds N members that each fuse as above with one H and one tanh flag, alone or as the mean of a GaussianActor.
+
+The landmark scenarios (basic_formation_env, formation_hd_partial_env, formation_hd_partial_range_env, formation_hd_obs_env)
+fuse too (`fg_rollout_scenario_actor`), under the same rule with their own facts: the input width is the scenario's observation
+width D instead of 6N, H in {32, 64}, and the shape is one of the seven the one-env-per-lane kernel is built for
+(LANDMARK_FUSED_SHAPES).  H = 128 and a PerAgentActor run host-paced there.  The scenario states these facts
+(`ActorRolloutMixin.actor_fused_rule`) and `MultiAgentEnv.actor_path` hands them to the functions below as keyword
+arguments, whose defaults are formation_hd_env's."""
 import math
 
 import torch
@@ -20,14 +27,33 @@ LOG_2PI = math.log(2.0 * math.pi)
 
 FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)
 FUSED_HIDDEN = (32, 64, 128)
+# the landmark scenarios: (scenario kind, agents, landmarks, obstacles, neighbours observed) -> fused; kind as _native.FG_SCN_*
+LANDMARK_FUSED_SHAPES = ((1, 3, 3, 0, 2), (2, 5, 5, 0, 3), (2, 3, 5, 0, 3), (3, 4, 4, 0, 3), (3, 3, 4, 0, 2),
+                         (4, 4, 4, 3, 3), (4, 3, 4, 3, 2))
+LANDMARK_FUSED_HIDDEN = (32, 64)
 
 
-def actor_spec(actor, num_agents, device=None):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate `actor` for `num_agents` agents, else
-    None.  `device`: the env's device (None: not checked).  The tensors are the actor's own parameters (b* may be None)."""
-    nn = torch.nn
-    if type(actor) is not nn.Sequential or int(num_agents) not in FUSED_N:
+def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_dim, variant=0):
+    """The keyword facts of `actor_path` / `actor_spec` for a landmark scenario whose shape has the fused actor launch - one of
+    LANDMARK_FUSED_SHAPES, not the run-time-count kernel (variant 1) - else None: host-paced.  `num_obs` counts only for
+    formation_hd_partial_env (kind 2); the other kinds observe all N - 1 neighbours."""
+    N = int(num_agents)
+    nbr = int(num_obs) if int(kind) == 2 else N - 1
+    if int(variant) == 1 or (int(kind), N, int(num_landmarks), int(num_obstacles), nbr) not in LANDMARK_FUSED_SHAPES:
         return None
+    return dict(in_features=int(obs_dim), fused_n=(N,), fused_hidden=LANDMARK_FUSED_HIDDEN, per_agent=False)
+
+
+def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate `actor` for `num_agents` agents, else
+    None.  `device`: the env's device (None: not checked).  The tensors are the actor's own parameters (b* may be None).
+    The scenario's facts: `in_features` the actor's input width (None: formation_hd_env's 6N), `fused_n` the agent counts and
+    `fused_hidden` the hidden widths its kernel is built for."""
+    nn = torch.nn
+    if type(actor) is not nn.Sequential or int(num_agents) not in fused_n:
+        return None
+    if in_features is None:
+        in_features = 6 * int(num_agents)
     mods = list(actor)
     kinds = [type(m) for m in mods]
     body = [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear]
@@ -35,7 +61,7 @@ def actor_spec(actor, num_agents, device=None):
         return None
     l1, l2, l3 = mods[0], mods[2], mods[4]
     H = l1.out_features
-    if H not in FUSED_HIDDEN or l1.in_features != 6 * int(num_agents) or (l2.in_features, l2.out_features) != (H, H) \
+    if H not in fused_hidden or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
             or (l3.in_features, l3.out_features) != (H, 2):
         return None
     params = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
@@ -117,14 +143,17 @@ def _on_device(t, device):
     return t.device.type == dev.type and (dev.index is None or t.device.index == dev.index)
 
 
-def sample_spec(actor, num_agents, device=None):
+def sample_spec(actor, num_agents, device=None, **facts):
     """(actor_spec(actor.mean, ...), log_std) when the fused kernel can sample from the GaussianActor `actor` for
     `num_agents` agents, else None: its mean fuses (actor_spec; per_agent_spec for a PerAgentActor mean) and log_std is a contiguous fp32 [2] tensor on `device`
-    (None: not checked).  log_std is the actor's own parameter, read in place by every launch."""
+    (None: not checked).  log_std is the actor's own parameter, read in place by every launch.  `facts`: actor_spec's
+    keyword arguments for a shared mean (in_features, fused_n, fused_hidden)."""
     if not isinstance(actor, GaussianActor):
         return None
-    mean_spec = per_agent_spec if isinstance(actor.mean, PerAgentActor) else actor_spec
-    spec = mean_spec(actor.mean, num_agents, device)
+    if isinstance(actor.mean, PerAgentActor):
+        spec = per_agent_spec(actor.mean, num_agents, device)
+    else:
+        spec = actor_spec(actor.mean, num_agents, device, **facts)
     ls = actor.log_std
     if spec is None or not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) \
             or not ls.is_contiguous() or not _on_device(ls, device):
@@ -133,14 +162,19 @@ def sample_spec(actor, num_agents, device=None):
 
 
 def actor_path(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
-               callback=False):
+               callback=False, per_agent=True, **facts):
     """'fused' or 'host': the one decision `MultiAgentEnv.actor_path` / `rollout_actor` take.  The keyword facts describe the
     env: a scenario with the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls,
-    accel, max_speed, u_noise, per-agent properties), no post_step_callback."""
+    accel, max_speed, u_noise, per-agent properties), no post_step_callback.  `per_agent`: the scenario's launch takes a
+    PerAgentActor (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's keyword arguments
+    (in_features, fused_n, fused_hidden), as the scenario states them."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return "host"
+    mean = actor.mean if isinstance(actor, GaussianActor) else actor
+    if isinstance(mean, PerAgentActor) and not per_agent:
+        return "host"
     if isinstance(actor, GaussianActor):
-        return "fused" if sample_spec(actor, num_agents, device) is not None else "host"
+        return "fused" if sample_spec(actor, num_agents, device, **facts) is not None else "host"
     if isinstance(actor, PerAgentActor):
         return "fused" if per_agent_spec(actor, num_agents, device) is not None else "host"
-    return "fused" if actor_spec(actor, num_agents, device) is not None else "host"
+    return "fused" if actor_spec(actor, num_agents, device, **facts) is not None else "host"

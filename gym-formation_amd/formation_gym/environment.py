@@ -364,16 +364,27 @@ class MultiAgentEnv(object):
             else:
                 world_options = bool(p.num_walls > 0 or p.u_noise > 0 or p.max_speed > 0 or p.accel > 0 or p.agent_props
                                      or p.comm_state)
+        facts = self._actor_facts() if fused else {}
+        if facts is None:                                  # a landmark scenario at a shape without the fused launch
+            fused, facts = False, {}
         return actor_rollout.actor_path(actor, self.num_agents, self.world.device, fused_scenario=fused,
                                         continuous=not self._action_mode(), silent=not self.world.any_non_silent(),
-                                        world_options=world_options, callback=self.post_step_callback is not None)
+                                        world_options=world_options, callback=self.post_step_callback is not None, **facts)
+
+    def _actor_facts(self):
+        """The scenario's own facts for `actor_rollout.actor_path` / `actor_spec` (input width, admissible agent counts and
+        hidden widths, whether a PerAgentActor fuses): {} for formation_hd_env (the functions' defaults), a landmark
+        scenario's `actor_fused_rule(world)` - None where its shape has no fused launch."""
+        rule = getattr(self.scenario, "actor_fused_rule", None)
+        return {} if rule is None else rule(self.world)
 
     def rollout_actor(self, K, actor, out=None, obs_every=1):
         """The loop of a learned actor for K steps in one call:
             act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
         from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
-        after the device auto-reset, when `auto_reset` is set); each agent's observation row [6N] is one row of the actor's
-        input batch.  Results come back like `rollout_policy`'s, with the actions taken under info['actions'] [K, B, N, 2],
+        after the device auto-reset, when `auto_reset` is set); each agent's observation row (6N floats in formation_hd_env,
+        the scenario's observation width in the landmark scenarios) is one row of the actor's input batch.  Results come back
+        like `rollout_policy`'s, with the actions taken under info['actions'] [K, B, N, 2],
         and with its aliasing rules for `out`.
         `actor_path(actor)` tells which loop runs.  'fused': ONE launch (`fg_rollout_hd_actor`) with the actor - one
         Sequential(Linear(6N, H), ReLU, Linear(H, H), ReLU, Linear(H, 2) [, Tanh]) shared by all agents, H in {32, 64, 128} -
@@ -387,7 +398,10 @@ class MultiAgentEnv(object):
         It fuses (`fg_rollout_hd_actor_sample`) when its mean would and log_std is a contiguous fp32 [2] tensor on the env's
         device, read in place like the weights.
         A `PerAgentActor([actor_0, ..., actor_{N-1}])` gives agent i its own network, alone or as a GaussianActor's mean; it
-        fuses (`fg_rollout_hd_actor_per_agent`) when every member would, with one H and one tanh flag."""
+        fuses (`fg_rollout_hd_actor_per_agent`) when every member would, with one H and one tanh flag.
+        The landmark scenarios (basic_formation_env, formation_hd_partial_env, formation_hd_partial_range_env,
+        formation_hd_obs_env) fuse a shared actor, deterministic or Gaussian, at their seven reference shapes with H in
+        {32, 64} (`fg_rollout_scenario_actor`); H = 128 and a PerAgentActor run host-paced there."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
@@ -397,12 +411,13 @@ class MultiAgentEnv(object):
         if self.actor_path(actor) == "host":
             return self._rollout_actor_by_steps(K, actor, obs_every)
         log_std = None
+        facts = {k: v for k, v in self._actor_facts().items() if k != "per_agent"}     # actor_spec's keyword arguments
         if gaussian:
-            (hidden, out_tanh, weights), log_std = actor_rollout.sample_spec(actor, self.num_agents, self.world.device)
+            (hidden, out_tanh, weights), log_std = actor_rollout.sample_spec(actor, self.num_agents, self.world.device, **facts)
         elif isinstance(actor, actor_rollout.PerAgentActor):
             hidden, out_tanh, weights = actor_rollout.per_agent_spec(actor, self.num_agents, self.world.device)
         else:
-            hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device)
+            hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device, **facts)
         per_agent = bool(weights) and isinstance(weights[0], list)      # per_agent_spec: one weight list per agent
         flat = [t for ws in weights for t in ws] if per_agent else weights
         B, N = self.num_envs, self.num_agents
@@ -578,13 +593,16 @@ class MultiAgentEnv(object):
             self.placement = {"tried": 1, "probed": False}
             return dict(small, obs=alloc())
         snap = self._snapshot()
-        acts = None if policy else torch.zeros((K, B, N, 2), **f)
+        # a scenario without a built-in controller (the landmark scenarios: `policy` asks for the buffers of rollout_actor)
+        # is timed on its open-loop rollout of zero actions - the same store stream into the candidate
+        closed = policy and getattr(self.scenario, "rollout_policy_batch", None) is not None
+        acts = None if closed else torch.zeros((K, B, N, 2), **f)
 
-        per_layer = self._policy_per_layer() if policy else 0
+        per_layer = self._policy_per_layer() if closed else 0
 
         def time_fn(obs):
             out = dict(small, obs=obs)
-            if policy:
+            if closed:
                 self.rollout_policy(K, per_layer, out=out, obs_every=obs_every)
             else:
                 self.rollout(acts, out=out, obs_every=obs_every)

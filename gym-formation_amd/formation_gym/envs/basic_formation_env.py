@@ -12,10 +12,10 @@ import torch
 from formation_gym import _native
 from formation_gym.core import World, Agent, Landmark
 from formation_gym.scenario import BaseScenario
-from formation_gym.landmark_scenario import MtResetMixin
+from formation_gym.landmark_scenario import MtResetMixin, ActorRolloutMixin
 
 
-class Scenario(MtResetMixin, BaseScenario):
+class Scenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
     def make_world(self, num_agents=3, num_landmarks=3, num_envs=1, device=None):
         world = World(num_envs=num_envs, device=device)      # world_length = 50 (core.py:113)
         world.dim_c = 2

@@ -507,6 +507,31 @@ int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors,
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
                                        int K, int obs_every, char* out, int out_len);
 
+/* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
+ * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
+ * (scn_lane_actor, or scn_lane_actor_gauss when log_std is not NULL), with the actor
+ *     Linear(D, hidden) - ReLU - Linear(hidden, hidden) - ReLU - Linear(hidden, 2) [- tanh],   hidden 32 or 64,
+ * D the scenario's observation width, shared by every agent (FgActor, w1 [hidden][D]).  Step 0 acts on the observation of
+ * the current state, step k on the one step k-1 returned (after the device auto-reset, when params->auto_reset is set).
+ * State pointers, outputs and obs_every as fg_rollout_scenario's (obs may be NULL: not written); act_out [K][B][N][2] is an
+ * OUTPUT (the actions taken, required, 8-byte aligned), and fg_rollout_scenario driven by it from the same state returns the
+ * same bits.  log_std [2] / logp [K][B][N] (NULL: not written) as in fg_rollout_hd_actor_sample, the same eps draws
+ * (fg_actor_noise); log_std == NULL is the deterministic actor, and logp must then be NULL.
+ * Shapes: the seven (scenario, N, landmarks, obstacles, num_obs) the one-env-per-lane kernel is built for - basic (3,3,0),
+ * partial (5,5,0,3) and (3,5,0,3), range (4,4,0) and (3,4,0), obstacle (4,4,3) and (3,4,3); any other returns
+ * FG_ERR_UNSUPPORTED_N.  agent_props, comm_state, scenario->variant == 1 or an unsupported hidden return FG_ERR_BAD_ARG;
+ * there is no fall-back inside the library.  B == 0 returns FG_OK without a launch. */
+int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario, const FgActor* actor, const float* log_std,
+                              int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                              float* landmarks, float* obst_pos, float* obst_vel, int32_t* step,
+                              float* obs, float* reward, float* indiv_reward, uint8_t* done, float* act_out, float* logp,
+                              int obs_every, void* stream);
+/* Dry run of fg_rollout_scenario_actor: same checks and status codes (those on the state and output pointers apart), names
+ * the scn_lane_actor<KIND,N,L,M,NBR,H> or scn_lane_actor_gauss<...> instantiation and its launch geometry.  Touches no
+ * device; log_std is only checked for NULL and alignment. */
+int fg_describe_scenario_actor_launch(const FgParams* params, const FgScenario* scenario, const FgActor* actor,
+                                      const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
+
 #ifdef __cplusplus
 }
 #endif
