@@ -1,0 +1,57 @@
+// fg_actor_mlp.inc - the MLP core of the fused actor rollouts: everything a wave pass of FG_ACTOR_ROWS rows does after layer 1
+// for the shared actor `w` - ReLU hand-over, layer 2 on the MFMA with its three WaveSync points, layer 3 and the tanh on the
+// VALU, the Gaussian step.  The one copy for fg_actor_rollout_body.inc (formation_hd_env, PER_AGENT = false) and
+// fg_scn_lane_actor_body.inc (landmark scenarios); layer 1 stays with each body, whose A operand differs.  Included inside the
+// pass loop of the body's `actor` lambda, right after its layer 1 (a textual include for the reason written at the top of
+// fg_actor_rollout_body.inc: as a lambda this text changed the kernels' instructions).  Not a header: no guard.
+//
+// The including scope provides: `acc` (layer 1's accumulators, bias included), `hb` (the wave's activation tile), `wsm` (the
+// LDS block fg_actor_mlp_preload.inc fills) and WS, `w`, `a` (a.p: KParams), `lane`, `col`, `kq`, `q0` (the pass's first row),
+// `b0` (the workgroup's first env), `off` (the counter offset of the step that takes the action), N, H, HS, CB, RT, SAMPLE.
+// It leaves in scope: `row`, `o` (the lane's row of the pass and output), `q` = q0 + row (env-major row of the workgroup:
+// env q / N, agent q % N), `y` (the lane's action component, noise added) and, SAMPLE only, the row's draw `n` with `ls0`,
+// `ls1` for gauss_logp(n, ls0, ls1).  The body stores them - each to its own place - and ends the pass with a WaveSync.
+            actor_store_tile(hb, HS, acc, col, kq);
+            WaveSync()();
+            // ---- layer 2 ----
+            actor_bias_init(acc, wsm + H, col);
+            // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would
+            // all be held in registers)
+            const float* w2row = w.w2 + (size_t)col * H;
+            asm volatile("" : "+v"(w2row));
+#pragma unroll 2
+            for (int ks = 0; ks < H / 4; ++ks) {
+                const int k = ks * 4 + kq;
+                float xa[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) {
+                    const float wb = w2row[cb * 16 * H + k];
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt)
+                        acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
+                }
+            }
+            WaveSync()();                          // every read of the layer-1 tile before it is overwritten
+            actor_store_tile(hb, HS, acc, col, kq);
+            WaveSync()();
+            // ---- layer 3 on the VALU: lane = (row of the pass, output), an ascending fmaf chain ----
+            const int row = lane >> 1, o = lane & 1;
+            const float* const hr = hb + row * HS;
+            const float* const w3 = wsm + 2 * H + o * H;
+            float y = wsm[4 * H + o];
+#pragma unroll 8
+            for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
+            if (w.out_tanh) y = tanhf(y);
+            // the pass's row as an env-major row of the workgroup: env q / N, agent q % N
+            const int q = q0 + row;
+            float2 n = {};                         // SAMPLE: the row's draw and log_std, for gauss_logp(n, ls0, ls1)
+            float ls0 = 0.f, ls1 = 0.f;
+            if constexpr (SAMPLE) {
+                const int ee = q / N;
+                // both lanes of a row draw the row's pair at counter offset `off`: lane o adds component o
+                n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
+                ls0 = wsm[WS + 2]; ls1 = wsm[WS + 3];
+                y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
+            }

@@ -1,0 +1,15 @@
+// fg_actor_mlp_preload.inc - the shared actor's small parameters into LDS: wsm = b1 [H] | b2 [H] | W3 [2][H] | b3 [2] |
+// (SAMPLE) log_std [2].  Included once at the top of fg_actor_rollout_body.inc (PER_AGENT = false) and of
+// fg_scn_lane_actor_body.inc, whose scope provides `w` (ActorW), `log_std`, `wsm`, `tid`, H, WS (= 4 H) and `constexpr bool
+// SAMPLE`; both kernels have FG_ACTOR_THREADS threads.  The workgroup barrier before the first actor pass publishes it.
+// fg_actor_mlp.inc and the bodies' layer 1 (actor_bias_init) read it back.  Not a header: no guard.
+    for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
+        wsm[q] = w.b1 ? w.b1[q] : 0.f;
+        wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
+        wsm[2 * H + q] = w.w3[q];
+        wsm[3 * H + q] = w.w3[H + q];
+    }
+    if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
+    if constexpr (SAMPLE) {
+        if (tid < 2) wsm[WS + 2 + tid] = log_std[tid];
+    }

@@ -3,6 +3,9 @@
 // (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
 // (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  Not a header: no guard.
+// This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
+// layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
+// scenarios' body, as is the LDS preload (fg_actor_mlp_preload.inc).  The per-agent branches stay here.
 //
 // Why a textual include and not a force-inlined __device__ function: behind a function boundary the kernel arguments reach
 // the body through a by-value copy, and even inlined early the copy changes how the arguments are loaded and the order in
@@ -43,15 +46,8 @@
     float* const SX = PY + NP; float* const SY = SX + NP;
 
     if constexpr (!PER_AGENT) {
-        for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
-            wsm[q] = w.b1 ? w.b1[q] : 0.f;
-            wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
-            wsm[2 * H + q] = w.w3[q];
-            wsm[3 * H + q] = w.w3[H + q];
-        }
-        if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
-    }
-    if constexpr (SAMPLE) {
+#include "fg_actor_mlp_preload.inc"
+    } else if constexpr (SAMPLE) {
         if (tid < 2) wsm[WS + 2 + tid] = log_std[tid];
     }
 
@@ -148,12 +144,7 @@
             if constexpr (PER_AGENT) {
                 bias_init(1);
             } else {
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const float bias = wsm[cb * 16 + col];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
-            }
+                actor_bias_init(acc, wsm, col);
             }
             // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would all
             // be held in registers)
@@ -200,109 +191,61 @@
             for (int ks = 0; ks < KA; ++ks) l1_chunk(ks);
 #pragma unroll 2
             for (int ks = KB0; ks < KB1; ++ks) l1_chunk(ks);
-            // ReLU -> activation tile: accumulator register j of lane l is row 4 (l >> 4) + j, column l & 15
-            auto store_tile = [&]() {
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            hb[(rt * 16 + kq * 4 + j) * HS + cb * 16 + col] = fmaxf(acc[rt][cb][j], 0.f);
-            };
-            store_tile();
-            WaveSync()();
-            // ---- layer 2 ----
             if constexpr (PER_AGENT) {
+                actor_store_tile(hb, HS, acc, col, kq);
+                WaveSync()();
+                // ---- layer 2 ----
                 bias_init(2);
-            } else {
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const float bias = wsm[H + cb * 16 + col];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
-            }
-            }
-            const float* w2row = w.w2 + (size_t)col * H;
-            gfloat* w2pa[RT];
-            if constexpr (PER_AGENT) {
+                gfloat* w2pa[RT];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) w2pa[rt] = (gfloat*)tab.w2[ra[rt]];
-            } else {
-            asm volatile("" : "+v"(w2row));
-            }
 #pragma unroll 2
-            for (int ks = 0; ks < H / 4; ++ks) {
-                const int k = ks * 4 + kq;
-                int ro = 0;
-                if constexpr (PER_AGENT) {
-                    ro = col * H;
+                for (int ks = 0; ks < H / 4; ++ks) {
+                    const int k = ks * 4 + kq;
+                    int ro = col * H;
                     asm volatile("" : "+v"(ro));
-                }
-                float xa[RT];
+                    float xa[RT];
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
+                    for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
 #pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    if constexpr (PER_AGENT) {
+                    for (int cb = 0; cb < CB; ++cb) {
                         float wb[RT];
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt) wb[rt] = w2pa[rt][ro + cb * 16 * H + k];
 #pragma unroll
                         for (int rt = 0; rt < RT; ++rt)
                             acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb[rt], acc[rt][cb], 0, 0, 0);
-                    } else {
-                    const float wb = w2row[cb * 16 * H + k];
-#pragma unroll
-                    for (int rt = 0; rt < RT; ++rt)
-                        acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
                     }
                 }
-            }
-            WaveSync()();                              // every read of the layer-1 tile before it is overwritten
-            store_tile();
-            WaveSync()();
-            // ---- layer 3 on the VALU: lane = (row, output) ----
-            {
+                WaveSync()();                          // every read of the layer-1 tile before it is overwritten
+                actor_store_tile(hb, HS, acc, col, kq);
+                WaveSync()();
+                // ---- layer 3 on the VALU: lane = (row, output), the row's tile's agent through L1 ----
                 const int row = lane >> 1, o = lane & 1;
                 const float* const hr = hb + row * HS;
-                float y;
-                if constexpr (PER_AGENT) {             // the row's tile's agent, through L1
-                    gfloat* const b3 = (gfloat*)(row < 16 ? tab.b3[ra[0]] : tab.b3[ra[1]]);
-                    gfloat* const w3 = (gfloat*)(row < 16 ? tab.w3[ra[0]] : tab.w3[ra[1]]) + o * H;
-                    y = b3 ? b3[o] : 0.f;
-#pragma unroll 8
-                    for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
-                } else {
-                const float* const w3 = wsm + 2 * H + o * H;
-                y = wsm[4 * H + o];
+                gfloat* const b3 = (gfloat*)(row < 16 ? tab.b3[ra[0]] : tab.b3[ra[1]]);
+                gfloat* const w3 = (gfloat*)(row < 16 ? tab.w3[ra[0]] : tab.w3[ra[1]]) + o * H;
+                float y = b3 ? b3[o] : 0.f;
 #pragma unroll 8
                 for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
-                }
                 if (w.out_tanh) y = tanhf(y);
                 const int q = q0 + row;
-                if constexpr (PER_AGENT) {
-                    // the row's env and agent (agent-major rows), whether it is one of this workgroup's, its env-major slot
-                    const int ee = q % EP, r = q / EP, slot = ee * N + r;
-                    const bool ok = ee < El && r < N;
-                    if constexpr (SAMPLE) {            // actor_sample_kernel's draw of (env, agent)
-                        const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)r, off);
-                        const float ls0 = wsm[WS + 2], ls1 = wsm[WS + 3];
-                        y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
-                        if (ok && o == 0) logp_lds[slot] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
-                    }
-                    if (ok) reinterpret_cast<float*>(act_lds)[2 * slot + o] = y;
-                } else {
-                if constexpr (SAMPLE) {
-                    // both lanes of a row draw the row's pair: lane o adds component o and lane 0 keeps the log-density
-                    const int ee = q / N;
-                    const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
-                    const float ls0 = wsm[4 * H + 2], ls1 = wsm[4 * H + 3];
+                // the row's env and agent (agent-major rows), whether it is one of this workgroup's, its env-major slot
+                const int ee = q % EP, r = q / EP, slot = ee * N + r;
+                const bool ok = ee < El && r < N;
+                if constexpr (SAMPLE) {                // actor_sample_kernel's draw of (env, agent)
+                    const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)r, off);
+                    const float ls0 = wsm[WS + 2], ls1 = wsm[WS + 3];
                     y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
-                    if (q < M && o == 0) logp_lds[q] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
+                    if (ok && o == 0) logp_lds[slot] = gauss_logp(n, ls0, ls1);
+                }
+                if (ok) reinterpret_cast<float*>(act_lds)[2 * slot + o] = y;
+            } else {
+#include "fg_actor_mlp.inc"
+                if constexpr (SAMPLE) {
+                    if (q < M && o == 0) logp_lds[q] = gauss_logp(n, ls0, ls1);
                 }
                 if (q < M) reinterpret_cast<float*>(act_lds)[2 * q + o] = y;
-                }
             }
             WaveSync()();                              // the tile is free for the next pass
         }

@@ -19,6 +19,9 @@
 //            the VALU, one lane per (row, output).  Layer 1 reads its input straight from the tables - the units the
 //            observation writers store - and skips the communication block (zero for silent agents).
 // No atomics: two launches from the same state and weights give the same bits.
+// The actor network after layer 1 (ReLU hand-over, layer 2, layer 3, tanh, Gaussian step) and the LDS preload of b1 | b2 | W3 |
+// b3 | log_std are fg_actor_mlp.inc and fg_actor_mlp_preload.inc, the one copy that fg_actor_rollout_body.inc and the landmark
+// scenarios' fg_scn_lane_actor_body.inc include; actor_bias_init, actor_store_tile and gauss_logp below are their small pieces.
 //
 // actor_sample_kernel<N,H> (fg_rollout_hd_actor_sample) is the same body with a state-independent diagonal Gaussian on top of
 // the actor's output: each lane (row, o) of layer 3 adds exp(log_std[o]) * eps[o], eps = actor_eps(...) drawn from the
@@ -81,6 +84,35 @@ template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false> constexpr 
 FG_DEV float2 actor_eps(uint64_t seed, uint32_t g, uint32_t i, uint64_t offset) {
     const real2 n = motor_noise(seed, g, i | 0x20000000u, offset);
     return make_float2((float)n.x, (float)n.y);
+}
+
+// The log-density of the standard-normal pair n under N(mean, diag(exp(log_std))^2) at mean + exp(log_std) n:
+// -0.5 |n|^2 - (ls0 + ls1) - log(2 pi).  The one spelling for the shared, per-agent and landmark kernels.
+FG_DEV float gauss_logp(float2 n, float ls0, float ls1) {
+    return -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
+}
+
+// The pieces of one wave pass of the actor MLP (fg_actor_mlp.inc) that layer 1 of each body shares with it.  acc: the pass's
+// accumulators, register j of lane l holding row 4 (l >> 4) + j, column l & 15 of its 16 x 16 tile; col = l & 15, kq = l >> 4.
+// The bias (H floats in LDS) as the accumulators' initial value:
+template <int RT, int CB>
+FG_DEV void actor_bias_init(f32x4 (&acc)[RT][CB], const float* bias, int col) {
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        const float bv = bias[cb * 16 + col];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bv, bv, bv, bv};
+    }
+}
+// ReLU -> the wave's activation tile hb [16 RT][HS]:
+template <int RT, int CB>
+FG_DEV void actor_store_tile(float* hb, int HS, const f32x4 (&acc)[RT][CB], int col, int kq) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hb[(rt * 16 + kq * 4 + j) * HS + cb * 16 + col] = fmaxf(acc[rt][cb][j], 0.f);
 }
 
 // One step's eps for every (env, agent) at rng_base(p) (fg_actor_noise): the host-paced loop of a Gaussian actor draws

@@ -2,7 +2,9 @@
 // Included inside each kernel, whose scope provides the kernel arguments `a` (ScnArgs: a.do_phys = 1, a.act and a.near_ag
 // unused), `w` (ActorW), `act_out`, the template parameters KIND, N, L, M, NBR, H, `constexpr bool SAMPLE` and `log_std` /
 // `logp` (SAMPLE = false: nullptr).  Not a header: no guard.  (A textual include for the reason written at the top of
-// fg_actor_rollout_body.inc.)
+// fg_actor_rollout_body.inc.)  This body holds the producer's step, the block stream and layer 1 on the composed block (one
+// padded K range); the LDS preload and everything after layer 1 are formation_hd_env's text: fg_actor_mlp_preload.inc and
+// fg_actor_mlp.inc.  Nothing per-agent is declared here.
     static_assert(!FG_F64, "the actor rollout is an fp32 kernel");
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
@@ -14,6 +16,7 @@
     constexpr bool BASIC = KIND == FG_SCN_BASIC;
     constexpr int BLOCK_UNITS = scn_lane_block_bytes(KIND, N, L, M, NBR, 1) / 8;
     constexpr int HS = actor_hstride(H), CB = H / 16, RT = FG_ACTOR_ROWS / 16;
+    constexpr int WS = 4 * H;                           // floats of b1 | b2 | W3 in LDS
     constexpr int TILES = (ENVS * N + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
     static_assert(NE <= 8 && L <= 8, "one env per lane: a handful of entities");
     static_assert(H % 16 == 0 && D % 2 == 0 && RT == 2, "bad actor geometry");
@@ -21,7 +24,7 @@
     float2* const smem = smem_all;
     float* const act_lds = reinterpret_cast<float*>(smem_all + BLOCK_UNITS);            // [64 N][2]
     float* const wsm = act_lds + 2 * ENVS * N;                                           // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + 4 * H + 4;
+    float* const hbuf = wsm + WS + 4;
 
     const int tid = threadIdx.x, lane = tid & 63;
     // consecutive workgroup ids take consecutive 64-env spans within an XCD's eighth of the batch (scn_lane_kernel's map)
@@ -37,16 +40,7 @@
     const int El = min(ENVS, a.B - b0);
     const int KS = a.K;
 
-    for (int q = tid; q < H; q += FG_SCN_ACTOR_THREADS) {
-        wsm[q] = w.b1 ? w.b1[q] : 0.f;
-        wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
-        wsm[2 * H + q] = w.w3[q];
-        wsm[3 * H + q] = w.w3[H + q];
-    }
-    if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
-    if constexpr (SAMPLE) {
-        if (tid < 2) wsm[4 * H + 2 + tid] = log_std[tid];
-    }
+#include "fg_actor_mlp_preload.inc"
 
     // the producer lane's env (wave 0; the other waves never touch these)
     float2 p[NE], v[NE], lm[L];
@@ -80,12 +74,7 @@
             }
             f32x4 acc[RT][CB];
             // ---- layer 1: K = D padded up to a multiple of 4 with zero operands ----
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const float bias = wsm[cb * 16 + col];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
-            }
+            actor_bias_init(acc, wsm, col);
             // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would all
             // be held in registers)
             const float* w1row = w.w1 + (size_t)col * D;
@@ -110,67 +99,13 @@
                         acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
                 }
             }
-            // ReLU -> activation tile: accumulator register j of lane l is row 4 (l >> 4) + j, column l & 15
-            auto store_tile = [&]() {
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            hb[(rt * 16 + kq * 4 + j) * HS + cb * 16 + col] = fmaxf(acc[rt][cb][j], 0.f);
-            };
-            store_tile();
-            WaveSync()();
-            // ---- layer 2 ----
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) {
-                const float bias = wsm[H + cb * 16 + col];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc[rt][cb] = (f32x4){bias, bias, bias, bias};
+#include "fg_actor_mlp.inc"
+            if constexpr (SAMPLE) {
+                if (logp && q < rows && o == 0) logp[out0 + q] = gauss_logp(n, ls0, ls1);
             }
-            const float* w2row = w.w2 + (size_t)col * H;
-            asm volatile("" : "+v"(w2row));
-#pragma unroll 2
-            for (int kc = 0; kc < H / 4; ++kc) {
-                const int k = kc * 4 + kq;
-                float xa[RT];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) xa[rt] = hb[(rt * 16 + col) * HS + k];
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) {
-                    const float wb = w2row[cb * 16 * H + k];
-#pragma unroll
-                    for (int rt = 0; rt < RT; ++rt)
-                        acc[rt][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[rt], wb, acc[rt][cb], 0, 0, 0);
-                }
-            }
-            WaveSync()();                              // every read of the layer-1 tile before it is overwritten
-            store_tile();
-            WaveSync()();
-            // ---- layer 3 on the VALU: lane = (row, output) ----
-            {
-                const int row = lane >> 1, o = lane & 1;
-                const float* const hr = hb + row * HS;
-                const float* const w3 = wsm + 2 * H + o * H;
-                float y = wsm[4 * H + o];
-#pragma unroll 8
-                for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
-                if (w.out_tanh) y = tanhf(y);
-                const int q = q0 + row;
-                if constexpr (SAMPLE) {
-                    // both lanes of a row draw the row's pair: lane o adds component o and lane 0 stores the log-density
-                    const int ee = q / N;
-                    const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
-                    const float ls0 = wsm[4 * H + 2], ls1 = wsm[4 * H + 3];
-                    y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
-                    if (logp && q < rows && o == 0)
-                        logp[out0 + q] = -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
-                }
-                if (q < rows) {
-                    act_lds[2 * q + o] = y;
-                    act_out[2 * out0 + 2 * q + o] = y;     // the wave's 32 rows: 256 contiguous bytes
-                }
+            if (q < rows) {
+                act_lds[2 * q + o] = y;
+                act_out[2 * out0 + 2 * q + o] = y;         // the wave's 32 rows: 256 contiguous bytes
             }
             WaveSync()();                              // the tile is free for the next pass
         }

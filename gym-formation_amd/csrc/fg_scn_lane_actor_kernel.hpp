@@ -15,7 +15,8 @@
 //             is the actor's input whether or not obs_every stores it.  Waves 1-3 wait at the barrier.
 //   stream +  all four waves store the step's block (fg_scn_lane_write.inc: observations on the obs_every steps, rewards,
 //   actor     individual rewards, done flags), then evaluate the MLP for the next step on the block's 64 N rows, 32 rows per wave
-//             pass (two 16-row tiles sharing every weight fragment) as the formation_hd_env body does: layers 1 and 2 on
+//             pass (two 16-row tiles sharing every weight fragment) with the formation_hd_env body's own text after layer 1
+//             (fg_actor_mlp.inc; the preload of the small parameters is fg_actor_mlp_preload.inc): layers 1 and 2 on
 //             v_mfma_f32_16x16x4_f32 (exact fp32, k ascending, one accumulator chain per output element, bias as the
 //             accumulator's initial value), the A operand of layer 1 straight from the block (row r of env e starts at float
 //             2 SU e + D r: the odd float2 pitch SU is per env, rows inside an env are contiguous), K = D padded to a multiple
@@ -39,6 +40,7 @@ namespace fg {
 
 constexpr int FG_SCN_ACTOR_THREADS = 256;
 constexpr int FG_SCN_ACTOR_ENVS = 64;         // one producer wave, one env per lane
+static_assert(FG_SCN_ACTOR_THREADS == FG_ACTOR_THREADS, "fg_actor_mlp_preload.inc strides by FG_ACTOR_THREADS");
 // LDS (floats): the hand-over block of scn_lane_kernel (observations [64][SU] float2 | reward | individual reward | done, each
 //               [64 N]) | actions [64 N][2] | (SAMPLE: log-probs [64 N]) | b1 [H] b2 [H] W3 [2][H] b3 [2] log_std [2] |
 //               activations [4][32][H + 4]

@@ -31,6 +31,7 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #include "fg_common.hpp"
 #include "fg_pair_loops.hpp"
@@ -64,6 +65,13 @@ struct Geometry { int G, T, E, lds; };
 // snapshot, not just a timing somebody may or may not look at.
 static thread_local char* g_describe = nullptr;
 static thread_local int g_describe_cap = 0;
+// describe mode for the calling thread while in scope; off again on every way out
+struct DescribeScope {
+    DescribeScope(char* out, int cap) { g_describe = out; g_describe_cap = cap; }
+    ~DescribeScope() { g_describe = nullptr; g_describe_cap = 0; }
+    DescribeScope(const DescribeScope&) = delete;
+    DescribeScope& operator=(const DescribeScope&) = delete;
+};
 static bool describe(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 static bool describe(const char* fmt, ...) {
     if (!g_describe) return false;
@@ -1457,28 +1465,64 @@ int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void*
 static bool actor_n_supported(int N) {
     return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
 }
-// log_std == NULL: actor_rollout_kernel (the deterministic actor); else actor_sample_kernel (the Gaussian actor)
-template <int NC, int H>
-static int launch_actor_v(const Args& a, const ActorW& w, const float* log_std, float* logp, hipStream_t st) {
+// Describe-or-launch of an actor kernel: Det (the deterministic actor; log_std == NULL) or its sampling twin Smp (the Gaussian
+// actor), which takes (log_std, logp) after Det's arguments `args`.  `targs` spells the template arguments and `unit` the word
+// before the thread count in the describe string; `lds` is the chosen kernel's.  One LDS-limit mask per kernel.
+template <auto Det, auto Smp, class... A>
+static int launch_actor_pair(const char* det_name, const char* smp_name, const char* targs, const char* unit, int grid,
+                             int threads, int envs, int lds, const char* fail_fmt, hipStream_t st, const float* log_std,
+                             float* logp, const A&... args) {
     const bool sample = log_std != nullptr;
-    constexpr int E = actor_envs(NC);
-    const int lds = sample ? actor_lds_bytes<NC, H, true>() : actor_lds_bytes<NC, H>();
-    static_assert(actor_lds_bytes<NC, H, true>() <= 160 * 1024, "actor rollout LDS");
-    const int grid = (a.B + E - 1) / E;
-    if (describe("%s<%d,%d> grid %d block %d envs/wg %d lds %d; ", sample ? "actor_sample_kernel" : "actor_rollout_kernel",
-                 NC, H, grid, FG_ACTOR_THREADS, E, lds))
+    if (describe("%s<%s> grid %d %s %d envs/wg %d lds %d; ", sample ? smp_name : det_name, targs, grid, unit, threads, envs, lds))
         return FG_OK;
     static std::atomic<unsigned long long> raised{0}, raised_sample{0};
-    hipError_t err = sample ? raise_lds_limit((const void*)&actor_sample_kernel<NC, H>, lds, &raised_sample)
-                            : raise_lds_limit((const void*)&actor_rollout_kernel<NC, H>, lds, &raised);
+    hipError_t err = sample ? raise_lds_limit((const void*)Smp, lds, &raised_sample) : raise_lds_limit((const void*)Det, lds, &raised);
     if (err == hipSuccess) {
         if (sample)
-            hipLaunchKernelGGL((actor_sample_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w, log_std, logp);
+            hipLaunchKernelGGL(Smp, dim3(grid), dim3(threads), lds, st, args..., log_std, logp);
         else
-            hipLaunchKernelGGL((actor_rollout_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, w);
+            hipLaunchKernelGGL(Det, dim3(grid), dim3(threads), lds, st, args...);
         err = hipGetLastError();
     }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor rollout launch failed: %s", hipGetErrorString(err));
+    if (err != hipSuccess) return fail(FG_ERR_HIP, fail_fmt, hipGetErrorString(err));
+    return FG_OK;
+}
+// the shared actor of formation_hd_env: actor_rollout_kernel / actor_sample_kernel
+template <int NC, int H>
+static int launch_actor_v(const Args& a, const ActorW& w, const float* log_std, float* logp, hipStream_t st) {
+    constexpr int E = actor_envs(NC);
+    static_assert(actor_lds_bytes<NC, H, true>() <= 160 * 1024, "actor rollout LDS");
+    char targs[16];
+    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    return launch_actor_pair<&actor_rollout_kernel<NC, H>, &actor_sample_kernel<NC, H>>(
+        "actor_rollout_kernel", "actor_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? actor_lds_bytes<NC, H, true>() : actor_lds_bytes<NC, H>(), "actor rollout launch failed: %s", st, log_std, logp,
+        a, w);
+}
+// The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
+// the messages name, `max_hidden` / `widths` its admissible hidden widths (32, 64 and up to max_hidden), `also` further
+// pointers that share the weights' 4-byte alignment check and `aligned` what the alignment message calls them all.
+static int actor_struct_check(const FgActor* actor, const char* who, int max_hidden, const char* widths, uintptr_t also,
+                              const char* aligned) {
+    char msg[160];
+    auto bad = [&](int code, const char* what, const char* arg = "") {
+        snprintf(msg, sizeof(msg), what, who, arg);
+        return fail(code, "%s", msg);
+    };
+    if (!actor) return bad(FG_ERR_BAD_ARG, "%s: actor is NULL");
+    if (actor->hidden != 32 && actor->hidden != 64 && !(actor->hidden == 128 && max_hidden == 128))
+        return bad(FG_ERR_BAD_ARG, "%s: hidden must be %s", widths);
+    if (!actor->w1 || !actor->w2 || !actor->w3) return bad(FG_ERR_BAD_ARG, "%s: a weight pointer is NULL");
+    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
+         (uintptr_t)actor->b3 | also) & 3u)
+        return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", aligned);
+    return FG_OK;
+}
+static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
+    const int rc = actor_struct_check(actor, "fg_rollout_hd_actor", 128, "32, 64 or 128", 0, "weights");
+    if (rc) return rc;
+    if (world_options_set(*params))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
     return FG_OK;
 }
 // the checks every actor entry shares (no device touched): FG_OK, or the status of the first one that fails
@@ -1487,16 +1531,7 @@ static int actor_check(const FgParams* params, const FgActor* actor, int B, int 
     if (rc) return rc;
     if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: B >= 0 and K >= 1 required%s");
     if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
-    if (!actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: actor is NULL%s");
-    if (actor->hidden != 32 && actor->hidden != 64 && actor->hidden != 128)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: hidden must be 32, 64 or 128%s");
-    if (!actor->w1 || !actor->w2 || !actor->w3) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a weight pointer is NULL%s");
-    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
-         (uintptr_t)actor->b3) & 3u)
-        return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor: weights must be 4-byte aligned%s");
-    if (world_options_set(*params))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
-    return FG_OK;
+    return hd_actor_struct_check(params, actor);
 }
 // the Gaussian actor's extra argument: FG_OK or the status of the first check that fails (no device touched)
 static int actor_sample_check(const float* log_std) {
@@ -1504,43 +1539,38 @@ static int actor_sample_check(const float* log_std) {
     if ((uintptr_t)log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
     return FG_OK;
 }
-static int actor_dispatch(const Args& a, const FgActor& actor, const float* log_std, float* logp, hipStream_t st) {
-    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+// The (N, H) instantiations of the formation_hd_env actor kernels, shared and per-agent: launch(n, h) with N and H as the
+// `value` of the arguments' types, or `unsupported` when N is not in the list (hidden is 32, 64 or 128: actor_struct_check).
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F>
+static int actor_nh_dispatch(int N, int hidden, const char* unsupported, F&& launch) {
 #define FG_ACTOR(NN) \
-    if (a.N == NN) return actor.hidden == 32 ? launch_actor_v<NN, 32>(a, w, log_std, logp, st) \
-                        : actor.hidden == 64 ? launch_actor_v<NN, 64>(a, w, log_std, logp, st)  \
-                                             : launch_actor_v<NN, 128>(a, w, log_std, logp, st);
+    if (N == NN) return hidden == 32 ? launch(IntC<NN>{}, IntC<32>{}) : hidden == 64 ? launch(IntC<NN>{}, IntC<64>{}) \
+                                                                                    : launch(IntC<NN>{}, IntC<128>{});
     FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
 #undef FG_ACTOR
-    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    return fail(FG_ERR_UNSUPPORTED_N, unsupported);
+}
+static int actor_dispatch(const Args& a, const FgActor& actor, const float* log_std, float* logp, hipStream_t st) {
+    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+    return actor_nh_dispatch(a.N, actor.hidden, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s", [&](auto n, auto h) {
+        return launch_actor_v<decltype(n)::value, decltype(h)::value>(a, w, log_std, logp, st);
+    });
 }
 
 // ---- one actor per agent (pa_actor_kernel / pa_sample_kernel) ----
-// log_std == NULL: pa_actor_kernel (deterministic); else pa_sample_kernel (the Gaussian on top of the per-agent means)
 template <int NC, int H>
 static int launch_pa_v(const Args& a, const ActorTab& tab, const float* log_std, float* logp, hipStream_t st) {
-    const bool sample = log_std != nullptr;
     constexpr int E = actor_envs(NC);
-    const int lds = sample ? actor_lds_bytes<NC, H, true, true>() : actor_lds_bytes<NC, H, false, true>();
     static_assert(actor_lds_bytes<NC, H, true, true>() <= 160 * 1024, "per-agent actor rollout LDS");
-    const int grid = (a.B + E - 1) / E;
-    if (describe("%s<%d,%d> grid %d block %d envs/wg %d lds %d; ", sample ? "pa_sample_kernel" : "pa_actor_kernel",
-                 NC, H, grid, FG_ACTOR_THREADS, E, lds))
-        return FG_OK;
-    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
-    hipError_t err = sample ? raise_lds_limit((const void*)&pa_sample_kernel<NC, H>, lds, &raised_sample)
-                            : raise_lds_limit((const void*)&pa_actor_kernel<NC, H>, lds, &raised);
-    if (err == hipSuccess) {
-        if (sample)
-            hipLaunchKernelGGL((pa_sample_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, tab, log_std, logp);
-        else
-            hipLaunchKernelGGL((pa_actor_kernel<NC, H>), dim3(grid), dim3(FG_ACTOR_THREADS), lds, st, a, tab);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "per-agent actor rollout launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    char targs[16];
+    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    return launch_actor_pair<&pa_actor_kernel<NC, H>, &pa_sample_kernel<NC, H>>(
+        "pa_actor_kernel", "pa_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? actor_lds_bytes<NC, H, true, true>() : actor_lds_bytes<NC, H, false, true>(),
+        "per-agent actor rollout launch failed: %s", st, log_std, logp, a, tab);
 }
-// actor_check on every member, then: every member has member 0's hidden width and tanh flag (no device touched)
+// the FgActor checks on every member, then: every member has member 0's hidden width and tanh flag (no device touched)
 static int actor_per_agent_check(const FgParams* params, const FgActor* actors, int B, int N, int K) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1550,7 +1580,7 @@ static int actor_per_agent_check(const FgParams* params, const FgActor* actors, 
     if (!actors) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
     char idx[16];
     for (int i = 0; i < N; ++i) {
-        if ((rc = actor_check(params, &actors[i], B, N, K)) != FG_OK) return rc;
+        if ((rc = hd_actor_struct_check(params, &actors[i])) != FG_OK) return rc;
         if (actors[i].hidden != actors[0].hidden || (actors[i].out_tanh != 0) != (actors[0].out_tanh != 0)) {
             snprintf(idx, sizeof(idx), "%d", i);
             return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
@@ -1567,19 +1597,11 @@ static int actor_per_agent_dispatch(const Args& a, const FgActor* actors, const 
         tab.b2[i] = actors[i].b2; tab.w3[i] = actors[i].w3; tab.b3[i] = actors[i].b3;
     }
     tab.out_tanh = actors[0].out_tanh ? 1 : 0;
-    const int hidden = actors[0].hidden;
-#define FG_ACTOR(NN) \
-    if (a.N == NN) return hidden == 32 ? launch_pa_v<NN, 32>(a, tab, log_std, logp, st) \
-                        : hidden == 64 ? launch_pa_v<NN, 64>(a, tab, log_std, logp, st)  \
-                                       : launch_pa_v<NN, 128>(a, tab, log_std, logp, st);
-    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
-#undef FG_ACTOR
-    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    return actor_nh_dispatch(a.N, actors[0].hidden, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s",
+                             [&](auto n, auto h) {
+        return launch_pa_v<decltype(n)::value, decltype(h)::value>(a, tab, log_std, logp, st);
+    });
 }
-
-extern "C" {
-
-}  // extern "C"
 
 // per_agent: `actor` is a host array of N members (actor_per_agent_dispatch), else the one shared actor
 static int rollout_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
@@ -1675,11 +1697,9 @@ static int describe_actor_impl(const FgParams* params, const FgActor* actor, con
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
     int rc = set_obs_pitch(&a);
     if (rc != FG_OK) return rc;
-    g_describe = out; g_describe_cap = out_len;
-    rc = per_agent ? actor_per_agent_dispatch(a, actor, log_std, nullptr, nullptr)
-                   : actor_dispatch(a, *actor, log_std, nullptr, nullptr);
-    g_describe = nullptr; g_describe_cap = 0;
-    return rc;
+    const DescribeScope describing(out, out_len);
+    return per_agent ? actor_per_agent_dispatch(a, actor, log_std, nullptr, nullptr)
+                     : actor_dispatch(a, *actor, log_std, nullptr, nullptr);
 }
 
 extern "C" {
@@ -1719,26 +1739,13 @@ int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* ac
 // log_std == NULL: scn_lane_actor (the deterministic actor); else scn_lane_actor_gauss (the Gaussian actor)
 template <int KIND, int NN, int LL, int MM, int NBR, int H>
 static int launch_scn_actor(const ScnArgs& a, const ActorW& w, float* act_out, const float* log_std, float* logp, hipStream_t st) {
-    const bool sample = log_std != nullptr;
-    const int lds = scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, sample);
     static_assert(scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, true) <= 160 * 1024, "scenario actor rollout LDS");
-    const int grid = 8 * (((a.B + FG_SCN_ACTOR_ENVS - 1) / FG_SCN_ACTOR_ENVS + 7) / 8);
-    if (describe("%s<%d,%d,%d,%d,%d,%d> grid %d threads %d envs/wg %d lds %d; ", sample ? "scn_lane_actor_gauss" : "scn_lane_actor",
-                 KIND, NN, LL, MM, NBR, H, grid, FG_SCN_ACTOR_THREADS, FG_SCN_ACTOR_ENVS, lds)) return FG_OK;
-    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
-    hipError_t err = sample ? raise_lds_limit((const void*)&scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>, lds, &raised_sample)
-                            : raise_lds_limit((const void*)&scn_lane_actor<KIND, NN, LL, MM, NBR, H>, lds, &raised);
-    if (err == hipSuccess) {
-        if (sample)
-            hipLaunchKernelGGL((scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>), dim3(grid), dim3(FG_SCN_ACTOR_THREADS), lds, st,
-                               a, w, act_out, log_std, logp);
-        else
-            hipLaunchKernelGGL((scn_lane_actor<KIND, NN, LL, MM, NBR, H>), dim3(grid), dim3(FG_SCN_ACTOR_THREADS), lds, st,
-                               a, w, act_out);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario actor rollout launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    char targs[48];
+    snprintf(targs, sizeof(targs), "%d,%d,%d,%d,%d,%d", KIND, NN, LL, MM, NBR, H);
+    return launch_actor_pair<&scn_lane_actor<KIND, NN, LL, MM, NBR, H>, &scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>>(
+        "scn_lane_actor", "scn_lane_actor_gauss", targs, "threads", 8 * (((a.B + FG_SCN_ACTOR_ENVS - 1) / FG_SCN_ACTOR_ENVS + 7) / 8),
+        FG_SCN_ACTOR_THREADS, FG_SCN_ACTOR_ENVS, scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, log_std != nullptr),
+        "scenario actor rollout launch failed: %s", st, log_std, logp, a, w, act_out);
 }
 
 // the checks both scenario-actor entries share (no device touched): FG_OK, or the status of the first one that fails
@@ -1750,13 +1757,9 @@ static int scn_actor_check(const FgParams* params, const FgScenario* sc, const F
     if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: B >= 0 and K >= 1 required%s");
     if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: unknown scenario kind%s");
-    if (!actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: actor is NULL%s");
-    if (actor->hidden != 32 && actor->hidden != 64)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: hidden must be 32 or 64%s");
-    if (!actor->w1 || !actor->w2 || !actor->w3) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: a weight pointer is NULL%s");
-    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
-         (uintptr_t)actor->b3 | (uintptr_t)log_std | (uintptr_t)logp) & 3u)
-        return fail(FG_ERR_ALIGNMENT, "fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned%s");
+    if ((rc = actor_struct_check(actor, "fg_rollout_scenario_actor", 64, "32 or 64", (uintptr_t)log_std | (uintptr_t)logp,
+                                 "weights, log_std and logp")) != FG_OK)
+        return rc;
     if (!log_std && logp) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: logp without log_std%s");
     if (params->agent_props || params->comm_state || sc->variant == 1)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported%s");
@@ -1810,10 +1813,9 @@ int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario
     scn_actor_args(&a, params, scenario, B, N, K, obs_every);
     if (B == 0) {                                      // nothing to launch; an unsupported shape is still reported
         char dry[8];
-        g_describe = dry; g_describe_cap = (int)sizeof(dry); dry[0] = 0; a.B = 1;
-        rc = scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
-        g_describe = nullptr; g_describe_cap = 0;
-        return rc;
+        dry[0] = 0; a.B = 1;
+        const DescribeScope describing(dry, (int)sizeof(dry));
+        return scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
     }
     const DeviceGuard device_guard(stream, pos_x);
     a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.lm = landmarks; a.opos = obst_pos; a.ovel = obst_vel; a.step = step;
@@ -1830,10 +1832,8 @@ int fg_describe_scenario_actor_launch(const FgParams* params, const FgScenario* 
     if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_scenario_actor_launch: B > 0 required%s");
     ScnArgs a;
     scn_actor_args(&a, params, scenario, B, N, K, obs_every);
-    g_describe = out; g_describe_cap = out_len;
-    rc = scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
-    g_describe = nullptr; g_describe_cap = 0;
-    return rc;
+    const DescribeScope describing(out, out_len);
+    return scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
 }
 
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,
@@ -1847,7 +1847,7 @@ int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B
     float* const f = reinterpret_cast<float*>((uintptr_t)4096);
     int32_t* const i32 = reinterpret_cast<int32_t*>((uintptr_t)4096);
     uint8_t* const u8 = reinterpret_cast<uint8_t*>((uintptr_t)4096);
-    g_describe = out; g_describe_cap = out_len;
+    const DescribeScope describing(out, out_len);
     if (scenario) {
         rc = launch_scenario(params, scenario, B, N, 1, f, f, f, f, f, f, scenario->num_obstacles ? f : nullptr,
                              scenario->num_obstacles ? f : nullptr, i32, f, f, f, u8, nullptr, nullptr, K < 1 ? 1 : K,
@@ -1873,7 +1873,6 @@ int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B
             }
         }
     }
-    g_describe = nullptr; g_describe_cap = 0;
     return rc;
 }
 

@@ -191,6 +191,19 @@ def check(code):
         raise FormationHipError(code, load().fg_last_error().decode("utf-8", "replace"))
 
 
+def bind_launch(fn, p, *args, keep=None):
+    """`launch(rng_offset)` for a bound K-step launch: sets the FgParams struct `p`'s RNG offset, makes the ONE ctypes call
+    `fn(p, *args)` with everything else resolved by the caller, raises on a non-zero status and returns `keep` - what the
+    launch reads in place and must outlive it.  The closure is the only Python frame per launch."""
+    def launch(rng_offset=0):
+        p.rng_offset = rng_offset
+        rc = fn(p, *args)
+        if rc:
+            check(rc)
+        return keep
+    return launch
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

@@ -17,8 +17,10 @@ The landmark scenarios (basic_formation_env, formation_hd_partial_env, formation
 fuse too (`fg_rollout_scenario_actor`), under the same rule with their own facts: the input width is the scenario's observation
 width D instead of 6N, H in {32, 64}, and the shape is one of the seven the one-env-per-lane kernel is built for
 (LANDMARK_FUSED_SHAPES).  H = 128 and a PerAgentActor run host-paced there.  The scenario states these facts
-(`ActorRolloutMixin.actor_fused_rule`) and `MultiAgentEnv.actor_path` hands them to the functions below as keyword
-arguments, whose defaults are formation_hd_env's."""
+(`ActorRolloutMixin.actor_fused_rule`) and `MultiAgentEnv` hands them to `resolve_actor` below as keyword arguments, whose
+defaults are formation_hd_env's.  `resolve_actor` answers the whole question once per call: None (host-paced) or the
+FusedActor record the scenario's `bind_rollout_actor` takes."""
+import collections
 import math
 
 import torch
@@ -161,20 +163,42 @@ def sample_spec(actor, num_agents, device=None, **facts):
     return spec, ls
 
 
-def actor_path(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
-               callback=False, per_agent=True, **facts):
-    """'fused' or 'host': the one decision `MultiAgentEnv.actor_path` / `rollout_actor` take.  The keyword facts describe the
-    env: a scenario with the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls,
-    accel, max_speed, u_noise, per-agent properties), no post_step_callback.  `per_agent`: the scenario's launch takes a
-    PerAgentActor (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's keyword arguments
-    (in_features, fused_n, fused_hidden), as the scenario states them."""
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std")):
+    """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
+    [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
+    N for a PerAgentActor (`per_agent`) - and `log_std`, a GaussianActor's [2] parameter (None: deterministic)."""
+    __slots__ = ()
+
+
+def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
+                  callback=False, per_agent=True, **facts):
+    """The one decision `MultiAgentEnv.actor_path` / `rollout_actor` take, with what the launch needs: a FusedActor when
+    `rollout_actor(K, actor)` runs fused, None when it runs host-paced.  The keyword facts describe the env: a scenario with
+    the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls, accel, max_speed,
+    u_noise, per-agent properties), no post_step_callback.  `per_agent`: the scenario's launch takes a PerAgentActor
+    (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's keyword arguments (in_features,
+    fused_n, fused_hidden), as the scenario states them."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
-        return "host"
-    mean = actor.mean if isinstance(actor, GaussianActor) else actor
-    if isinstance(mean, PerAgentActor) and not per_agent:
-        return "host"
-    if isinstance(actor, GaussianActor):
-        return "fused" if sample_spec(actor, num_agents, device, **facts) is not None else "host"
-    if isinstance(actor, PerAgentActor):
-        return "fused" if per_agent_spec(actor, num_agents, device) is not None else "host"
-    return "fused" if actor_spec(actor, num_agents, device, **facts) is not None else "host"
+        return None
+    gaussian = isinstance(actor, GaussianActor)
+    members_own = isinstance(actor.mean if gaussian else actor, PerAgentActor)
+    if members_own and not per_agent:
+        return None
+    log_std = None
+    if gaussian:
+        spec = sample_spec(actor, num_agents, device, **facts)
+        if spec is not None:
+            spec, log_std = spec
+    elif members_own:
+        spec = per_agent_spec(actor, num_agents, device)
+    else:
+        spec = actor_spec(actor, num_agents, device, **facts)
+    if spec is None:
+        return None
+    hidden, out_tanh, weights = spec
+    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std)
+
+
+def actor_path(actor, num_agents, device=None, **facts):
+    """'fused' or 'host': whether `resolve_actor` (same arguments) finds a fused launch."""
+    return "host" if resolve_actor(actor, num_agents, device, **facts) is None else "fused"

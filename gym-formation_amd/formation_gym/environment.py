@@ -353,6 +353,11 @@ class MultiAgentEnv(object):
     def actor_path(self, actor):
         """'fused' when `rollout_actor(K, actor)` runs as ONE launch with the actor inside the rollout kernel
         (`fg_rollout_hd_actor`), 'host' when it runs the host-paced loop.  The rules: formation_gym/actor_rollout.py."""
+        return "host" if self._resolve_actor(actor) is None else "fused"
+
+    def _resolve_actor(self, actor):
+        """`actor_rollout.resolve_actor` with this env's facts: the FusedActor record of the fused launch, or None (host-paced).
+        The one resolution `actor_path` and `rollout_actor` share."""
         sc = self.scenario
         fused = getattr(sc, "bind_rollout_actor", None) is not None
         world_options = False
@@ -367,12 +372,13 @@ class MultiAgentEnv(object):
         facts = self._actor_facts() if fused else {}
         if facts is None:                                  # a landmark scenario at a shape without the fused launch
             fused, facts = False, {}
-        return actor_rollout.actor_path(actor, self.num_agents, self.world.device, fused_scenario=fused,
-                                        continuous=not self._action_mode(), silent=not self.world.any_non_silent(),
-                                        world_options=world_options, callback=self.post_step_callback is not None, **facts)
+        return actor_rollout.resolve_actor(actor, self.num_agents, self.world.device, fused_scenario=fused,
+                                           continuous=not self._action_mode(), silent=not self.world.any_non_silent(),
+                                           world_options=world_options, callback=self.post_step_callback is not None,
+                                           **facts)
 
     def _actor_facts(self):
-        """The scenario's own facts for `actor_rollout.actor_path` / `actor_spec` (input width, admissible agent counts and
+        """The scenario's own facts for `actor_rollout.resolve_actor` (input width, admissible agent counts and
         hidden widths, whether a PerAgentActor fuses): {} for formation_hd_env (the functions' defaults), a landmark
         scenario's `actor_fused_rule(world)` - None where its shape has no fused launch."""
         rule = getattr(self.scenario, "actor_fused_rule", None)
@@ -407,19 +413,11 @@ class MultiAgentEnv(object):
         K, obs_every = int(K), int(obs_every)
         if K < 1 or obs_every < 1:
             raise ValueError("need K >= 1 steps and obs_every >= 1")
-        gaussian = isinstance(actor, actor_rollout.GaussianActor)
-        if self.actor_path(actor) == "host":
+        fused = self._resolve_actor(actor)
+        if fused is None:
             return self._rollout_actor_by_steps(K, actor, obs_every)
-        log_std = None
-        facts = {k: v for k, v in self._actor_facts().items() if k != "per_agent"}     # actor_spec's keyword arguments
-        if gaussian:
-            (hidden, out_tanh, weights), log_std = actor_rollout.sample_spec(actor, self.num_agents, self.world.device, **facts)
-        elif isinstance(actor, actor_rollout.PerAgentActor):
-            hidden, out_tanh, weights = actor_rollout.per_agent_spec(actor, self.num_agents, self.world.device)
-        else:
-            hidden, out_tanh, weights = actor_rollout.actor_spec(actor, self.num_agents, self.world.device, **facts)
-        per_agent = bool(weights) and isinstance(weights[0], list)      # per_agent_spec: one weight list per agent
-        flat = [t for ws in weights for t in ws] if per_agent else weights
+        log_std = fused.log_std
+        gaussian = log_std is not None
         B, N = self.num_envs, self.num_agents
         D = self._out["obs"].shape[-1]
         f = dict(dtype=torch.float32, device=self._act.device)
@@ -441,7 +439,8 @@ class MultiAgentEnv(object):
         # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
         key = None
         if own_buffers and all(k in out for k in want):
-            key = ("actor", K, hidden, bool(out_tanh), per_agent, tuple(0 if t is None else t.data_ptr() for t in flat),
+            key = ("actor", K, fused.hidden, fused.out_tanh, fused.per_agent,
+                   tuple(0 if t is None else t.data_ptr() for ws in fused.members for t in ws),
                    0 if log_std is None else log_std.data_ptr(),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
@@ -451,8 +450,8 @@ class MultiAgentEnv(object):
             for k, shp in want.items():
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
-            launch = self.scenario.bind_rollout_actor(self.world, K, (hidden, out_tanh, weights), out, obs_every=obs_every,
-                                                      auto_reset=self.auto_reset, log_std=log_std)
+            launch = self.scenario.bind_rollout_actor(self.world, K, fused, out, obs_every=obs_every,
+                                                      auto_reset=self.auto_reset)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()

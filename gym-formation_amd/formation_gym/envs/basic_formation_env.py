@@ -146,14 +146,7 @@ class Scenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
         p, d = self.params(world, auto_reset=auto_reset), self._descriptor(world)
         args = self._rollout_args(world, act_seq, out, obs_every)
         keep = (act_seq, out)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, d, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
+        return _native.bind_launch(fn, p, d, *args, keep=keep)
 
     def reset_device(self, world, mask=None, rng_offset=0):
         """Throughput-mode reset on the GPU (counter RNG, distributional parity only): the draws the fused auto-reset makes."""

@@ -251,76 +251,36 @@ class Scenario(BaseScenario):
                 world.step_count.data_ptr(),
                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
-        fn = lib.fg_rollout_hd_policy
-        keep = out
+        return _native.bind_launch(lib.fg_rollout_hd_policy, p, *args, keep=out)
 
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
-
-    def bind_rollout_actor(self, world, K, spec, out, obs_every=1, auto_reset=False, log_std=None):
-        """K closed-loop steps with the caller's MLP actor (`fg_rollout_hd_actor`), every pointer and the FgParams struct
-        resolved once: returns `launch(rng_offset)`.  spec = (hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) from
-        `actor_rollout.actor_spec`; the kernel reads those tensors in place at every launch, and the launcher keeps them
-        alive.  out["act"] [K,B,N,2] receives the actions taken, the other tensors are those of `rollout_batch`.
-        log_std [2] (a GaussianActor's, read in place like the weights): the sampling launch
-        (`fg_rollout_hd_actor_sample`), with the actions' log-densities in out["log_prob"] [K,B,N].
-        spec from `actor_rollout.per_agent_spec` (one weight list per agent): `fg_rollout_hd_actor_per_agent`, agent i's rows
-        through agent i's weights, every member's tensors kept alive."""
+    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
+        """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
+        `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
+        in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
+        other tensors are those of `rollout_batch`.  The entry point by (per_agent, log_std):
+          one shared actor                      `fg_rollout_hd_actor`
+          ... with a GaussianActor's log_std    `fg_rollout_hd_actor_sample`, the log-densities in out["log_prob"] [K,B,N]
+          one actor per agent                   `fg_rollout_hd_actor_per_agent` (log_std or NULL), agent i's rows through
+                                                member i's weights"""
         lib = _native.load()
-        hidden, out_tanh, weights = spec
-        if weights and isinstance(weights[0], list):
-            return self._bind_rollout_actor_per_agent(lib, world, K, spec, out, obs_every, auto_reset, log_std)
-        fa = _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in weights])
+        log_std = actor.log_std
+        fas = (_native.FgActor * len(actor.members))(*[
+            _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
         p = self.params(world, auto_reset, 0, out.get("obs"))
-        args = (world.num_envs, len(world.agents), int(K),
-                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                world.step_count.data_ptr(),
-                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
-        fn = lib.fg_rollout_hd_actor
-        keep = (out, tuple(weights), fa)
-        if log_std is not None:
-            fn = lib.fg_rollout_hd_actor_sample
-            keep = keep + (log_std,)
-            args = (log_std.data_ptr(),) + args[:-2] + (out["log_prob"].data_ptr(),) + args[-2:]
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, fa, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
-
-    def _bind_rollout_actor_per_agent(self, lib, world, K, spec, out, obs_every, auto_reset, log_std):
-        hidden, out_tanh, members = spec
-        fas = (_native.FgActor * len(members))(*[
-            _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in ws])
-            for ws in members])
-        p = self.params(world, auto_reset, 0, out.get("obs"))
-        args = (None if log_std is None else log_std.data_ptr(), world.num_envs, len(world.agents), int(K),
-                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                world.step_count.data_ptr(),
-                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                _native.ptr(out.get("done")), None if log_std is None else out["log_prob"].data_ptr(),
-                int(obs_every), _native.current_stream(world.device))
-        fn = lib.fg_rollout_hd_actor_per_agent
-        keep = (out, tuple(tuple(ws) for ws in members), fas, log_std)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, fas, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
+        state = (world.num_envs, len(world.agents), int(K),
+                 world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                 out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
+                 world.step_count.data_ptr(),
+                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
+                 _native.ptr(out.get("done")))
+        tail = (int(obs_every), _native.current_stream(world.device))
+        if actor.per_agent or log_std is not None:
+            fn = lib.fg_rollout_hd_actor_per_agent if actor.per_agent else lib.fg_rollout_hd_actor_sample
+            logp = None if log_std is None else out["log_prob"].data_ptr()
+            args = (fas, _native.ptr(log_std)) + state + (logp,) + tail
+        else:
+            fn, args = lib.fg_rollout_hd_actor, (fas,) + state + tail
+        return _native.bind_launch(fn, p, *args, keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std))
 
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the
@@ -346,16 +306,7 @@ class Scenario(BaseScenario):
                 world.step_count.data_ptr(),
                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
-        fn = lib.fg_rollout_hd
-        keep = (act_seq, out)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
+        return _native.bind_launch(lib.fg_rollout_hd, p, *args, keep=(act_seq, out))
 
     def upload_mt_streams(self, world):
         """Copy every env's legacy MT19937 state (RandomState(seed + 1000 b), at its CURRENT

@@ -78,7 +78,7 @@ class ActorRolloutMixin(object):
         return self._descriptor(world) if hasattr(self, "_descriptor") else self.descriptor()
 
     def actor_fused_rule(self, world):
-        """The facts `actor_rollout.actor_path` needs when this world's shape has a fused actor launch - the seven shapes of
+        """The facts `actor_rollout.resolve_actor` needs when this world's shape has a fused actor launch - the seven shapes of
         the one-env-per-lane kernel, not the run-time-count kernel (`kernel_variant = 1`) - else None: host-paced.  (World
         options and per-agent properties are `MultiAgentEnv.actor_path`'s own checks, as for formation_hd_env.)"""
         from formation_gym import actor_rollout
@@ -86,31 +86,23 @@ class ActorRolloutMixin(object):
         return actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
                                             self.obs_dim(world), d.variant)
 
-    def bind_rollout_actor(self, world, K, spec, out, obs_every=1, auto_reset=False, log_std=None):
+    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs
-        resolved once: returns `launch(rng_offset)`.  spec = (hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) from
-        `actor_rollout.actor_spec`; the kernel reads those tensors (and log_std [2], a GaussianActor's) in place at every
-        launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, out["log_prob"] [K,B,N]
-        the log-densities of a Gaussian actor's, the other tensors are those of `rollout_batch`."""
+        resolved once: returns `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`, one
+        shared actor; the kernel reads its tensors (and log_std [2], a GaussianActor's) in place at every launch, and the
+        launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, out["log_prob"] [K,B,N] the
+        log-densities of a Gaussian actor's, the other tensors are those of `rollout_batch`."""
         fn = _native.load().fg_rollout_scenario_actor
-        hidden, out_tanh, weights = spec
-        if weights and isinstance(weights[0], list):
+        if actor.per_agent:
             raise NotImplementedError("one actor per agent has no fused launch in %s" % type(self).__name__)
-        fa = _native.FgActor(int(hidden), int(bool(out_tanh)), *[None if t is None else t.data_ptr() for t in weights])
+        weights, log_std = actor.members[0], actor.log_std
+        fa = _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in weights])
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)
         # _rollout_args with the recorded actions in the place of the action sequence: (B, N, K, state ..., act, landmarks, ...)
         r = self._rollout_args(world, out["act"][:int(K)], out, obs_every)
-        args = (None if log_std is None else log_std.data_ptr(),) + r[:7] + r[8:16] + \
+        args = (_native.ptr(log_std),) + r[:7] + r[8:16] + \
                (r[7], None if log_std is None else out["log_prob"].data_ptr(), r[17], r[18])
-        keep = (out, tuple(weights), fa, log_std)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, d, fa, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
+        return _native.bind_launch(fn, p, d, fa, *args, keep=(out, tuple(weights), fa, log_std))
 
 
 class LandmarkScenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
@@ -288,14 +280,7 @@ class LandmarkScenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
         p, d = self.params(world, auto_reset=auto_reset), self.descriptor()
         args = self._rollout_args(world, act_seq, out, obs_every)
         keep = (act_seq, out)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, d, *args)
-            if rc:
-                _native.check(rc)
-            return keep
-        return launch
+        return _native.bind_launch(fn, p, d, *args, keep=keep)
 
     def reset_device(self, world, mask=None, rng_offset=0):
         """Throughput-mode reset on the GPU (counter RNG, distributional parity only): the draws the fused auto-reset makes."""

@@ -107,6 +107,7 @@ def test_environment_uses_the_scenario_rule():
                                                 comm_state=None)
     env = types.SimpleNamespace(scenario=sc, world=world, num_agents=4, post_step_callback=None, _action_mode=lambda: 0)
     env._actor_facts = lambda: MultiAgentEnv._actor_facts(env)
+    env._resolve_actor = lambda actor: MultiAgentEnv._resolve_actor(env, actor)
     assert MultiAgentEnv.actor_path(env, _mlp(28, 64)) == "fused"
     assert MultiAgentEnv.actor_path(env, _mlp(24, 64)) == "host"
     assert MultiAgentEnv.actor_path(env, PerAgentActor([_mlp(28, 64) for _ in range(4)])) == "host"
@@ -247,10 +248,7 @@ def test_landmark_actor_kernels_resources():
     kernel could not launch, and up to 512 the LDS footprint (36-74 KiB), not the registers, limits workgroups per CU to two -
     a second workgroup per CU needs <= 256 registers, which the widest shapes (obstacle, H = 64) exceed and run one workgroup
     per CU for; that is recorded in profiles/actor_landmark.md, not asserted."""
-    import re
-    import subprocess
-    import tempfile
-    from tests.isa_scan import LLVM_BIN, kernel_resources
+    from tests.isa_scan import kernel_disassembly, kernel_resources
     ks = [k for k in kernel_resources(LIB) if "scn_lane_actor" in k["demangled"]]
     assert len(ks) == 28
     assert len([k for k in ks if "scn_lane_actor<" in k["demangled"]]) == 14
@@ -259,29 +257,9 @@ def test_landmark_actor_kernels_resources():
         assert k["private_segment"] == 0 and k["vgpr_spill"] == 0, k
         assert k["vgpr"] <= 512, k
     # instruction scan of the 28 kernels' code
-    with tempfile.TemporaryDirectory() as tmp:
-        local = os.path.join(tmp, "lib.so")
-        with open(LIB, "rb") as src, open(local, "wb") as dst:
-            dst.write(src.read())
-        subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "--offloading", local], check=True, cwd=tmp,
-                       stdout=subprocess.DEVNULL)
-        objs = [f for f in os.listdir(tmp) if "gfx950" in f]
-        assert objs
-        text = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", "--no-show-raw-insn", os.path.join(tmp, objs[0])],
-                              check=True, capture_output=True, text=True).stdout
     wanted = {k["name"] for k in ks}
-    seen, cur = {}, None
-    for line in text.split("\n"):
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            cur = m.group(1) if m.group(1) in wanted else None
-            if cur:
-                seen[cur] = {"mfma": 0, "atomic": 0}
-        elif cur and line.strip():
-            if "v_mfma_f32_16x16x4" in line:
-                seen[cur]["mfma"] += 1
-            if "atomic" in line:
-                seen[cur]["atomic"] += 1
+    seen = {name: {"mfma": sum("v_mfma_f32_16x16x4" in ins for ins in code), "atomic": sum("atomic" in ins for ins in code)}
+            for name, code in kernel_disassembly(LIB).items() if name in wanted}
     assert set(seen) == wanted
     for name, c in seen.items():
         assert c["mfma"] > 0 and c["atomic"] == 0, (name, c)

@@ -2,8 +2,6 @@
 dry-run description of the fused launch, argument checks that touch no device, and the new kernels' resources."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -36,6 +34,35 @@ def test_per_agent_actor_fuses_for_every_shape(H, tanh):
         hidden, out_tanh, members = per_agent_spec(pa, N)
         assert (hidden, out_tanh) == (H, tanh) and len(members) == N and all(len(ws) == 6 for ws in members)
         assert members[-1][0] is pa.actors[-1][0].weight
+
+
+def test_resolve_actor_returns_one_record_for_every_kind():
+    """The record `MultiAgentEnv.rollout_actor` hands to `bind_rollout_actor`: the members are the actors' own tensors, one
+    entry for a shared actor and N for a PerAgentActor; the env's facts and the scenario's per_agent fact send it host-paced."""
+    from formation_gym.actor_rollout import actor_spec, landmark_facts, resolve_actor
+    N, H = 9, 64
+    shared, pa = _mlp(N, H, True), _pa(N, H, False)
+    r = resolve_actor(shared, N)
+    assert (r.hidden, r.out_tanh, r.per_agent, r.log_std) == (H, True, False, None)
+    assert len(r.members) == 1 and all(x is y for x, y in zip(r.members[0], actor_spec(shared, N)[2]))
+    g = GaussianActor(shared)
+    r = resolve_actor(g, N)
+    assert r.log_std is g.log_std and not r.per_agent and r.members[0][0] is shared[0].weight
+    r = resolve_actor(pa, N)
+    assert (r.hidden, r.out_tanh, r.per_agent, r.log_std) == (H, False, True, None) and len(r.members) == N
+    assert all(ws[0] is a[0].weight and len(ws) == 6 for ws, a in zip(r.members, pa.actors))
+    g = GaussianActor(pa)
+    r = resolve_actor(g, N)
+    assert r.per_agent and r.log_std is g.log_std and len(r.members) == N
+    with pytest.raises(AttributeError):
+        r.hidden = 32                                     # immutable
+    for actor in (shared, pa, g):
+        assert resolve_actor(actor, N, callback=True) is None and actor_path(actor, N, callback=True) == "host"
+        assert resolve_actor(actor, N, world_options=True) is None and resolve_actor(actor, N, silent=False) is None
+    assert resolve_actor(pa, N, per_agent=False) is None and resolve_actor(shared, N, per_agent=False) is not None
+    assert resolve_actor(_mlp(N, 48, True), N) is None and resolve_actor(lambda o: o, N) is None
+    facts = landmark_facts(1, 3, 3, 0, 0, 18)
+    assert resolve_actor(_mlp(3, 64, True), 3, **facts).hidden == 64 and resolve_actor(_pa(3, 64, True), 3, **facts) is None
 
 
 def test_bias_free_member_fuses():
@@ -162,30 +189,8 @@ def test_bad_arguments_rejected_without_a_device():
     assert _describe(lib, 9, 64, actors=misaligned)[0] == -3
 
 
-def _kernarg_sizes():
-    """.kernarg_segment_size of every kernel in the gfx950 code object, by mangled name."""
-    import shutil
-    import tempfile
-    from tests.isa_scan import LLVM_BIN
-    tmp = tempfile.mkdtemp(prefix="fg_kernarg_")
-    try:
-        local = os.path.join(tmp, "lib.so")
-        shutil.copy(LIB, local)
-        subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "--offloading", local], check=True, cwd=tmp,
-                       stdout=subprocess.DEVNULL)
-        obj = [f for f in os.listdir(tmp) if f.endswith("gfx950")][0]
-        notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", os.path.join(tmp, obj)], check=True,
-                               capture_output=True, text=True).stdout
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    out = {}
-    for block in re.split(r"\n\s+- \.agpr_count", notes)[1:]:
-        out[re.search(r"\.name:\s+(\S+)", block).group(1)] = int(re.search(r"\.kernarg_segment_size:\s+(\d+)", block).group(1))
-    return out
-
-
 def test_per_agent_kernels_use_no_scratch():
-    from tests.isa_scan import kernel_resources
+    from tests.isa_scan import kernarg_sizes, kernel_resources
     ks = kernel_resources(LIB)
     for kern in ("pa_actor_kernel<", "pa_sample_kernel<"):
         sel = [k for k in ks if kern in k["demangled"]]
@@ -193,7 +198,7 @@ def test_per_agent_kernels_use_no_scratch():
         for k in sel:
             assert k["private_segment"] == 0 and k["vgpr_spill"] == 0, k
             assert k["vgpr"] <= 320, k                    # the bound of the shared actor kernels
-    sizes = _kernarg_sizes()
+    sizes = kernarg_sizes(LIB)
     pa = {n: s for n, s in sizes.items() if "pa_actor_kernel" in n or "pa_sample_kernel" in n}
     assert len(pa) == 2 * len(FUSED_N) * len(FUSED_HIDDEN)
     # the by-value table of 6 x 32 weight pointers rides in the kernel arguments: within HIP's 4 KiB kernel-argument limit
