@@ -11,8 +11,14 @@
 // It leaves in scope: `row`, `o` (the lane's row of the pass and output), `q` = q0 + row (env-major row of the workgroup:
 // env q / N, agent q % N), `y` (the lane's action component, noise added) and, SAMPLE only, the row's draw `n` with `ls0`,
 // `ls1` for gauss_logp(n, ls0, ls1).  The body stores them - each to its own place - and ends the pass with a WaveSync.
+// `constexpr bool LNORM` (with `nw`): a LayerNorm over each row of the tile after either ReLU hand-over (actor_row_norm on
+// gamma | beta at wsm + WS + 4, fg_actor_mlp_preload.inc), with a WaveSync of its own before the next layer reads the tile.
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
+            if constexpr (LNORM) {
+                actor_row_norm<H>(hb, HS, wsm + WS + 4, nw.eps1, lane);
+                WaveSync()();
+            }
             // ---- layer 2 ----
             actor_bias_init(acc, wsm + H, col);
             // (opaque per pass: the weight fragments do not depend on the tile, and hoisted out of the tile loop they would
@@ -36,6 +42,10 @@
             WaveSync()();                          // every read of the layer-1 tile before it is overwritten
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
+            if constexpr (LNORM) {
+                actor_row_norm<H>(hb, HS, wsm + WS + 4 + 2 * H, nw.eps2, lane);
+                WaveSync()();
+            }
             // ---- layer 3 on the VALU: lane = (row of the pass, output), an ascending fmaf chain ----
             const int row = lane >> 1, o = lane & 1;
             const float* const hr = hb + row * HS;

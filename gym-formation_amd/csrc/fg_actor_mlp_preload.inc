@@ -3,6 +3,8 @@
 // fg_scn_lane_actor_body.inc, whose scope provides `w` (ActorW), `log_std`, `wsm`, `tid`, H, WS (= 4 H) and `constexpr bool
 // SAMPLE`; both kernels have FG_ACTOR_THREADS threads.  The workgroup barrier before the first actor pass publishes it.
 // fg_actor_mlp.inc and the bodies' layer 1 (actor_bias_init) read it back.  Not a header: no guard.
+// `constexpr bool LNORM` (with `nw`, ActorNormW): the two hidden LayerNorms' gamma1 [H] | beta1 [H] | gamma2 [H] | beta2 [H]
+// follow at wsm + WS + 4, a NULL gamma as ones and a NULL beta as zeros.
     for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
         wsm[q] = w.b1 ? w.b1[q] : 0.f;
         wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
@@ -12,4 +14,13 @@
     if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;
     if constexpr (SAMPLE) {
         if (tid < 2) wsm[WS + 2 + tid] = log_std[tid];
+    }
+    if constexpr (LNORM) {
+        float* const lnp = wsm + WS + 4;
+        for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
+            lnp[q] = nw.g1 ? nw.g1[q] : 1.f;
+            lnp[H + q] = nw.be1 ? nw.be1[q] : 0.f;
+            lnp[2 * H + q] = nw.g2 ? nw.g2[q] : 1.f;
+            lnp[3 * H + q] = nw.be2 ? nw.be2[q] : 0.f;
+        }
     }

@@ -2,7 +2,10 @@
 // (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
 // (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
-// (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  Not a header: no guard.
+// (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;
+// LNORM = false: an empty constant) selects ln_actor_kernel / ln_sample_kernel: the hidden LayerNorms are fg_actor_mlp.inc's,
+// the input LayerNorm (nw.in_norm, wave-uniform) is here - row statistics from the tables, then layer 1 over the whole k range
+// on the normalised operand.  Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
 // scenarios' body, as is the LDS preload (fg_actor_mlp_preload.inc).  The per-agent branches stay here.
@@ -23,13 +26,16 @@
     constexpr int TILES = ((PER_AGENT ? EP * N : E * N) + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
     constexpr int WS = PER_AGENT ? 0 : 4 * H;           // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
     static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
+    constexpr int LNS = actor_norm_floats(N, H, LNORM), DP = actor_in_pad(N);   // LNORM: gamma / beta of the three norms in LDS
+    static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
     float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
     float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + 4;
+    float* const hbuf = wsm + WS + 4 + LNS;
+    const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -49,6 +55,15 @@
 #include "fg_actor_mlp_preload.inc"
     } else if constexpr (SAMPLE) {
         if (tid < 2) wsm[WS + 2 + tid] = log_std[tid];
+    }
+    if constexpr (LNORM) {
+        if (nw.in_norm) {
+            float* const lnp = wsm + WS + 4 + 4 * H;
+            for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
+                lnp[q] = q < D ? (nw.g0 ? nw.g0[q] : 1.f) : 0.f;
+                lnp[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
+            }
+        }
     }
 
     const float one_minus_damp = 1.0f - a.p.damping;
@@ -128,6 +143,31 @@
                 const float x = (k & 1) ? val.y - sub.y : val.x - sub.x;
                 return (row_ok[rt] && k < D) ? x : 0.f;
             };
+            // LNORM with an input norm: each row's mean and rstd over all D features (x_in is zero at k >= D), a quarter of
+            // the row per k lane, then the two steps across the four lanes that share the row
+            constexpr int KA = (2 * N + 3) / 4, KB0 = (4 * N - 2) / 4, KB1 = (D + 3) / 4;
+            const bool in_norm = LNORM && nw.in_norm != 0;
+            float xmean[RT] = {}, xrstd[RT] = {};
+            if constexpr (LNORM) {
+                if (in_norm) {
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) {
+                        float sum = 0.f;
+                        for (int ks = 0; ks < KB1; ++ks) sum += x_in(rt, ks * 4 + kq);
+                        sum = bfly<32, R_SUM>(bfly<16, R_SUM>(sum));
+                        const float mean = sum * (1.0f / (float)D);
+                        float ssq = 0.f;
+                        for (int ks = 0; ks < KB1; ++ks) {
+                            const int k = ks * 4 + kq;
+                            const float d = k < D ? x_in(rt, k) - mean : 0.f;
+                            ssq = __builtin_fmaf(d, d, ssq);
+                        }
+                        ssq = bfly<32, R_SUM>(bfly<16, R_SUM>(ssq));
+                        xmean[rt] = mean;
+                        xrstd[rt] = 1.0f / sqrtf(ssq * (1.0f / (float)D) + nw.eps0);
+                    }
+                }
+            }
             f32x4 acc[RT][CB];
             // ---- layer 1: relative positions and velocity (k < 2N), then ideal shape and velocity (k >= 4N - 2) ----
             // PER_AGENT: each tile its own agent's bias and weight rows (the same two agents for the whole pass)
@@ -168,6 +208,13 @@
                 float xa[RT];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) xa[rt] = x_in(rt, k);
+                if constexpr (LNORM) {
+                    if (in_norm) {                     // k < DP: gamma0 = beta0 = 0 at k >= D
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt)
+                            xa[rt] = __builtin_fmaf((xa[rt] - xmean[rt]) * xrstd[rt], ln0[k], ln0[DP + k]);
+                    }
+                }
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
                     if constexpr (PER_AGENT) {
@@ -185,10 +232,16 @@
                     }
                 }
             };
-            constexpr int KA = (2 * N + 3) / 4, KB0 = (4 * N - 2) / 4, KB1 = (D + 3) / 4;
             static_assert(KB0 >= KA, "the two input blocks overlap");
+            // (an input norm: the communication block too - its normalised zeros are not zero)
 #pragma unroll 2
             for (int ks = 0; ks < KA; ++ks) l1_chunk(ks);
+            if constexpr (LNORM) {
+                if (in_norm) {
+#pragma unroll 2
+                    for (int ks = KA; ks < KB0; ++ks) l1_chunk(ks);
+                }
+            }
 #pragma unroll 2
             for (int ks = KB0; ks < KB1; ++ks) l1_chunk(ks);
             if constexpr (PER_AGENT) {

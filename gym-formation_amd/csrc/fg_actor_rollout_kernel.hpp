@@ -34,6 +34,22 @@
 // index: scalar loads).  Biases and W3 are read through L1 instead of LDS (4H + 2 floats per agent, 66 KB at 32 x 128).
 // At E = 8 (N > 16) the tiles are half full.  Same instructions in the same k order per output element as the shared
 // kernels: N identical members give their bits.
+//
+// ln_actor_kernel<N,H> / ln_sample_kernel<N,H> (fg_rollout_hd_actor_norm, H in {32, 64}) are the shared-actor body with the
+// LayerNorms of onpolicy's MLPBase (the MAPPO trainers' actor):
+//     [LayerNorm(6N) -] Linear - ReLU - LayerNorm(H) - Linear - ReLU - LayerNorm(H) - Linear(H, 2) [- Tanh]
+// selected by `constexpr bool LNORM` (false in every other kernel, whose instructions it leaves as they were).  Each norm is
+// torch's: mean and biased variance of the row in fp32, the variance from the centred values (mean first, then the sum of
+// squared deviations), rstd = 1 / sqrt(var + eps), y = (x - mean) rstd gamma + beta; gamma / beta read in place (NULL: 1 / 0).
+//   hidden norms  on the wave's 32 x H activation tile in LDS, between actor_store_tile and the next layer's reads
+//                 (actor_row_norm): four lanes per row, 16 rows at a time, lane (row, c) holding columns c, c + 4, ... - with
+//                 the row pitch H + 4 the 32 lanes of a ds_read_b32 / ds_write_b32 group (8 rows x 4 columns) fall on 32
+//                 different banks - the two row sums by DPP quad permutes.
+//   input norm    a run-time, wave-uniform fact of the launch (ActorNormW::in_norm).  The row statistics come from the
+//                 observation tables over all 6N features, the zero communication block included, summed by the four
+//                 lanes (k = lane >> 4) that share a row of the A operand; layer 1 then normalises its A operand on the fly
+//                 and runs over the WHOLE k range (a normalised zero is beta - mean rstd gamma, not zero).
+// gamma / beta of the three norms sit in LDS behind b3 | log_std (fg_actor_mlp_preload.inc; the input norm's from the body).
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -52,6 +68,16 @@ struct ActorW {
     int out_tanh;
 };
 
+// the LayerNorms of ln_*_kernel (FgActorNorm): gamma / beta (NULL: 1 / 0) and eps of the input norm (read only when in_norm)
+// and of the two hidden norms
+struct ActorNormW {
+    const float* g0; const float* be0;        // [6N]
+    const float* g1; const float* be1;        // [H]
+    const float* g2; const float* be2;        // [H]
+    float eps0, eps1, eps2;
+    int in_norm;
+};
+
 // one actor per agent (pa_*_kernel): agent i's parameters; entries at i >= N are never read
 constexpr int FG_ACTOR_MAX_AGENTS = 32;
 struct ActorTab {
@@ -67,14 +93,18 @@ __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 
 __host__ __device__ constexpr int actor_envs(int n) { return FG_ACTOR_THREADS / actor_lanes(n); }
 __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // row pitch of the activation tile: 16 rows x 4 k conflict-free
 // LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
-//               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) | activations [4][32][H + 4]
+//               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) |
+//               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
+//               activations [4][32][H + 4]
 // (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false> constexpr int actor_lds_floats() {
+__host__ __device__ constexpr int actor_in_pad(int n) { return (6 * n + 3) / 4 * 4; }
+__host__ __device__ constexpr int actor_norm_floats(int n, int h, bool lnorm) { return lnorm ? 4 * h + 2 * actor_in_pad(n) : 0; }
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false> constexpr int actor_lds_floats() {
     return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
-           (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H);
+           actor_norm_floats(NC, H, LNORM) + (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H);
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false> constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT>() * (int)sizeof(float);
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false> constexpr int actor_lds_bytes() {
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -115,6 +145,32 @@ FG_DEV void actor_store_tile(float* hb, int HS, const f32x4 (&acc)[RT][CB], int 
             for (int j = 0; j < 4; ++j) hb[(rt * 16 + kq * 4 + j) * HS + cb * 16 + col] = fmaxf(acc[rt][cb][j], 0.f);
 }
 
+// LayerNorm over each row of the wave's activation tile hb [FG_ACTOR_ROWS][HS], in place (LNORM kernels): gb = gamma [H] |
+// beta [H] in LDS.  Lane = (row lane >> 2 of 16, c = lane & 3) holds columns c, c + 4, ... of its row in registers: the mean,
+// then the centred sum of squares, each finished by two DPP quad steps (the four lanes of a row end with the same bits).
+// A row of zeros comes back as beta exactly.  The caller orders it against the tile's writers and readers (WaveSync).
+template <int H>
+FG_DEV void actor_row_norm(float* hb, int HS, const float* gb, float eps, int lane) {
+    const int c = lane & 3;
+#pragma unroll
+    for (int part = 0; part < FG_ACTOR_ROWS / 16; ++part) {
+        float* const hr = hb + (part * 16 + (lane >> 2)) * HS + c;
+        float x[H / 4];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < H / 4; ++j) { x[j] = hr[4 * j]; sum += x[j]; }
+        sum = bfly<2, R_SUM>(bfly<1, R_SUM>(sum));
+        const float mean = sum * (1.0f / (float)H);
+        float ssq = 0.f;
+#pragma unroll
+        for (int j = 0; j < H / 4; ++j) { x[j] -= mean; ssq = __builtin_fmaf(x[j], x[j], ssq); }
+        ssq = bfly<2, R_SUM>(bfly<1, R_SUM>(ssq));
+        const float rstd = 1.0f / sqrtf(ssq * (1.0f / (float)H) + eps);
+#pragma unroll
+        for (int j = 0; j < H / 4; ++j) hr[4 * j] = __builtin_fmaf(x[j] * rstd, gb[4 * j + c], gb[H + 4 * j + c]);
+    }
+}
+
 // One step's eps for every (env, agent) at rng_base(p) (fg_actor_noise): the host-paced loop of a Gaussian actor draws
 // what actor_sample_kernel draws.
 __global__ __launch_bounds__(256) void actor_noise_kernel(const KParams p, int B, int N, float2* __restrict__ eps) {
@@ -124,10 +180,21 @@ __global__ __launch_bounds__(256) void actor_noise_kernel(const KParams p, int B
     eps[t] = actor_eps(p.seed, (uint32_t)(b + p.env_index_base), (uint32_t)i, rng_base(p));
 }
 
+// The log-density of each of `count` draws eps [count][2] under log_std [2] (fg_actor_log_prob): gauss_logp on the values the
+// fused kernels give it, so that the host-paced loop of a Gaussian actor returns the fused launch's bits.
+__global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const float2* __restrict__ eps,
+                                                         const float* __restrict__ log_std, float* __restrict__ logp) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    logp[t] = gauss_logp(eps[t], log_std[0], log_std[1]);
+}
+
 // SAMPLE = false: the deterministic actor.
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const Args a, const ActorW w) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
+    constexpr bool LNORM = false;
+    constexpr ActorNormW nw{};
     constexpr ActorTab tab{};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -139,6 +206,8 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Args a, const ActorW w, const float* log_std,
                                                                          float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
+    constexpr bool LNORM = false;
+    constexpr ActorNormW nw{};
     constexpr ActorTab tab{};
 #include "fg_actor_rollout_body.inc"
 }
@@ -147,6 +216,8 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Ar
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_actor_kernel(const Args a, const ActorTab tab) {
     constexpr bool SAMPLE = false, PER_AGENT = true;
+    constexpr bool LNORM = false;
+    constexpr ActorNormW nw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -158,7 +229,30 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args a, const ActorTab tab, const float* log_std,
                                                                       float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = true;
+    constexpr bool LNORM = false;
+    constexpr ActorNormW nw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
+#include "fg_actor_rollout_body.inc"
+}
+
+// LNORM = true: the shared actor with LayerNorms `nw` (the deterministic actor).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_actor_kernel(const Args a, const ActorW w, const ActorNormW nw) {
+    constexpr bool SAMPLE = false, PER_AGENT = false;
+    constexpr bool LNORM = true;
+    constexpr ActorTab tab{};
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// LNORM = true, SAMPLE = true: the LayerNorm mean with actor_sample_kernel's Gaussian.
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
+                                                                      const float* log_std, float* logp) {
+    constexpr bool SAMPLE = true, PER_AGENT = false;
+    constexpr bool LNORM = true;
+    constexpr ActorTab tab{};
 #include "fg_actor_rollout_body.inc"
 }
 

@@ -6,6 +6,8 @@
 // padded K range); the LDS preload and everything after layer 1 are formation_hd_env's text: fg_actor_mlp_preload.inc and
 // fg_actor_mlp.inc.  Nothing per-agent is declared here.
     static_assert(!FG_F64, "the actor rollout is an fp32 kernel");
+    constexpr bool LNORM = false;                       // no LayerNorm actor in the landmark scenarios' launch
+    constexpr ActorNormW nw{};
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
     constexpr int NE = N + M;

@@ -29,6 +29,7 @@
 // points.  formation_hip_f64.hip builds the step kernel's source in double (tests only).
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <type_traits>
@@ -1603,12 +1604,59 @@ static int actor_per_agent_dispatch(const Args& a, const FgActor* actors, const 
     });
 }
 
-// per_agent: `actor` is a host array of N members (actor_per_agent_dispatch), else the one shared actor
+// ---- the shared actor with LayerNorms (ln_actor_kernel / ln_sample_kernel) ----
+template <int NC, int H>
+static int launch_ln_v(const Args& a, const ActorW& w, const ActorNormW& nw, const float* log_std, float* logp, hipStream_t st) {
+    constexpr int E = actor_envs(NC);
+    static_assert(actor_lds_bytes<NC, H, true, false, true>() <= 160 * 1024, "LayerNorm actor rollout LDS");
+    char targs[16];
+    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    return launch_actor_pair<&ln_actor_kernel<NC, H>, &ln_sample_kernel<NC, H>>(
+        "ln_actor_kernel", "ln_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? actor_lds_bytes<NC, H, true, false, true>() : actor_lds_bytes<NC, H, false, false, true>(),
+        "LayerNorm actor rollout launch failed: %s", st, log_std, logp, a, w, nw);
+}
+// fg_rollout_hd_actor's checks, then FgActorNorm's (no device touched): hidden 32 or 64, every eps that is read positive and
+// finite, gamma / beta 4-byte aligned
+static int actor_norm_check(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, int B, int N, int K) {
+    int rc = actor_check(params, actor, B, N, K);
+    if (rc) return rc;
+    if (!norm) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: norm is NULL%s");
+    if (actor->hidden != 32 && actor->hidden != 64)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms%s");
+    auto eps_ok = [](float e) { return e > 0.0f && std::isfinite(e); };
+    if (norm->in_norm && !eps_ok(norm->in_eps))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: in_eps must be positive and finite%s");
+    if (!eps_ok(norm->h1_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite%s");
+    if (!eps_ok(norm->h2_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h2_eps must be positive and finite%s");
+    const struct { const float* p; const char* name; } ptrs[] = {
+        {norm->in_gamma, "in_gamma"}, {norm->in_beta, "in_beta"}, {norm->h1_gamma, "h1_gamma"},
+        {norm->h1_beta, "h1_beta"},   {norm->h2_gamma, "h2_gamma"}, {norm->h2_beta, "h2_beta"}};
+    for (const auto& q : ptrs)
+        if ((uintptr_t)q.p & 3u) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: %s must be 4-byte aligned", q.name);
+    return FG_OK;
+}
+static int actor_norm_dispatch(const Args& a, const FgActor& actor, const FgActorNorm& norm, const float* log_std, float* logp,
+                               hipStream_t st) {
+    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+    const bool in_norm = norm.in_norm != 0;
+    const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
+                           norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
+#define FG_ACTOR_LN(NN) \
+    if (a.N == NN) return actor.hidden == 32 ? launch_ln_v<NN, 32>(a, w, nw, log_std, logp, st) \
+                                             : launch_ln_v<NN, 64>(a, w, nw, log_std, logp, st);
+    FG_ACTOR_LN(3) FG_ACTOR_LN(4) FG_ACTOR_LN(8) FG_ACTOR_LN(9) FG_ACTOR_LN(16) FG_ACTOR_LN(25) FG_ACTOR_LN(27) FG_ACTOR_LN(32)
+#undef FG_ACTOR_LN
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_norm: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+}
+
+// per_agent: `actor` is a host array of N members (actor_per_agent_dispatch), else the one shared actor - with LayerNorms
+// when `norm` is not NULL (actor_norm_dispatch)
 static int rollout_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
-                              int obs_every, void* stream, bool per_agent = false) {
+                              int obs_every, void* stream, bool per_agent = false, const FgActorNorm* norm = nullptr) {
     if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
     if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
@@ -1625,6 +1673,7 @@ static int rollout_actor_impl(const FgParams* params, const FgActor* actor, cons
     a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
     a.act_out = act_seq;
     if (per_agent) return actor_per_agent_dispatch(a, actor, log_std, logp_seq, (hipStream_t)stream);
+    if (norm) return actor_norm_dispatch(a, *actor, *norm, log_std, logp_seq, (hipStream_t)stream);
     return actor_dispatch(a, *actor, log_std, logp_seq, (hipStream_t)stream);
 }
 
@@ -1672,6 +1721,23 @@ int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors,
                               step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream, true);
 }
 
+int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
+                             int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                             float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                             float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                             int obs_every, void* stream) {
+    int rc = actor_norm_check(params, actor, norm, B, N, K);
+    if (rc) return rc;
+    if (log_std) {
+        if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
+        if ((uintptr_t)logp_seq & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_norm: logp_seq must be 4-byte aligned%s");
+    } else {
+        logp_seq = nullptr;
+    }
+    return rollout_actor_impl(params, actor, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
+                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream, false, norm);
+}
+
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1688,16 +1754,32 @@ int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* strea
     return FG_OK;
 }
 
+int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, float* logp, void* stream) {
+    if (count < 0) return fail(FG_ERR_BAD_ARG, "fg_actor_log_prob: count >= 0 required%s");
+    if (count == 0) return FG_OK;
+    if (!eps || !log_std || !logp) return fail(FG_ERR_BAD_ARG, "fg_actor_log_prob: eps, log_std and logp are required%s");
+    if (((uintptr_t)eps & 7u) || (((uintptr_t)log_std | (uintptr_t)logp) & 3u))
+        return fail(FG_ERR_ALIGNMENT, "fg_actor_log_prob: eps must be 8-byte, log_std and logp 4-byte aligned%s");
+    const DeviceGuard device_guard(stream, eps);
+    hipLaunchKernelGGL(actor_logp_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (long long)count, reinterpret_cast<const float2*>(eps), log_std, logp);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor log-prob launch failed: %s", hipGetErrorString(err));
+    return FG_OK;
+}
+
 }  // extern "C"
 
 static int describe_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
-                               int obs_every, char* out, int out_len, bool per_agent = false) {
+                               int obs_every, char* out, int out_len, bool per_agent = false,
+                               const FgActorNorm* norm = nullptr) {
     if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
     Args a; memset(&a, 0, sizeof(a));
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
     int rc = set_obs_pitch(&a);
     if (rc != FG_OK) return rc;
     const DescribeScope describing(out, out_len);
+    if (norm) return actor_norm_dispatch(a, *actor, *norm, log_std, nullptr, nullptr);
     return per_agent ? actor_per_agent_dispatch(a, actor, log_std, nullptr, nullptr)
                      : actor_dispatch(a, *actor, log_std, nullptr, nullptr);
 }
@@ -1721,6 +1803,16 @@ int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor
     if (rc) return rc;
     if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
     return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
+                                  int B, int N, int K, int obs_every, char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_norm_launch: out buffer required%s");
+    out[0] = 0;
+    int rc = actor_norm_check(params, actor, norm, B, N, K);
+    if (rc) return rc;
+    if (log_std && (rc = actor_sample_check(log_std)) != FG_OK) return rc;
+    return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len, false, norm);
 }
 
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,

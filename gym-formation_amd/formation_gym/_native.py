@@ -95,6 +95,26 @@ class FgActor(ctypes.Structure):
     ]
 
 
+class FgActorNorm(ctypes.Structure):
+    """Mirror of `struct FgActorNorm` (include/formation_hip.h): the LayerNorms of fg_rollout_hd_actor_norm's actor."""
+    _fields_ = [
+        ("in_gamma", ctypes.c_void_p), ("in_beta", ctypes.c_void_p),
+        ("h1_gamma", ctypes.c_void_p), ("h1_beta", ctypes.c_void_p),
+        ("h2_gamma", ctypes.c_void_p), ("h2_beta", ctypes.c_void_p),
+        ("in_eps", ctypes.c_float), ("h1_eps", ctypes.c_float), ("h2_eps", ctypes.c_float),
+        ("in_norm", ctypes.c_int32),            # 1: the actor starts with a LayerNorm over its input
+    ]
+
+
+def actor_norm(norms):
+    """FgActorNorm of an `actor_rollout.ActorNorms`: (weight, bias, eps) of the input norm (None: absent) and of the two
+    hidden norms; a None tensor is a NULL pointer (weight 1, bias 0)."""
+    n0, n1, n2 = norms
+    g0, b0, e0 = n0 if n0 is not None else (None, None, 1e-5)        # in_norm = 0: never read
+    return FgActorNorm(ptr(g0), ptr(b0), ptr(n1[0]), ptr(n1[1]), ptr(n2[0]), ptr(n2[1]), e0, n1[2], n2[2],
+                       0 if n0 is None else 1)
+
+
 class FormationHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libformation_hip: status %d: %s" % (code, msg))
@@ -146,9 +166,14 @@ SIGNATURES = {
     "fg_describe_actor_launch": (_I, [_PP, ctypes.POINTER(FgActor), _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor_sample": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),
     "fg_actor_noise": (_I, [_PP, _I, _I, _P, _P]),
+    "fg_actor_log_prob": (_I, [_P, _P, ctypes.c_int64, _P, _P]),
     "fg_describe_actor_sample_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),
     "fg_describe_actor_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_norm": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), _P, _I, _I, _I] + [_P] * 13
+                                 + [_I, _P]),
+    "fg_describe_actor_norm_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), _P, _I, _I, _I, _I,
+                                           ctypes.c_char_p, _I]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,

@@ -7,6 +7,16 @@ with H in {32, 64, 128}, fp32 contiguous parameters on the env's device (a None 
 {3, 4, 8, 9, 16, 25, 27, 32} agents of formation_hd_env with continuous actions, silent agents, no World options and no
 post_step_callback.  Anything else runs host-paced: a shape or option the kernel cannot honour never runs fused.
 
+The MAPPO trainers' actor (onpolicy's MLPBase) is the same body with LayerNorms: exactly
+    Sequential([LayerNorm(6N),] Linear(6N, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2) [, Tanh()])
+with H in FUSED_LN_HIDDEN = {32, 64}; the leading LayerNorm (feature normalisation) is optional, the two hidden ones come
+together.  Each LayerNorm normalises the last axis only (normalized_shape == (width,)), with any positive finite eps and either
+fp32 contiguous weight / bias on the env's device or none (a missing weight counts as 1, a missing bias as 0).  It fuses
+(`fg_rollout_hd_actor_norm`) under the Linear body's rule, alone or as a GaussianActor's mean, in formation_hd_env only.
+Host-paced: H = 128 with norms, a single hidden norm, a norm before the ReLU or anywhere else, a norm over more than the last
+axis, norm parameters in another dtype, non-contiguous or off the device, PerAgentActor members with norms, and any LayerNorm
+actor in the landmark scenarios (their `actor_fused_rule` states `fused_ln_hidden=()`: no such kernel).
+
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
 
@@ -29,6 +39,7 @@ LOG_2PI = math.log(2.0 * math.pi)
 
 FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)
 FUSED_HIDDEN = (32, 64, 128)
+FUSED_LN_HIDDEN = (32, 64)             # hidden widths of the LayerNorm actor's kernels (ln_actor_kernel / ln_sample_kernel)
 # the landmark scenarios: (scenario kind, agents, landmarks, obstacles, neighbours observed) -> fused; kind as _native.FG_SCN_*
 LANDMARK_FUSED_SHAPES = ((1, 3, 3, 0, 2), (2, 5, 5, 0, 3), (2, 3, 5, 0, 3), (3, 4, 4, 0, 3), (3, 3, 4, 0, 2),
                          (4, 4, 4, 3, 3), (4, 3, 4, 3, 2))
@@ -46,11 +57,13 @@ def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_
     return dict(in_features=int(obs_dim), fused_n=(N,), fused_hidden=LANDMARK_FUSED_HIDDEN, per_agent=False)
 
 
-def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN):
+def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
+               fused_ln_hidden=None):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate `actor` for `num_agents` agents, else
     None.  `device`: the env's device (None: not checked).  The tensors are the actor's own parameters (b* may be None).
     The scenario's facts: `in_features` the actor's input width (None: formation_hd_env's 6N), `fused_n` the agent counts and
-    `fused_hidden` the hidden widths its kernel is built for."""
+    `fused_hidden` the hidden widths its kernel is built for.  (`fused_ln_hidden` is `layernorm_spec`'s fact, taken here so
+    that a scenario's facts pass whole; this function never accepts a LayerNorm.)"""
     nn = torch.nn
     if type(actor) is not nn.Sequential or int(num_agents) not in fused_n:
         return None
@@ -61,7 +74,11 @@ def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     body = [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear]
     if kinds != body and kinds != body + [nn.Tanh]:
         return None
-    l1, l2, l3 = mods[0], mods[2], mods[4]
+    return _linears_spec(mods[0], mods[2], mods[4], len(mods) == 6, in_features, device, fused_hidden)
+
+
+def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
+    """actor_spec's answer for the three Linears of a body whose module kinds have been checked."""
     H = l1.out_features
     if H not in fused_hidden or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
             or (l3.in_features, l3.out_features) != (H, 2):
@@ -75,7 +92,64 @@ def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
             return None
         if not _on_device(t, dev):
             return None
-    return H, len(mods) == 6, params
+    return H, out_tanh, params
+
+
+class ActorNorms(collections.namedtuple("ActorNorms", "input hidden1 hidden2")):
+    """The LayerNorms of a fused LayerNorm actor (`layernorm_spec`): each a (weight, bias, eps) triple - the module's own
+    parameter tensors, None where it has none (weight: 1, bias: 0), and its eps as a float; `input` is None when the actor has
+    no leading LayerNorm."""
+    __slots__ = ()
+
+
+def _norm_triple(m, width, device):
+    """(weight, bias, eps) of the LayerNorm `m` over a last axis of `width`, as the fused kernel can read it, else None."""
+    if type(m) is not torch.nn.LayerNorm or tuple(m.normalized_shape) != (int(width),):
+        return None
+    eps = float(m.eps)
+    if not (eps > 0.0 and math.isfinite(eps)):
+        return None
+    g, b = m.weight, getattr(m, "bias", None)
+    for t in (g, b):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (int(width),) or not t.is_contiguous() \
+                or not _on_device(t, device):
+            return None
+    return g, b, eps
+
+
+def layernorm_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=None,
+                   fused_ln_hidden=FUSED_LN_HIDDEN):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms) when the fused LayerNorm kernel can evaluate `actor` for
+    `num_agents` agents, else None: exactly
+        Sequential([LayerNorm(D),] Linear(D, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2) [, Tanh()])
+    with H in `fused_ln_hidden`, the Linears passing `actor_spec` and every LayerNorm over its last axis alone with fp32
+    contiguous parameters on `device` or none.  An actor without LayerNorms is `actor_spec`'s, not this function's.
+    (`fused_hidden` is `actor_spec`'s fact, taken here so that a scenario's facts pass whole.)"""
+    nn = torch.nn
+    if type(actor) is not nn.Sequential or int(num_agents) not in fused_n or not fused_ln_hidden:
+        return None
+    if in_features is None:
+        in_features = 6 * int(num_agents)
+    mods = list(actor)
+    lead = bool(mods) and type(mods[0]) is nn.LayerNorm
+    rest = mods[1:] if lead else mods
+    kinds = [type(m) for m in rest]
+    body = [nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear]
+    if kinds != body and kinds != body + [nn.Tanh]:
+        return None
+    # the three Linears under actor_spec's rule, with this kernel's widths
+    spec = _linears_spec(rest[0], rest[3], rest[6], len(rest) == 8, in_features, device, tuple(fused_ln_hidden))
+    if spec is None:
+        return None
+    H, out_tanh, params = spec
+    dev = None if device is None else torch.device(device)
+    n0 = _norm_triple(mods[0], rest[0].in_features, dev) if lead else None
+    n1, n2 = _norm_triple(rest[2], H, dev), _norm_triple(rest[5], H, dev)
+    if (lead and n0 is None) or n1 is None or n2 is None:
+        return None
+    return H, out_tanh, params, ActorNorms(n0, n1, n2)
 
 
 class PerAgentActor(torch.nn.Module):
@@ -149,24 +223,34 @@ def sample_spec(actor, num_agents, device=None, **facts):
     """(actor_spec(actor.mean, ...), log_std) when the fused kernel can sample from the GaussianActor `actor` for
     `num_agents` agents, else None: its mean fuses (actor_spec; per_agent_spec for a PerAgentActor mean) and log_std is a contiguous fp32 [2] tensor on `device`
     (None: not checked).  log_std is the actor's own parameter, read in place by every launch.  `facts`: actor_spec's
-    keyword arguments for a shared mean (in_features, fused_n, fused_hidden)."""
+    keyword arguments for a shared mean (in_features, fused_n, fused_hidden).  A LayerNorm mean is not looked for here:
+    `resolve_actor` asks `layernorm_spec` for it."""
     if not isinstance(actor, GaussianActor):
         return None
     if isinstance(actor.mean, PerAgentActor):
         spec = per_agent_spec(actor.mean, num_agents, device)
     else:
         spec = actor_spec(actor.mean, num_agents, device, **facts)
-    ls = actor.log_std
-    if spec is None or not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) \
-            or not ls.is_contiguous() or not _on_device(ls, device):
+    ls = _fused_log_std(actor, device)
+    if spec is None or ls is None:
         return None
     return spec, ls
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std")):
+def _fused_log_std(actor, device):
+    """The GaussianActor's log_std when the fused launch can read it in place (contiguous fp32 [2] on `device`), else None."""
+    ls = actor.log_std
+    if not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) or not ls.is_contiguous() \
+            or not _on_device(ls, device):
+        return None
+    return ls
+
+
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms", defaults=(None,))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
-    N for a PerAgentActor (`per_agent`) - and `log_std`, a GaussianActor's [2] parameter (None: deterministic)."""
+    N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
+    ActorNorms of a LayerNorm actor (None: the actor has no LayerNorm)."""
     __slots__ = ()
 
 
@@ -176,8 +260,10 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     `rollout_actor(K, actor)` runs fused, None when it runs host-paced.  The keyword facts describe the env: a scenario with
     the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls, accel, max_speed,
     u_noise, per-agent properties), no post_step_callback.  `per_agent`: the scenario's launch takes a PerAgentActor
-    (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's keyword arguments (in_features,
-    fused_n, fused_hidden), as the scenario states them."""
+    (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's and layernorm_spec's keyword arguments
+    (in_features, fused_n, fused_hidden, fused_ln_hidden), as the scenario states them.  A shared actor that actor_spec does
+    not take is tried as a LayerNorm actor (layernorm_spec: formation_hd_env, H in {32, 64}); PerAgentActor members with
+    LayerNorms and the landmark scenarios (`fused_ln_hidden=()`) run host-paced."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return None
     gaussian = isinstance(actor, GaussianActor)
@@ -193,6 +279,13 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
         spec = per_agent_spec(actor, num_agents, device)
     else:
         spec = actor_spec(actor, num_agents, device, **facts)
+    if spec is None and not members_own:               # the shared actor with LayerNorms, alone or as a Gaussian's mean
+        spec = layernorm_spec(actor.mean if gaussian else actor, num_agents, device, **facts)
+        log_std = _fused_log_std(actor, device) if gaussian else None
+        if spec is None or (gaussian and log_std is None):
+            return None
+        hidden, out_tanh, weights, norms = spec
+        return FusedActor(hidden, bool(out_tanh), [weights], False, log_std, norms)
     if spec is None:
         return None
     hidden, out_tanh, weights = spec

@@ -407,7 +407,13 @@ class MultiAgentEnv(object):
         fuses (`fg_rollout_hd_actor_per_agent`) when every member would, with one H and one tanh flag.
         The landmark scenarios (basic_formation_env, formation_hd_partial_env, formation_hd_partial_range_env,
         formation_hd_obs_env) fuse a shared actor, deterministic or Gaussian, at their seven reference shapes with H in
-        {32, 64} (`fg_rollout_scenario_actor`); H = 128 and a PerAgentActor run host-paced there."""
+        {32, 64} (`fg_rollout_scenario_actor`); H = 128 and a PerAgentActor run host-paced there.
+        The MAPPO trainers' LayerNorm actor (onpolicy's MLPBase) - Sequential([LayerNorm(6N),] Linear(6N, H), ReLU,
+        LayerNorm(H), Linear(H, H), ReLU, LayerNorm(H), Linear(H, 2) [, Tanh]), H in {32, 64} - fuses in formation_hd_env
+        (`fg_rollout_hd_actor_norm`), alone or as a GaussianActor's mean with the same eps draws and log_prob; its norm
+        parameters are read in place like the weights.  Host-paced: H = 128 with norms, any other placement of norms, norm
+        parameters in another dtype / non-contiguous / off the device, PerAgentActor members with norms, and a LayerNorm
+        actor in the landmark scenarios."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
@@ -442,6 +448,8 @@ class MultiAgentEnv(object):
             key = ("actor", K, fused.hidden, fused.out_tanh, fused.per_agent,
                    tuple(0 if t is None else t.data_ptr() for ws in fused.members for t in ws),
                    0 if log_std is None else log_std.data_ptr(),
+                   None if fused.norms is None else tuple(
+                       None if n is None else (_native.ptr(n[0]), _native.ptr(n[1]), n[2]) for n in fused.norms),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))
@@ -479,10 +487,19 @@ class MultiAgentEnv(object):
         _native.check(_native.load().fg_actor_noise(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
         return out
 
+    def _noise_log_prob(self, eps, log_std):
+        """-(eps_0^2 + eps_1^2) / 2 - sum(log_std) - log(2 pi) of eps [B, N, 2] (`fg_actor_log_prob`): [B, N]."""
+        eps, log_std = eps.contiguous(), log_std.contiguous()
+        out = torch.empty(eps.shape[:-1], dtype=torch.float32, device=eps.device)
+        _native.check(_native.load().fg_actor_log_prob(eps.data_ptr(), log_std.data_ptr(), out.numel(), out.data_ptr(),
+                                                       _native.current_stream(self.world.device)))
+        return out
+
     def _rollout_actor_by_steps(self, K, actor, obs_every):
         """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
         launch's (fresh tensors).  A GaussianActor: mean(obs) + exp(log_std) * eps with eps from `actor_noise`, the draws
-        of the fused kernel, and the log-density from eps by the kernel's formula."""
+        of the fused kernel, and the log-density from eps by the kernel's own device function (`fg_actor_log_prob`): for the
+        same eps and log_std, the fused launch's bits."""
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
         observe = getattr(self.scenario, "observe_batch", None)
         if observe is not None:                            # the observation of the current state (a multi-step launch
@@ -495,8 +512,7 @@ class MultiAgentEnv(object):
                     eps = self.actor_noise()
                     ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
                     act = actor.mean(obs) + torch.exp(ls) * eps
-                    res["logp"].append(-0.5 * (eps[..., 0] * eps[..., 0] + eps[..., 1] * eps[..., 1]) - (ls[0] + ls[1])
-                                       - actor_rollout.LOG_2PI)
+                    res["logp"].append(self._noise_log_prob(eps, ls))
                 else:
                     act = actor(obs)
                 res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))

@@ -261,9 +261,11 @@ class Scenario(BaseScenario):
           one shared actor                      `fg_rollout_hd_actor`
           ... with a GaussianActor's log_std    `fg_rollout_hd_actor_sample`, the log-densities in out["log_prob"] [K,B,N]
           one actor per agent                   `fg_rollout_hd_actor_per_agent` (log_std or NULL), agent i's rows through
-                                                member i's weights"""
+                                                member i's weights
+          one shared actor with LayerNorms      `fg_rollout_hd_actor_norm` (log_std or NULL), `actor.norms` as FgActorNorm"""
         lib = _native.load()
         log_std = actor.log_std
+        norm = None if actor.norms is None else _native.actor_norm(actor.norms)
         fas = (_native.FgActor * len(actor.members))(*[
             _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
         p = self.params(world, auto_reset, 0, out.get("obs"))
@@ -274,13 +276,19 @@ class Scenario(BaseScenario):
                  _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                  _native.ptr(out.get("done")))
         tail = (int(obs_every), _native.current_stream(world.device))
-        if actor.per_agent or log_std is not None:
+        if norm is not None:
+            if actor.per_agent:
+                raise NotImplementedError("PerAgentActor members with LayerNorms have no fused launch")
+            logp = None if log_std is None else out["log_prob"].data_ptr()
+            fn, args = lib.fg_rollout_hd_actor_norm, (fas, norm, _native.ptr(log_std)) + state + (logp,) + tail
+        elif actor.per_agent or log_std is not None:
             fn = lib.fg_rollout_hd_actor_per_agent if actor.per_agent else lib.fg_rollout_hd_actor_sample
             logp = None if log_std is None else out["log_prob"].data_ptr()
             args = (fas, _native.ptr(log_std)) + state + (logp,) + tail
         else:
             fn, args = lib.fg_rollout_hd_actor, (fas,) + state + tail
-        return _native.bind_launch(fn, p, *args, keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std))
+        return _native.bind_launch(fn, p, *args,
+                                   keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm))
 
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the

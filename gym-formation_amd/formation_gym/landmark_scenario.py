@@ -80,11 +80,13 @@ class ActorRolloutMixin(object):
     def actor_fused_rule(self, world):
         """The facts `actor_rollout.resolve_actor` needs when this world's shape has a fused actor launch - the seven shapes of
         the one-env-per-lane kernel, not the run-time-count kernel (`kernel_variant = 1`) - else None: host-paced.  (World
-        options and per-agent properties are `MultiAgentEnv.actor_path`'s own checks, as for formation_hd_env.)"""
+        options and per-agent properties are `MultiAgentEnv.actor_path`'s own checks, as for formation_hd_env.)
+        `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here."""
         from formation_gym import actor_rollout
         d = self._actor_descriptor(world)
-        return actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
-                                            self.obs_dim(world), d.variant)
+        facts = actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
+                                             self.obs_dim(world), d.variant)
+        return None if facts is None else dict(facts, fused_ln_hidden=())
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs
@@ -95,6 +97,8 @@ class ActorRolloutMixin(object):
         fn = _native.load().fg_rollout_scenario_actor
         if actor.per_agent:
             raise NotImplementedError("one actor per agent has no fused launch in %s" % type(self).__name__)
+        if actor.norms is not None:
+            raise NotImplementedError("a LayerNorm actor has no fused launch in %s" % type(self).__name__)
         weights, log_std = actor.members[0], actor.log_std
         fa = _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in weights])
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)

@@ -485,6 +485,11 @@ int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, con
  * host-paced loop of a Gaussian actor calls it once per step and draws the same numbers.  `params` passes the usual checks;
  * the draw reads only its seed, env_index_base and offset.  N < 2^29 (the stream's counter word keeps three top bits). */
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream);
+/* The log-density of `count` draws: logp [count] = -(eps_0^2 + eps_1^2) / 2 - (log_std_0 + log_std_1) - log(2 pi) for
+ * eps [count][2] (8-byte aligned) and log_std [2], all fp32 in DEVICE memory, from the device function the fused Gaussian
+ * kernels use (the same bits as their logp_seq for the same eps and log_std): the host-paced loop of a Gaussian actor calls
+ * it once per step on fg_actor_noise's draw.  count == 0 is a no-op. */
+int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, float* logp, void* stream);
 /* Dry run of fg_rollout_hd_actor_sample (the twin of fg_describe_actor_launch): same checks and status codes, names the
  * actor_sample_kernel<N,H> instantiation.  Touches no device; log_std is only checked for NULL and alignment. */
 int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
@@ -506,6 +511,43 @@ int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors,
  * pa_sample_kernel<N,H> instantiation.  Touches no device. */
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
                                        int K, int obs_every, char* out, int out_len);
+
+/* The LayerNorms of fg_rollout_hd_actor_norm's actor (the MAPPO trainers' actor, onpolicy's MLPBase):
+ *     [LayerNorm(6N) -] Linear(6N, hidden) - ReLU - LayerNorm(hidden) - Linear(hidden, hidden) - ReLU - LayerNorm(hidden) -
+ *     Linear(hidden, 2) [- tanh]
+ * in_*: the norm over the actor's input, present when in_norm is 1 (else in_gamma, in_beta and in_eps are not read);
+ * h1_*, h2_*: the norms after the first and the second ReLU.  gamma / beta: fp32 [width] in DEVICE memory, read in place by
+ * every launch like the weights; NULL is the identity (gamma 1, beta 0).  Each norm is torch.nn.LayerNorm over the last axis:
+ * mean and biased variance of the row in fp32 (the variance from the centred values), y = (x - mean) / sqrt(var + eps) *
+ * gamma + beta, with its own positive, finite eps. */
+typedef struct FgActorNorm {
+    const float* in_gamma;   /* [6N] or NULL */
+    const float* in_beta;    /* [6N] or NULL */
+    const float* h1_gamma;   /* [hidden] or NULL */
+    const float* h1_beta;    /* [hidden] or NULL */
+    const float* h2_gamma;   /* [hidden] or NULL */
+    const float* h2_beta;    /* [hidden] or NULL */
+    float in_eps;
+    float h1_eps;
+    float h2_eps;
+    int32_t in_norm;         /* 1: the actor starts with a LayerNorm over its input */
+} FgActorNorm;
+
+/* fg_rollout_hd_actor (log_std == NULL; logp_seq ignored) or fg_rollout_hd_actor_sample (log_std [2] and logp_seq as there,
+ * the same eps draws) with the LayerNorm actor `actor` + `norm` shared by every agent (ln_actor_kernel / ln_sample_kernel).
+ * actor->hidden: 32 or 64.  Every other argument, check and status code is fg_rollout_hd_actor_sample's
+ * (FG_ERR_UNSUPPORTED_N for N as in fg_rollout_hd_actor); FG_ERR_BAD_ARG, the message naming the field, for a NULL norm, an
+ * eps that is not positive and finite, a gamma / beta pointer that is not 4-byte aligned, or hidden = 128.  Two launches from
+ * one state give the same bits, and fg_rollout_hd driven by the recorded act_seq returns the same results bit for bit. */
+int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
+                             int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                             float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                             float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                             int obs_every, void* stream);
+/* Dry run of fg_rollout_hd_actor_norm: same checks and status codes, names the ln_actor_kernel<N,H> or
+ * ln_sample_kernel<N,H> instantiation and its launch geometry.  Touches no device. */
+int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
+                                  int B, int N, int K, int obs_every, char* out, int out_len);
 
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
