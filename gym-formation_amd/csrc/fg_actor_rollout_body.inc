@@ -1,5 +1,5 @@
-// fg_actor_rollout_body.inc - the one body of actor_rollout_kernel, actor_sample_kernel, pa_actor_kernel and pa_sample_kernel
-// (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
+// fg_actor_rollout_body.inc - the one body of the six formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
+// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel and ln_sample_kernel (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
 // (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
 // (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;

@@ -1466,6 +1466,9 @@ int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void*
 static bool actor_n_supported(int N) {
     return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
 }
+static ActorW actor_w(const FgActor& actor) {
+    return {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+}
 // Describe-or-launch of an actor kernel: Det (the deterministic actor; log_std == NULL) or its sampling twin Smp (the Gaussian
 // actor), which takes (log_std, logp) after Det's arguments `args`.  `targs` spells the template arguments and `unit` the word
 // before the thread count in the describe string; `lds` is the chosen kernel's.  One LDS-limit mask per kernel.
@@ -1488,17 +1491,34 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
     if (err != hipSuccess) return fail(FG_ERR_HIP, fail_fmt, hipGetErrorString(err));
     return FG_OK;
 }
-// the shared actor of formation_hd_env: actor_rollout_kernel / actor_sample_kernel
-template <int NC, int H>
-static int launch_actor_v(const Args& a, const ActorW& w, const float* log_std, float* logp, hipStream_t st) {
-    constexpr int E = actor_envs(NC);
-    static_assert(actor_lds_bytes<NC, H, true>() <= 160 * 1024, "actor rollout LDS");
+// The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
+// per agent (pa_*_kernel) and the shared actor with LayerNorms (ln_*_kernel).  `w`: the kernel's arguments after `a` - an
+// ActorW, an ActorTab, or an ActorW and an ActorNormW.
+template <int NC, int H, bool PER_AGENT, bool LNORM, class... W>
+static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
+    static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
+    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() <= 160 * 1024, "actor rollout LDS");
+    constexpr int E = actor_envs(NC), V = LNORM ? 2 : PER_AGENT ? 1 : 0;
+    constexpr auto det = [] {
+        if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
+        else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
+        else return &actor_rollout_kernel<NC, H>;
+    }();
+    constexpr auto smp = [] {
+        if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
+        else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
+        else return &actor_sample_kernel<NC, H>;
+    }();
+    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel"};
+    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel"};
+    static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
+                                           "LayerNorm actor rollout launch failed: %s"};
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    return launch_actor_pair<&actor_rollout_kernel<NC, H>, &actor_sample_kernel<NC, H>>(
-        "actor_rollout_kernel", "actor_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true>() : actor_lds_bytes<NC, H>(), "actor rollout launch failed: %s", st, log_std, logp,
-        a, w);
+    return launch_actor_pair<det, smp>(
+        det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM>(),
+        fail_fmt[V], st, log_std, logp, a, w...);
 }
 // The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
 // the messages name, `max_hidden` / `widths` its admissible hidden widths (32, 64 and up to max_hidden), `also` further
@@ -1526,101 +1546,23 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
     return FG_OK;
 }
-// the checks every actor entry shares (no device touched): FG_OK, or the status of the first one that fails
-static int actor_check(const FgParams* params, const FgActor* actor, int B, int N, int K) {
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: B >= 0 and K >= 1 required%s");
-    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
-    return hd_actor_struct_check(params, actor);
-}
-// the Gaussian actor's extra argument: FG_OK or the status of the first check that fails (no device touched)
-static int actor_sample_check(const float* log_std) {
-    if (!log_std) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
-    if ((uintptr_t)log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
-    return FG_OK;
-}
-// The (N, H) instantiations of the formation_hd_env actor kernels, shared and per-agent: launch(n, h) with N and H as the
-// `value` of the arguments' types, or `unsupported` when N is not in the list (hidden is 32, 64 or 128: actor_struct_check).
-template <int V> using IntC = std::integral_constant<int, V>;
-template <class F>
-static int actor_nh_dispatch(int N, int hidden, const char* unsupported, F&& launch) {
-#define FG_ACTOR(NN) \
-    if (N == NN) return hidden == 32 ? launch(IntC<NN>{}, IntC<32>{}) : hidden == 64 ? launch(IntC<NN>{}, IntC<64>{}) \
-                                                                                    : launch(IntC<NN>{}, IntC<128>{});
-    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
-#undef FG_ACTOR
-    return fail(FG_ERR_UNSUPPORTED_N, unsupported);
-}
-static int actor_dispatch(const Args& a, const FgActor& actor, const float* log_std, float* logp, hipStream_t st) {
-    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
-    return actor_nh_dispatch(a.N, actor.hidden, "fg_rollout_hd_actor: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s", [&](auto n, auto h) {
-        return launch_actor_v<decltype(n)::value, decltype(h)::value>(a, w, log_std, logp, st);
-    });
-}
 
-// ---- one actor per agent (pa_actor_kernel / pa_sample_kernel) ----
-template <int NC, int H>
-static int launch_pa_v(const Args& a, const ActorTab& tab, const float* log_std, float* logp, hipStream_t st) {
-    constexpr int E = actor_envs(NC);
-    static_assert(actor_lds_bytes<NC, H, true, true>() <= 160 * 1024, "per-agent actor rollout LDS");
-    char targs[16];
-    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    return launch_actor_pair<&pa_actor_kernel<NC, H>, &pa_sample_kernel<NC, H>>(
-        "pa_actor_kernel", "pa_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, true>() : actor_lds_bytes<NC, H, false, true>(),
-        "per-agent actor rollout launch failed: %s", st, log_std, logp, a, tab);
-}
-// the FgActor checks on every member, then: every member has member 0's hidden width and tanh flag (no device touched)
-static int actor_per_agent_check(const FgParams* params, const FgActor* actors, int B, int N, int K) {
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: B >= 0 and K >= 1 required%s");
-    if (!actor_n_supported(N))
-        return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
-    if (!actors) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
-    char idx[16];
-    for (int i = 0; i < N; ++i) {
-        if ((rc = hd_actor_struct_check(params, &actors[i])) != FG_OK) return rc;
-        if (actors[i].hidden != actors[0].hidden || (actors[i].out_tanh != 0) != (actors[0].out_tanh != 0)) {
-            snprintf(idx, sizeof(idx), "%d", i);
-            return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
-                        idx);
-        }
-    }
-    return FG_OK;
-}
-static int actor_per_agent_dispatch(const Args& a, const FgActor* actors, const float* log_std, float* logp, hipStream_t st) {
-    ActorTab tab;
-    memset(&tab, 0, sizeof(tab));
-    for (int i = 0; i < a.N; ++i) {
-        tab.w1[i] = actors[i].w1; tab.b1[i] = actors[i].b1; tab.w2[i] = actors[i].w2;
-        tab.b2[i] = actors[i].b2; tab.w3[i] = actors[i].w3; tab.b3[i] = actors[i].b3;
-    }
-    tab.out_tanh = actors[0].out_tanh ? 1 : 0;
-    return actor_nh_dispatch(a.N, actors[0].hidden, "fg_rollout_hd_actor_per_agent: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s",
-                             [&](auto n, auto h) {
-        return launch_pa_v<decltype(n)::value, decltype(h)::value>(a, tab, log_std, logp, st);
-    });
-}
-
-// ---- the shared actor with LayerNorms (ln_actor_kernel / ln_sample_kernel) ----
-template <int NC, int H>
-static int launch_ln_v(const Args& a, const ActorW& w, const ActorNormW& nw, const float* log_std, float* logp, hipStream_t st) {
-    constexpr int E = actor_envs(NC);
-    static_assert(actor_lds_bytes<NC, H, true, false, true>() <= 160 * 1024, "LayerNorm actor rollout LDS");
-    char targs[16];
-    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    return launch_actor_pair<&ln_actor_kernel<NC, H>, &ln_sample_kernel<NC, H>>(
-        "ln_actor_kernel", "ln_sample_kernel", targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, false, true>() : actor_lds_bytes<NC, H, false, false, true>(),
-        "LayerNorm actor rollout launch failed: %s", st, log_std, logp, a, w, nw);
-}
-// fg_rollout_hd_actor's checks, then FgActorNorm's (no device touched): hidden 32 or 64, every eps that is read positive and
-// finite, gamma / beta 4-byte aligned
-static int actor_norm_check(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, int B, int N, int K) {
-    int rc = actor_check(params, actor, B, N, K);
-    if (rc) return rc;
+// One call of a formation_hd_env actor entry, fg_rollout_hd_actor* or its fg_describe_actor*_launch twin, as its checks
+// (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
+// host array of N members; `norm` counts for HD_ACTOR_NORM only; `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE
+// requires it); `logp`: the log-densities' destination, NULL from a describe twin.
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM };
+static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
+                                             "fg_rollout_hd_actor_norm"};
+struct HdActorCall {
+    HdActorKind kind;
+    const FgActor* actor;
+    const FgActorNorm* norm;
+    const float* log_std;
+    float* logp;
+};
+// FgActorNorm's checks (no device touched): hidden 32 or 64, every eps that is read positive and finite, gamma / beta 4-byte aligned
+static int actor_norm_check(const FgActor* actor, const FgActorNorm* norm) {
     if (!norm) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: norm is NULL%s");
     if (actor->hidden != 32 && actor->hidden != 64)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms%s");
@@ -1636,27 +1578,92 @@ static int actor_norm_check(const FgParams* params, const FgActor* actor, const 
         if ((uintptr_t)q.p & 3u) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: %s must be 4-byte aligned", q.name);
     return FG_OK;
 }
-static int actor_norm_dispatch(const Args& a, const FgActor& actor, const FgActorNorm& norm, const float* log_std, float* logp,
-                               hipStream_t st) {
-    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+// The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
+// this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
+// the norms, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
+// log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
+static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
+    const char* const who = hd_actor_entry[c.kind];
+    const char* const shared = hd_actor_entry[c.kind == HD_ACTOR_PER_AGENT ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 1 required", shared);
+    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", shared);
+    if (c.kind == HD_ACTOR_PER_AGENT) {
+        if (!c.actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
+        char idx[16];
+        for (int i = 0; i < N; ++i) {
+            if ((rc = hd_actor_struct_check(params, &c.actor[i])) != FG_OK) return rc;
+            if (c.actor[i].hidden != c.actor[0].hidden || (c.actor[i].out_tanh != 0) != (c.actor[0].out_tanh != 0)) {
+                snprintf(idx, sizeof(idx), "%d", i);
+                return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
+                            idx);
+            }
+        }
+    } else if ((rc = hd_actor_struct_check(params, c.actor)) != FG_OK) {
+        return rc;
+    }
+    if (c.kind == HD_ACTOR_NORM && (rc = actor_norm_check(c.actor, c.norm)) != FG_OK) return rc;
+    if (!c.log_std) {
+        if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
+        c.logp = nullptr;
+        return FG_OK;
+    }
+    if ((uintptr_t)c.log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
+    if ((uintptr_t)c.logp & 3u) return fail(FG_ERR_ALIGNMENT, "%s: logp_seq must be 4-byte aligned", who);
+    return FG_OK;
+}
+// The one N x H grid of the formation_hd_env actor kernels: launch(n, h) with N and H as the `value` of the arguments' types,
+// or UNSUPPORTED_N in `who`'s name when N is not in the list.  MAXH is the widest H of the caller's kernels: `hidden` is 32,
+// 64 or - MAXH == 128 only - 128 (actor_struct_check, actor_norm_check), and no launch(n, 128) is instantiated below that.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <int MAXH, class F>
+static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
+#define FG_ACTOR(NN)                                                                      \
+    if (N == NN) {                                                                        \
+        if (hidden == 32) return launch(IntC<NN>{}, IntC<32>{});                          \
+        if constexpr (MAXH == 128) if (hidden != 64) return launch(IntC<NN>{}, IntC<128>{}); \
+        return launch(IntC<NN>{}, IntC<64>{});                                            \
+    }
+    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
+#undef FG_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
+}
+// a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
+static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
+    const char* const who = hd_actor_entry[c.kind == HD_ACTOR_SAMPLE ? HD_ACTOR_SHARED : c.kind];
+    if (c.kind == HD_ACTOR_PER_AGENT) {
+        ActorTab tab;
+        memset(&tab, 0, sizeof(tab));
+        for (int i = 0; i < a.N; ++i) {
+            tab.w1[i] = c.actor[i].w1; tab.b1[i] = c.actor[i].b1; tab.w2[i] = c.actor[i].w2;
+            tab.b2[i] = c.actor[i].b2; tab.w3[i] = c.actor[i].w3; tab.b3[i] = c.actor[i].b3;
+        }
+        tab.out_tanh = c.actor[0].out_tanh ? 1 : 0;
+        return actor_nh_dispatch<128>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false>(a, c.log_std, c.logp, st, tab);
+        });
+    }
+    const ActorW w = actor_w(*c.actor);
+    if (c.kind != HD_ACTOR_NORM)
+        return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
+        });
+    const FgActorNorm& norm = *c.norm;
     const bool in_norm = norm.in_norm != 0;
     const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
                            norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
-#define FG_ACTOR_LN(NN) \
-    if (a.N == NN) return actor.hidden == 32 ? launch_ln_v<NN, 32>(a, w, nw, log_std, logp, st) \
-                                             : launch_ln_v<NN, 64>(a, w, nw, log_std, logp, st);
-    FG_ACTOR_LN(3) FG_ACTOR_LN(4) FG_ACTOR_LN(8) FG_ACTOR_LN(9) FG_ACTOR_LN(16) FG_ACTOR_LN(25) FG_ACTOR_LN(27) FG_ACTOR_LN(32)
-#undef FG_ACTOR_LN
-    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_actor_norm: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true>(a, c.log_std, c.logp, st, w, nw);
+    });
 }
 
-// per_agent: `actor` is a host array of N members (actor_per_agent_dispatch), else the one shared actor - with LayerNorms
-// when `norm` is not NULL (actor_norm_dispatch)
-static int rollout_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
+// the buffers' checks and the launch of a call that has passed hd_actor_check
+static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int B, int N, int K,
                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
-                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
-                              int obs_every, void* stream, bool per_agent = false, const FgActorNorm* norm = nullptr) {
+                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                              int obs_every, void* stream) {
     if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
         return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
     if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
@@ -1672,9 +1679,7 @@ static int rollout_actor_impl(const FgParams* params, const FgActor* actor, cons
     a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
     a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
     a.act_out = act_seq;
-    if (per_agent) return actor_per_agent_dispatch(a, actor, log_std, logp_seq, (hipStream_t)stream);
-    if (norm) return actor_norm_dispatch(a, *actor, *norm, log_std, logp_seq, (hipStream_t)stream);
-    return actor_dispatch(a, *actor, log_std, logp_seq, (hipStream_t)stream);
+    return hd_actor_dispatch(a, c, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -1684,10 +1689,10 @@ int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int
                         float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
                         int obs_every, void* stream) {
-    int rc = actor_check(params, actor, B, N, K);
-    if (rc) return rc;
-    return rollout_actor_impl(params, actor, nullptr, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
-                              step, obs_seq, reward_seq, indiv_seq, done_seq, nullptr, obs_every, stream);
+    HdActorCall c = {HD_ACTOR_SHARED, actor, nullptr, nullptr, nullptr};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
@@ -1695,12 +1700,10 @@ int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, con
                                float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                int obs_every, void* stream) {
-    int rc = actor_check(params, actor, B, N, K);
-    if (rc) return rc;
-    if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
-    if ((uintptr_t)logp_seq & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: logp_seq must be 4-byte aligned%s");
-    return rollout_actor_impl(params, actor, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
-                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream);
+    HdActorCall c = {HD_ACTOR_SAMPLE, actor, nullptr, log_std, logp_seq};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N, int K,
@@ -1708,17 +1711,10 @@ int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors,
                                   float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                   float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                   int obs_every, void* stream) {
-    int rc = actor_per_agent_check(params, actors, B, N, K);
-    if (rc) return rc;
-    if (log_std) {
-        if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
-        if ((uintptr_t)logp_seq & 3u)
-            return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_per_agent: logp_seq must be 4-byte aligned%s");
-    } else {
-        logp_seq = nullptr;
-    }
-    return rollout_actor_impl(params, actors, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
-                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream, true);
+    HdActorCall c = {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, logp_seq};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
@@ -1726,16 +1722,10 @@ int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const
                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                              int obs_every, void* stream) {
-    int rc = actor_norm_check(params, actor, norm, B, N, K);
-    if (rc) return rc;
-    if (log_std) {
-        if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
-        if ((uintptr_t)logp_seq & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_norm: logp_seq must be 4-byte aligned%s");
-    } else {
-        logp_seq = nullptr;
-    }
-    return rollout_actor_impl(params, actor, log_std, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel,
-                              step, obs_seq, reward_seq, indiv_seq, done_seq, logp_seq, obs_every, stream, false, norm);
+    HdActorCall c = {HD_ACTOR_NORM, actor, norm, log_std, logp_seq};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
@@ -1770,59 +1760,45 @@ int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, flo
 
 }  // extern "C"
 
-static int describe_actor_impl(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
-                               int obs_every, char* out, int out_len, bool per_agent = false,
-                               const FgActorNorm* norm = nullptr) {
+// the describe twin `who` of the call `c`: the out buffer's check, the call's own checks, then the dry run of its dispatch
+static int describe_actor_impl(const char* who, const FgParams* params, HdActorCall c, int B, int N, int K, int obs_every,
+                               char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "%s: out buffer required", who);
+    out[0] = 0;
+    int rc = hd_actor_check(params, c, B, N, K);
+    if (rc) return rc;
     if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
     Args a; memset(&a, 0, sizeof(a));
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    int rc = set_obs_pitch(&a);
-    if (rc != FG_OK) return rc;
+    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
     const DescribeScope describing(out, out_len);
-    if (norm) return actor_norm_dispatch(a, *actor, *norm, log_std, nullptr, nullptr);
-    return per_agent ? actor_per_agent_dispatch(a, actor, log_std, nullptr, nullptr)
-                     : actor_dispatch(a, *actor, log_std, nullptr, nullptr);
+    return hd_actor_dispatch(a, c, nullptr);
 }
 
 extern "C" {
 
 int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
                              char* out, int out_len) {
-    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: out buffer required%s");
-    out[0] = 0;
-    int rc = actor_check(params, actor, B, N, K);
-    if (rc) return rc;
-    return describe_actor_impl(params, actor, nullptr, B, N, K, obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_launch", params, {HD_ACTOR_SHARED, actor, nullptr, nullptr, nullptr}, B, N, K,
+                               obs_every, out, out_len);
 }
 
 int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
                                     int obs_every, char* out, int out_len) {
-    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_sample_launch: out buffer required%s");
-    out[0] = 0;
-    int rc = actor_check(params, actor, B, N, K);
-    if (rc) return rc;
-    if ((rc = actor_sample_check(log_std)) != FG_OK) return rc;
-    return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_sample_launch", params, {HD_ACTOR_SAMPLE, actor, nullptr, log_std, nullptr},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
                                   int B, int N, int K, int obs_every, char* out, int out_len) {
-    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_norm_launch: out buffer required%s");
-    out[0] = 0;
-    int rc = actor_norm_check(params, actor, norm, B, N, K);
-    if (rc) return rc;
-    if (log_std && (rc = actor_sample_check(log_std)) != FG_OK) return rc;
-    return describe_actor_impl(params, actor, log_std, B, N, K, obs_every, out, out_len, false, norm);
+    return describe_actor_impl("fg_describe_actor_norm_launch", params, {HD_ACTOR_NORM, actor, norm, log_std, nullptr}, B, N, K,
+                               obs_every, out, out_len);
 }
 
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
                                       int K, int obs_every, char* out, int out_len) {
-    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_per_agent_launch: out buffer required%s");
-    out[0] = 0;
-    int rc = actor_per_agent_check(params, actors, B, N, K);
-    if (rc) return rc;
-    if (log_std && (rc = actor_sample_check(log_std)) != FG_OK) return rc;
-    return describe_actor_impl(params, actors, log_std, B, N, K, obs_every, out, out_len, true);
+    return describe_actor_impl("fg_describe_actor_per_agent_launch", params,
+                               {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, nullptr}, B, N, K, obs_every, out, out_len);
 }
 
 }  // extern "C"
@@ -1860,7 +1836,7 @@ static int scn_actor_check(const FgParams* params, const FgScenario* sc, const F
 
 static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act_out, const float* log_std, float* logp,
                               hipStream_t st) {
-    const ActorW w = {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+    const ActorW w = actor_w(actor);
     const int L = a.sc.num_landmarks, M = a.sc.num_obstacles;
     const int nbr = a.sc.kind == FG_SCN_PARTIAL ? a.sc.num_obs : a.N - 1;
     // the shapes of launch_scenario's FG_SCN_LANE list

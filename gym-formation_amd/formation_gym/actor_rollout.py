@@ -57,30 +57,67 @@ def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_
     return dict(in_features=int(obs_dim), fused_n=(N,), fused_hidden=LANDMARK_FUSED_HIDDEN, per_agent=False)
 
 
-def actor_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-               fused_ln_hidden=None):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate `actor` for `num_agents` agents, else
-    None.  `device`: the env's device (None: not checked).  The tensors are the actor's own parameters (b* may be None).
-    The scenario's facts: `in_features` the actor's input width (None: formation_hd_env's 6N), `fused_n` the agent counts and
-    `fused_hidden` the hidden widths its kernel is built for.  (`fused_ln_hidden` is `layernorm_spec`'s fact, taken here so
-    that a scenario's facts pass whole; this function never accepts a LayerNorm.)"""
+def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
+               fused_ln_hidden=FUSED_LN_HIDDEN):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], norms) when a fused kernel can evaluate the shared actor body `actor` for
+    `num_agents` agents, else None.  The two forms, each with its own kernels and so its own hidden widths:
+        Sequential(Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])              H in `fused_hidden`
+        Sequential([LayerNorm(D),] Linear(D, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2)
+                   [, Tanh()])                                                                       H in `fused_ln_hidden`
+    `norms` is None for the first and the ActorNorms of the second, whose every LayerNorm is over its last axis alone with
+    fp32 contiguous parameters on `device` or none.  `device`: the env's device (None: not checked).  The tensors are the
+    actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
+    formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
+    are built for (None or empty: it has no kernel for that form)."""
     nn = torch.nn
     if type(actor) is not nn.Sequential or int(num_agents) not in fused_n:
         return None
     if in_features is None:
         in_features = 6 * int(num_agents)
     mods = list(actor)
-    kinds = [type(m) for m in mods]
-    body = [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear]
-    if kinds != body and kinds != body + [nn.Tanh]:
+    lead = bool(mods) and type(mods[0]) is nn.LayerNorm
+    rest = mods[1:] if lead else mods
+    kinds = [type(m) for m in rest]
+    out_tanh = kinds[-1:] == [nn.Tanh]
+    if out_tanh:
+        kinds.pop()
+    if kinds == [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] and not lead:
+        spec = _linears_spec(rest[0], rest[2], rest[4], out_tanh, in_features, device, fused_hidden)
+        return None if spec is None else spec + (None,)
+    if kinds != [nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear]:
         return None
-    return _linears_spec(mods[0], mods[2], mods[4], len(mods) == 6, in_features, device, fused_hidden)
+    spec = _linears_spec(rest[0], rest[3], rest[6], out_tanh, in_features, device, fused_ln_hidden)
+    if spec is None:
+        return None
+    dev = None if device is None else torch.device(device)
+    n0 = _norm_triple(mods[0], rest[0].in_features, dev) if lead else None
+    n1, n2 = _norm_triple(rest[2], spec[0], dev), _norm_triple(rest[5], spec[0], dev)
+    if (lead and n0 is None) or n1 is None or n2 is None:
+        return None
+    return spec + (ActorNorms(n0, n1, n2),)
+
+
+def actor_spec(actor, num_agents, device=None, **facts):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate the actor without LayerNorms `actor`
+    for `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its first form.  This function never
+    accepts a LayerNorm."""
+    spec = _body_spec(actor, num_agents, device, **facts)
+    return spec[:3] if spec is not None and spec[3] is None else None
+
+
+def layernorm_spec(actor, num_agents, device=None, **facts):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms) when the fused LayerNorm kernel can evaluate `actor` for
+    `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its second form.  An actor without
+    LayerNorms is `actor_spec`'s, not this function's."""
+    spec = _body_spec(actor, num_agents, device, **facts)
+    return spec if spec is not None and spec[3] is not None else None
 
 
 def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
-    """actor_spec's answer for the three Linears of a body whose module kinds have been checked."""
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) of the three Linears of a body whose module kinds have been checked, else
+    None.  `fused_hidden`: the hidden widths of that body's kernels (None or empty: none)."""
     H = l1.out_features
-    if H not in fused_hidden or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
+    if H not in tuple(fused_hidden or ()) or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
             or (l3.in_features, l3.out_features) != (H, 2):
         return None
     params = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
@@ -96,7 +133,7 @@ def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
 
 
 class ActorNorms(collections.namedtuple("ActorNorms", "input hidden1 hidden2")):
-    """The LayerNorms of a fused LayerNorm actor (`layernorm_spec`): each a (weight, bias, eps) triple - the module's own
+    """The LayerNorms of a fused LayerNorm actor (`_body_spec`): each a (weight, bias, eps) triple - the module's own
     parameter tensors, None where it has none (weight: 1, bias: 0), and its eps as a float; `input` is None when the actor has
     no leading LayerNorm."""
     __slots__ = ()
@@ -117,39 +154,6 @@ def _norm_triple(m, width, device):
                 or not _on_device(t, device):
             return None
     return g, b, eps
-
-
-def layernorm_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=None,
-                   fused_ln_hidden=FUSED_LN_HIDDEN):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms) when the fused LayerNorm kernel can evaluate `actor` for
-    `num_agents` agents, else None: exactly
-        Sequential([LayerNorm(D),] Linear(D, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2) [, Tanh()])
-    with H in `fused_ln_hidden`, the Linears passing `actor_spec` and every LayerNorm over its last axis alone with fp32
-    contiguous parameters on `device` or none.  An actor without LayerNorms is `actor_spec`'s, not this function's.
-    (`fused_hidden` is `actor_spec`'s fact, taken here so that a scenario's facts pass whole.)"""
-    nn = torch.nn
-    if type(actor) is not nn.Sequential or int(num_agents) not in fused_n or not fused_ln_hidden:
-        return None
-    if in_features is None:
-        in_features = 6 * int(num_agents)
-    mods = list(actor)
-    lead = bool(mods) and type(mods[0]) is nn.LayerNorm
-    rest = mods[1:] if lead else mods
-    kinds = [type(m) for m in rest]
-    body = [nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear]
-    if kinds != body and kinds != body + [nn.Tanh]:
-        return None
-    # the three Linears under actor_spec's rule, with this kernel's widths
-    spec = _linears_spec(rest[0], rest[3], rest[6], len(rest) == 8, in_features, device, tuple(fused_ln_hidden))
-    if spec is None:
-        return None
-    H, out_tanh, params = spec
-    dev = None if device is None else torch.device(device)
-    n0 = _norm_triple(mods[0], rest[0].in_features, dev) if lead else None
-    n1, n2 = _norm_triple(rest[2], H, dev), _norm_triple(rest[5], H, dev)
-    if (lead and n0 is None) or n1 is None or n2 is None:
-        return None
-    return H, out_tanh, params, ActorNorms(n0, n1, n2)
 
 
 class PerAgentActor(torch.nn.Module):
@@ -221,10 +225,9 @@ def _on_device(t, device):
 
 def sample_spec(actor, num_agents, device=None, **facts):
     """(actor_spec(actor.mean, ...), log_std) when the fused kernel can sample from the GaussianActor `actor` for
-    `num_agents` agents, else None: its mean fuses (actor_spec; per_agent_spec for a PerAgentActor mean) and log_std is a contiguous fp32 [2] tensor on `device`
-    (None: not checked).  log_std is the actor's own parameter, read in place by every launch.  `facts`: actor_spec's
-    keyword arguments for a shared mean (in_features, fused_n, fused_hidden).  A LayerNorm mean is not looked for here:
-    `resolve_actor` asks `layernorm_spec` for it."""
+    `num_agents` agents, else None: its mean fuses without LayerNorms (actor_spec; per_agent_spec for a PerAgentActor mean)
+    and log_std is a contiguous fp32 [2] tensor on `device` (None: not checked).  log_std is the actor's own parameter, read
+    in place by every launch.  `facts`: the scenario's facts for a shared mean, as `_body_spec` takes them."""
     if not isinstance(actor, GaussianActor):
         return None
     if isinstance(actor.mean, PerAgentActor):
@@ -260,36 +263,28 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     `rollout_actor(K, actor)` runs fused, None when it runs host-paced.  The keyword facts describe the env: a scenario with
     the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls, accel, max_speed,
     u_noise, per-agent properties), no post_step_callback.  `per_agent`: the scenario's launch takes a PerAgentActor
-    (formation_hd_env's does, the landmark scenarios' does not); `facts`: actor_spec's and layernorm_spec's keyword arguments
-    (in_features, fused_n, fused_hidden, fused_ln_hidden), as the scenario states them.  A shared actor that actor_spec does
-    not take is tried as a LayerNorm actor (layernorm_spec: formation_hd_env, H in {32, 64}); PerAgentActor members with
-    LayerNorms and the landmark scenarios (`fused_ln_hidden=()`) run host-paced."""
+    (formation_hd_env's does, the landmark scenarios' does not); `facts`: `_body_spec`'s keyword arguments (in_features,
+    fused_n, fused_hidden, fused_ln_hidden), as the scenario states them.  A GaussianActor is unwrapped once, into its mean and
+    its log_std; the mean - or the actor itself - is a PerAgentActor (per_agent_spec: members without LayerNorms) or a shared
+    body (`_body_spec`: with LayerNorms where the scenario has such a kernel - formation_hd_env, H in {32, 64}; the landmark
+    scenarios state `fused_ln_hidden=()`)."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return None
-    gaussian = isinstance(actor, GaussianActor)
-    members_own = isinstance(actor.mean if gaussian else actor, PerAgentActor)
-    if members_own and not per_agent:
-        return None
-    log_std = None
-    if gaussian:
-        spec = sample_spec(actor, num_agents, device, **facts)
-        if spec is not None:
-            spec, log_std = spec
-    elif members_own:
-        spec = per_agent_spec(actor, num_agents, device)
-    else:
-        spec = actor_spec(actor, num_agents, device, **facts)
-    if spec is None and not members_own:               # the shared actor with LayerNorms, alone or as a Gaussian's mean
-        spec = layernorm_spec(actor.mean if gaussian else actor, num_agents, device, **facts)
-        log_std = _fused_log_std(actor, device) if gaussian else None
-        if spec is None or (gaussian and log_std is None):
+    mean, log_std = actor, None
+    if isinstance(actor, GaussianActor):
+        mean, log_std = actor.mean, _fused_log_std(actor, device)
+        if log_std is None:
             return None
-        hidden, out_tanh, weights, norms = spec
-        return FusedActor(hidden, bool(out_tanh), [weights], False, log_std, norms)
+    members_own = isinstance(mean, PerAgentActor)
+    if members_own:
+        spec = per_agent_spec(mean, num_agents, device) if per_agent else None
+        spec = None if spec is None else spec + (None,)
+    else:
+        spec = _body_spec(mean, num_agents, device, **facts)
     if spec is None:
         return None
-    hidden, out_tanh, weights = spec
-    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std)
+    hidden, out_tanh, weights, norms = spec
+    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms)
 
 
 def actor_path(actor, num_agents, device=None, **facts):

@@ -257,7 +257,7 @@ class Scenario(BaseScenario):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
-        other tensors are those of `rollout_batch`.  The entry point by (per_agent, log_std):
+        other tensors are those of `rollout_batch`.  The entry point by (norms, per_agent, log_std):
           one shared actor                      `fg_rollout_hd_actor`
           ... with a GaussianActor's log_std    `fg_rollout_hd_actor_sample`, the log-densities in out["log_prob"] [K,B,N]
           one actor per agent                   `fg_rollout_hd_actor_per_agent` (log_std or NULL), agent i's rows through
@@ -276,17 +276,18 @@ class Scenario(BaseScenario):
                  _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                  _native.ptr(out.get("done")))
         tail = (int(obs_every), _native.current_stream(world.device))
-        if norm is not None:
-            if actor.per_agent:
-                raise NotImplementedError("PerAgentActor members with LayerNorms have no fused launch")
-            logp = None if log_std is None else out["log_prob"].data_ptr()
-            fn, args = lib.fg_rollout_hd_actor_norm, (fas, norm, _native.ptr(log_std)) + state + (logp,) + tail
-        elif actor.per_agent or log_std is not None:
-            fn = lib.fg_rollout_hd_actor_per_agent if actor.per_agent else lib.fg_rollout_hd_actor_sample
-            logp = None if log_std is None else out["log_prob"].data_ptr()
-            args = (fas, _native.ptr(log_std)) + state + (logp,) + tail
-        else:
-            fn, args = lib.fg_rollout_hd_actor, (fas,) + state + tail
+        # (norms, per_agent, gaussian) -> (entry point, its arguments before the state, logp_seq follows the state)
+        ls = _native.ptr(log_std)
+        pa, ln = (lib.fg_rollout_hd_actor_per_agent, (fas, ls), True), (lib.fg_rollout_hd_actor_norm, (fas, norm, ls), True)
+        table = {(False, False, False): (lib.fg_rollout_hd_actor, (fas,), False),
+                 (False, False, True): (lib.fg_rollout_hd_actor_sample, (fas, ls), True),
+                 (False, True, False): pa, (False, True, True): pa, (True, False, False): ln, (True, False, True): ln}
+        key = (norm is not None, bool(actor.per_agent), log_std is not None)
+        if key not in table:
+            raise NotImplementedError("PerAgentActor members with LayerNorms have no fused launch")
+        fn, lead, with_logp = table[key]
+        logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
+        args = lead + state + logp + tail
         return _native.bind_launch(fn, p, *args,
                                    keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm))
 

@@ -77,7 +77,8 @@ def kernarg_sizes(lib_path, arch="gfx950"):
 
 def kernel_disassembly(lib_path, arch="gfx950"):
     """{mangled kernel name: its instruction lines}.  A line is mnemonic and operands: comments, the `<label>` operands and the
-    target addresses of branches are stripped, as is the padding between kernels, so code that only moved compares equal."""
+    target addresses of branches are stripped, as is the padding between kernels (objdump's `...` and the `s_nop` lines behind a
+    kernel's last `s_endpgm`), so code that only moved compares equal."""
     names = {k["name"] for k in kernel_resources(lib_path, arch)}
     out, cur = {}, None
     with code_objects(lib_path, arch) as objs:
@@ -93,6 +94,11 @@ def kernel_disassembly(lib_path, arch="gfx950"):
                         ins = ins.split()[0]
                     if ins and ins != "...":               # "...": zero padding between kernels, elided by objdump
                         cur.append(ins)
+    for code in out.values():                              # the s_nop lines that align whatever follows the kernel's end
+        if "s_endpgm" in code:
+            end = len(code) - code[::-1].index("s_endpgm")
+            if all(ins.startswith("s_nop") for ins in code[end:]):
+                del code[end:]
     return out
 
 

@@ -1,7 +1,6 @@
 """CPU checks of the learned-actor rollout in the landmark scenarios (`fg_rollout_scenario_actor`): which path an actor takes,
 the dry-run description of the fused launch, argument checks that touch no device, and the new kernels' resources."""
 import ctypes
-import os
 import types
 
 import pytest
@@ -10,9 +9,7 @@ import torch
 from formation_gym import _native, actor_rollout, load_scenario
 from formation_gym.actor_rollout import (FUSED_HIDDEN, FUSED_N, LANDMARK_FUSED_HIDDEN, LANDMARK_FUSED_SHAPES, GaussianActor,
                                          PerAgentActor, actor_path, actor_spec, landmark_facts, sample_spec)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gym-formation_amd", "lib", "libformation_hip.so")
+from tests.actor_testlib import LIB, describe, fake_actor as _fake_actor, params
 
 # (scenario file, agents, landmarks, obstacles, num_obs) of the seven shapes, and the observation width the kernel composes
 SHAPES = [("basic_formation_env", 3, 3, 0, 0, 18), ("formation_hd_partial_env", 5, 5, 0, 3, 26),
@@ -140,11 +137,7 @@ def test_formation_hd_decisions_unchanged():
 
 
 def _params():
-    p = _native.FgParams()
-    p.dt, p.damping, p.contact_force, p.contact_margin = 0.1, 0.25, 100.0, 0.001
-    p.sensitivity, p.mass, p.dist_min, p.collide_thresh = 5.0, 1.0, 0.2, 0.2
-    p.world_length = 50
-    return p
+    return params(dist_min=0.2, collide_thresh=0.2, world_length=50)
 
 
 KIND = {"basic_formation_env": _native.FG_SCN_BASIC, "formation_hd_partial_env": _native.FG_SCN_PARTIAL,
@@ -157,16 +150,9 @@ def _desc(name, L, M, num_obs, variant=0):
                               variant=variant)
 
 
-def _fake_actor(H, tanh=1):
-    addr = 4096                                       # stand-ins: only NULL-ness and alignment are looked at
-    return _native.FgActor(H, tanh, addr, addr, addr, addr, addr, addr)
-
-
 def _describe(lib, name, N, L, M, num_obs, H, sample, B=4096, K=20, params=None, variant=0):
-    buf = ctypes.create_string_buffer(512)
-    rc = lib.fg_describe_scenario_actor_launch(params or _params(), _desc(name, L, M, num_obs, variant), _fake_actor(H),
-                                               ctypes.c_void_p(4096) if sample else None, B, N, K, 1, buf, 512)
-    return rc, buf.value.decode()
+    lead = (_desc(name, L, M, num_obs, variant), _fake_actor(H), ctypes.c_void_p(4096) if sample else None)
+    return describe(lib, "fg_describe_scenario_actor_launch", lead, N, B, K, params or _params())
 
 
 def test_describe_names_one_instantiation_per_shape():

@@ -11,9 +11,8 @@ import torch
 from formation_gym import GaussianActor, PerAgentActor, _native, load_scenario
 from formation_gym.actor_rollout import (FUSED_HIDDEN, FUSED_LN_HIDDEN, FUSED_N, FusedActor, actor_path, actor_spec,
                                          layernorm_spec, resolve_actor)
+from tests.actor_testlib import LIB, ROOT, describe, fake_actor as _fake_actor, fake_actors, params as _params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gym-formation_amd", "lib", "libformation_hip.so")
 nn = torch.nn
 
 
@@ -176,17 +175,6 @@ def test_landmark_scenarios_run_layernorm_actors_host_paced(name, N, L, M, num_o
 
 
 # ---- the C ABI without a device ----
-def _params():
-    p = _native.FgParams()
-    p.dt, p.damping, p.contact_force, p.contact_margin = 0.1, 0.25, 100.0, 0.001
-    p.sensitivity, p.mass, p.dist_min, p.collide_thresh = 5.0, 1.0, 0.06, 0.03
-    p.world_length = 100
-    return p
-
-
-def _fake_actor(H, tanh=1):
-    addr = 4096                                       # stand-ins: only NULL-ness and alignment are looked at
-    return _native.FgActor(H, tanh, addr, addr, addr, addr, addr, addr)
 
 
 def _fake_norm(in_norm=1, eps=1e-5, **kw):
@@ -198,10 +186,8 @@ def _fake_norm(in_norm=1, eps=1e-5, **kw):
 
 
 def _describe(lib, N, H, sample, norm="default", B=4096, K=20):
-    buf = ctypes.create_string_buffer(512)
     norm = _fake_norm() if norm == "default" else norm
-    rc = lib.fg_describe_actor_norm_launch(_params(), _fake_actor(H), norm, 4096 if sample else None, B, N, K, 1, buf, 512)
-    return rc, buf.value.decode()
+    return describe(lib, "fg_describe_actor_norm_launch", (_fake_actor(H), norm, 4096 if sample else None), N, B, K)
 
 
 def test_struct_layout_matches_the_header(tmp_path):
@@ -267,6 +253,92 @@ def test_bad_arguments_rejected_without_a_device():
         assert _describe(lib, 9, 64, sample, norm=None)[0] == -1
         assert _describe(lib, 9, 64, sample, norm=_fake_norm(eps=0.0))[0] == -1
         assert _describe(lib, 9, 64, sample, B=0)[0] == -1
+
+
+# ---- the eight hd-actor entry points: every failing check's status and fg_last_error() text, and the order of the checks ----
+HD_ACTOR_ENTRIES = {"shared": ("fg_rollout_hd_actor", "fg_describe_actor_launch"),
+                    "sample": ("fg_rollout_hd_actor_sample", "fg_describe_actor_sample_launch"),
+                    "per_agent": ("fg_rollout_hd_actor_per_agent", "fg_describe_actor_per_agent_launch"),
+                    "norm": ("fg_rollout_hd_actor_norm", "fg_describe_actor_norm_launch")}
+_ALL, _ONE, _PA, _LN = tuple(HD_ACTOR_ENTRIES), ("shared", "sample", "norm"), ("per_agent",), ("norm",)
+_GAUSS, _RUN, _DRY, _BOTH = ("sample", "per_agent", "norm"), (False,), (True,), (False, True)
+_N_LIST = "N must be 3, 4, 8, 9, 16, 25, 27 or 32"
+# (entries, the rollout entry and / or its describe twin, what is wrong with the call, status, fg_last_error()); a text of None:
+# the call succeeds.  The literals are the answers of the library before the entries shared one check-and-run.
+HD_ACTOR_BAD_CALLS = [
+    (_ONE, _BOTH, dict(actor=None), -1, "fg_rollout_hd_actor: actor is NULL"),
+    (_PA, _BOTH, dict(actor=None), -1, "fg_rollout_hd_actor_per_agent: actors is NULL"),
+    (_ALL, _BOTH, dict(H=48), -1, "fg_rollout_hd_actor: hidden must be 32, 64 or 128"),
+    (_ONE, _BOTH, dict(N=81), -2, "fg_rollout_hd_actor: " + _N_LIST),
+    (_PA, _BOTH, dict(N=81), -2, "fg_rollout_hd_actor_per_agent: " + _N_LIST),
+    (_ONE, _BOTH, dict(K=0), -1, "fg_rollout_hd_actor: B >= 0 and K >= 1 required"),
+    (_PA, _BOTH, dict(K=0), -1, "fg_rollout_hd_actor_per_agent: B >= 0 and K >= 1 required"),
+    (_ONE, _BOTH, dict(B=-1), -1, "fg_rollout_hd_actor: B >= 0 and K >= 1 required"),
+    (_PA, _BOTH, dict(B=-1), -1, "fg_rollout_hd_actor_per_agent: B >= 0 and K >= 1 required"),
+    (_ONE, _BOTH, dict(N=81, H=48), -2, "fg_rollout_hd_actor: " + _N_LIST),                         # N before the actor
+    (_PA, _BOTH, dict(N=81, H=48), -2, "fg_rollout_hd_actor_per_agent: " + _N_LIST),
+    (_ONE, _BOTH, dict(K=0, N=81), -1, "fg_rollout_hd_actor: B >= 0 and K >= 1 required"),          # B and K before N
+    (_PA, _BOTH, dict(K=0, N=81), -1, "fg_rollout_hd_actor_per_agent: B >= 0 and K >= 1 required"),
+    (_LN, _BOTH, dict(H=128), -1, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms"),
+    (_LN, _BOTH, dict(H=128, norm=None), -1, "fg_rollout_hd_actor_norm: norm is NULL"),             # norm before hidden
+    (_LN, _BOTH, dict(H=128, log_std=4098), -1, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms"),
+    (_LN, _BOTH, dict(norm=None), -1, "fg_rollout_hd_actor_norm: norm is NULL"),
+    (_LN, _BOTH, dict(norm=dict(h1_eps=0.0)), -1, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite"),
+    (_LN, _BOTH, dict(norm=dict(h1_eps=0.0, h2_beta=4098)), -1, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite"),
+    (_LN, _BOTH, dict(norm=dict(h2_beta=4098)), -1, "fg_rollout_hd_actor_norm: h2_beta must be 4-byte aligned"),
+    (_LN, _BOTH, dict(norm=dict(h2_beta=4098), log_std=4098), -1, "fg_rollout_hd_actor_norm: h2_beta must be 4-byte aligned"),
+    (_PA, _BOTH, dict(member=(3, 32)), -1, "fg_rollout_hd_actor_per_agent: member 3 differs from member 0 in hidden or out_tanh"),
+    (_PA, _BOTH, dict(member=(3, 48)), -1, "fg_rollout_hd_actor: hidden must be 32, 64 or 128"),    # a member's own checks first
+    (_PA, _BOTH, dict(member=(3, 32), log_std=4098), -1,
+     "fg_rollout_hd_actor_per_agent: member 3 differs from member 0 in hidden or out_tanh"),
+    # NULL log_std: an error for the sampling entry; the deterministic actor elsewhere, whose logp_seq is then not looked at
+    (("sample",), _BOTH, dict(log_std=None, B=0, logp=4098), -1, "fg_rollout_hd_actor_sample: log_std is NULL"),
+    (("per_agent", "norm"), _RUN, dict(log_std=None, B=0, logp=4098), 0, None),
+    (_GAUSS, _BOTH, dict(log_std=4098), -3, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned"),
+    (("sample",), _RUN, dict(logp=4098), -3, "fg_rollout_hd_actor_sample: logp_seq must be 4-byte aligned"),
+    (_PA, _RUN, dict(logp=4098), -3, "fg_rollout_hd_actor_per_agent: logp_seq must be 4-byte aligned"),
+    (_LN, _RUN, dict(logp=4098), -3, "fg_rollout_hd_actor_norm: logp_seq must be 4-byte aligned"),
+    (_GAUSS, _RUN, dict(log_std=4098, logp=4098), -3, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned"),
+    # an empty batch: nothing to launch, but nothing to describe either - after the call's own checks
+    (_ALL, _RUN, dict(B=0), 0, None),
+    (_ALL, _DRY, dict(B=0), -1, "fg_describe_actor_launch: B > 0 required"),
+    (_ONE, _DRY, dict(B=0, N=81), -2, "fg_rollout_hd_actor: " + _N_LIST),
+    (_PA, _DRY, dict(B=0, N=81), -2, "fg_rollout_hd_actor_per_agent: " + _N_LIST),
+    # the describe twins look at their out buffer first, each in its own name
+    (("shared",), _DRY, dict(out=None, actor=None), -1, "fg_describe_actor_launch: out buffer required"),
+    (("sample",), _DRY, dict(out=None, actor=None), -1, "fg_describe_actor_sample_launch: out buffer required"),
+    (_PA, _DRY, dict(out=None, actor=None), -1, "fg_describe_actor_per_agent_launch: out buffer required"),
+    (_LN, _DRY, dict(out=None, actor=None), -1, "fg_describe_actor_norm_launch: out buffer required"),
+]
+
+
+def _hd_actor_call(lib, kind, dry, H=64, N=9, K=20, B=128, actor="fake", member=None, norm="fake", log_std=4096, logp=4096,
+                   out="buffer"):
+    """(status, fg_last_error()) of the `kind` entry (its describe twin when `dry`) on stand-in pointers.  `member`:
+    (index, hidden) of one per-agent member to alter; `norm`: None, or _fake_norm's keyword arguments."""
+    if actor == "fake":
+        actor = fake_actors(9, H) if kind == "per_agent" else _fake_actor(H)
+        if member is not None:
+            actor[member[0]].hidden = member[1]
+    norm = _fake_norm() if norm == "fake" else norm if norm is None else _fake_norm(**norm)
+    lead = {"shared": (actor,), "sample": (actor, log_std), "per_agent": (actor, log_std), "norm": (actor, norm, log_std)}[kind]
+    if dry:
+        buf = ctypes.create_string_buffer(512) if out == "buffer" else None
+        rc = getattr(lib, HD_ACTOR_ENTRIES[kind][1])(_params(), *lead, B, N, K, 1, buf, 512)
+    else:
+        state = [ctypes.c_void_p(4096)] * 12 + ([] if kind == "shared" else [logp])
+        rc = getattr(lib, HD_ACTOR_ENTRIES[kind][0])(_params(), *lead, B, N, K, *state, 1, None)
+    return rc, lib.fg_last_error().decode()
+
+
+def test_hd_actor_entries_fail_in_one_order_with_one_text():
+    lib = _native.load()
+    for kinds, dries, wrong, status, text in HD_ACTOR_BAD_CALLS:
+        assert status != 0 or wrong.get("B") == 0, "a call that would launch: %r" % (wrong,)
+        for kind in kinds:
+            for dry in dries:
+                rc, got = _hd_actor_call(lib, kind, dry, **wrong)
+                assert rc == status and (text is None or got == text), (kind, dry, wrong, rc, got)
 
 
 def test_log_prob_entry_checks_its_arguments_without_a_device():

@@ -1,16 +1,13 @@
 """CPU checks of per-agent actors (`PerAgentActor`, `fg_rollout_hd_actor_per_agent`): which path they take, `forward`, the
 dry-run description of the fused launch, argument checks that touch no device, and the new kernels' resources."""
 import ctypes
-import os
 
 import pytest
 import torch
 
 from formation_gym import PerAgentActor, _native
 from formation_gym.actor_rollout import FUSED_HIDDEN, FUSED_N, GaussianActor, actor_path, per_agent_spec
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gym-formation_amd", "lib", "libformation_hip.so")
+from tests.actor_testlib import LIB, describe, fake_actors as _fake_actors, params as _params
 
 
 def _mlp(N, H, tanh, dtype=torch.float32):
@@ -122,24 +119,9 @@ def test_forward_is_the_per_agent_loop():
         pa(obs[..., :3, :])
 
 
-def _params():
-    p = _native.FgParams()
-    p.dt, p.damping, p.contact_force, p.contact_margin = 0.1, 0.25, 100.0, 0.001
-    p.sensitivity, p.mass, p.dist_min, p.collide_thresh = 5.0, 1.0, 0.06, 0.03
-    p.world_length = 100
-    return p
-
-
-def _fake_actors(N, H, tanh=1):
-    addr = 4096                                       # stand-ins: only NULL-ness and alignment are looked at
-    return (_native.FgActor * N)(*[_native.FgActor(H, tanh, addr, addr, addr, addr, addr, addr) for _ in range(N)])
-
-
 def _describe(lib, N, H, log_std=None, B=4096, K=20, actors=None):
-    buf = ctypes.create_string_buffer(512)
-    rc = lib.fg_describe_actor_per_agent_launch(_params(), actors if actors is not None else _fake_actors(N, H), log_std,
-                                                B, N, K, 1, buf, 512)
-    return rc, buf.value.decode()
+    actors = actors if actors is not None else _fake_actors(N, H)
+    return describe(lib, "fg_describe_actor_per_agent_launch", (actors, log_std), N, B, K)
 
 
 @pytest.mark.parametrize("sample", [False, True])

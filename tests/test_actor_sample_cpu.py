@@ -2,16 +2,13 @@
 GaussianActor takes, the dry-run description of the sampling launch, argument checks that touch no device, the sampling
 kernels' resources, and the distribution methods against torch.distributions.Normal."""
 import ctypes
-import os
 
 import pytest
 import torch
 
 from formation_gym import GaussianActor, _native
 from formation_gym.actor_rollout import FUSED_HIDDEN, FUSED_N, actor_path
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "gym-formation_amd", "lib", "libformation_hip.so")
+from tests.actor_testlib import LIB, describe, fake_actor as _fake_actor, params as _params
 
 
 def _mlp(N, H, tanh=False, dtype=torch.float32):
@@ -51,26 +48,10 @@ def test_plain_actor_unchanged():
     assert actor_spec(m, 9) is not None and actor_path(m, 9) == "fused"
 
 
-def _params():
-    p = _native.FgParams()
-    p.dt, p.damping, p.contact_force, p.contact_margin = 0.1, 0.25, 100.0, 0.001
-    p.sensitivity, p.mass, p.dist_min, p.collide_thresh = 5.0, 1.0, 0.06, 0.03
-    p.world_length = 100
-    return p
-
-
-def _fake_actor(H, tanh=1):
-    addr = 4096                                       # stand-ins: only NULL-ness and alignment are looked at
-    return _native.FgActor(H, tanh, addr, addr, addr, addr, addr, addr)
-
-
 def _describe(lib, N, H, B=4096, K=20, log_std=4096, sample=True):
-    buf = ctypes.create_string_buffer(512)
     if sample:
-        rc = lib.fg_describe_actor_sample_launch(_params(), _fake_actor(H), log_std, B, N, K, 1, buf, 512)
-    else:
-        rc = lib.fg_describe_actor_launch(_params(), _fake_actor(H), B, N, K, 1, buf, 512)
-    return rc, buf.value.decode()
+        return describe(lib, "fg_describe_actor_sample_launch", (_fake_actor(H), log_std), N, B, K)
+    return describe(lib, "fg_describe_actor_launch", (_fake_actor(H),), N, B, K)
 
 
 def test_describe_names_one_sample_instantiation_per_shape():

@@ -16,23 +16,20 @@ each step's offset, and its log-prob with -(eps_0^2 + eps_1^2) / 2 - sum(log_std
 import copy
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import formation_gym
-from formation_gym import _native, placement
+from formation_gym import placement
 from formation_gym.actor_rollout import GaussianActor
 from formation_gym.core import Wall
 from formation_gym.vec_env import FormationVecEnv
+from tests.actor_testlib import (B, DEV, K, Wrap as _Wrap, clone as _clone, current_obs as _current_obs, env as _make_env,
+                                 hand_loop as _hand_loop, noise_at as _noise_at, obs_before as _obs_before, scaled_mlp as _mlp)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-B = 133                  # ragged against 64- and 256-env workgroups
 B_BIG = 300              # more than 256 envs: several workgroups, the last one ragged
-K = 24
-ACT_SCALE = 1.5
 TOL = 1e-5
 # the seven shapes of the one-env-per-lane kernel: (scenario, agents)
 SHAPES = [("basic_formation_env", 3), ("formation_hd_partial_env", 5), ("formation_hd_partial_env", 3),
@@ -42,28 +39,7 @@ REFERENCE = SHAPES[:2] + [SHAPES[3], SHAPES[5]]
 
 
 def _env(name, N, seed=3, num_envs=B):
-    env = formation_gym.make_env(name, False, N, num_envs=num_envs, device=DEV)
-    env.seed(seed)
-    env.reset()
-    env.auto_reset = True
-    # an episode boundary inside the launch for a third of the envs
-    wl = int(env.world.world_length)
-    step0 = np.random.RandomState(seed).randint(0, wl, num_envs)
-    step0[::3] = wl - 7
-    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
-    return env
-
-
-def _mlp(D, H, tanh=True, seed=0):
-    torch.manual_seed(seed)
-    mods = [torch.nn.Linear(D, H), torch.nn.ReLU(), torch.nn.Linear(H, H), torch.nn.ReLU(), torch.nn.Linear(H, 2)]
-    if tanh:
-        mods.append(torch.nn.Tanh())
-    actor = torch.nn.Sequential(*mods).to(DEV)
-    with torch.no_grad():
-        for p in actor.parameters():
-            p.mul_(ACT_SCALE)
-    return actor
+    return _make_env(N, seed, num_envs, name)
 
 
 def _actor(env, H, tanh=True, gauss=False, seed=0):
@@ -73,41 +49,9 @@ def _actor(env, H, tanh=True, gauss=False, seed=0):
     return GaussianActor(mean, torch.nn.Parameter(torch.tensor([-0.5, 0.3], device=DEV)))
 
 
-class _Wrap(torch.nn.Module):
-    """The same function behind a module the path rule does not recognise: runs host-paced."""
-
-    def __init__(self, m):
-        super().__init__()
-        self.m = m
-
-    def forward(self, x):
-        return self.m(x)
-
-
-def _current_obs(env):
-    obs = torch.empty_like(env._out["obs"])
-    env.scenario.observe_batch(env.world, {"obs": obs})
-    return obs
-
-
 def _state(env):
     w = env.world
     return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.landmark_pos, w.obstacle_pos, w.obstacle_vel, w.step_count)]
-
-
-def _clone(res):
-    obs, rew, done, info = res
-    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
-
-
-def _noise_at(env, k):
-    """fg_actor_noise at the offset of step k of the next launch."""
-    sc = env.scenario
-    p = env.world.native_params(seed=sc._seed, rng_offset=env._launch_rng_offset() + k)
-    p.env_index_base = int(getattr(sc, "env_base", 0))
-    eps = torch.empty((env.num_envs, env.num_agents, 2), dtype=torch.float32, device=DEV)
-    _native.check(_native.load().fg_actor_noise(p, env.num_envs, env.num_agents, eps.data_ptr(), _native.current_stream(DEV)))
-    return eps
 
 
 def _check_fidelity(mean, obs_before, acts, tanh, steps=None, what=""):
@@ -124,10 +68,6 @@ def _check_fidelity(mean, obs_before, acts, tanh, steps=None, what=""):
         worst = max(worst, float((err / bound).max()))
         assert bool((err <= bound).all()), "%s step %d: max err %.3g" % (what, k, float(err.max()))
     print("%s fidelity: worst err / bound %.3f" % (what, worst))
-
-
-def _obs_before(obs0, obs, K_):
-    return [obs0] + [obs[k - 1] for k in range(1, K_)]
 
 
 def _replay_and_fidelity(env, actor, H, tanh, gauss, what):
@@ -319,18 +259,6 @@ def test_placed_buffers_at_the_benchmark_shape():
     ptr = obs.data_ptr()
     obs2, _, _, info2 = env.rollout_actor(Kn, actor)
     assert obs2.data_ptr() == ptr and info2["actions"].data_ptr() == info["actions"].data_ptr()
-
-
-def _hand_loop(env, actor, K_):
-    obs = _current_obs(env)
-    acts, obss, rews = [], [], []
-    with torch.no_grad():
-        for _ in range(K_):
-            a = actor(obs)
-            acts.append(a.clone())
-            obs, r, d, info = env.step(a)
-            obss.append(obs.clone()); rews.append(r.clone())
-    return torch.stack(acts), torch.stack(obss), torch.stack(rews)
 
 
 @pytest.mark.parametrize("case", ["basic4", "h128", "walls"])

@@ -25,20 +25,16 @@ all K steps where the actions are the noise itself (zeroed mean): there the two 
 """
 import copy
 
-import numpy as np
 import pytest
 import torch
 
-import formation_gym
 from formation_gym import GaussianActor, _native
-from formation_gym.actor_rollout import FUSED_N, LOG_2PI
+from formation_gym.actor_rollout import FUSED_N
+from tests.actor_testlib import (ACT_SCALE, B, DEV, K, Wrap as _Wrap, clone as _clone, current_obs as _current_obs, env as _env,
+                                 logp_formula as _logp_formula, noise_at as _noise_at, obs_before as _obs_before, state as _state)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-B = 133                  # not a multiple of any workgroup's env count (8, 16, 32, 64)
-K = 24
-ACT_SCALE = 1.5
 TOL = 1e-5
 # (N, H, input norm, tanh): every N at H = 64, alternating with and without the input norm, plus two shapes at H = 32
 CASES = [(n, 64, i % 2 == 0, i % 4 < 2) for i, n in enumerate(FUSED_N)] + [(9, 32, False, True), (27, 32, True, False)]
@@ -66,49 +62,6 @@ def _ln_actor(N, H, in_norm, tanh=False, seed=0, zero_head=False, eps=1e-5):
             head.weight.zero_()
             head.bias.zero_()
     return m.to(DEV)
-
-
-class _Wrap(nn.Module):
-    """The same modules behind a module the path rule does not recognise: the host-paced loop."""
-
-    def __init__(self, m):
-        super().__init__()
-        self.m = m
-
-    def forward(self, x):
-        return self.m(x)
-
-
-def _env(N, seed=3):
-    env = formation_gym.make_env("formation_hd_env", False, N, num_envs=B, device=DEV)
-    env.seed(seed)
-    env.reset()
-    env.auto_reset = True
-    wl = int(env.world.world_length)
-    step0 = np.random.RandomState(seed).randint(0, wl, B)
-    step0[::3] = wl - 7                                  # an episode boundary inside the launch for a third of the envs
-    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
-    return env
-
-
-def _current_obs(env):
-    obs = torch.empty_like(env._out["obs"])
-    env.scenario.observe_batch(env.world, {"obs": obs})
-    return obs
-
-
-def _state(env):
-    w, sc = env.world, env.scenario
-    return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.step_count, sc.ideal_shape, sc.ideal_vel)]
-
-
-def _clone(res):
-    obs, rew, done, info = res
-    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
-
-
-def _obs_before(obs0, obs, K_):
-    return [obs0] + [obs[k - 1] for k in range(1, K_)]
 
 
 def _ref64(ref, o):
@@ -196,21 +149,6 @@ def test_dead_rows_return_beta(N, H, in_norm):
     # beta exactly: with dead rows the actor is a constant, the same bits for every row and step
     flat = info["actions"].reshape(-1, 2)
     assert bool((flat == flat[0]).all())
-
-
-def _noise_at(env, k):
-    """fg_actor_noise at the offset of step k of the next launch."""
-    sc = env.scenario
-    p = env.world.native_params(seed=sc._seed, rng_offset=env._launch_rng_offset() + k)
-    p.env_index_base = int(getattr(sc, "env_base", 0))
-    eps = torch.empty((env.num_envs, env.num_agents, 2), dtype=torch.float32, device=DEV)
-    _native.check(_native.load().fg_actor_noise(p, env.num_envs, env.num_agents, eps.data_ptr(),
-                                                _native.current_stream(DEV)))
-    return eps
-
-
-def _logp_formula(eps, log_std):
-    return -0.5 * (eps[..., 0] * eps[..., 0] + eps[..., 1] * eps[..., 1]) - (log_std[0] + log_std[1]) - LOG_2PI
 
 
 @pytest.mark.parametrize("N,in_norm", [(9, True), (27, False)])

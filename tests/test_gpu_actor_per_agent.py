@@ -3,82 +3,27 @@ pa_actor_kernel / pa_sample_kernel) and host-paced.  Fidelity bound: that of the
 member is evaluated with the same instructions in the same k order - 1e-5 abs for tanh outputs, 1e-5 max(1, |a|) without."""
 import copy
 
-import numpy as np
 import pytest
 import torch
 
-import formation_gym
 from formation_gym import GaussianActor, PerAgentActor
 from formation_gym.actor_rollout import FUSED_N
+from tests.actor_testlib import (B, DEV, K, Wrap as _Wrap, clone as _clone, current_obs as _current_obs, env as _env,
+                                 obs_before as _obs_before, scaled_mlp, state as _state)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-B = 133                  # not a multiple of any workgroup's env count (8, 16, 32, 64)
-K = 24
-ACT_SCALE = 1.5
 TOL = 1e-5
 CASES = [(n, 64) for n in FUSED_N] + [(9, 32), (9, 128), (27, 32), (27, 128)]
 
 
 def _mlp(N, H, tanh=True, seed=0):
-    torch.manual_seed(seed)
-    mods = [torch.nn.Linear(6 * N, H), torch.nn.ReLU(), torch.nn.Linear(H, H), torch.nn.ReLU(), torch.nn.Linear(H, 2)]
-    if tanh:
-        mods.append(torch.nn.Tanh())
-    m = torch.nn.Sequential(*mods).to(DEV)
-    with torch.no_grad():
-        for p in m.parameters():
-            p.mul_(ACT_SCALE)
-    return m
+    return scaled_mlp(6 * N, H, tanh, seed)
 
 
 def _pa(N, H, tanh=True):
     """Distinct random weights per agent."""
     return PerAgentActor([_mlp(N, H, tanh, seed=100 + i) for i in range(N)])
-
-
-class _Wrap(torch.nn.Module):
-    """The same member behind a module actor_spec does not accept: makes a PerAgentActor unfusable."""
-
-    def __init__(self, m):
-        super().__init__()
-        self.m = m
-
-    def forward(self, x):
-        return self.m(x)
-
-
-def _env(N, seed=3):
-    env = formation_gym.make_env("formation_hd_env", False, N, num_envs=B, device=DEV)
-    env.seed(seed)
-    env.reset()
-    env.auto_reset = True
-    wl = int(env.world.world_length)
-    step0 = np.random.RandomState(seed).randint(0, wl, B)
-    step0[::3] = wl - 7                                  # an episode boundary inside the launch for a third of the envs
-    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
-    return env
-
-
-def _current_obs(env):
-    obs = torch.empty_like(env._out["obs"])
-    env.scenario.observe_batch(env.world, {"obs": obs})
-    return obs
-
-
-def _state(env):
-    w, sc = env.world, env.scenario
-    return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.step_count, sc.ideal_shape, sc.ideal_vel)]
-
-
-def _clone(res):
-    obs, rew, done, info = res
-    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
-
-
-def _obs_before(obs0, obs, K_):
-    return [obs0] + [obs[k - 1] for k in range(1, K_)]
 
 
 def _check_fidelity(actor, obs_before, acts, tanh):

@@ -11,63 +11,22 @@ observations, rewards and done flags.
 """
 import copy
 
-import numpy as np
 import pytest
 import torch
 
-import formation_gym
 from formation_gym.actor_rollout import FUSED_N
 from formation_gym.vec_env import FormationVecEnv
+from tests.actor_testlib import (B, DEV, K, clone as _clone, current_obs as _current_obs, env as _env, hand_loop as _hand_loop,
+                                 obs_before as _obs_before, scaled_mlp, state as _state)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-B = 133                  # not a multiple of any workgroup's env count (8, 16, 32, 64)
-K = 24
-ACT_SCALE = 1.5
 TOL = 1e-5
 CASES = [(n, 64) for n in FUSED_N] + [(9, 32), (9, 128), (27, 32), (27, 128)]
 
 
 def _actor(N, H, tanh=True, seed=0):
-    torch.manual_seed(seed)
-    mods = [torch.nn.Linear(6 * N, H), torch.nn.ReLU(), torch.nn.Linear(H, H), torch.nn.ReLU(), torch.nn.Linear(H, 2)]
-    if tanh:
-        mods.append(torch.nn.Tanh())
-    actor = torch.nn.Sequential(*mods).to(DEV)
-    with torch.no_grad():
-        for p in actor.parameters():
-            p.mul_(ACT_SCALE)
-    return actor
-
-
-def _env(N, seed=3):
-    env = formation_gym.make_env("formation_hd_env", False, N, num_envs=B, device=DEV)
-    env.seed(seed)
-    env.reset()
-    env.auto_reset = True
-    # an episode boundary inside the launch for a third of the envs
-    wl = int(env.world.world_length)
-    step0 = np.random.RandomState(seed).randint(0, wl, B)
-    step0[::3] = wl - 7
-    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
-    return env
-
-
-def _current_obs(env):
-    obs = torch.empty_like(env._out["obs"])
-    env.scenario.observe_batch(env.world, {"obs": obs})
-    return obs
-
-
-def _state(env):
-    w, sc = env.world, env.scenario
-    return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.step_count, sc.ideal_shape, sc.ideal_vel)]
-
-
-def _clone(res):
-    obs, rew, done, info = res
-    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
+    return scaled_mlp(6 * N, H, tanh, seed)
 
 
 def _check_fidelity(actor, obs_before, acts, tanh, steps=None):
@@ -80,10 +39,6 @@ def _check_fidelity(actor, obs_before, acts, tanh, steps=None):
         bound = TOL if tanh else TOL * torch.clamp(want.abs(), min=1.0)
         err = (got - want).abs()
         assert bool((err <= bound).all()), "step %d: max err %.3g" % (k, float(err.max()))
-
-
-def _obs_before(obs0, obs, K_):
-    return [obs0] + [obs[k - 1] for k in range(1, K_)]
 
 
 @pytest.mark.parametrize("N,H", CASES)
@@ -165,18 +120,6 @@ def test_layouts_and_options(N):
     assert torch.equal(v_obs, ref[0]) and torch.equal(v_info["actions"], ref[3]["actions"])
     for a, b in zip(state, _state(env)):
         assert torch.equal(a, b)
-
-
-def _hand_loop(env, actor, K_):
-    obs = _current_obs(env)
-    acts, obss, rews = [], [], []
-    with torch.no_grad():
-        for _ in range(K_):
-            a = actor(obs)
-            acts.append(a.clone())
-            obs, r, d, info = env.step(a)
-            obss.append(obs.clone()); rews.append(r.clone())
-    return torch.stack(acts), torch.stack(obss), torch.stack(rews)
 
 
 def test_per_agent_props_run_host_paced():

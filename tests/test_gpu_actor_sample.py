@@ -22,76 +22,22 @@ import pytest
 import torch
 
 import formation_gym
-from formation_gym import GaussianActor, _native
-from formation_gym.actor_rollout import FUSED_N, LOG_2PI
+from formation_gym import GaussianActor
+from formation_gym.actor_rollout import FUSED_N
+from tests.actor_testlib import (ACT_SCALE, B, DEV, K, Wrap as _Wrap, clone as _clone, env as _env, logp_formula as _logp_formula,
+                                 noise_at as _noise_at, scaled_mlp, state as _state)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-B = 133                  # not a multiple of any workgroup's env count (8, 16, 32, 64)
-K = 24
-ACT_SCALE = 1.5
 CASES = [(n, 64) for n in FUSED_N] + [(9, 32), (9, 128), (27, 32), (27, 128)]
 
 
 def _mlp(N, H, tanh=False, seed=0, zero=False):
-    torch.manual_seed(seed)
-    mods = [torch.nn.Linear(6 * N, H), torch.nn.ReLU(), torch.nn.Linear(H, H), torch.nn.ReLU(), torch.nn.Linear(H, 2)]
-    if tanh:
-        mods.append(torch.nn.Tanh())
-    m = torch.nn.Sequential(*mods).to(DEV)
-    with torch.no_grad():
-        for p in m.parameters():
-            p.mul_(0.0 if zero else ACT_SCALE)
-    return m
+    return scaled_mlp(6 * N, H, tanh, seed, 0.0 if zero else ACT_SCALE)      # zero: every parameter, biases included
 
 
 def _zero_actor(N, H=64):
     return GaussianActor(_mlp(N, H, zero=True), torch.nn.Parameter(torch.zeros(2, device=DEV)))
-
-
-class _Wrap(torch.nn.Module):
-    """The same mean behind a module actor_spec does not accept: the host-paced path."""
-
-    def __init__(self, m):
-        super().__init__()
-        self.m = m
-
-    def forward(self, x):
-        return self.m(x)
-
-
-def _env(N, seed=3, num_envs=B):
-    env = formation_gym.make_env("formation_hd_env", False, N, num_envs=num_envs, device=DEV)
-    env.seed(seed)
-    env.reset()
-    env.auto_reset = True
-    wl = int(env.world.world_length)
-    step0 = np.random.RandomState(seed).randint(0, wl, num_envs)
-    step0[::3] = wl - 7                                  # an episode boundary inside the launch for a third of the envs
-    env.world.step_count.copy_(torch.as_tensor(step0, dtype=torch.int32))
-    return env
-
-
-def _state(env):
-    w, sc = env.world, env.scenario
-    return [t.clone() for t in (w.pos_x, w.pos_y, w.vel_x, w.vel_y, w.step_count, sc.ideal_shape, sc.ideal_vel)]
-
-
-def _clone(res):
-    obs, rew, done, info = res
-    return obs.clone(), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
-
-
-def _noise_at(env, k):
-    """fg_actor_noise at the offset of step k of the next launch."""
-    sc = env.scenario
-    p = env.world.native_params(seed=sc._seed, rng_offset=env._launch_rng_offset() + k)
-    p.env_index_base = int(getattr(sc, "env_base", 0))
-    eps = torch.empty((env.num_envs, env.num_agents, 2), dtype=torch.float32, device=DEV)
-    _native.check(_native.load().fg_actor_noise(p, env.num_envs, env.num_agents, eps.data_ptr(),
-                                                _native.current_stream(DEV)))
-    return eps
 
 
 # ---- NumPy Philox4x32-10 and fp64 Box-Muller ----
@@ -119,10 +65,6 @@ def _eps_ref(seed, Bn, N, offset, base=0):
     a = float(np.float32(6.2831853)) * ((c[1] >> np.uint64(8)).astype(np.float64) / 16777216.0)
     r = np.sqrt(-2.0 * np.log(u))
     return np.stack([r * np.cos(a), r * np.sin(a)], -1)
-
-
-def _logp_formula(eps, log_std):
-    return -0.5 * (eps[..., 0] * eps[..., 0] + eps[..., 1] * eps[..., 1]) - (log_std[0] + log_std[1]) - LOG_2PI
 
 
 @pytest.mark.parametrize("N", [9, 27])
