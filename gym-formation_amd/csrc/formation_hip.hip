@@ -113,12 +113,11 @@ static int resolve_device(void* stream, const void* data) {
 struct DeviceGuard {
     int prev = -1;
     bool switched = false;
-    DeviceGuard(void* stream, const void* data) {
-        if (visible_devices() < 2) return;
-        const int target = resolve_device(stream, data);
-        if (target < 0) return;
-        if (hipGetDevice(&prev) == hipSuccess && prev != target) switched = hipSetDevice(target) == hipSuccess;
+    // `target`: a device resolved earlier (resolve_device; fg_step_hd_plan resolves once, so that a planned step pays no query)
+    explicit DeviceGuard(int target) {
+        if (target >= 0 && hipGetDevice(&prev) == hipSuccess && prev != target) switched = hipSetDevice(target) == hipSuccess;
     }
+    DeviceGuard(void* stream, const void* data) : DeviceGuard(visible_devices() < 2 ? -1 : resolve_device(stream, data)) {}
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
@@ -137,34 +136,56 @@ static hipError_t raise_lds_limit(const void* fn, int lds, std::atomic<unsigned 
     return err;
 }
 
-static int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
-template <int NC, int G, int T, int E, bool IDX, bool OPTS>
-static hipError_t launch_v(const Args& a, int grid, int lds, hipStream_t st) {
-    const int n_split = a.N | ((E == 1 && a.split > 1 ? a.split : 0) << 16);
-    if (describe("step_kernel<%d,%d,%d,%d,%d,%d,%d> grid %d lds %d%s; ", NC, G, T, E, (int)IDX, (int)OPTS,
-                 (int)(!IDX && !OPTS && NC >= 27 && a.K == 1 && a.obs_every == 1), grid, lds, a.obs_only ? " obs-only" : ""))
-        return hipSuccess;
-    if (lds > 64 * 1024) {                 // run-time N close to 1024 (+ the per-agent tables of the OPTS instantiation)
-        static std::atomic<unsigned long long> raised{0};
-        const hipError_t err = raise_lds_limit((const void*)&step_kernel<NC, G, T, E, IDX, OPTS>, lds, &raised);
-        if (err != hipSuccess) return err;
+// THE launch of this file: the kernel's LDS opt-in (the mask is the kernel's own by construction), the launch, the runtime's
+// answer as a status - FG_OK, or FG_ERR_HIP with `fail_fmt`, the caller's name for the launch, around the runtime's text.
+// A caller with a dry run (describe) asks it first, so that its describe string stays its own.
+template <auto Kernel> static std::atomic<unsigned long long> g_lds_raised{0};
+template <auto Kernel, class... A>
+static int launch(unsigned grid, int threads, int lds, hipStream_t st, const char* fail_fmt, const A&... args) {
+    hipError_t err = raise_lds_limit((const void*)Kernel, lds, &g_lds_raised<Kernel>);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, st, args...);
+        err = hipGetLastError();
     }
-    // the single-step instantiation (no step loop, no slot arithmetic) of the plain variants from 27 agents up: 27 x 4096
-    // 15.15 -> 15.03 us, 81 x 2048 -1 %; at 3 and 9 agents it is slower (profiles/r02_step/kone.txt)
-    if (!IDX && !OPTS && NC >= 27 && a.K == 1 && a.obs_every == 1) {
-        hipLaunchKernelGGL((step_kernel<NC, G, T, E, false, false, (!IDX && !OPTS && NC >= 27)>), dim3(grid), dim3(T), lds, st,
-                           a.B, n_split, (const float*)a.px, (const float*)a.py, (const float*)a.vx, (const float*)a.vy,
-                           (const float*)a.shape, (const float*)a.ivel, (const int32_t*)a.step, a);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((step_kernel<NC, G, T, E, IDX, OPTS>), dim3(grid), dim3(T), lds, st,
-                       a.B, n_split, (const float*)a.px, (const float*)a.py, (const float*)a.vx, (const float*)a.vy,
-                       (const float*)a.shape, (const float*)a.ivel, (const int32_t*)a.step, a);
-    return hipGetLastError();
+    return err == hipSuccess ? FG_OK : fail(FG_ERR_HIP, fail_fmt, hipGetErrorString(err));
 }
 
-using LaunchFn = hipError_t (*)(const Args&, int, int, hipStream_t);
+static int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+
+// A run-time G in {4, 8, ..., 1024} as a compile-time <G, max(G, 64)> (lanes per env, threads per workgroup: reset_kernel,
+// scn_kernel): run(g, t) with both as the `value` of the arguments' types
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F>
+static int pow2_dispatch(int G, F&& run) {
+#define FG_G(GG) if (G == GG) return run(IntC<GG>{}, IntC<(GG < 64 ? 64 : GG)>{});
+    FG_G(4) FG_G(8) FG_G(16) FG_G(32) FG_G(64) FG_G(128) FG_G(256) FG_G(512)
+#undef FG_G
+    return run(IntC<1024>{}, IntC<1024>{});
+}
+
+// step_kernel's arguments: the state pointers ahead of `a` (kernarg preload, fg_step_kernel.hpp)
+template <auto Kernel>
+static int launch_step_kernel(const Args& a, int n_split, int grid, int threads, int lds, hipStream_t st) {
+    return launch<Kernel>(grid, threads, lds, st, "kernel launch failed: %s", a.B, n_split, (const float*)a.px, (const float*)a.py,
+                          (const float*)a.vx, (const float*)a.vy, (const float*)a.shape, (const float*)a.ivel,
+                          (const int32_t*)a.step, a);
+}
+template <int NC, int G, int T, int E, bool IDX, bool OPTS>
+static int launch_v(const Args& a, int grid, int lds, hipStream_t st) {
+    const int n_split = a.N | ((E == 1 && a.split > 1 ? a.split : 0) << 16);
+    // the single-step instantiation (no step loop, no slot arithmetic) of the plain variants from 27 agents up: 27 x 4096
+    // 15.15 -> 15.03 us, 81 x 2048 -1 %; at 3 and 9 agents it is slower (profiles/r02_step/kone.txt)
+    constexpr bool HAS_KONE = !IDX && !OPTS && NC >= 27;
+    const bool kone = HAS_KONE && a.K == 1 && a.obs_every == 1;
+    if (describe("step_kernel<%d,%d,%d,%d,%d,%d,%d> grid %d lds %d%s; ", NC, G, T, E, (int)IDX, (int)OPTS, (int)kone, grid, lds,
+                 a.obs_only ? " obs-only" : ""))
+        return FG_OK;
+    // (each instantiation has its own LDS opt-in; above 64 KiB: run-time N close to 1024, + the per-agent tables of OPTS)
+    if (kone) return launch_step_kernel<&step_kernel<NC, G, T, E, false, false, HAS_KONE>>(a, n_split, grid, T, lds, st);
+    return launch_step_kernel<&step_kernel<NC, G, T, E, IDX, OPTS>>(a, n_split, grid, T, lds, st);
+}
+
+using LaunchFn = int (*)(const Args&, int, int, hipStream_t);
 // One entry per (agent count, workgroup shape).  plain / idx (+ landmark-index outputs) / opts (idx + World options
 // no reference scenario enables).  min_B: the entry is the default from that batch size up (MI355X sweeps,
 // profiles/README.md: a batch that fills the chip many times over streams best with 8 envs per workgroup, a
@@ -220,6 +241,14 @@ static bool geometry_for(int N, Geometry* g, int B = 0, bool need_full = false, 
     return true;
 }
 
+// the N checks: any scenario-free launch takes 2 ... 1024 agents, formation_hd_env's observation and reward need 3
+static int generic_n_check(int N) {
+    return N < 2 || N > FG_MAX_AGENTS ? fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s") : FG_OK;
+}
+static int hd_n_check(int N) {
+    return N < 3 || N > FG_MAX_AGENTS ? fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s") : FG_OK;
+}
+
 static bool world_options_set(const FgParams& p) {
     return p.num_walls > 0 || p.u_noise > 0.f || p.max_speed > 0.f || p.accel > 0.f || p.agent_props || p.comm_state;
 }
@@ -229,8 +258,9 @@ static int launch_step(Args a, hipStream_t st) {
     const bool opts = world_options_set(a.p);
     const bool idx = a.near_lm || a.near_ag || a.hd_idx;
     const bool generic = a.p.comm_state != nullptr;
-    const Variant* v = variant_for(a.N, a.B, opts || idx, generic);
-    if (!v || !geometry_for(a.N, &g, a.B, opts || idx, generic)) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s");
+    if (const int rc = generic_n_check(a.N)) return rc;
+    const Variant* v = variant_for(a.N, a.B, opts || idx, generic);      // (never NULL: the run-time-N entries cover every N in range)
+    geometry_for(a.N, &g, a.B, opts || idx, generic);
     if (opts) g.lds += (3 * npad(a.N) + 2 * g.E * a.N) * (int)sizeof(float);    // per-agent mass / size / flags, per-env comm states
     a.coll_scale = (float)((double)a.p.collide_thresh / (double)a.p.dist_min);
     const int grid = (a.B + g.E - 1) / g.E;
@@ -244,18 +274,14 @@ static int launch_step(Args a, hipStream_t st) {
         int S = 256 / a.B;
         if (S > 8) S = 8;
         Args a1 = a; a1.obs = nullptr;
-        hipError_t err = (opts ? v->opts : idx ? v->idx : v->plain)(a1, grid, g.lds, st);
-        if (err != hipSuccess) return fail(FG_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(err));
+        const int rc = (opts ? v->opts : idx ? v->idx : v->plain)(a1, grid, g.lds, st);
+        if (rc) return rc;
         Args a2 = a;
         a2.do_phys = 0; a2.obs_only = 1; a2.split = S; a2.p.auto_reset = 0;
         a2.rew = nullptr; a2.indiv = nullptr; a2.done = nullptr; a2.near_lm = nullptr; a2.near_ag = nullptr; a2.hd_idx = nullptr;
-        err = (generic ? v->opts : v->plain)(a2, grid * S, g.lds, st);   // the communication block lives in the OPTS instantiation
-        if (err != hipSuccess) return fail(FG_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(err));
-        return FG_OK;
+        return (generic ? v->opts : v->plain)(a2, grid * S, g.lds, st);   // the communication block lives in the OPTS instantiation
     }
-    const hipError_t err = (opts ? v->opts : idx ? v->idx : v->plain)(a, grid, g.lds, st);
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return (opts ? v->opts : idx ? v->idx : v->plain)(a, grid, g.lds, st);
 }
 
 // 64 < N <= 256: producer / writer pipelined kernel (rollout: over steps; single step: over env batches)
@@ -276,14 +302,7 @@ static int launch_wide_v(Args a, hipStream_t st) {
                     (PER > 0 ? E * policy_block_units(NC) * (int)sizeof(float2) : 0);
     if (describe("rollout_kernel_wide<%d,%d,%d,%d,%d,%d> grid %d lds %d groups %d; ", NC, A, E, TW, PER, (int)BATCHES, grid, lds, a.groups))
         return FG_OK;
-    static std::atomic<unsigned long long> raised{0};
-    hipError_t err = raise_lds_limit((const void*)&rollout_kernel_wide<NC, A, E, TW, PER, BATCHES>, lds, &raised);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL((rollout_kernel_wide<NC, A, E, TW, PER, BATCHES>), dim3(grid), dim3(E * 64 + TW), lds, st, a);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "pipelined launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&rollout_kernel_wide<NC, A, E, TW, PER, BATCHES>>(grid, E * 64 + TW, lds, st, "pipelined launch failed: %s", a);
 }
 // 4 envs (= producer waves) and 4 writer waves per workgroup (MI355X sweeps: profiles/README.md, profiles/r03_wide/)
 template <int NC, int PER>
@@ -307,14 +326,7 @@ static int launch_roll_v(const Args& a, hipStream_t st) {
     const int grid = (a.B + E - 1) / E;
     constexpr int lds = roll_lds_bytes<NC, TW, E, WR, PER>();     // env blocks, writer tiles, controller tables, reward hand-over
     if (describe("rollout_kernel<%d,%d,%d,%d,%d,%d,%d,%d> grid %d lds %d; ", NC, G, TP, TW, E, WR, PER, (int)STREAM, grid, lds)) return FG_OK;
-    static std::atomic<unsigned long long> raised{0};
-    hipError_t err = raise_lds_limit((const void*)&rollout_kernel<NC, G, TP, TW, E, WR, PER, STREAM>, lds, &raised);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL((rollout_kernel<NC, G, TP, TW, E, WR, PER, STREAM>), dim3(grid), dim3(TP + TW), lds, st, a);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "rollout launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&rollout_kernel<NC, G, TP, TW, E, WR, PER, STREAM>>(grid, TP + TW, lds, st, "rollout launch failed: %s", a);
 }
 // writer of the pipelined kernels per agent count: 1 + rows per LDS tile (the rows must divide N: 9 of 27 and 9, 5 of 25,
 // 8 of 16 and 32), 0 = register-cached rows (few agents: a tile is too small to pay; 64 agents: a row is a wave)
@@ -510,13 +522,7 @@ static int launch_hd_lane(const Args& a, hipStream_t st) {
     const int grid = 8 * (((a.B + 64 * PW - 1) / (64 * PW) + 7) / 8);
     constexpr int lds = hd_lane_lds_bytes(NC, PW);
     if (describe("hd_lane_kernel<%d,%d,%d> grid %d lds %d; ", NC, PER, PW, grid, lds)) return FG_OK;
-    static std::atomic<unsigned long long> raised{0};
-    hipError_t err = raise_lds_limit((const void*)&hd_lane_kernel<NC, PER, PW>, lds, &raised);
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "rollout launch failed: %s", hipGetErrorString(err));
-    hipLaunchKernelGGL((hd_lane_kernel<NC, PER, PW>), dim3(grid), dim3(128 * PW), lds, st, a);
-    err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "rollout launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&hd_lane_kernel<NC, PER, PW>>(grid, 128 * PW, lds, st, "rollout launch failed: %s", a);
 }
 // One-env-per-lane kernels with four producer waves (256-env workgroups): how full the generations of 256 such workgroups (one per CU) must be - profiles/r05_fill_rule_ab.txt, eleven batch sizes per kernel:
 // whole generations or a last one at least three quarters full (a single one: seven eighths: 57344 envs +12 %, 49152 -11 %); `half`:
@@ -609,6 +615,64 @@ static int check_params(const FgParams* p) {
     return FG_OK;
 }
 
+// ---- the pieces an entry point builds its call from.  Each check is a function the entry calls at ITS point: the entries do
+// not agree on the order (fg_step_hd checks N before it looks at an empty batch, the rollouts after), and the order is ABI.
+static int null_pointer(const char* who) { return fail(FG_ERR_BAD_ARG, "%s: a required pointer is NULL", who); }
+
+// the buffers of a K-step formation_hd_env rollout: fg_rollout_hd, fg_rollout_hd_policy and the fused-actor entries, as `who`
+static int rollout_buffers_check(const char* who, const float* px, const float* py, const float* vx, const float* vy,
+                                 const float* act_seq, const float* shape, const float* ivel, const int32_t* step,
+                                 const float* obs_seq, const float* reward_seq) {
+    if (!px || !py || !vx || !vy || !act_seq || !shape || !ivel || !step || !reward_seq) return null_pointer(who);
+    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)shape & 7u) || ((uintptr_t)ivel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
+    return FG_OK;
+}
+
+static int policy_levels_check(const char* who, int N, int per, FgPolicyLevels* pl) {
+    if (policy_levels_for(N, per, pl)) return FG_OK;
+    return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be per_layer^L with 2 <= per_layer <= 8", who);
+}
+
+// The start of every formation_hd_env launch description: zeroed, the scalars, the observation pitch (checked).
+static int hd_args(Args* a, const FgParams* params, int B, int N, int K, int obs_every, int do_phys, int do_post) {
+    memset(a, 0, sizeof(*a));
+    a->p = *params; a->B = B; a->N = N; a->inv_n = 1.0f / (float)N; a->K = K; a->obs_every = obs_every < 1 ? 1 : obs_every;
+    a->do_phys = do_phys; a->do_post = do_post;
+    return set_obs_pitch(a);
+}
+// ... and its state and output buffers (the actions, a.act or a.act_out, and the index outputs are the entry's own)
+static void hd_buffers(Args* a, float* px, float* py, float* vx, float* vy, float* shape, float* ivel, int32_t* step,
+                       float* obs, float* rew, float* indiv, uint8_t* done) {
+    a->px = px; a->py = py; a->vx = vx; a->vy = vy; a->shape = shape; a->ivel = ivel; a->step = step;
+    a->obs = obs; a->rew = rew; a->indiv = indiv; a->done = done;
+}
+
+// ---- the reference's demo controller (fg_policy_kernels.hpp): one launch geometry and one PER switch for both of its kernels
+struct PolicyGeometry { int lpe, grid, lds; };                         // lpe lanes per env, 256 threads per workgroup
+static PolicyGeometry policy_geometry(int B, int N) {
+    const int lpe = N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : 256;
+    const int E = 256 / lpe;
+    return {lpe, (B + E - 1) / E, E * policy_block_units(N) * (int)sizeof(float2)};     // lds <= 56 KiB
+}
+template <class F>
+static int policy_per_dispatch(int per, F&& run) {                     // run(per) with `per` as the `value` of the argument's type
+#define FG_POLICY(PER) case PER: return run(IntC<PER>{});
+    switch (per) { FG_POLICY(2) FG_POLICY(3) FG_POLICY(4) FG_POLICY(5) FG_POLICY(6) FG_POLICY(7) FG_POLICY(8) }
+#undef FG_POLICY
+    return FG_OK;                                                      // (policy_levels_for admits 2 ... 8 only)
+}
+// the controller from the simulator state: one launch, shared by fg_policy_bfs_state and the chained closed loop
+static int launch_policy_state(int B, int N, const FgPolicyLevels& pl, const float* px, const float* py,
+                               const float* shape, const float* ivel, float* act, hipStream_t st) {
+    const PolicyGeometry g = policy_geometry(B, N);
+    if (describe("policy_state_kernel<%d> grid %d lds %d; ", pl.per, g.grid, g.lds)) return FG_OK;
+    return policy_per_dispatch(pl.per, [&](auto per) {
+        return launch<&policy_state_kernel<decltype(per)::value>>(g.grid, 256, g.lds, st, "policy launch failed: %s", B, N, g.lpe,
+                                                                  pl, px, py, shape, ivel, act);
+    });
+}
+
 // one env per lane, PW producer waves (64 PW envs) and PW * scn_lane_writers(KIND) writer waves per workgroup
 // Four producer waves - 256 envs, one span of 55 ... 133 KB per workgroup and step instead of four - where such workgroups
 // come in whole generations of 256 (one per CU; or in six generations and more) - profiles/r05_lane_pw_ab.txt:
@@ -630,16 +694,490 @@ static int launch_scn_lane(const ScnArgs& a, hipStream_t st) {
     constexpr int threads = 64 * PW * (1 + scn_lane_writers(KIND));
     const int grid = 8 * (((a.B + 64 * PW - 1) / (64 * PW) + 7) / 8);
     if (describe("scn_lane_kernel<%d,%d,%d,%d,%d,%d> grid %d threads %d lds %d; ", KIND, NN, LL, MM, NBR, PW, grid, threads, lds)) return FG_OK;
-    static std::atomic<unsigned long long> raised{0};
-    const hipError_t err = raise_lds_limit((const void*)&scn_lane_kernel<KIND, NN, LL, MM, NBR, PW>, lds, &raised);
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario launch failed: %s", hipGetErrorString(err));
-    hipLaunchKernelGGL((scn_lane_kernel<KIND, NN, LL, MM, NBR, PW>), dim3(grid), dim3(threads), lds, st, a);
-    return FG_OK;
+    return launch<&scn_lane_kernel<KIND, NN, LL, MM, NBR, PW>>(grid, threads, lds, st, "scenario launch failed: %s", a);
 }
+// The reference's own scenario shapes, every count a compile-time constant (fg_scn_lane_kernel.hpp, fg_scn_lane_actor_kernel.hpp):
+// X(kind, agents, landmarks, obstacles, neighbours an agent sees, WIDE).  WIDE: the 256-env form of the lane kernel exists for
+// this shape (scn_lane_wide); the fused-actor kernels have no such form.
+#define FG_SCN_SHAPES(X)                                                                                                 \
+    X(FG_SCN_BASIC, 3, 3, 0, 2, true)            /* basic_formation_env.py:7 */                                             \
+    X(FG_SCN_PARTIAL, 5, 5, 0, 3, true)          /* formation_hd_partial_env.py:15 */                                       \
+    X(FG_SCN_RANGE, 4, 4, 0, 3, true)            /* formation_hd_partial_range_env.py:15 */                                 \
+    X(FG_SCN_OBSTACLE, 4, 4, 3, 3, false)        /* formation_hd_obs_env.py:14 */                                           \
+    X(FG_SCN_PARTIAL, 3, 5, 0, 3, false)         /* make_env(name) passes its own default num_agents = 3 (__init__.py:6-11) */ \
+    X(FG_SCN_RANGE, 3, 4, 0, 2, false)                                                                                   \
+    X(FG_SCN_OBSTACLE, 3, 4, 3, 2, false)
 
 }  // namespace fg
 
 using namespace fg;
+
+// ---------------------------------------------------------------------------
+// What the entry points below are made of: an entry checks its call, builds the launch description (hd_args / scn_args and
+// the buffers) and hands it to a dispatch; the dispatches are also walked dry by the fg_describe_* entries.
+// ---------------------------------------------------------------------------
+
+// fg_step_hd in two halves: argument checks + the launch description, and the dispatch of a checked description
+static int step_hd_describe(const FgParams* params, int B, int N,
+                            float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                            const float* act, float* ideal_shape, float* ideal_vel, int32_t* step,
+                            float* obs, float* reward, float* indiv_reward, uint8_t* done,
+                            int32_t* near_lm, int32_t* near_ag, int32_t* hd_idx, Args* a) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
+    if ((rc = hd_n_check(N))) return rc;
+    if (B > 0 && (!pos_x || !pos_y || !vel_x || !vel_y || !act || !ideal_shape || !ideal_vel || !step || !obs || !reward))
+        return null_pointer("fg_step_hd");
+    if (((uintptr_t)obs & 15u) || ((uintptr_t)act & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned%s");
+    if ((rc = hd_args(a, params, B, N, 1, 1, 1, 1))) return rc;
+    hd_buffers(a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs, reward, indiv_reward, done);
+    a->act = act; a->near_lm = near_lm; a->near_ag = near_ag; a->hd_idx = hd_idx;
+    return FG_OK;
+}
+
+static int step_hd_dispatch(const Args& a, hipStream_t stream) {
+    if (a.B == 0) return FG_OK;                       // an empty batch is a no-op (e.g. a rank that owns no envs)
+    const bool plain = !world_options_set(a.p) && !a.near_lm && !a.near_ag && !a.hd_idx;
+    // 243 agents, >= 4096 envs: pipeline over env batches inside the launch (no index outputs, no World options):
+    // 1.85-2.2 ms vs 2.1-2.3 ms at 243 x 8192 (round 1; 1.75 ms on placed buffers).
+    if (a.N == 243 && a.B >= FG_WIDE243_MIN_B && plain) return launch_wide<243, 0>(a, stream);
+    // 81 agents: the pipelined kernel pays from 16 env batches per workgroup on (81 x 16384: 419 vs 448 us; 81 x 12288 equal,
+    // 81 x 2048 62 vs 56: profiles/r03_step/pipelined_single_step_81.txt)
+    if (a.N == 81 && a.B >= FG_WIDE81_MIN_B && plain) return launch_wide<81, 0>(a, stream);
+    return launch_step(a, stream);
+}
+
+// A step loop that re-uses its buffers launches the same description again and again with only the RNG offset moving: the
+// plan keeps the checked description, so the per-step host work is one two-argument call and the kernel launch (a ctypes
+// call with 19 arguments cost 1.7 us per env.step on top of the 7.7 us kernel at 9 x 4096: VERDICT r4).
+namespace { struct StepPlan { Args a; hipStream_t stream; int device; }; }
+
+// the tail of fg_rollout_hd: which kernel runs a checked K-step description (also walked dry by fg_describe_launch)
+static int rollout_hd_dispatch(const Args& a, hipStream_t st) {
+    int rc = FG_OK;
+    // K >= 2 at the specialised agent counts: producer / writer pipelined kernels.  World options (walls, max_speed,
+    // accel, u_noise) exist only in step_kernel's OPTS instantiation, whose K-loop runs the rollout then.
+    if (a.K == 1 && !world_options_set(a.p)) {                                                       // as fg_step_hd
+        if (a.N == 243 && a.B >= FG_WIDE243_MIN_B) return launch_wide<243, 0>(a, st);
+        if (a.N == 81 && a.B >= FG_WIDE81_MIN_B) return launch_wide<81, 0>(a, st);
+    }
+    if (a.K >= 2 && !world_options_set(a.p) && launch_pipelined(a, 0, st, &rc)) return rc;
+    return launch_step(a, st);
+}
+
+// ... and of fg_rollout_hd_policy (a.pl, a.act_out set)
+static int rollout_hd_policy_dispatch(const Args& a, int per_layer, hipStream_t st) {
+    int rc = FG_OK;
+    // N = per^L up to 243 agents (per 2, 3, 4, 5, 8): the controller runs inside the pipelined kernels, ONE launch
+    if (!world_options_set(a.p) && launch_pipelined(a, per_layer, st, &rc)) return rc;
+    // everything else: K times (controller launch, single-step launch) chained on the stream - the same device
+    // function on the same state, so the results equal the in-kernel loop's and fg_policy_bfs on the written rows
+    const size_t bn = (size_t)a.B * a.N;
+    for (int k = 0; k < a.K; ++k) {
+        float* act_k = a.act_out + (size_t)k * bn * 2;
+        rc = launch_policy_state(a.B, a.N, a.pl, a.px, a.py, a.shape, a.ivel, act_k, st);
+        if (rc) return rc;
+        Args s1 = a;
+        s1.K = 1; s1.obs_every = 1; s1.act = act_k; s1.act_out = nullptr;
+        s1.p.rng_offset = a.p.rng_offset + (uint64_t)k;
+        s1.rew = a.rew + (size_t)k * bn;
+        s1.indiv = a.indiv ? a.indiv + (size_t)k * bn : nullptr;
+        s1.done = a.done ? a.done + (size_t)k * bn : nullptr;
+        s1.obs = (a.obs && (k + 1) % a.obs_every == 0)
+                     ? a.obs + (size_t)(k / a.obs_every) * (size_t)a.B * (size_t)a.obs_pitch * 2 : nullptr;
+        rc = launch_step(s1, st);
+        if (rc) return rc;
+        if (g_describe && k == 0 && a.K > 1) { describe("x %d chained; ", a.K); break; }   // dry run: one round says it all
+    }
+    return FG_OK;
+}
+
+static int launch_mt_reset(int B, int N, const uint8_t* mask, uint32_t* mt_state,
+                           float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                           float* ideal_shape, float* ideal_vel, float* landmark_pos, int32_t* step,
+                           int world_length, float* obs, long long obs_env_pitch, void* stream) {
+    const DeviceGuard device_guard(stream, pos_x);
+    if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
+    if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
+    if (const int rc = generic_n_check(N)) return rc;
+    if (!mt_state || !pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel) return null_pointer("fg_reset_hd_mt");
+    const long long nenv = 6LL * N * N;
+    const long long pitch = obs_env_pitch ? obs_env_pitch : nenv;
+    if (obs && (pitch < nenv || (pitch & 1))) return fail(FG_ERR_BAD_ARG, "obs_env_pitch must be 0 or an even number of floats >= 6 N^2%s");
+    if ((uintptr_t)obs & 7u) return fail(FG_ERR_ALIGNMENT, "obs must be 8-byte aligned%s");
+    const int lds = (624 + ((8 * N + 4 + 1) & ~1)) * (int)sizeof(uint32_t) + 2 * (int)sizeof(double) +
+                    (2 * N + 1) * (int)sizeof(float2);
+    return launch<&mt_reset_kernel>(B, 256, lds, (hipStream_t)stream, "mt reset launch failed: %s", B, N, mask, mt_state, pos_x, pos_y,
+                                    vel_x, vel_y, ideal_shape, ideal_vel, landmark_pos, step, world_length, obs, pitch / 2);
+}
+
+// ---- the landmark scenarios: the checks the step / rollout entries and the two resets share, each called at the entry's own
+// point (the resets name themselves in their pointer check and do not look at the buffers the step needs)
+constexpr int FG_NOOP = 1;         // a check's answer to zero steps or an empty batch: the entry returns FG_OK without a launch
+static int scn_given(const FgScenario* sc) { return sc ? FG_OK : fail(FG_ERR_BAD_ARG, "scenario descriptor is NULL%s"); }
+static int scn_kind_check(const FgScenario* sc) {
+    return sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE ? fail(FG_ERR_BAD_ARG, "unknown scenario kind%s") : FG_OK;
+}
+static int scn_counts_check(const FgScenario* sc, int B, int N) {
+    const int L = sc->num_landmarks, M = sc->num_obstacles;
+    if (B < 0 || L <= 0 || M < 0) return fail(FG_ERR_BAD_ARG, "B >= 0, L > 0, M >= 0 required%s");
+    if (N < 2 || N + M > FG_MAX_AGENTS || L > 1024)
+        return fail(FG_ERR_UNSUPPORTED_N, "scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024%s");
+    return FG_OK;
+}
+// a NULL among the world's buffers (the obstacles' only where the scenario has any)
+static bool scn_world_null(const FgScenario* sc, const float* px, const float* py, const float* vx, const float* vy,
+                           const float* landmarks, const float* obst_pos, const float* obst_vel) {
+    return !px || !py || !vx || !vy || !landmarks || (sc->num_obstacles > 0 && (!obst_pos || !obst_vel));
+}
+static int scn_reset_align_check(const float* landmarks, const float* obst_pos, const float* obst_vel) {
+    if (((uintptr_t)landmarks & 7u) || ((uintptr_t)obst_pos & 7u) || ((uintptr_t)obst_vel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "landmarks / obstacle buffers must be 8-byte aligned%s");
+    return FG_OK;
+}
+
+// The scalars of a landmark-scenario launch description (the fused-actor entries come here with a descriptor whose landmark
+// count nobody has checked yet: their dispatch refuses every shape but the reference's).
+static void scn_args(ScnArgs* a, const FgParams* params, const FgScenario* sc, int B, int N, int do_physics, int K, int obs_every) {
+    a->p = *params; a->sc = *sc; a->B = B; a->N = N; a->do_phys = do_physics ? 1 : 0; a->K = K; a->obs_every = obs_every < 1 ? 1 : obs_every;
+    a->inv_n = (float)(1.0 / (double)N); a->inv_l = (float)(1.0 / (double)(sc->num_landmarks > 0 ? sc->num_landmarks : 1));
+    a->coll_scale = (float)((double)params->collide_thresh / (double)params->dist_min);
+}
+// ... and its buffers: a zeroed description with the caller's pointers in it
+static ScnArgs scn_buffers(float* px, float* py, float* vx, float* vy, const float* act, float* landmarks, float* obst_pos,
+                           float* obst_vel, int32_t* step, float* obs, float* rew, float* indiv, uint8_t* done, int32_t* near_ag) {
+    ScnArgs a; memset(&a, 0, sizeof(a));
+    a.px = px; a.py = py; a.vx = vx; a.vy = vy; a.act = act; a.lm = landmarks; a.opos = obst_pos; a.ovel = obst_vel; a.step = step;
+    a.obs = obs; a.rew = rew; a.indiv = indiv; a.done = done; a.near_ag = near_ag;
+    return a;
+}
+
+// The checks of a step / rollout of a landmark scenario before its buffers: FG_OK, FG_NOOP, or the status of the first that fails
+static int scenario_check(const FgParams* params, const FgScenario* sc, int B, int N, int do_physics, int K, int obs_every) {
+    int rc = check_params(params);
+    if (rc || (rc = scn_given(sc))) return rc;
+    if (K == 0) return FG_NOOP;
+    if (K < 0 || obs_every < 1) return fail(FG_ERR_BAD_ARG, "K >= 0 and obs_every >= 1 required%s");
+    if (K > 1 && !do_physics) return fail(FG_ERR_BAD_ARG, "a multi-step launch steps the physics%s");
+    if (params->comm_state)
+        return fail(FG_ERR_BAD_ARG, "comm_state is honoured by the formation_hd_env entry points only%s");
+    if ((rc = scn_kind_check(sc))) return rc;
+    if (B == 0) return FG_NOOP;
+    if ((rc = scn_counts_check(sc, B, N))) return rc;
+    if (sc->kind == FG_SCN_PARTIAL && (sc->num_obs < 0 || sc->num_obs > 1024)) return fail(FG_ERR_BAD_ARG, "bad num_obs%s");
+    return FG_OK;
+}
+
+// which kernel runs a checked description (also walked dry by fg_describe_launch)
+static int scenario_dispatch(ScnArgs a, hipStream_t st) {
+    const int B = a.B, N = a.N, L = a.sc.num_landmarks, M = a.sc.num_obstacles;
+    const int nbr = a.sc.kind == FG_SCN_PARTIAL ? a.sc.num_obs : N - 1;
+    if (a.sc.variant != 1 && !a.p.agent_props) {           // (per-agent tables: the run-time-count kernel)
+        // the reference's own shapes: one env per lane, every count a compile-time constant (fg_scn_lane_kernel.hpp)
+        const double obs_bytes = (double)(a.K / a.obs_every) * B * N * 4.0 * scn_obs_dim(a.sc.kind, N, L, M, nbr);
+#define FG_SCN_LANE(KIND, NN, LL, MM, NBR, WIDE)                                                         \
+        if (a.sc.kind == KIND && N == NN && L == LL && M == MM && nbr == NBR)                            \
+            return WIDE && scn_lane_wide<KIND>(B, obs_bytes) ? launch_scn_lane<KIND, NN, LL, MM, NBR, (WIDE ? 4 : 1)>(a, st) \
+                                                             : launch_scn_lane<KIND, NN, LL, MM, NBR, 1>(a, st);
+        FG_SCN_SHAPES(FG_SCN_LANE)
+#undef FG_SCN_LANE
+    }
+    constexpr int FG_SCN_T = 64;      // threads per workgroup of the scenario kernel up to 64 entities per env
+    const int G = pow2ceil(N + M) < 4 ? 4 : pow2ceil(N + M);
+    const int E = G <= 64 ? FG_SCN_T / G : 1;         // more than 64 entities: one env per workgroup of G threads
+    const int grid = (B + E - 1) / E;
+    int lds = (E * (2 * (N + M) + L) + (G > 64 ? 32 : 0)) * (int)sizeof(float2);
+    {   // observation rows composed in LDS and streamed out contiguously when the workgroup's block fits
+        const long long D = 2 + (a.sc.kind == FG_SCN_BASIC ? 2 : 0) + 2LL * L + 2LL * M + 2LL * nbr + 2LL * (N - 1);
+        const long long stage = (long long)E * N * D * (long long)sizeof(float);
+        a.stage = (lds + stage <= 48 * 1024) ? 1 : 0;
+        if (a.stage) lds += (int)stage;
+    }
+    if (describe("scn_kernel<%d,%d> grid %d lds %d stage %d; ", G, G <= 64 ? FG_SCN_T : G, grid, lds, a.stage)) return FG_OK;
+    return pow2_dispatch(G, [&](auto g, auto t) {
+        return launch<&scn_kernel<decltype(g)::value, decltype(t)::value>>(grid, decltype(t)::value, lds, st, "scenario launch failed: %s", a);
+    });
+}
+
+// fg_step_scenario, fg_step_basic and fg_rollout_scenario: `a` holds the caller's buffers (scn_buffers)
+static int launch_scenario(const FgParams* params, const FgScenario* sc, int B, int N, int do_physics, int K, int obs_every,
+                           ScnArgs a, void* stream) {
+    const DeviceGuard device_guard(stream, a.px);
+    const int rc = scenario_check(params, sc, B, N, do_physics, K, obs_every);
+    if (rc) return rc == FG_NOOP ? FG_OK : rc;
+    if (scn_world_null(sc, a.px, a.py, a.vx, a.vy, a.lm, a.opos, a.ovel) || !a.obs || (do_physics && (!a.act || !a.rew)))
+        return null_pointer("scenario step");
+    if (((uintptr_t)a.obs & 7u) || ((uintptr_t)a.lm & 7u) || (a.act && ((uintptr_t)a.act & 7u)) ||
+        ((uintptr_t)a.opos & 7u) || ((uintptr_t)a.ovel & 7u))
+        return fail(FG_ERR_ALIGNMENT, "obs/landmarks/act/obstacle buffers must be 8-byte aligned%s");
+    scn_args(&a, params, sc, B, N, do_physics, K, obs_every);
+    return scenario_dispatch(a, (hipStream_t)stream);
+}
+
+// ---- closed loop with the caller's MLP actor (fg_actor_rollout_kernel.hpp) ----
+static bool actor_n_supported(int N) {
+    return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
+}
+static ActorW actor_w(const FgActor& actor) {
+    return {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+}
+// Describe-or-launch of an actor kernel: Det (the deterministic actor; log_std == NULL) or its sampling twin Smp (the Gaussian
+// actor), which takes (log_std, logp) after Det's arguments `args`.  `targs` spells the template arguments and `unit` the word
+// before the thread count in the describe string; `lds` is the chosen kernel's.
+template <auto Det, auto Smp, class... A>
+static int launch_actor_pair(const char* det_name, const char* smp_name, const char* targs, const char* unit, int grid,
+                             int threads, int envs, int lds, const char* fail_fmt, hipStream_t st, const float* log_std,
+                             float* logp, const A&... args) {
+    const bool sample = log_std != nullptr;
+    if (describe("%s<%s> grid %d %s %d envs/wg %d lds %d; ", sample ? smp_name : det_name, targs, grid, unit, threads, envs, lds))
+        return FG_OK;
+    if (sample) return launch<Smp>(grid, threads, lds, st, fail_fmt, args..., log_std, logp);
+    return launch<Det>(grid, threads, lds, st, fail_fmt, args...);
+}
+// The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
+// per agent (pa_*_kernel) and the shared actor with LayerNorms (ln_*_kernel).  `w`: the kernel's arguments after `a` - an
+// ActorW, an ActorTab, or an ActorW and an ActorNormW.
+template <int NC, int H, bool PER_AGENT, bool LNORM, class... W>
+static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
+    static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
+    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() <= 160 * 1024, "actor rollout LDS");
+    constexpr int E = actor_envs(NC), V = LNORM ? 2 : PER_AGENT ? 1 : 0;
+    constexpr auto det = [] {
+        if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
+        else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
+        else return &actor_rollout_kernel<NC, H>;
+    }();
+    constexpr auto smp = [] {
+        if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
+        else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
+        else return &actor_sample_kernel<NC, H>;
+    }();
+    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel"};
+    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel"};
+    static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
+                                           "LayerNorm actor rollout launch failed: %s"};
+    char targs[16];
+    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    return launch_actor_pair<det, smp>(
+        det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM>(),
+        fail_fmt[V], st, log_std, logp, a, w...);
+}
+// The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
+// the messages name, `max_hidden` / `widths` its admissible hidden widths (32, 64 and up to max_hidden), `also` further
+// pointers that share the weights' 4-byte alignment check and `aligned` what the alignment message calls them all.
+static int actor_struct_check(const FgActor* actor, const char* who, int max_hidden, const char* widths, uintptr_t also,
+                              const char* aligned) {
+    char msg[160];
+    auto bad = [&](int code, const char* what, const char* arg = "") {
+        snprintf(msg, sizeof(msg), what, who, arg);
+        return fail(code, "%s", msg);
+    };
+    if (!actor) return bad(FG_ERR_BAD_ARG, "%s: actor is NULL");
+    if (actor->hidden != 32 && actor->hidden != 64 && !(actor->hidden == 128 && max_hidden == 128))
+        return bad(FG_ERR_BAD_ARG, "%s: hidden must be %s", widths);
+    if (!actor->w1 || !actor->w2 || !actor->w3) return bad(FG_ERR_BAD_ARG, "%s: a weight pointer is NULL");
+    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
+         (uintptr_t)actor->b3 | also) & 3u)
+        return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", aligned);
+    return FG_OK;
+}
+static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
+    const int rc = actor_struct_check(actor, "fg_rollout_hd_actor", 128, "32, 64 or 128", 0, "weights");
+    if (rc) return rc;
+    if (world_options_set(*params))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
+    return FG_OK;
+}
+
+// One call of a formation_hd_env actor entry, fg_rollout_hd_actor* or its fg_describe_actor*_launch twin, as its checks
+// (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
+// host array of N members; `norm` counts for HD_ACTOR_NORM only; `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE
+// requires it); `logp`: the log-densities' destination, NULL from a describe twin.
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM };
+static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
+                                             "fg_rollout_hd_actor_norm"};
+struct HdActorCall {
+    HdActorKind kind;
+    const FgActor* actor;
+    const FgActorNorm* norm;
+    const float* log_std;
+    float* logp;
+};
+// FgActorNorm's checks (no device touched): hidden 32 or 64, every eps that is read positive and finite, gamma / beta 4-byte aligned
+static int actor_norm_check(const FgActor* actor, const FgActorNorm* norm) {
+    if (!norm) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: norm is NULL%s");
+    if (actor->hidden != 32 && actor->hidden != 64)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms%s");
+    auto eps_ok = [](float e) { return e > 0.0f && std::isfinite(e); };
+    if (norm->in_norm && !eps_ok(norm->in_eps))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: in_eps must be positive and finite%s");
+    if (!eps_ok(norm->h1_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite%s");
+    if (!eps_ok(norm->h2_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h2_eps must be positive and finite%s");
+    const struct { const float* p; const char* name; } ptrs[] = {
+        {norm->in_gamma, "in_gamma"}, {norm->in_beta, "in_beta"}, {norm->h1_gamma, "h1_gamma"},
+        {norm->h1_beta, "h1_beta"},   {norm->h2_gamma, "h2_gamma"}, {norm->h2_beta, "h2_beta"}};
+    for (const auto& q : ptrs)
+        if ((uintptr_t)q.p & 3u) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: %s must be 4-byte aligned", q.name);
+    return FG_OK;
+}
+// The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
+// this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
+// the norms, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
+// log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
+static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
+    const char* const who = hd_actor_entry[c.kind];
+    const char* const shared = hd_actor_entry[c.kind == HD_ACTOR_PER_AGENT ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 1 required", shared);
+    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", shared);
+    if (c.kind == HD_ACTOR_PER_AGENT) {
+        if (!c.actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
+        char idx[16];
+        for (int i = 0; i < N; ++i) {
+            if ((rc = hd_actor_struct_check(params, &c.actor[i])) != FG_OK) return rc;
+            if (c.actor[i].hidden != c.actor[0].hidden || (c.actor[i].out_tanh != 0) != (c.actor[0].out_tanh != 0)) {
+                snprintf(idx, sizeof(idx), "%d", i);
+                return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
+                            idx);
+            }
+        }
+    } else if ((rc = hd_actor_struct_check(params, c.actor)) != FG_OK) {
+        return rc;
+    }
+    if (c.kind == HD_ACTOR_NORM && (rc = actor_norm_check(c.actor, c.norm)) != FG_OK) return rc;
+    if (!c.log_std) {
+        if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
+        c.logp = nullptr;
+        return FG_OK;
+    }
+    if ((uintptr_t)c.log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
+    if ((uintptr_t)c.logp & 3u) return fail(FG_ERR_ALIGNMENT, "%s: logp_seq must be 4-byte aligned", who);
+    return FG_OK;
+}
+// The one N x H grid of the formation_hd_env actor kernels: launch(n, h) with N and H as the `value` of the arguments' types,
+// or UNSUPPORTED_N in `who`'s name when N is not in the list.  MAXH is the widest H of the caller's kernels: `hidden` is 32,
+// 64 or - MAXH == 128 only - 128 (actor_struct_check, actor_norm_check), and no launch(n, 128) is instantiated below that.
+template <int MAXH, class F>
+static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
+#define FG_ACTOR(NN)                                                                      \
+    if (N == NN) {                                                                        \
+        if (hidden == 32) return launch(IntC<NN>{}, IntC<32>{});                          \
+        if constexpr (MAXH == 128) if (hidden != 64) return launch(IntC<NN>{}, IntC<128>{}); \
+        return launch(IntC<NN>{}, IntC<64>{});                                            \
+    }
+    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
+#undef FG_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
+}
+// a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
+static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
+    const char* const who = hd_actor_entry[c.kind == HD_ACTOR_SAMPLE ? HD_ACTOR_SHARED : c.kind];
+    if (c.kind == HD_ACTOR_PER_AGENT) {
+        ActorTab tab;
+        memset(&tab, 0, sizeof(tab));
+        for (int i = 0; i < a.N; ++i) {
+            tab.w1[i] = c.actor[i].w1; tab.b1[i] = c.actor[i].b1; tab.w2[i] = c.actor[i].w2;
+            tab.b2[i] = c.actor[i].b2; tab.w3[i] = c.actor[i].w3; tab.b3[i] = c.actor[i].b3;
+        }
+        tab.out_tanh = c.actor[0].out_tanh ? 1 : 0;
+        return actor_nh_dispatch<128>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false>(a, c.log_std, c.logp, st, tab);
+        });
+    }
+    const ActorW w = actor_w(*c.actor);
+    if (c.kind != HD_ACTOR_NORM)
+        return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
+        });
+    const FgActorNorm& norm = *c.norm;
+    const bool in_norm = norm.in_norm != 0;
+    const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
+                           norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
+    return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true>(a, c.log_std, c.logp, st, w, nw);
+    });
+}
+
+// the buffers' checks and the launch of a call that has passed hd_actor_check
+static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int B, int N, int K,
+                              float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                              int obs_every, void* stream) {
+    int rc = rollout_buffers_check("fg_rollout_hd_actor", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq,
+                                   reward_seq);
+    if (rc) return rc;
+    if (B == 0) return FG_OK;
+    const DeviceGuard device_guard(stream, pos_x);
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
+    a.act_out = act_seq;
+    return hd_actor_dispatch(a, c, (hipStream_t)stream);
+}
+
+// the describe twin `who` of the call `c`: the out buffer's check, the call's own checks, then the dry run of its dispatch
+static int describe_actor_impl(const char* who, const FgParams* params, HdActorCall c, int B, int N, int K, int obs_every,
+                               char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "%s: out buffer required", who);
+    out[0] = 0;
+    int rc = hd_actor_check(params, c, B, N, K);
+    if (rc) return rc;
+    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    const DescribeScope describing(out, out_len);
+    return hd_actor_dispatch(a, c, nullptr);
+}
+
+// ---- closed loop with the caller's MLP actor in the landmark scenarios (fg_scn_lane_actor_kernel.hpp) ----
+// log_std == NULL: scn_lane_actor (the deterministic actor); else scn_lane_actor_gauss (the Gaussian actor)
+template <int KIND, int NN, int LL, int MM, int NBR, int H>
+static int launch_scn_actor(const ScnArgs& a, const ActorW& w, float* act_out, const float* log_std, float* logp, hipStream_t st) {
+    static_assert(scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, true) <= 160 * 1024, "scenario actor rollout LDS");
+    char targs[48];
+    snprintf(targs, sizeof(targs), "%d,%d,%d,%d,%d,%d", KIND, NN, LL, MM, NBR, H);
+    return launch_actor_pair<&scn_lane_actor<KIND, NN, LL, MM, NBR, H>, &scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>>(
+        "scn_lane_actor", "scn_lane_actor_gauss", targs, "threads", 8 * (((a.B + FG_SCN_ACTOR_ENVS - 1) / FG_SCN_ACTOR_ENVS + 7) / 8),
+        FG_SCN_ACTOR_THREADS, FG_SCN_ACTOR_ENVS, scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, log_std != nullptr),
+        "scenario actor rollout launch failed: %s", st, log_std, logp, a, w, act_out);
+}
+
+// the checks both scenario-actor entries share (no device touched): FG_OK, or the status of the first one that fails
+static int scn_actor_check(const FgParams* params, const FgScenario* sc, const FgActor* actor, const float* log_std,
+                           const float* logp, int B, int N, int K) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (!sc) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: scenario descriptor is NULL%s");
+    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: B >= 0 and K >= 1 required%s");
+    if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: unknown scenario kind%s");
+    if ((rc = actor_struct_check(actor, "fg_rollout_scenario_actor", 64, "32 or 64", (uintptr_t)log_std | (uintptr_t)logp,
+                                 "weights, log_std and logp")) != FG_OK)
+        return rc;
+    if (!log_std && logp) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: logp without log_std%s");
+    if (params->agent_props || params->comm_state || sc->variant == 1)
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported%s");
+    return FG_OK;
+}
+
+static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act_out, const float* log_std, float* logp,
+                              hipStream_t st) {
+    const ActorW w = actor_w(actor);
+    const int L = a.sc.num_landmarks, M = a.sc.num_obstacles;
+    const int nbr = a.sc.kind == FG_SCN_PARTIAL ? a.sc.num_obs : a.N - 1;
+#define FG_SCN_ACTOR(KIND, NN, LL, MM, NBR, WIDE)                                                            \
+    if (a.sc.kind == KIND && a.N == NN && L == LL && M == MM && nbr == NBR)                                  \
+        return actor.hidden == 32 ? launch_scn_actor<KIND, NN, LL, MM, NBR, 32>(a, w, act_out, log_std, logp, st) \
+                                  : launch_scn_actor<KIND, NN, LL, MM, NBR, 64>(a, w, act_out, log_std, logp, st);
+    FG_SCN_SHAPES(FG_SCN_ACTOR)
+#undef FG_SCN_ACTOR
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes%s");
+}
 
 extern "C" {
 
@@ -863,8 +1401,9 @@ const char* fg_last_error(void) { return g_err; }
 int fg_launch_device(void* stream, const void* data) { return resolve_device(stream, data); }
 
 int fg_kernel_config(int N, int* threads, int* envs_per_wg, int* lds_bytes) {
+    if (const int rc = generic_n_check(N)) return rc;
     Geometry g;
-    if (!geometry_for(N, &g)) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s");
+    geometry_for(N, &g);
     if (threads) *threads = g.T;
     if (envs_per_wg) *envs_per_wg = g.E;
     if (lds_bytes) *lds_bytes = g.lds;
@@ -872,43 +1411,6 @@ int fg_kernel_config(int N, int* threads, int* envs_per_wg, int* lds_bytes) {
 }
 
 int64_t fg_step_hd_bytes(int N) { return 24LL * N * N + 53LL * N + 16LL; }
-
-// fg_step_hd in two halves: argument checks + the launch description, and the dispatch of a checked description
-static int step_hd_describe(const FgParams* params, int B, int N,
-                            float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                            const float* act, float* ideal_shape, float* ideal_vel, int32_t* step,
-                            float* obs, float* reward, float* indiv_reward, uint8_t* done,
-                            int32_t* near_lm, int32_t* near_ag, int32_t* hd_idx, Args* out) {
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
-    if (B > 0 && (!pos_x || !pos_y || !vel_x || !vel_y || !act || !ideal_shape || !ideal_vel || !step || !obs || !reward))
-        return fail(FG_ERR_BAD_ARG, "fg_step_hd: a required pointer is NULL%s");
-    if (((uintptr_t)obs & 15u) || ((uintptr_t)act & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = 1; a.obs_every = 1; a.do_phys = 1; a.do_post = 1;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
-    a.near_lm = near_lm; a.near_ag = near_ag; a.hd_idx = hd_idx;
-    *out = a;
-    return FG_OK;
-}
-
-static int step_hd_dispatch(const Args& a, hipStream_t stream) {
-    if (a.B == 0) return FG_OK;                       // an empty batch is a no-op (e.g. a rank that owns no envs)
-    const bool plain = !world_options_set(a.p) && !a.near_lm && !a.near_ag && !a.hd_idx;
-    // 243 agents, >= 4096 envs: pipeline over env batches inside the launch (no index outputs, no World options):
-    // 1.85-2.2 ms vs 2.1-2.3 ms at 243 x 8192 (round 1; 1.75 ms on placed buffers).
-    if (a.N == 243 && a.B >= FG_WIDE243_MIN_B && plain) return launch_wide<243, 0>(a, stream);
-    // 81 agents: the pipelined kernel pays from 16 env batches per workgroup on (81 x 16384: 419 vs 448 us; 81 x 12288 equal,
-    // 81 x 2048 62 vs 56: profiles/r03_step/pipelined_single_step_81.txt)
-    if (a.N == 81 && a.B >= FG_WIDE81_MIN_B && plain) return launch_wide<81, 0>(a, stream);
-    return launch_step(a, stream);
-}
 
 int fg_step_hd(const FgParams* params, int B, int N,
                float* pos_x, float* pos_y, float* vel_x, float* vel_y,
@@ -922,11 +1424,6 @@ int fg_step_hd(const FgParams* params, int B, int N,
     if (rc) return rc;
     return step_hd_dispatch(a, (hipStream_t)stream);
 }
-
-// A step loop that re-uses its buffers launches the same description again and again with only the RNG offset moving: the
-// plan keeps the checked description, so the per-step host work is one two-argument call and the kernel launch (a ctypes
-// call with 19 arguments cost 1.7 us per env.step on top of the 7.7 us kernel at 9 x 4096: VERDICT r4).
-namespace { struct StepPlan { Args a; hipStream_t stream; int device; }; }
 
 int fg_step_hd_plan(const FgParams* params, int B, int N,
                     float* pos_x, float* pos_y, float* vel_x, float* vel_y,
@@ -948,60 +1445,13 @@ int fg_step_hd_plan(const FgParams* params, int B, int N,
 int fg_plan_launch(void* plan, uint64_t rng_offset) {
     StepPlan* sp = (StepPlan*)plan;
     if (!sp) return fail(FG_ERR_BAD_ARG, "fg_plan_launch: plan is NULL%s");
-    int prev = -1;
-    bool switched = false;
-    if (sp->device >= 0 && hipGetDevice(&prev) == hipSuccess && prev != sp->device) switched = hipSetDevice(sp->device) == hipSuccess;
+    const DeviceGuard device_guard(sp->device);       // resolved at plan time: no query per step
     sp->a.p.rng_offset = rng_offset;
-    const int rc = step_hd_dispatch(sp->a, sp->stream);
-    if (switched) (void)hipSetDevice(prev);
-    return rc;
+    return step_hd_dispatch(sp->a, sp->stream);
 }
 
 int fg_plan_destroy(void* plan) {
     delete (StepPlan*)plan;
-    return FG_OK;
-}
-
-// the tail of fg_rollout_hd: which kernel runs a checked K-step description (also walked dry by fg_describe_launch)
-static int rollout_hd_dispatch(const Args& a, hipStream_t st) {
-    int rc = FG_OK;
-    // K >= 2 at the specialised agent counts: producer / writer pipelined kernels.  World options (walls, max_speed,
-    // accel, u_noise) exist only in step_kernel's OPTS instantiation, whose K-loop runs the rollout then.
-    if (a.K == 1 && !world_options_set(a.p)) {                                                       // as fg_step_hd
-        if (a.N == 243 && a.B >= FG_WIDE243_MIN_B) return launch_wide<243, 0>(a, st);
-        if (a.N == 81 && a.B >= FG_WIDE81_MIN_B) return launch_wide<81, 0>(a, st);
-    }
-    if (a.K >= 2 && !world_options_set(a.p) && launch_pipelined(a, 0, st, &rc)) return rc;
-    return launch_step(a, st);
-}
-
-static int launch_policy_state(int B, int N, const FgPolicyLevels& pl, const float* px, const float* py,
-                               const float* shape, const float* ivel, float* act, hipStream_t st);
-
-// ... and of fg_rollout_hd_policy (a.pl, a.act_out set)
-static int rollout_hd_policy_dispatch(const Args& a, int per_layer, hipStream_t st) {
-    int rc = FG_OK;
-    // N = per^L up to 243 agents (per 2, 3, 4, 5, 8): the controller runs inside the pipelined kernels, ONE launch
-    if (!world_options_set(a.p) && launch_pipelined(a, per_layer, st, &rc)) return rc;
-    // everything else: K times (controller launch, single-step launch) chained on the stream - the same device
-    // function on the same state, so the results equal the in-kernel loop's and fg_policy_bfs on the written rows
-    const size_t bn = (size_t)a.B * a.N;
-    for (int k = 0; k < a.K; ++k) {
-        float* act_k = a.act_out + (size_t)k * bn * 2;
-        rc = launch_policy_state(a.B, a.N, a.pl, a.px, a.py, a.shape, a.ivel, act_k, st);
-        if (rc) return rc;
-        Args s1 = a;
-        s1.K = 1; s1.obs_every = 1; s1.act = act_k; s1.act_out = nullptr;
-        s1.p.rng_offset = a.p.rng_offset + (uint64_t)k;
-        s1.rew = a.rew + (size_t)k * bn;
-        s1.indiv = a.indiv ? a.indiv + (size_t)k * bn : nullptr;
-        s1.done = a.done ? a.done + (size_t)k * bn : nullptr;
-        s1.obs = (a.obs && (k + 1) % a.obs_every == 0)
-                     ? a.obs + (size_t)(k / a.obs_every) * (size_t)a.B * (size_t)a.obs_pitch * 2 : nullptr;
-        rc = launch_step(s1, st);
-        if (rc) return rc;
-        if (g_describe && k == 0 && a.K > 1) { describe("x %d chained; ", a.K); break; }   // dry run: one round says it all
-    }
     return FG_OK;
 }
 
@@ -1013,13 +1463,12 @@ int fg_physics_step(const FgParams* params, int B, int N,
     if (rc) return rc;
     if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 2 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !act)
-        return fail(FG_ERR_BAD_ARG, "fg_physics_step: a required pointer is NULL%s");
+    if ((rc = generic_n_check(N))) return rc;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !act) return null_pointer("fg_physics_step");
     if ((uintptr_t)act & 7u) return fail(FG_ERR_ALIGNMENT, "act must be 8-byte aligned%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.p.auto_reset = 0; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = 1; a.obs_every = 1; a.do_phys = 1; a.do_post = 0;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, 1, 1, 1, 0))) return rc;
+    a.p.auto_reset = 0;
     a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act;
     return launch_step(a, (hipStream_t)stream);
 }
@@ -1034,20 +1483,17 @@ int fg_observe_hd(const FgParams* params, int B, int N,
     if (rc) return rc;
     if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel)
-        return fail(FG_ERR_BAD_ARG, "fg_observe_hd: a required pointer is NULL%s");
+    if ((rc = hd_n_check(N))) return rc;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel) return null_pointer("fg_observe_hd");
     if (!obs && !reward) return fail(FG_ERR_BAD_ARG, "fg_observe_hd: obs and reward both NULL%s");
     if (((uintptr_t)obs & 15u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
         return fail(FG_ERR_ALIGNMENT, "obs must be 16-byte, ideal_shape/ideal_vel 8-byte aligned%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.p.auto_reset = 0; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = 1; a.obs_every = 1; a.do_phys = 0; a.do_post = 1;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    a.px = const_cast<float*>(pos_x); a.py = const_cast<float*>(pos_y);
-    a.vx = const_cast<float*>(vel_x); a.vy = const_cast<float*>(vel_y);
-    a.shape = const_cast<float*>(ideal_shape); a.ivel = const_cast<float*>(ideal_vel);
-    a.step = const_cast<int32_t*>(step);
-    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, 1, 1, 0, 1))) return rc;
+    a.p.auto_reset = 0;
+    hd_buffers(&a, const_cast<float*>(pos_x), const_cast<float*>(pos_y), const_cast<float*>(vel_x), const_cast<float*>(vel_y),
+               const_cast<float*>(ideal_shape), const_cast<float*>(ideal_vel), const_cast<int32_t*>(step), obs, reward,
+               indiv_reward, done);
     a.near_lm = near_lm; a.near_ag = near_ag; a.hd_idx = hd_idx;
     return launch_step(a, (hipStream_t)stream);
 }
@@ -1062,19 +1508,38 @@ int fg_rollout_hd(const FgParams* params, int B, int N, int K,
     if (rc) return rc;
     if (B == 0 || K == 0) return FG_OK;               // empty batch / zero steps: nothing to do
     if (B < 0 || K < 0) return fail(FG_ERR_BAD_ARG, "B and K must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd: a required pointer is NULL%s");
-    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    a.do_phys = 1; a.do_post = 1;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act_seq;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
+    if ((rc = hd_n_check(N))) return rc;
+    if ((rc = rollout_buffers_check("fg_rollout_hd", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq,
+                                    reward_seq)))
+        return rc;
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
+    a.act = act_seq;
     return rollout_hd_dispatch(a, (hipStream_t)stream);
+}
+
+int fg_rollout_hd_policy(const FgParams* params, int B, int N, int K, int per_layer,
+                         float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                         float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                         int obs_every, void* stream) {
+    const DeviceGuard device_guard(stream, pos_x);
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B == 0 || K == 0) return FG_OK;
+    if (B < 0 || K < 0) return fail(FG_ERR_BAD_ARG, "B and K must be >= 0%s");
+    if ((rc = hd_n_check(N))) return rc;
+    FgPolicyLevels pl;
+    if ((rc = policy_levels_check("fg_rollout_hd_policy", N, per_layer, &pl))) return rc;
+    if ((rc = rollout_buffers_check("fg_rollout_hd_policy", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                    obs_seq, reward_seq)))
+        return rc;
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
+    a.pl = pl; a.act_out = act_seq;
+    return rollout_hd_policy_dispatch(a, per_layer, (hipStream_t)stream);
 }
 
 int fg_reset_hd(const FgParams* params, int B, int N, const uint8_t* mask,
@@ -1085,140 +1550,18 @@ int fg_reset_hd(const FgParams* params, int B, int N, const uint8_t* mask,
     if (rc) return rc;
     if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
+    if ((rc = generic_n_check(N))) return rc;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel) return null_pointer("fg_reset_hd");
     Geometry g;
-    if (!geometry_for(N, &g)) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel)
-        return fail(FG_ERR_BAD_ARG, "fg_reset_hd: a required pointer is NULL%s");
+    geometry_for(N, &g);
+    // (no hd_args: a reset writes no observation and does not look at the observation pitch)
     Args a; memset(&a, 0, sizeof(a));
     a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    hipStream_t st = (hipStream_t)stream;
-    const int G = g.G;
-    int grid;
-#define FG_RESET(GG, TT) grid = (B + (TT / GG) - 1) / (TT / GG); \
-    hipLaunchKernelGGL((reset_kernel<GG, TT>), dim3(grid), dim3(TT), 0, st, a, mask)
-    if (G == 4) { FG_RESET(4, 64); } else if (G == 8) { FG_RESET(8, 64); }
-    else if (G == 16) { FG_RESET(16, 64); } else if (G == 32) { FG_RESET(32, 64); }
-    else if (G == 64) { FG_RESET(64, 64); } else if (G == 128) { FG_RESET(128, 128); }
-    else if (G == 256) { FG_RESET(256, 256); } else if (G == 512) { FG_RESET(512, 512); }
-    else { FG_RESET(1024, 1024); }
-#undef FG_RESET
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "reset launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
-}
-
-static int launch_scenario(const FgParams* params, const FgScenario* sc, int B, int N, int do_physics,
-                           float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                           const float* act, float* landmarks, float* obst_pos, float* obst_vel,
-                           int32_t* step, float* obs, float* reward, float* indiv_reward, uint8_t* done,
-                           int32_t* near_ag, void* stream, int K = 1, int obs_every = 1) {
-    const DeviceGuard device_guard(stream, pos_x);
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (!sc) return fail(FG_ERR_BAD_ARG, "scenario descriptor is NULL%s");
-    if (K == 0) return FG_OK;
-    if (K < 0 || obs_every < 1) return fail(FG_ERR_BAD_ARG, "K >= 0 and obs_every >= 1 required%s");
-    if (K > 1 && !do_physics) return fail(FG_ERR_BAD_ARG, "a multi-step launch steps the physics%s");
-    if (params->comm_state)
-        return fail(FG_ERR_BAD_ARG, "comm_state is honoured by the formation_hd_env entry points only%s");
-    const int L = sc->num_landmarks, M = sc->num_obstacles;
-    if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE) return fail(FG_ERR_BAD_ARG, "unknown scenario kind%s");
-    if (B == 0) return FG_OK;
-    if (B < 0 || L <= 0 || M < 0) return fail(FG_ERR_BAD_ARG, "B >= 0, L > 0, M >= 0 required%s");
-    if (N < 2 || N + M > FG_MAX_AGENTS || L > 1024)
-        return fail(FG_ERR_UNSUPPORTED_N, "scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024%s");
-    if (sc->kind == FG_SCN_PARTIAL && (sc->num_obs < 0 || sc->num_obs > 1024)) return fail(FG_ERR_BAD_ARG, "bad num_obs%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !landmarks || !obs || (do_physics && (!act || !reward)) ||
-        (M > 0 && (!obst_pos || !obst_vel)))
-        return fail(FG_ERR_BAD_ARG, "scenario step: a required pointer is NULL%s");
-    if (((uintptr_t)obs & 7u) || ((uintptr_t)landmarks & 7u) || (act && ((uintptr_t)act & 7u)) ||
-        ((uintptr_t)obst_pos & 7u) || ((uintptr_t)obst_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs/landmarks/act/obstacle buffers must be 8-byte aligned%s");
-    ScnArgs a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.sc = *sc; a.B = B; a.N = N; a.do_phys = do_physics ? 1 : 0; a.K = K; a.obs_every = obs_every;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act; a.lm = landmarks;
-    a.opos = obst_pos; a.ovel = obst_vel; a.step = step;
-    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done; a.near_ag = near_ag;
-    a.inv_n = (float)(1.0 / (double)N); a.inv_l = (float)(1.0 / (double)L);
-    a.coll_scale = (float)((double)params->collide_thresh / (double)params->dist_min);
-    hipStream_t st = (hipStream_t)stream;
-    if (sc->variant != 1 && !params->agent_props) {        // (per-agent tables: the run-time-count kernel)
-        // the reference's own shapes: one env per lane, every count a compile-time constant (fg_scn_lane_kernel.hpp)
-        const int nbr = sc->kind == FG_SCN_PARTIAL ? sc->num_obs : N - 1;
-        bool launched = false;
-        const double obs_bytes = (double)((K > 1 ? K : 1) / obs_every) * B * N * 4.0 * scn_obs_dim(sc->kind, N, L, M, nbr);
-#define FG_SCN_LANE(KIND, NN, LL, MM, NBR, WIDE)                                                                        \
-        if (!launched && sc->kind == KIND && N == NN && L == LL && M == MM && nbr == NBR) {                                 \
-            const int rc = (WIDE && scn_lane_wide<KIND>(B, obs_bytes)) ? launch_scn_lane<KIND, NN, LL, MM, NBR, (WIDE ? 4 : 1)>(a, st)  \
-                                                            : launch_scn_lane<KIND, NN, LL, MM, NBR, 1>(a, st);            \
-            if (g_describe) return rc;                                                                                      \
-            launched = true;                                                                                                \
-        }
-        // (WIDE: the 256-env form exists for this shape, see scn_lane_wide)
-        FG_SCN_LANE(FG_SCN_BASIC, 3, 3, 0, 2, true)            // basic_formation_env.py:7
-        FG_SCN_LANE(FG_SCN_PARTIAL, 5, 5, 0, 3, true)          // formation_hd_partial_env.py:15
-        FG_SCN_LANE(FG_SCN_RANGE, 4, 4, 0, 3, true)            // formation_hd_partial_range_env.py:15
-        FG_SCN_LANE(FG_SCN_OBSTACLE, 4, 4, 3, 3, false)        // formation_hd_obs_env.py:14
-        FG_SCN_LANE(FG_SCN_PARTIAL, 3, 5, 0, 3, false)         // make_env(name) passes its own default num_agents = 3 (__init__.py:6-11)
-        FG_SCN_LANE(FG_SCN_RANGE, 3, 4, 0, 2, false)
-        FG_SCN_LANE(FG_SCN_OBSTACLE, 3, 4, 3, 2, false)
-#undef FG_SCN_LANE
-        if (launched) {
-            const hipError_t err = hipGetLastError();
-            if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario launch failed: %s", hipGetErrorString(err));
-            return FG_OK;
-        }
-    }
-    constexpr int FG_SCN_T = 64;      // threads per workgroup of the scenario kernel up to 64 entities per env
-    const int G = pow2ceil(N + M) < 4 ? 4 : pow2ceil(N + M);
-    const int E = G <= 64 ? FG_SCN_T / G : 1;         // more than 64 entities: one env per workgroup of G threads
-    const int grid = (B + E - 1) / E;
-    int lds = (E * (2 * (N + M) + L) + (G > 64 ? 32 : 0)) * (int)sizeof(float2);
-    {   // observation rows composed in LDS and streamed out contiguously when the workgroup's block fits
-        const int nbr = (sc->kind == FG_SCN_PARTIAL) ? sc->num_obs : (N - 1);
-        const long long D = 2 + (sc->kind == FG_SCN_BASIC ? 2 : 0) + 2LL * L + 2LL * M + 2LL * nbr + 2LL * (N - 1);
-        const long long stage = (long long)E * N * D * (long long)sizeof(float);
-        a.stage = (lds + stage <= 48 * 1024) ? 1 : 0;
-        if (a.stage) lds += (int)stage;
-    }
-    if (describe("scn_kernel<%d,%d> grid %d lds %d stage %d; ", G, G <= 64 ? FG_SCN_T : G, grid, lds, a.stage)) return FG_OK;
-    if (G == 4) hipLaunchKernelGGL((scn_kernel<4, FG_SCN_T>), dim3(grid), dim3(FG_SCN_T), lds, st, a);
-    else if (G == 8) hipLaunchKernelGGL((scn_kernel<8, FG_SCN_T>), dim3(grid), dim3(FG_SCN_T), lds, st, a);
-    else if (G == 16) hipLaunchKernelGGL((scn_kernel<16, FG_SCN_T>), dim3(grid), dim3(FG_SCN_T), lds, st, a);
-    else if (G == 32) hipLaunchKernelGGL((scn_kernel<32, FG_SCN_T>), dim3(grid), dim3(FG_SCN_T), lds, st, a);
-    else if (G == 64) hipLaunchKernelGGL((scn_kernel<64, FG_SCN_T>), dim3(grid), dim3(FG_SCN_T), lds, st, a);
-    else if (G == 128) hipLaunchKernelGGL((scn_kernel<128, 128>), dim3(grid), dim3(128), lds, st, a);
-    else if (G == 256) hipLaunchKernelGGL((scn_kernel<256, 256>), dim3(grid), dim3(256), lds, st, a);
-    else if (G == 512) hipLaunchKernelGGL((scn_kernel<512, 512>), dim3(grid), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((scn_kernel<1024, 1024>), dim3(grid), dim3(1024), lds, st, a);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
-}
-
-static int launch_mt_reset(int B, int N, const uint8_t* mask, uint32_t* mt_state,
-                           float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                           float* ideal_shape, float* ideal_vel, float* landmark_pos, int32_t* step,
-                           int world_length, float* obs, long long obs_env_pitch, void* stream) {
-    const DeviceGuard device_guard(stream, pos_x);
-    if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
-    if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 2 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [2, 1024]%s");
-    if (!mt_state || !pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel)
-        return fail(FG_ERR_BAD_ARG, "fg_reset_hd_mt: a required pointer is NULL%s");
-    const long long nenv = 6LL * N * N;
-    const long long pitch = obs_env_pitch ? obs_env_pitch : nenv;
-    if (obs && (pitch < nenv || (pitch & 1))) return fail(FG_ERR_BAD_ARG, "obs_env_pitch must be 0 or an even number of floats >= 6 N^2%s");
-    if ((uintptr_t)obs & 7u) return fail(FG_ERR_ALIGNMENT, "obs must be 8-byte aligned%s");
-    const int lds = (624 + ((8 * N + 4 + 1) & ~1)) * (int)sizeof(uint32_t) + 2 * (int)sizeof(double) +
-                    (2 * N + 1) * (int)sizeof(float2);
-    hipLaunchKernelGGL(mt_reset_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, B, N, mask, mt_state,
-                       pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, landmark_pos, step, world_length, obs, pitch / 2);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "mt reset launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, nullptr, nullptr, nullptr, nullptr);
+    return pow2_dispatch(g.G, [&](auto lanes, auto threads) {
+        constexpr int GG = decltype(lanes)::value, TT = decltype(threads)::value;
+        return launch<&reset_kernel<GG, TT>>((B + (TT / GG) - 1) / (TT / GG), TT, 0, (hipStream_t)stream, "reset launch failed: %s", a, mask);
+    });
 }
 
 int fg_reset_hd_mt(int B, int N, const uint8_t* mask, uint32_t* mt_state,
@@ -1238,28 +1581,40 @@ int fg_reset_hd_mt_done(int B, int N, int world_length, uint32_t* mt_state,
                            world_length, obs, (long long)obs_env_pitch, stream);
 }
 
+int fg_reset_scenario(const FgParams* params, const FgScenario* scenario, int B, int N, const uint8_t* mask,
+                      float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                      float* landmarks, float* obst_pos, float* obst_vel, int32_t* step, void* stream) {
+    const DeviceGuard device_guard(stream, pos_x);
+    int rc = check_params(params);
+    if (rc || (rc = scn_given(scenario)) || (rc = scn_kind_check(scenario))) return rc;
+    if (B == 0) return FG_OK;
+    if ((rc = scn_counts_check(scenario, B, N))) return rc;
+    if (scn_world_null(scenario, pos_x, pos_y, vel_x, vel_y, landmarks, obst_pos, obst_vel)) return null_pointer("fg_reset_scenario");
+    if ((rc = scn_reset_align_check(landmarks, obst_pos, obst_vel))) return rc;
+    const long long count = (long long)B * (N + scenario->num_landmarks + scenario->num_obstacles);
+    return launch<&scn_reset_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "scenario reset launch failed: %s",
+                                     *params, *scenario, B, N, mask, pos_x, pos_y, vel_x, vel_y, reinterpret_cast<float2*>(landmarks),
+                                     reinterpret_cast<float2*>(obst_pos), reinterpret_cast<float2*>(obst_vel), step);
+}
+
 int fg_reset_scenario_mt(const FgScenario* scenario, int B, int N, const uint8_t* mask, int world_length, uint32_t* mt_state,
                          float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                          float* landmarks, float* obst_pos, float* obst_vel, int32_t* step, void* stream) {
     const DeviceGuard device_guard(stream, pos_x);
-    if (!scenario) return fail(FG_ERR_BAD_ARG, "scenario descriptor is NULL%s");
-    const int L = scenario->num_landmarks, M = scenario->num_obstacles;
+    int rc = scn_given(scenario);                     // (no kind check: the MT19937 reset draws the same for every kind)
+    if (rc) return rc;
     if (B == 0) return FG_OK;
-    if (B < 0 || L <= 0 || M < 0) return fail(FG_ERR_BAD_ARG, "B >= 0, L > 0, M >= 0 required%s");
-    if (N < 2 || N + M > FG_MAX_AGENTS || L > 1024)
-        return fail(FG_ERR_UNSUPPORTED_N, "scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024%s");
-    if (!mt_state || !pos_x || !pos_y || !vel_x || !vel_y || !landmarks || (M > 0 && (!obst_pos || !obst_vel)))
-        return fail(FG_ERR_BAD_ARG, "fg_reset_scenario_mt: a required pointer is NULL%s");
+    if ((rc = scn_counts_check(scenario, B, N))) return rc;
+    if (!mt_state || scn_world_null(scenario, pos_x, pos_y, vel_x, vel_y, landmarks, obst_pos, obst_vel))
+        return null_pointer("fg_reset_scenario_mt");
     if (!mask && world_length > 0 && !step) return fail(FG_ERR_BAD_ARG, "fg_reset_scenario_mt: the done rule needs the step counters%s");
-    if (((uintptr_t)landmarks & 7u) || ((uintptr_t)obst_pos & 7u) || ((uintptr_t)obst_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "landmarks / obstacle buffers must be 8-byte aligned%s");
+    if ((rc = scn_reset_align_check(landmarks, obst_pos, obst_vel))) return rc;
+    const int L = scenario->num_landmarks, M = scenario->num_obstacles;
     const int lds = (624 + 4 * (N + L + M)) * (int)sizeof(uint32_t);
-    hipLaunchKernelGGL(mt_reset_scn_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, B, N, L, M, mask, mt_state,
-                       pos_x, pos_y, vel_x, vel_y, reinterpret_cast<float2*>(landmarks), reinterpret_cast<float2*>(obst_pos),
-                       reinterpret_cast<float2*>(obst_vel), step, world_length, scenario->obstacle_vx, scenario->obstacle_vy);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "mt reset launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&mt_reset_scn_kernel>(B, 256, lds, (hipStream_t)stream, "mt reset launch failed: %s", B, N, L, M, mask, mt_state,
+                                        pos_x, pos_y, vel_x, vel_y, reinterpret_cast<float2*>(landmarks),
+                                        reinterpret_cast<float2*>(obst_pos), reinterpret_cast<float2*>(obst_vel), step, world_length,
+                                        scenario->obstacle_vx, scenario->obstacle_vy);
 }
 
 int fg_update_comm(const FgParams* params, int B, int N, const float* action_c, float* comm_state, void* stream) {
@@ -1269,15 +1624,12 @@ int fg_update_comm(const FgParams* params, int B, int N, const float* action_c, 
     if (B == 0) return FG_OK;
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
     if (N < 1 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [1, 1024]%s");
-    if (!action_c || !comm_state) return fail(FG_ERR_BAD_ARG, "fg_update_comm: a required pointer is NULL%s");
+    if (!action_c || !comm_state) return null_pointer("fg_update_comm");
     if (((uintptr_t)action_c & 7u) || ((uintptr_t)comm_state & 7u))
         return fail(FG_ERR_ALIGNMENT, "action_c and comm_state must be 8-byte aligned%s");
     const long long count = (long long)B * N;
-    hipLaunchKernelGGL(update_comm_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       *params, B, N, reinterpret_cast<const float2*>(action_c), reinterpret_cast<float2*>(comm_state));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "comm launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&update_comm_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "comm launch failed: %s", *params,
+                                       B, N, reinterpret_cast<const float2*>(action_c), reinterpret_cast<float2*>(comm_state));
 }
 
 int fg_update_comm_dim(const FgParams* params, int B, int N, int dim_c, const float* action_c, float* comm_state, void* stream) {
@@ -1288,15 +1640,12 @@ int fg_update_comm_dim(const FgParams* params, int B, int N, int dim_c, const fl
     if (B == 0 || dim_c == 0) return FG_OK;
     if (B < 0 || dim_c < 0 || dim_c > 4096) return fail(FG_ERR_BAD_ARG, "B >= 0 and 0 <= dim_c <= 4096 required%s");
     if (N < 1 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "N must be in [1, 1024]%s");
-    if (!action_c || !comm_state) return fail(FG_ERR_BAD_ARG, "fg_update_comm_dim: a required pointer is NULL%s");
+    if (!action_c || !comm_state) return null_pointer("fg_update_comm_dim");
     if (((uintptr_t)action_c & 3u) || ((uintptr_t)comm_state & 3u))
         return fail(FG_ERR_ALIGNMENT, "action_c and comm_state must be 4-byte aligned%s");
     const long long count = (long long)B * N * ((dim_c + 1) / 2);
-    hipLaunchKernelGGL(update_comm_dim_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       *params, B, N, dim_c, action_c, comm_state);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "comm launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&update_comm_dim_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "comm launch failed: %s",
+                                           *params, B, N, dim_c, action_c, comm_state);
 }
 
 int fg_step_scenario(const FgParams* params, const FgScenario* scenario, int B, int N, int do_physics,
@@ -1304,8 +1653,9 @@ int fg_step_scenario(const FgParams* params, const FgScenario* scenario, int B, 
                      const float* act, float* landmarks, float* obst_pos, float* obst_vel,
                      int32_t* step, float* obs, float* reward, float* indiv_reward, uint8_t* done,
                      void* stream) {
-    return launch_scenario(params, scenario, B, N, do_physics, pos_x, pos_y, vel_x, vel_y, act, landmarks,
-                           obst_pos, obst_vel, step, obs, reward, indiv_reward, done, nullptr, stream);
+    return launch_scenario(params, scenario, B, N, do_physics, 1, 1,
+                           scn_buffers(pos_x, pos_y, vel_x, vel_y, act, landmarks, obst_pos, obst_vel, step, obs, reward,
+                                       indiv_reward, done, nullptr), stream);
 }
 
 int fg_step_basic(const FgParams* params, int B, int N, int L, int do_physics,
@@ -1315,8 +1665,9 @@ int fg_step_basic(const FgParams* params, int B, int N, int L, int do_physics,
                   int32_t* near_ag, void* stream) {
     FgScenario sc; memset(&sc, 0, sizeof(sc));
     sc.kind = FG_SCN_BASIC; sc.num_landmarks = L; sc.penalty = 1.0f;
-    return launch_scenario(params, &sc, B, N, do_physics, pos_x, pos_y, vel_x, vel_y, act, landmarks,
-                           nullptr, nullptr, step, obs, reward, indiv_reward, done, near_ag, stream);
+    return launch_scenario(params, &sc, B, N, do_physics, 1, 1,
+                           scn_buffers(pos_x, pos_y, vel_x, vel_y, act, landmarks, nullptr, nullptr, step, obs, reward,
+                                       indiv_reward, done, near_ag), stream);
 }
 
 int fg_rollout_scenario(const FgParams* params, const FgScenario* scenario, int B, int N, int K,
@@ -1324,52 +1675,9 @@ int fg_rollout_scenario(const FgParams* params, const FgScenario* scenario, int 
                         const float* act_seq, float* landmarks, float* obst_pos, float* obst_vel,
                         int32_t* step, float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
                         int32_t* near_ag_seq, int obs_every, void* stream) {
-    return launch_scenario(params, scenario, B, N, 1, pos_x, pos_y, vel_x, vel_y, act_seq, landmarks,
-                           obst_pos, obst_vel, step, obs_seq, reward_seq, indiv_seq, done_seq, near_ag_seq, stream,
-                           K, obs_every < 1 ? 1 : obs_every);
-}
-
-int fg_reset_scenario(const FgParams* params, const FgScenario* scenario, int B, int N, const uint8_t* mask,
-                      float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                      float* landmarks, float* obst_pos, float* obst_vel, int32_t* step, void* stream) {
-    const DeviceGuard device_guard(stream, pos_x);
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (!scenario) return fail(FG_ERR_BAD_ARG, "scenario descriptor is NULL%s");
-    const int L = scenario->num_landmarks, M = scenario->num_obstacles;
-    if (scenario->kind < FG_SCN_BASIC || scenario->kind > FG_SCN_OBSTACLE) return fail(FG_ERR_BAD_ARG, "unknown scenario kind%s");
-    if (B == 0) return FG_OK;
-    if (B < 0 || L <= 0 || M < 0) return fail(FG_ERR_BAD_ARG, "B >= 0, L > 0, M >= 0 required%s");
-    if (N < 2 || N + M > FG_MAX_AGENTS || L > 1024)
-        return fail(FG_ERR_UNSUPPORTED_N, "scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !landmarks || (M > 0 && (!obst_pos || !obst_vel)))
-        return fail(FG_ERR_BAD_ARG, "fg_reset_scenario: a required pointer is NULL%s");
-    if (((uintptr_t)landmarks & 7u) || ((uintptr_t)obst_pos & 7u) || ((uintptr_t)obst_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "landmarks / obstacle buffers must be 8-byte aligned%s");
-    const long long count = (long long)B * (N + L + M);
-    hipLaunchKernelGGL(scn_reset_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       *params, *scenario, B, N, mask, pos_x, pos_y, vel_x, vel_y, reinterpret_cast<float2*>(landmarks),
-                       reinterpret_cast<float2*>(obst_pos), reinterpret_cast<float2*>(obst_vel), step);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "scenario reset launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
-}
-
-// the controller from the simulator state: one launch, shared by fg_policy_bfs_state and the chained closed loop
-static int launch_policy_state(int B, int N, const FgPolicyLevels& pl, const float* px, const float* py,
-                               const float* shape, const float* ivel, float* act, hipStream_t st) {
-    const int lpe = N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : 256;      // lanes per env
-    const int E = 256 / lpe;
-    const int grid = (B + E - 1) / E;
-    const int lds = E * policy_block_units(N) * (int)sizeof(float2);        // <= 56 KiB
-    if (describe("policy_state_kernel<%d> grid %d lds %d; ", pl.per, grid, lds)) return FG_OK;
-#define FG_POLICY(PER) case PER: hipLaunchKernelGGL((policy_state_kernel<PER>), dim3(grid), dim3(256), lds, st, B, N, lpe, pl, \
-                                                   px, py, shape, ivel, act); break;
-    switch (pl.per) { FG_POLICY(2) FG_POLICY(3) FG_POLICY(4) FG_POLICY(5) FG_POLICY(6) FG_POLICY(7) FG_POLICY(8) }
-#undef FG_POLICY
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "policy launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch_scenario(params, scenario, B, N, 1, K, obs_every < 1 ? 1 : obs_every,
+                           scn_buffers(pos_x, pos_y, vel_x, vel_y, act_seq, landmarks, obst_pos, obst_vel, step, obs_seq,
+                                       reward_seq, indiv_seq, done_seq, near_ag_seq), stream);
 }
 
 int fg_policy_bfs_state(int B, int N, int per_layer, const float* pos_x, const float* pos_y,
@@ -1377,70 +1685,33 @@ int fg_policy_bfs_state(int B, int N, int per_layer, const float* pos_x, const f
     const DeviceGuard device_guard(stream, pos_x);
     if (B == 0) return FG_OK;
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
+    int rc = hd_n_check(N);
+    if (rc) return rc;
     FgPolicyLevels pl;
-    if (!policy_levels_for(N, per_layer, &pl))
-        return fail(FG_ERR_UNSUPPORTED_N, "fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8%s");
-    if (!pos_x || !pos_y || !ideal_shape || !ideal_vel || !act)
-        return fail(FG_ERR_BAD_ARG, "fg_policy_bfs_state: a required pointer is NULL%s");
+    if ((rc = policy_levels_check("fg_policy_bfs_state", N, per_layer, &pl))) return rc;
+    if (!pos_x || !pos_y || !ideal_shape || !ideal_vel || !act) return null_pointer("fg_policy_bfs_state");
     if (((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u) || ((uintptr_t)act & 7u))
         return fail(FG_ERR_ALIGNMENT, "ideal_shape, ideal_vel and act must be 8-byte aligned%s");
     return launch_policy_state(B, N, pl, pos_x, pos_y, ideal_shape, ideal_vel, act, (hipStream_t)stream);
-}
-
-int fg_rollout_hd_policy(const FgParams* params, int B, int N, int K, int per_layer,
-                         float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                         float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
-                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
-                         int obs_every, void* stream) {
-    const DeviceGuard device_guard(stream, pos_x);
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (B == 0 || K == 0) return FG_OK;
-    if (B < 0 || K < 0) return fail(FG_ERR_BAD_ARG, "B and K must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
-    FgPolicyLevels pl;
-    if (!policy_levels_for(N, per_layer, &pl))
-        return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8%s");
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_policy: a required pointer is NULL%s");
-    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    a.do_phys = 1; a.do_post = 1;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
-    a.pl = pl; a.act_out = act_seq;
-    return rollout_hd_policy_dispatch(a, per_layer, (hipStream_t)stream);
 }
 
 int fg_policy_bfs(int B, int N, int per_layer, const float* obs, int64_t obs_env_stride, float* act, void* stream) {
     const DeviceGuard device_guard(stream, act);    // the actions (obs may live in an fg_arena, whose pointers carry no device attribute on every runtime)
     if (B == 0) return FG_OK;
     if (B < 0) return fail(FG_ERR_BAD_ARG, "B must be >= 0%s");
-    if (N < 3 || N > FG_MAX_AGENTS) return fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
+    int rc = hd_n_check(N);
+    if (rc) return rc;
     FgPolicyLevels pl;
-    if (!policy_levels_for(N, per_layer, &pl))
-        return fail(FG_ERR_UNSUPPORTED_N, "fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8%s");
-    if (!obs || !act) return fail(FG_ERR_BAD_ARG, "fg_policy_bfs: a required pointer is NULL%s");
+    if ((rc = policy_levels_check("fg_policy_bfs", N, per_layer, &pl))) return rc;
+    if (!obs || !act) return null_pointer("fg_policy_bfs");
     const int64_t stride = obs_env_stride ? obs_env_stride : 6LL * N * N;
     if (stride < 6LL * N || (stride & 1)) return fail(FG_ERR_BAD_ARG, "fg_policy_bfs: obs_env_stride must be even and >= 6 N%s");
     if (((uintptr_t)obs & 7u) || ((uintptr_t)act & 7u)) return fail(FG_ERR_ALIGNMENT, "obs and act must be 8-byte aligned%s");
-    const int lpe = N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : 256;      // lanes per env
-    const int E = 256 / lpe;
-    const int grid = (B + E - 1) / E;
-    const int lds = E * policy_block_units(N) * (int)sizeof(float2);        // <= 56 KiB
-    hipStream_t st = (hipStream_t)stream;
-#define FG_POLICY(PER) case PER: hipLaunchKernelGGL((policy_bfs_kernel<PER>), dim3(grid), dim3(256), lds, st, B, N, lpe, pl, \
-                                                   obs, (long long)stride, act); break;
-    switch (per_layer) { FG_POLICY(2) FG_POLICY(3) FG_POLICY(4) FG_POLICY(5) FG_POLICY(6) FG_POLICY(7) FG_POLICY(8) }
-#undef FG_POLICY
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "policy launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    const PolicyGeometry g = policy_geometry(B, N);
+    return policy_per_dispatch(per_layer, [&](auto per) {
+        return launch<&policy_bfs_kernel<decltype(per)::value>>(g.grid, 256, g.lds, (hipStream_t)stream, "policy launch failed: %s", B, N,
+                                                                g.lpe, pl, obs, (long long)stride, act);
+    });
 }
 
 int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void* stream) {
@@ -1449,241 +1720,14 @@ int fg_decode_actions(int mode, int64_t count, void* action, float* u_out, void*
         return fail(FG_ERR_BAD_ARG, "fg_decode_actions: unknown mode%s");
     if (count == 0) return FG_OK;
     if (count < 0 || count > ((int64_t)1 << 38)) return fail(FG_ERR_BAD_ARG, "fg_decode_actions: count out of range%s");
-    if (!action || !u_out) return fail(FG_ERR_BAD_ARG, "fg_decode_actions: a required pointer is NULL%s");
+    if (!action || !u_out) return null_pointer("fg_decode_actions");
     if (((uintptr_t)u_out & 7) || (mode == FG_ACT_ARGMAX && ((uintptr_t)action & 7)))
         return fail(FG_ERR_ALIGNMENT, "fg_decode_actions: buffers must be 8-byte aligned%s");
-    const unsigned grid = (unsigned)((count + 255) / 256);
-    hipLaunchKernelGGL(decode_actions_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, mode, count, action,
-                       reinterpret_cast<float2*>(u_out));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "decode launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&decode_actions_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "decode launch failed: %s",
+                                          mode, count, action, reinterpret_cast<float2*>(u_out));
 }
 
-}  // extern "C"
-
-// ---- closed loop with the caller's MLP actor (fg_actor_rollout_kernel.hpp) ----
-static bool actor_n_supported(int N) {
-    return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
-}
-static ActorW actor_w(const FgActor& actor) {
-    return {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
-}
-// Describe-or-launch of an actor kernel: Det (the deterministic actor; log_std == NULL) or its sampling twin Smp (the Gaussian
-// actor), which takes (log_std, logp) after Det's arguments `args`.  `targs` spells the template arguments and `unit` the word
-// before the thread count in the describe string; `lds` is the chosen kernel's.  One LDS-limit mask per kernel.
-template <auto Det, auto Smp, class... A>
-static int launch_actor_pair(const char* det_name, const char* smp_name, const char* targs, const char* unit, int grid,
-                             int threads, int envs, int lds, const char* fail_fmt, hipStream_t st, const float* log_std,
-                             float* logp, const A&... args) {
-    const bool sample = log_std != nullptr;
-    if (describe("%s<%s> grid %d %s %d envs/wg %d lds %d; ", sample ? smp_name : det_name, targs, grid, unit, threads, envs, lds))
-        return FG_OK;
-    static std::atomic<unsigned long long> raised{0}, raised_sample{0};
-    hipError_t err = sample ? raise_lds_limit((const void*)Smp, lds, &raised_sample) : raise_lds_limit((const void*)Det, lds, &raised);
-    if (err == hipSuccess) {
-        if (sample)
-            hipLaunchKernelGGL(Smp, dim3(grid), dim3(threads), lds, st, args..., log_std, logp);
-        else
-            hipLaunchKernelGGL(Det, dim3(grid), dim3(threads), lds, st, args...);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) return fail(FG_ERR_HIP, fail_fmt, hipGetErrorString(err));
-    return FG_OK;
-}
-// The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
-// per agent (pa_*_kernel) and the shared actor with LayerNorms (ln_*_kernel).  `w`: the kernel's arguments after `a` - an
-// ActorW, an ActorTab, or an ActorW and an ActorNormW.
-template <int NC, int H, bool PER_AGENT, bool LNORM, class... W>
-static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
-    static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
-    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() <= 160 * 1024, "actor rollout LDS");
-    constexpr int E = actor_envs(NC), V = LNORM ? 2 : PER_AGENT ? 1 : 0;
-    constexpr auto det = [] {
-        if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
-        else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
-        else return &actor_rollout_kernel<NC, H>;
-    }();
-    constexpr auto smp = [] {
-        if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
-        else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
-        else return &actor_sample_kernel<NC, H>;
-    }();
-    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel"};
-    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel"};
-    static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
-                                           "LayerNorm actor rollout launch failed: %s"};
-    char targs[16];
-    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    return launch_actor_pair<det, smp>(
-        det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM>(),
-        fail_fmt[V], st, log_std, logp, a, w...);
-}
-// The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
-// the messages name, `max_hidden` / `widths` its admissible hidden widths (32, 64 and up to max_hidden), `also` further
-// pointers that share the weights' 4-byte alignment check and `aligned` what the alignment message calls them all.
-static int actor_struct_check(const FgActor* actor, const char* who, int max_hidden, const char* widths, uintptr_t also,
-                              const char* aligned) {
-    char msg[160];
-    auto bad = [&](int code, const char* what, const char* arg = "") {
-        snprintf(msg, sizeof(msg), what, who, arg);
-        return fail(code, "%s", msg);
-    };
-    if (!actor) return bad(FG_ERR_BAD_ARG, "%s: actor is NULL");
-    if (actor->hidden != 32 && actor->hidden != 64 && !(actor->hidden == 128 && max_hidden == 128))
-        return bad(FG_ERR_BAD_ARG, "%s: hidden must be %s", widths);
-    if (!actor->w1 || !actor->w2 || !actor->w3) return bad(FG_ERR_BAD_ARG, "%s: a weight pointer is NULL");
-    if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
-         (uintptr_t)actor->b3 | also) & 3u)
-        return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", aligned);
-    return FG_OK;
-}
-static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
-    const int rc = actor_struct_check(actor, "fg_rollout_hd_actor", 128, "32, 64 or 128", 0, "weights");
-    if (rc) return rc;
-    if (world_options_set(*params))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: World options, per-agent properties and communication are not supported%s");
-    return FG_OK;
-}
-
-// One call of a formation_hd_env actor entry, fg_rollout_hd_actor* or its fg_describe_actor*_launch twin, as its checks
-// (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
-// host array of N members; `norm` counts for HD_ACTOR_NORM only; `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE
-// requires it); `logp`: the log-densities' destination, NULL from a describe twin.
-enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM };
-static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
-                                             "fg_rollout_hd_actor_norm"};
-struct HdActorCall {
-    HdActorKind kind;
-    const FgActor* actor;
-    const FgActorNorm* norm;
-    const float* log_std;
-    float* logp;
-};
-// FgActorNorm's checks (no device touched): hidden 32 or 64, every eps that is read positive and finite, gamma / beta 4-byte aligned
-static int actor_norm_check(const FgActor* actor, const FgActorNorm* norm) {
-    if (!norm) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: norm is NULL%s");
-    if (actor->hidden != 32 && actor->hidden != 64)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms%s");
-    auto eps_ok = [](float e) { return e > 0.0f && std::isfinite(e); };
-    if (norm->in_norm && !eps_ok(norm->in_eps))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: in_eps must be positive and finite%s");
-    if (!eps_ok(norm->h1_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite%s");
-    if (!eps_ok(norm->h2_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h2_eps must be positive and finite%s");
-    const struct { const float* p; const char* name; } ptrs[] = {
-        {norm->in_gamma, "in_gamma"}, {norm->in_beta, "in_beta"}, {norm->h1_gamma, "h1_gamma"},
-        {norm->h1_beta, "h1_beta"},   {norm->h2_gamma, "h2_gamma"}, {norm->h2_beta, "h2_beta"}};
-    for (const auto& q : ptrs)
-        if ((uintptr_t)q.p & 3u) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: %s must be 4-byte aligned", q.name);
-    return FG_OK;
-}
-// The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
-// this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
-// the norms, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
-// log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
-static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
-    const char* const who = hd_actor_entry[c.kind];
-    const char* const shared = hd_actor_entry[c.kind == HD_ACTOR_PER_AGENT ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 1 required", shared);
-    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", shared);
-    if (c.kind == HD_ACTOR_PER_AGENT) {
-        if (!c.actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
-        char idx[16];
-        for (int i = 0; i < N; ++i) {
-            if ((rc = hd_actor_struct_check(params, &c.actor[i])) != FG_OK) return rc;
-            if (c.actor[i].hidden != c.actor[0].hidden || (c.actor[i].out_tanh != 0) != (c.actor[0].out_tanh != 0)) {
-                snprintf(idx, sizeof(idx), "%d", i);
-                return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: member %s differs from member 0 in hidden or out_tanh",
-                            idx);
-            }
-        }
-    } else if ((rc = hd_actor_struct_check(params, c.actor)) != FG_OK) {
-        return rc;
-    }
-    if (c.kind == HD_ACTOR_NORM && (rc = actor_norm_check(c.actor, c.norm)) != FG_OK) return rc;
-    if (!c.log_std) {
-        if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
-        c.logp = nullptr;
-        return FG_OK;
-    }
-    if ((uintptr_t)c.log_std & 3u) return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_actor_sample: log_std must be 4-byte aligned%s");
-    if ((uintptr_t)c.logp & 3u) return fail(FG_ERR_ALIGNMENT, "%s: logp_seq must be 4-byte aligned", who);
-    return FG_OK;
-}
-// The one N x H grid of the formation_hd_env actor kernels: launch(n, h) with N and H as the `value` of the arguments' types,
-// or UNSUPPORTED_N in `who`'s name when N is not in the list.  MAXH is the widest H of the caller's kernels: `hidden` is 32,
-// 64 or - MAXH == 128 only - 128 (actor_struct_check, actor_norm_check), and no launch(n, 128) is instantiated below that.
-template <int V> using IntC = std::integral_constant<int, V>;
-template <int MAXH, class F>
-static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
-#define FG_ACTOR(NN)                                                                      \
-    if (N == NN) {                                                                        \
-        if (hidden == 32) return launch(IntC<NN>{}, IntC<32>{});                          \
-        if constexpr (MAXH == 128) if (hidden != 64) return launch(IntC<NN>{}, IntC<128>{}); \
-        return launch(IntC<NN>{}, IntC<64>{});                                            \
-    }
-    FG_ACTOR(3) FG_ACTOR(4) FG_ACTOR(8) FG_ACTOR(9) FG_ACTOR(16) FG_ACTOR(25) FG_ACTOR(27) FG_ACTOR(32)
-#undef FG_ACTOR
-    return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
-}
-// a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
-static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
-    const char* const who = hd_actor_entry[c.kind == HD_ACTOR_SAMPLE ? HD_ACTOR_SHARED : c.kind];
-    if (c.kind == HD_ACTOR_PER_AGENT) {
-        ActorTab tab;
-        memset(&tab, 0, sizeof(tab));
-        for (int i = 0; i < a.N; ++i) {
-            tab.w1[i] = c.actor[i].w1; tab.b1[i] = c.actor[i].b1; tab.w2[i] = c.actor[i].w2;
-            tab.b2[i] = c.actor[i].b2; tab.w3[i] = c.actor[i].w3; tab.b3[i] = c.actor[i].b3;
-        }
-        tab.out_tanh = c.actor[0].out_tanh ? 1 : 0;
-        return actor_nh_dispatch<128>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false>(a, c.log_std, c.logp, st, tab);
-        });
-    }
-    const ActorW w = actor_w(*c.actor);
-    if (c.kind != HD_ACTOR_NORM)
-        return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
-        });
-    const FgActorNorm& norm = *c.norm;
-    const bool in_norm = norm.in_norm != 0;
-    const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
-                           norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
-    return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-        return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true>(a, c.log_std, c.logp, st, w, nw);
-    });
-}
-
-// the buffers' checks and the launch of a call that has passed hd_actor_check
-static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int B, int N, int K,
-                              float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
-                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
-                              int obs_every, void* stream) {
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !act_seq || !ideal_shape || !ideal_vel || !step || !reward_seq)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor: a required pointer is NULL%s");
-    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)ideal_shape & 7u) || ((uintptr_t)ideal_vel & 7u))
-        return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
-    if (B == 0) return FG_OK;
-    const DeviceGuard device_guard(stream, pos_x);
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    int rc = set_obs_pitch(&a);
-    if (rc != FG_OK) return rc;
-    a.do_phys = 1; a.do_post = 1;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y;
-    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.obs = obs_seq; a.rew = reward_seq; a.indiv = indiv_seq; a.done = done_seq;
-    a.act_out = act_seq;
-    return hd_actor_dispatch(a, c, (hipStream_t)stream);
-}
-
-extern "C" {
-
+// ---- closed loop with the caller's MLP actor ----
 int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int N, int K,
                         float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                         float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
@@ -1737,11 +1781,8 @@ int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* strea
     if (B == 0) return FG_OK;
     const DeviceGuard device_guard(stream, eps);
     const long long count = (long long)B * N;
-    hipLaunchKernelGGL(actor_noise_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       *params, B, N, reinterpret_cast<float2*>(eps));
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor noise launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&actor_noise_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "actor noise launch failed: %s",
+                                       *params, B, N, reinterpret_cast<float2*>(eps));
 }
 
 int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, float* logp, void* stream) {
@@ -1751,31 +1792,9 @@ int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, flo
     if (((uintptr_t)eps & 7u) || (((uintptr_t)log_std | (uintptr_t)logp) & 3u))
         return fail(FG_ERR_ALIGNMENT, "fg_actor_log_prob: eps must be 8-byte, log_std and logp 4-byte aligned%s");
     const DeviceGuard device_guard(stream, eps);
-    hipLaunchKernelGGL(actor_logp_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (long long)count, reinterpret_cast<const float2*>(eps), log_std, logp);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(FG_ERR_HIP, "actor log-prob launch failed: %s", hipGetErrorString(err));
-    return FG_OK;
+    return launch<&actor_logp_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "actor log-prob launch failed: %s",
+                                      (long long)count, reinterpret_cast<const float2*>(eps), log_std, logp);
 }
-
-}  // extern "C"
-
-// the describe twin `who` of the call `c`: the out buffer's check, the call's own checks, then the dry run of its dispatch
-static int describe_actor_impl(const char* who, const FgParams* params, HdActorCall c, int B, int N, int K, int obs_every,
-                               char* out, int out_len) {
-    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "%s: out buffer required", who);
-    out[0] = 0;
-    int rc = hd_actor_check(params, c, B, N, K);
-    if (rc) return rc;
-    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_actor_launch: B > 0 required%s");
-    Args a; memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-    if ((rc = set_obs_pitch(&a)) != FG_OK) return rc;
-    const DescribeScope describing(out, out_len);
-    return hd_actor_dispatch(a, c, nullptr);
-}
-
-extern "C" {
 
 int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
                              char* out, int out_len) {
@@ -1801,69 +1820,6 @@ int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* ac
                                {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, nullptr}, B, N, K, obs_every, out, out_len);
 }
 
-}  // extern "C"
-
-// ---- closed loop with the caller's MLP actor in the landmark scenarios (fg_scn_lane_actor_kernel.hpp) ----
-// log_std == NULL: scn_lane_actor (the deterministic actor); else scn_lane_actor_gauss (the Gaussian actor)
-template <int KIND, int NN, int LL, int MM, int NBR, int H>
-static int launch_scn_actor(const ScnArgs& a, const ActorW& w, float* act_out, const float* log_std, float* logp, hipStream_t st) {
-    static_assert(scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, true) <= 160 * 1024, "scenario actor rollout LDS");
-    char targs[48];
-    snprintf(targs, sizeof(targs), "%d,%d,%d,%d,%d,%d", KIND, NN, LL, MM, NBR, H);
-    return launch_actor_pair<&scn_lane_actor<KIND, NN, LL, MM, NBR, H>, &scn_lane_actor_gauss<KIND, NN, LL, MM, NBR, H>>(
-        "scn_lane_actor", "scn_lane_actor_gauss", targs, "threads", 8 * (((a.B + FG_SCN_ACTOR_ENVS - 1) / FG_SCN_ACTOR_ENVS + 7) / 8),
-        FG_SCN_ACTOR_THREADS, FG_SCN_ACTOR_ENVS, scn_actor_lds_bytes(KIND, NN, LL, MM, NBR, H, log_std != nullptr),
-        "scenario actor rollout launch failed: %s", st, log_std, logp, a, w, act_out);
-}
-
-// the checks both scenario-actor entries share (no device touched): FG_OK, or the status of the first one that fails
-static int scn_actor_check(const FgParams* params, const FgScenario* sc, const FgActor* actor, const float* log_std,
-                           const float* logp, int B, int N, int K) {
-    int rc = check_params(params);
-    if (rc) return rc;
-    if (!sc) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: scenario descriptor is NULL%s");
-    if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: B >= 0 and K >= 1 required%s");
-    if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: unknown scenario kind%s");
-    if ((rc = actor_struct_check(actor, "fg_rollout_scenario_actor", 64, "32 or 64", (uintptr_t)log_std | (uintptr_t)logp,
-                                 "weights, log_std and logp")) != FG_OK)
-        return rc;
-    if (!log_std && logp) return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: logp without log_std%s");
-    if (params->agent_props || params->comm_state || sc->variant == 1)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported%s");
-    return FG_OK;
-}
-
-static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act_out, const float* log_std, float* logp,
-                              hipStream_t st) {
-    const ActorW w = actor_w(actor);
-    const int L = a.sc.num_landmarks, M = a.sc.num_obstacles;
-    const int nbr = a.sc.kind == FG_SCN_PARTIAL ? a.sc.num_obs : a.N - 1;
-    // the shapes of launch_scenario's FG_SCN_LANE list
-#define FG_SCN_ACTOR(KIND, NN, LL, MM, NBR)                                                                  \
-    if (a.sc.kind == KIND && a.N == NN && L == LL && M == MM && nbr == NBR)                                  \
-        return actor.hidden == 32 ? launch_scn_actor<KIND, NN, LL, MM, NBR, 32>(a, w, act_out, log_std, logp, st) \
-                                  : launch_scn_actor<KIND, NN, LL, MM, NBR, 64>(a, w, act_out, log_std, logp, st);
-    FG_SCN_ACTOR(FG_SCN_BASIC, 3, 3, 0, 2)
-    FG_SCN_ACTOR(FG_SCN_PARTIAL, 5, 5, 0, 3)
-    FG_SCN_ACTOR(FG_SCN_RANGE, 4, 4, 0, 3)
-    FG_SCN_ACTOR(FG_SCN_OBSTACLE, 4, 4, 3, 3)
-    FG_SCN_ACTOR(FG_SCN_PARTIAL, 3, 5, 0, 3)
-    FG_SCN_ACTOR(FG_SCN_RANGE, 3, 4, 0, 2)
-    FG_SCN_ACTOR(FG_SCN_OBSTACLE, 3, 4, 3, 2)
-#undef FG_SCN_ACTOR
-    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes%s");
-}
-
-static void scn_actor_args(ScnArgs* a, const FgParams* params, const FgScenario* sc, int B, int N, int K, int obs_every) {
-    memset(a, 0, sizeof(*a));
-    a->p = *params; a->sc = *sc; a->B = B; a->N = N; a->do_phys = 1; a->K = K; a->obs_every = obs_every < 1 ? 1 : obs_every;
-    a->inv_n = (float)(1.0 / (double)N); a->inv_l = (float)(1.0 / (double)(sc->num_landmarks > 0 ? sc->num_landmarks : 1));
-    a->coll_scale = (float)((double)params->collide_thresh / (double)params->dist_min);
-}
-
-extern "C" {
-
 int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario, const FgActor* actor, const float* log_std,
                               int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                               float* landmarks, float* obst_pos, float* obst_vel, int32_t* step,
@@ -1871,14 +1827,14 @@ int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario
                               int obs_every, void* stream) {
     int rc = scn_actor_check(params, scenario, actor, log_std, logp, B, N, K);
     if (rc) return rc;
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !landmarks || !step || !reward || !act_out ||
-        (scenario->num_obstacles > 0 && (!obst_pos || !obst_vel)))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_scenario_actor: a required pointer is NULL%s");
+    if (scn_world_null(scenario, pos_x, pos_y, vel_x, vel_y, landmarks, obst_pos, obst_vel) || !step || !reward || !act_out)
+        return null_pointer("fg_rollout_scenario_actor");
     if (((uintptr_t)obs & 7u) || ((uintptr_t)landmarks & 7u) || ((uintptr_t)act_out & 7u) || ((uintptr_t)obst_pos & 7u) ||
         ((uintptr_t)obst_vel & 7u))
         return fail(FG_ERR_ALIGNMENT, "fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned%s");
-    ScnArgs a;
-    scn_actor_args(&a, params, scenario, B, N, K, obs_every);
+    ScnArgs a = scn_buffers(pos_x, pos_y, vel_x, vel_y, nullptr, landmarks, obst_pos, obst_vel, step, obs, reward, indiv_reward,
+                            done, nullptr);
+    scn_args(&a, params, scenario, B, N, 1, K, obs_every);
     if (B == 0) {                                      // nothing to launch; an unsupported shape is still reported
         char dry[8];
         dry[0] = 0; a.B = 1;
@@ -1886,8 +1842,6 @@ int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario
         return scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
     }
     const DeviceGuard device_guard(stream, pos_x);
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.lm = landmarks; a.opos = obst_pos; a.ovel = obst_vel; a.step = step;
-    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
     return scn_actor_dispatch(a, *actor, act_out, log_std, logp, (hipStream_t)stream);
 }
 
@@ -1898,12 +1852,15 @@ int fg_describe_scenario_actor_launch(const FgParams* params, const FgScenario* 
     int rc = scn_actor_check(params, scenario, actor, log_std, nullptr, B, N, K);
     if (rc) return rc;
     if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_scenario_actor_launch: B > 0 required%s");
-    ScnArgs a;
-    scn_actor_args(&a, params, scenario, B, N, K, obs_every);
+    ScnArgs a; memset(&a, 0, sizeof(a));
+    scn_args(&a, params, scenario, B, N, 1, K, obs_every);
     const DescribeScope describing(out, out_len);
     return scn_actor_dispatch(a, *actor, nullptr, log_std, nullptr, nullptr);
 }
 
+// The dry run of fg_step_hd (K = 0), fg_rollout_hd (K steps), fg_rollout_hd_policy (per_layer > 0) or, with a scenario,
+// fg_rollout_scenario: the entry's checks before its buffers, then its dispatch.  Nothing is dereferenced on the way; only the
+// NULL-ness of the observation and index outputs steers the formation_hd_env dispatch, hence the stand-ins.
 int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B, int N, int K, int per_layer, int obs_every,
                        int index_outputs, char* out, int out_len) {
     if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_launch: out buffer required%s");
@@ -1911,37 +1868,27 @@ int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B
     if (rc) return rc;
     if (B <= 0 || K < 0) return fail(FG_ERR_BAD_ARG, "fg_describe_launch: B > 0 and K >= 0 required%s");
     out[0] = 0;
-    // stand-ins for the caller's buffers: only their NULL-ness and alignment steer the dispatch, nothing is dereferenced
-    float* const f = reinterpret_cast<float*>((uintptr_t)4096);
-    int32_t* const i32 = reinterpret_cast<int32_t*>((uintptr_t)4096);
-    uint8_t* const u8 = reinterpret_cast<uint8_t*>((uintptr_t)4096);
     const DescribeScope describing(out, out_len);
     if (scenario) {
-        rc = launch_scenario(params, scenario, B, N, 1, f, f, f, f, f, f, scenario->num_obstacles ? f : nullptr,
-                             scenario->num_obstacles ? f : nullptr, i32, f, f, f, u8, nullptr, nullptr, K < 1 ? 1 : K,
-                             obs_every < 1 ? 1 : obs_every);
-    } else if (N < 3 || N > FG_MAX_AGENTS) {
-        rc = fail(FG_ERR_UNSUPPORTED_N, "formation_hd_env needs 3 <= N <= 1024%s");
-    } else {
-        Args a; memset(&a, 0, sizeof(a));
-        a.p = *params; a.B = B; a.N = N; a.inv_n = 1.0f / (float)N; a.K = K < 1 ? 1 : K; a.obs_every = obs_every < 1 ? 1 : obs_every;
-        a.do_phys = 1; a.do_post = 1;
-        a.px = f; a.py = f; a.vx = f; a.vy = f; a.act = f; a.shape = f; a.ivel = f; a.step = i32;
-        a.obs = f; a.rew = f; a.indiv = f; a.done = u8;
-        if (index_outputs) { a.near_lm = i32; a.near_ag = i32; a.hd_idx = i32; }
-        rc = set_obs_pitch(&a);
-        if (rc == FG_OK) {
-            if (per_layer > 0) {
-                if (!policy_levels_for(N, per_layer, &a.pl)) rc = fail(FG_ERR_UNSUPPORTED_N, "N must be per_layer^L with 2 <= per_layer <= 8%s");
-                else { a.act_out = f; rc = rollout_hd_policy_dispatch(a, per_layer, nullptr); }
-            } else if (K == 0) {
-                rc = step_hd_dispatch(a, nullptr);                      // fg_step_hd
-            } else {
-                rc = rollout_hd_dispatch(a, nullptr);                   // fg_rollout_hd with K steps
-            }
-        }
+        if ((rc = scenario_check(params, scenario, B, N, 1, K < 1 ? 1 : K, obs_every < 1 ? 1 : obs_every))) return rc;
+        ScnArgs a; memset(&a, 0, sizeof(a));
+        scn_args(&a, params, scenario, B, N, 1, K < 1 ? 1 : K, obs_every);
+        return scenario_dispatch(a, nullptr);
     }
-    return rc;
+    if ((rc = hd_n_check(N))) return rc;
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K < 1 ? 1 : K, obs_every, 1, 1))) return rc;
+    float* const f = reinterpret_cast<float*>((uintptr_t)4096);
+    int32_t* const i32 = reinterpret_cast<int32_t*>((uintptr_t)4096);
+    hd_buffers(&a, f, f, f, f, f, f, i32, f, f, f, reinterpret_cast<uint8_t*>((uintptr_t)4096));
+    a.act = f;
+    if (index_outputs) { a.near_lm = i32; a.near_ag = i32; a.hd_idx = i32; }
+    if (per_layer > 0) {
+        if (!policy_levels_for(N, per_layer, &a.pl)) return fail(FG_ERR_UNSUPPORTED_N, "N must be per_layer^L with 2 <= per_layer <= 8%s");
+        a.act_out = f;
+        return rollout_hd_policy_dispatch(a, per_layer, nullptr);
+    }
+    return K == 0 ? step_hd_dispatch(a, nullptr) : rollout_hd_dispatch(a, nullptr);   // fg_step_hd : fg_rollout_hd with K steps
 }
 
 }  // extern "C"

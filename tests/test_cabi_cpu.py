@@ -166,6 +166,595 @@ def test_argument_validation_before_any_launch(lib):
         _native.check(lib.fg_step_hd(P, -1, 9, *ok_ptrs))
 
 
+# ---- every non-actor entry point that checks arguments: status and fg_last_error() of each failing check, and their order ----
+# An entry's arguments in C order.  A bare name is a stand-in pointer (address 4096: aligned for everything, never dereferenced
+# before a launch), NAME=V an integer or None, `params` / `scenario` / `actor` a struct built from keyword arguments (None: NULL),
+# `out` a 512-byte text buffer followed by its length, `plan` a void** to receive a plan.
+_STATE = "pos_x pos_y vel_x vel_y "
+_HD_OUT = "obs reward indiv done "
+_SCN_STATE = _STATE + "act landmarks obst_pos obst_vel step " + _HD_OUT
+CABI_ENTRIES = {
+    "fg_step_hd": "params B=4 N=9 " + _STATE + "act ideal_shape ideal_vel step " + _HD_OUT + "near_lm near_ag hd_idx stream=None",
+    "fg_step_hd_plan": "params B=4 N=9 " + _STATE + "act ideal_shape ideal_vel step " + _HD_OUT
+                       + "near_lm near_ag hd_idx stream=None plan",
+    "fg_physics_step": "params B=4 N=9 " + _STATE + "act stream=None",
+    "fg_observe_hd": "params B=4 N=9 " + _STATE + "ideal_shape ideal_vel step " + _HD_OUT + "near_lm near_ag hd_idx stream=None",
+    "fg_rollout_hd": "params B=4 N=9 K=5 " + _STATE + "act ideal_shape ideal_vel step " + _HD_OUT + "obs_every=1 stream=None",
+    "fg_rollout_hd_policy": "params B=4 N=9 K=5 per=3 " + _STATE + "act ideal_shape ideal_vel step " + _HD_OUT
+                            + "obs_every=1 stream=None",
+    "fg_reset_hd": "params B=4 N=9 mask " + _STATE + "ideal_shape ideal_vel step stream=None",
+    "fg_reset_hd_mt": "B=4 N=9 mask mt_state " + _STATE + "ideal_shape ideal_vel landmark_pos step stream=None",
+    "fg_reset_hd_mt_done": "B=4 N=9 world_length=100 mt_state " + _STATE + "ideal_shape ideal_vel landmark_pos step obs "
+                           "obs_env_pitch=0 stream=None",
+    "fg_reset_scenario": "params scenario B=4 N=4 mask " + _STATE + "landmarks obst_pos obst_vel step stream=None",
+    "fg_reset_scenario_mt": "scenario B=4 N=4 mask world_length=100 mt_state " + _STATE + "landmarks obst_pos obst_vel step "
+                            "stream=None",
+    "fg_step_scenario": "params scenario B=4 N=4 do_physics=1 " + _SCN_STATE + "stream=None",
+    "fg_step_basic": "params B=4 N=3 L=3 do_physics=1 " + _STATE + "act landmarks step " + _HD_OUT + "near_ag stream=None",
+    "fg_rollout_scenario": "params scenario B=4 N=4 K=5 " + _SCN_STATE + "near_ag obs_every=1 stream=None",
+    "fg_update_comm": "params B=4 N=9 action_c comm_state stream=None",
+    "fg_update_comm_dim": "params B=4 N=9 dim_c=3 action_c comm_state stream=None",
+    "fg_policy_bfs": "B=4 N=9 per=3 obs obs_env_stride=0 act stream=None",
+    "fg_policy_bfs_state": "B=4 N=9 per=3 pos_x pos_y ideal_shape ideal_vel act stream=None",
+    "fg_decode_actions": "mode=%d count=12 action u_out stream=None" % _native.FG_ACT_ARGMAX,
+    "fg_actor_noise": "params B=4 N=9 eps stream=None",
+    "fg_kernel_config": "N=9 threads=None envs_per_wg=None lds_bytes=None",
+    "fg_describe_launch": "params scenario=None B=4 N=9 K=5 per=0 obs_every=1 index_outputs=0 out",
+    "fg_rollout_scenario_actor": "params scenario actor log_std B=4 N=4 K=5 " + _STATE + "landmarks obst_pos obst_vel step "
+                                 + _HD_OUT + "act_out logp obs_every=1 stream=None",
+    "fg_describe_scenario_actor_launch": "params scenario actor log_std B=4 N=4 K=5 obs_every=1 out",
+}
+_OBSTACLE = dict(kind=_native.FG_SCN_OBSTACLE, num_landmarks=4, num_obstacles=3, penalty=2.0)     # N = 4: a reference shape
+_ACTOR = dict(hidden=64, out_tanh=1, w1=4096, b1=4096, w2=4096, b2=4096, w3=4096, b3=4096)
+
+
+_STRUCTS = {"params": (_params, {}), "scenario": (_native.FgScenario, _OBSTACLE), "actor": (_native.FgActor, _ACTOR)}
+
+
+def _cabi_call(lib, entry, **wrong):
+    """(status, fg_last_error()) of `entry` with CABI_ENTRIES' arguments, `wrong` replacing some by name: a struct's value is
+    None or keyword arguments that update its defaults, `out=None` passes no text buffer."""
+    names = [tok.partition("=")[0] for tok in CABI_ENTRIES[entry].split()]
+    assert set(wrong) <= set(names), (entry, wrong)
+    args = []
+    for tok in CABI_ENTRIES[entry].split():
+        name, _, default = tok.partition("=")
+        value = wrong[name] if name in wrong else eval(default) if default else {} if name in _STRUCTS else 4096
+        if name in _STRUCTS and value is not None:
+            make, base = _STRUCTS[name]
+            value = make(**dict(base, **value))
+        elif name == "out":
+            args.append(ctypes.create_string_buffer(512) if value is not None else None)
+            value = 512
+        elif name == "plan" and value is not None:
+            value = ctypes.pointer(ctypes.c_void_p())
+        args.append(value)
+    rc = getattr(lib, entry)(*args)
+    return rc, lib.fg_last_error().decode()
+
+
+# (entry, what is wrong with the call, status, fg_last_error()); a text of None: the call succeeds without a launch (an empty
+# batch, zero steps).  The literals are the answers of the library before the entries shared one call builder and one launcher.
+CABI_BAD_CALLS = [
+    ('fg_step_hd', dict(params=None), -1, 'params is NULL'),
+    ('fg_step_hd_plan', dict(params=None), -1, 'params is NULL'),
+    ('fg_physics_step', dict(params=None), -1, 'params is NULL'),
+    ('fg_observe_hd', dict(params=None), -1, 'params is NULL'),
+    ('fg_rollout_hd', dict(params=None), -1, 'params is NULL'),
+    ('fg_rollout_hd_policy', dict(params=None), -1, 'params is NULL'),
+    ('fg_reset_hd', dict(params=None), -1, 'params is NULL'),
+    ('fg_reset_scenario', dict(params=None), -1, 'params is NULL'),
+    ('fg_step_scenario', dict(params=None), -1, 'params is NULL'),
+    ('fg_step_basic', dict(params=None), -1, 'params is NULL'),
+    ('fg_rollout_scenario', dict(params=None), -1, 'params is NULL'),
+    ('fg_update_comm', dict(params=None), -1, 'params is NULL'),
+    ('fg_update_comm_dim', dict(params=None), -1, 'params is NULL'),
+    ('fg_actor_noise', dict(params=None), -1, 'params is NULL'),
+    ('fg_describe_launch', dict(params=None), -1, 'params is NULL'),
+    ('fg_rollout_scenario_actor', dict(params=None), -1, 'params is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(params=None), -1, 'params is NULL'),
+    ('fg_step_hd', dict(params={'mass': 0.0}), -1, 'params: mass, contact_margin and dt must be > 0'),
+    ('fg_step_hd', dict(params={'num_walls': 5}), -1, 'params: 0 <= num_walls <= 4, accel/max_speed/u_noise >= 0'),
+    ('fg_step_hd', dict(params={'dist_min': 0.0}), -1, 'params: dist_min must be > 0'),
+    ('fg_step_hd', dict(params={'agent_props': 4098}), -3, 'params: agent_props must be 4-byte, comm_state 8-byte aligned'),
+    ('fg_step_hd', dict(params={'comm_state': 4100}), -3, 'params: agent_props must be 4-byte, comm_state 8-byte aligned'),
+    ('fg_step_hd', dict(params={'mass': 0.0, 'dist_min': 0.0, 'comm_state': 4100}), -1, 'params: mass, contact_margin and dt must be > 0'),
+    ('fg_step_hd', dict(params={'mass': 0.0}, B=-1, N=2, obs=None, act=4100), -1, 'params: mass, contact_margin and dt must be > 0'),
+    ('fg_rollout_hd', dict(params=None, B=-1, N=2, K=-1, pos_x=None, obs=4100), -1, 'params is NULL'),
+    ('fg_rollout_scenario', dict(params={'dt': 0.0}, scenario=None, B=-1, N=1, K=-1), -1, 'params: mass, contact_margin and dt must be > 0'),
+    ('fg_step_hd', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_step_hd', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd', dict(B=0, N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd', dict(B=-1, N=2), -1, 'B must be >= 0'),
+    ('fg_step_hd', dict(obs=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd', dict(step=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd', dict(reward=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd', dict(obs=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd', dict(act=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd', dict(ideal_vel=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd', dict(pos_x=None, obs=4100), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd', dict(N=2, obs=None), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_step_hd', dict(params={'obs_env_pitch': 484}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_step_hd', dict(params={'obs_env_pitch': 7}, obs=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd', dict(B=0, obs=4100, pos_x=None), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd_plan', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_step_hd_plan', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd_plan', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd_plan', dict(B=0, N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd_plan', dict(B=-1, N=2), -1, 'B must be >= 0'),
+    ('fg_step_hd_plan', dict(obs=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd_plan', dict(step=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd_plan', dict(reward=None), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd_plan', dict(obs=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd_plan', dict(act=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd_plan', dict(ideal_vel=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd_plan', dict(pos_x=None, obs=4100), -1, 'fg_step_hd: a required pointer is NULL'),
+    ('fg_step_hd_plan', dict(N=2, obs=None), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_step_hd_plan', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_step_hd_plan', dict(params={'obs_env_pitch': 484}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_step_hd_plan', dict(params={'obs_env_pitch': 7}, obs=4100), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd_plan', dict(B=0, obs=4100, pos_x=None), -3, 'obs must be 16-byte, act/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_step_hd', dict(B=0, pos_x=None, obs=None), 0, None),
+    ('fg_step_hd_plan', dict(plan=None), -1, 'fg_step_hd_plan: plan is NULL'),
+    ('fg_step_hd_plan', dict(plan=None, params=None, B=-1), -1, 'fg_step_hd_plan: plan is NULL'),
+    ('fg_physics_step', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_physics_step', dict(B=-1, N=1), -1, 'B must be >= 0'),
+    ('fg_physics_step', dict(N=1), -2, 'N must be in [2, 1024]'),
+    ('fg_physics_step', dict(N=1025), -2, 'N must be in [2, 1024]'),
+    ('fg_physics_step', dict(vel_y=None), -1, 'fg_physics_step: a required pointer is NULL'),
+    ('fg_physics_step', dict(act=None), -1, 'fg_physics_step: a required pointer is NULL'),
+    ('fg_physics_step', dict(act=4100), -3, 'act must be 8-byte aligned'),
+    ('fg_physics_step', dict(pos_x=None, act=4100), -1, 'fg_physics_step: a required pointer is NULL'),
+    ('fg_physics_step', dict(N=1, act=None), -2, 'N must be in [2, 1024]'),
+    ('fg_physics_step', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_physics_step', dict(params={'obs_env_pitch': 7}, act=4100), -3, 'act must be 8-byte aligned'),
+    ('fg_observe_hd', dict(B=0, N=2, pos_x=None), 0, None),
+    ('fg_observe_hd', dict(B=-1, N=2), -1, 'B must be >= 0'),
+    ('fg_observe_hd', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_observe_hd', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_observe_hd', dict(ideal_vel=None), -1, 'fg_observe_hd: a required pointer is NULL'),
+    ('fg_observe_hd', dict(obs=None, reward=None), -1, 'fg_observe_hd: obs and reward both NULL'),
+    ('fg_observe_hd', dict(pos_x=None, obs=None, reward=None), -1, 'fg_observe_hd: a required pointer is NULL'),
+    ('fg_observe_hd', dict(obs=4100), -3, 'obs must be 16-byte, ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_observe_hd', dict(ideal_shape=4100), -3, 'obs must be 16-byte, ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_observe_hd', dict(obs=4100, reward=None), -3, 'obs must be 16-byte, ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_observe_hd', dict(obs=None, reward=None, ideal_shape=4100), -1, 'fg_observe_hd: obs and reward both NULL'),
+    ('fg_observe_hd', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_observe_hd', dict(params={'obs_env_pitch': 7}, obs=4100), -3, 'obs must be 16-byte, ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_observe_hd', dict(N=2, pos_x=None), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd', dict(B=0, N=2, pos_x=None), 0, None),
+    ('fg_rollout_hd', dict(K=0, N=2, pos_x=None), 0, None),
+    ('fg_rollout_hd', dict(B=-1, K=0), 0, None),
+    ('fg_rollout_hd', dict(B=0, K=-1), 0, None),
+    ('fg_rollout_hd', dict(B=-1), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd', dict(K=-1), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd', dict(B=-1, N=2), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd', dict(pos_x=None), -1, 'fg_rollout_hd: a required pointer is NULL'),
+    ('fg_rollout_hd', dict(reward=None), -1, 'fg_rollout_hd: a required pointer is NULL'),
+    ('fg_rollout_hd', dict(step=None), -1, 'fg_rollout_hd: a required pointer is NULL'),
+    ('fg_rollout_hd', dict(obs=None, reward=None), -1, 'fg_rollout_hd: a required pointer is NULL'),
+    ('fg_rollout_hd', dict(obs=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd', dict(act=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd', dict(ideal_shape=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd', dict(reward=None, obs=4100), -1, 'fg_rollout_hd: a required pointer is NULL'),
+    ('fg_rollout_hd', dict(N=2, reward=None), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_rollout_hd', dict(params={'obs_env_pitch': 7}, obs=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd_policy', dict(B=0, N=2, pos_x=None), 0, None),
+    ('fg_rollout_hd_policy', dict(K=0, N=2, pos_x=None), 0, None),
+    ('fg_rollout_hd_policy', dict(B=-1, K=0), 0, None),
+    ('fg_rollout_hd_policy', dict(B=0, K=-1), 0, None),
+    ('fg_rollout_hd_policy', dict(B=-1), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd_policy', dict(K=-1), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd_policy', dict(B=-1, N=2), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd_policy', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd_policy', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd_policy', dict(pos_x=None), -1, 'fg_rollout_hd_policy: a required pointer is NULL'),
+    ('fg_rollout_hd_policy', dict(reward=None), -1, 'fg_rollout_hd_policy: a required pointer is NULL'),
+    ('fg_rollout_hd_policy', dict(step=None), -1, 'fg_rollout_hd_policy: a required pointer is NULL'),
+    ('fg_rollout_hd_policy', dict(obs=None, reward=None), -1, 'fg_rollout_hd_policy: a required pointer is NULL'),
+    ('fg_rollout_hd_policy', dict(obs=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd_policy', dict(act=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd_policy', dict(ideal_shape=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd_policy', dict(reward=None, obs=4100), -1, 'fg_rollout_hd_policy: a required pointer is NULL'),
+    ('fg_rollout_hd_policy', dict(N=2, reward=None), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd_policy', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_rollout_hd_policy', dict(params={'obs_env_pitch': 7}, obs=4100), -3, 'obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned'),
+    ('fg_rollout_hd_policy', dict(B=0, N=10), 0, None),
+    ('fg_rollout_hd_policy', dict(N=10), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_rollout_hd_policy', dict(N=81, per=9), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_rollout_hd_policy', dict(per=1), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_rollout_hd_policy', dict(N=2, per=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_rollout_hd_policy', dict(N=10, pos_x=None), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_rollout_hd_policy', dict(N=10, obs=4100), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_rollout_hd_policy', dict(B=-1, N=10), -1, 'B and K must be >= 0'),
+    ('fg_rollout_hd_policy', dict(N=10, params={'obs_env_pitch': 7}), -2, 'fg_rollout_hd_policy: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_reset_hd', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_reset_hd', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_reset_hd', dict(B=-1, N=1), -1, 'B must be >= 0'),
+    ('fg_reset_hd', dict(N=1), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd', dict(N=5000), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd', dict(pos_x=None), -1, 'fg_reset_hd: a required pointer is NULL'),
+    ('fg_reset_hd', dict(ideal_vel=None), -1, 'fg_reset_hd: a required pointer is NULL'),
+    ('fg_reset_hd', dict(N=1, pos_x=None), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt', dict(B=0, N=1, mt_state=None), 0, None),
+    ('fg_reset_hd_mt', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_reset_hd_mt', dict(B=-1, N=1), -1, 'B must be >= 0'),
+    ('fg_reset_hd_mt', dict(N=1), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt', dict(N=1025), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt', dict(mt_state=None), -1, 'fg_reset_hd_mt: a required pointer is NULL'),
+    ('fg_reset_hd_mt', dict(ideal_vel=None), -1, 'fg_reset_hd_mt: a required pointer is NULL'),
+    ('fg_reset_hd_mt', dict(N=1, mt_state=None), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt_done', dict(B=0, world_length=0, step=None), 0, None),
+    ('fg_reset_hd_mt_done', dict(world_length=0), -1, 'fg_reset_hd_mt_done: world_length > 0 and step required'),
+    ('fg_reset_hd_mt_done', dict(step=None), -1, 'fg_reset_hd_mt_done: world_length > 0 and step required'),
+    ('fg_reset_hd_mt_done', dict(B=-1, world_length=0), -1, 'fg_reset_hd_mt_done: world_length > 0 and step required'),
+    ('fg_reset_hd_mt_done', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_reset_hd_mt_done', dict(B=-1, N=1), -1, 'B must be >= 0'),
+    ('fg_reset_hd_mt_done', dict(N=1), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt_done', dict(N=1025), -2, 'N must be in [2, 1024]'),
+    ('fg_reset_hd_mt_done', dict(mt_state=None), -1, 'fg_reset_hd_mt: a required pointer is NULL'),
+    ('fg_reset_hd_mt_done', dict(obs_env_pitch=7), -1, 'obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_reset_hd_mt_done', dict(obs_env_pitch=484), -1, 'obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_reset_hd_mt_done', dict(obs=4100), -3, 'obs must be 8-byte aligned'),
+    ('fg_reset_hd_mt_done', dict(obs=4100, obs_env_pitch=7), -1, 'obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_reset_hd_mt_done', dict(mt_state=None, obs_env_pitch=7), -1, 'fg_reset_hd_mt: a required pointer is NULL'),
+    ('fg_reset_hd_mt_done', dict(N=1, step=None), -1, 'fg_reset_hd_mt_done: world_length > 0 and step required'),
+    ('fg_reset_scenario', dict(scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_reset_scenario', dict(scenario=None, B=-1, N=1), -1, 'scenario descriptor is NULL'),
+    ('fg_reset_scenario', dict(scenario={'kind': 9}, N=1), -1, 'unknown scenario kind'),
+    ('fg_reset_scenario', dict(scenario={'kind': 9}, B=0), -1, 'unknown scenario kind'),
+    ('fg_reset_scenario', dict(scenario={'kind': 9}, B=-1), -1, 'unknown scenario kind'),
+    ('fg_reset_scenario', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_reset_scenario', dict(B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario', dict(scenario={'num_landmarks': 0}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario', dict(scenario={'num_obstacles': -1}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario', dict(B=-1, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario', dict(N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario', dict(N=1022), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario', dict(scenario={'num_landmarks': 1025}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario', dict(scenario={'num_landmarks': 0}, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario', dict(pos_x=None), -1, 'fg_reset_scenario: a required pointer is NULL'),
+    ('fg_reset_scenario', dict(landmarks=None), -1, 'fg_reset_scenario: a required pointer is NULL'),
+    ('fg_reset_scenario', dict(obst_pos=None), -1, 'fg_reset_scenario: a required pointer is NULL'),
+    ('fg_reset_scenario', dict(obst_vel=None), -1, 'fg_reset_scenario: a required pointer is NULL'),
+    ('fg_reset_scenario', dict(landmarks=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario', dict(obst_pos=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario', dict(obst_vel=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario', dict(pos_x=None, landmarks=4100), -1, 'fg_reset_scenario: a required pointer is NULL'),
+    ('fg_reset_scenario', dict(N=1022, pos_x=None), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario', dict(scenario={'num_obstacles': 0}, obst_pos=None, obst_vel=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario_mt', dict(scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_reset_scenario_mt', dict(scenario=None, B=-1, N=1), -1, 'scenario descriptor is NULL'),
+    ('fg_reset_scenario_mt', dict(scenario={'kind': 9}, N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario_mt', dict(scenario={'kind': 9}, B=0), 0, None),
+    ('fg_reset_scenario_mt', dict(scenario={'kind': 9}, B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_reset_scenario_mt', dict(B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(scenario={'num_landmarks': 0}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(scenario={'num_obstacles': -1}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(B=-1, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario_mt', dict(N=1022), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario_mt', dict(scenario={'num_landmarks': 1025}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario_mt', dict(scenario={'num_landmarks': 0}, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_reset_scenario_mt', dict(pos_x=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(landmarks=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(obst_pos=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(obst_vel=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(landmarks=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario_mt', dict(obst_pos=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario_mt', dict(obst_vel=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario_mt', dict(pos_x=None, landmarks=4100), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(N=1022, pos_x=None), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_reset_scenario_mt', dict(scenario={'num_obstacles': 0}, obst_pos=None, obst_vel=4100), -3, 'landmarks / obstacle buffers must be 8-byte aligned'),
+    ('fg_reset_scenario_mt', dict(mt_state=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_reset_scenario_mt', dict(mask=None, step=None), -1, 'fg_reset_scenario_mt: the done rule needs the step counters'),
+    ('fg_reset_scenario_mt', dict(mask=None, step=None, landmarks=4100), -1, 'fg_reset_scenario_mt: the done rule needs the step counters'),
+    ('fg_reset_scenario_mt', dict(mask=None, step=None, pos_x=None), -1, 'fg_reset_scenario_mt: a required pointer is NULL'),
+    ('fg_step_scenario', dict(scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_step_scenario', dict(params={'comm_state': 4096}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_step_scenario', dict(params={'comm_state': 4096}, scenario={'kind': 9}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_step_scenario', dict(params={'comm_state': 4096}, scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_step_scenario', dict(scenario={'kind': 9}), -1, 'unknown scenario kind'),
+    ('fg_step_scenario', dict(scenario={'kind': 0}), -1, 'unknown scenario kind'),
+    ('fg_step_scenario', dict(scenario={'kind': 9}, B=0), -1, 'unknown scenario kind'),
+    ('fg_step_scenario', dict(scenario={'kind': 9}, B=-1), -1, 'unknown scenario kind'),
+    ('fg_step_scenario', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_step_scenario', dict(B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_scenario', dict(scenario={'num_landmarks': 0}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_scenario', dict(scenario={'num_obstacles': -1}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_scenario', dict(B=-1, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_scenario', dict(N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_scenario', dict(N=1022), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_scenario', dict(scenario={'num_landmarks': 1025}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_scenario', dict(scenario={'kind': 2, 'num_obs': -1}), -1, 'bad num_obs'),
+    ('fg_step_scenario', dict(scenario={'kind': 2, 'num_obs': 1025}), -1, 'bad num_obs'),
+    ('fg_step_scenario', dict(scenario={'kind': 2, 'num_obs': -1}, N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_scenario', dict(scenario={'kind': 2, 'num_obs': -1}, pos_x=None), -1, 'bad num_obs'),
+    ('fg_step_scenario', dict(pos_x=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(landmarks=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(obs=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(act=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(reward=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(obst_pos=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(obst_vel=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(obs=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(landmarks=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(act=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(obst_pos=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(obst_vel=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(pos_x=None, obs=4100), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_scenario', dict(N=1022, pos_x=None), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_rollout_scenario', dict(scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_rollout_scenario', dict(params={'comm_state': 4096}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_rollout_scenario', dict(params={'comm_state': 4096}, scenario={'kind': 9}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_rollout_scenario', dict(params={'comm_state': 4096}, scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 9}), -1, 'unknown scenario kind'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 0}), -1, 'unknown scenario kind'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 9}, B=0), -1, 'unknown scenario kind'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 9}, B=-1), -1, 'unknown scenario kind'),
+    ('fg_rollout_scenario', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_rollout_scenario', dict(B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_rollout_scenario', dict(scenario={'num_landmarks': 0}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_rollout_scenario', dict(scenario={'num_obstacles': -1}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_rollout_scenario', dict(B=-1, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_rollout_scenario', dict(N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_rollout_scenario', dict(N=1022), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_rollout_scenario', dict(scenario={'num_landmarks': 1025}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 2, 'num_obs': -1}), -1, 'bad num_obs'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 2, 'num_obs': 1025}), -1, 'bad num_obs'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 2, 'num_obs': -1}, N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_rollout_scenario', dict(scenario={'kind': 2, 'num_obs': -1}, pos_x=None), -1, 'bad num_obs'),
+    ('fg_rollout_scenario', dict(pos_x=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(landmarks=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(obs=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(act=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(reward=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(obst_pos=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(obst_vel=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(obs=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario', dict(landmarks=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario', dict(act=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario', dict(obst_pos=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario', dict(obst_vel=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario', dict(pos_x=None, obs=4100), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(N=1022, pos_x=None), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_scenario', dict(do_physics=0, act=None, reward=None, obs=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_scenario', dict(do_physics=0, act=4100, reward=None, obs=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_rollout_scenario', dict(K=0, pos_x=None), 0, None),
+    ('fg_rollout_scenario', dict(K=0, scenario=None), -1, 'scenario descriptor is NULL'),
+    ('fg_rollout_scenario', dict(K=0, params=None), -1, 'params is NULL'),
+    ('fg_rollout_scenario', dict(K=0, scenario={'kind': 9}, params={'comm_state': 4096}), 0, None),
+    ('fg_rollout_scenario', dict(K=-2), -1, 'K >= 0 and obs_every >= 1 required'),
+    ('fg_rollout_scenario', dict(K=-2, scenario={'kind': 9}), -1, 'K >= 0 and obs_every >= 1 required'),
+    ('fg_rollout_scenario', dict(K=-2, params={'comm_state': 4096}), -1, 'K >= 0 and obs_every >= 1 required'),
+    ('fg_rollout_scenario', dict(K=-2, B=0), -1, 'K >= 0 and obs_every >= 1 required'),
+    ('fg_step_basic', dict(params={'comm_state': 4096}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_step_basic', dict(B=0, N=1, pos_x=None), 0, None),
+    ('fg_step_basic', dict(B=-1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_basic', dict(L=0), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_basic', dict(B=-1, N=1100), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_basic', dict(N=1), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_basic', dict(N=1100), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_basic', dict(L=1025), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_step_basic', dict(L=0, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_step_basic', dict(pos_x=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_basic', dict(obs=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_basic', dict(act=None), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_basic', dict(do_physics=0, act=None, reward=None, obs=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_basic', dict(obs=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_basic', dict(landmarks=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_basic', dict(act=4100), -3, 'obs/landmarks/act/obstacle buffers must be 8-byte aligned'),
+    ('fg_step_basic', dict(landmarks=None, obs=4100), -1, 'scenario step: a required pointer is NULL'),
+    ('fg_step_basic', dict(params={'comm_state': 4096}, B=-1, N=1), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_update_comm', dict(B=0, N=0, action_c=None), 0, None),
+    ('fg_update_comm', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_update_comm', dict(B=-1, N=0), -1, 'B must be >= 0'),
+    ('fg_update_comm', dict(N=0), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm', dict(N=5000), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm', dict(action_c=None), -1, 'fg_update_comm: a required pointer is NULL'),
+    ('fg_update_comm', dict(comm_state=None), -1, 'fg_update_comm: a required pointer is NULL'),
+    ('fg_update_comm', dict(action_c=4100), -3, 'action_c and comm_state must be 8-byte aligned'),
+    ('fg_update_comm', dict(comm_state=4100), -3, 'action_c and comm_state must be 8-byte aligned'),
+    ('fg_update_comm', dict(action_c=None, comm_state=4100), -1, 'fg_update_comm: a required pointer is NULL'),
+    ('fg_update_comm', dict(N=0, action_c=None), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm_dim', dict(dim_c=2, B=-1), -1, 'B must be >= 0'),
+    ('fg_update_comm_dim', dict(dim_c=2, N=0), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm_dim', dict(dim_c=2, action_c=None), -1, 'fg_update_comm: a required pointer is NULL'),
+    ('fg_update_comm_dim', dict(dim_c=2, action_c=4100), -3, 'action_c and comm_state must be 8-byte aligned'),
+    ('fg_update_comm_dim', dict(dim_c=2, params=None), -1, 'params is NULL'),
+    ('fg_update_comm_dim', dict(B=0, N=0, action_c=None), 0, None),
+    ('fg_update_comm_dim', dict(dim_c=0, N=0, action_c=None), 0, None),
+    ('fg_update_comm_dim', dict(B=-1), -1, 'B >= 0 and 0 <= dim_c <= 4096 required'),
+    ('fg_update_comm_dim', dict(dim_c=-1), -1, 'B >= 0 and 0 <= dim_c <= 4096 required'),
+    ('fg_update_comm_dim', dict(dim_c=4097), -1, 'B >= 0 and 0 <= dim_c <= 4096 required'),
+    ('fg_update_comm_dim', dict(B=-1, N=0), -1, 'B >= 0 and 0 <= dim_c <= 4096 required'),
+    ('fg_update_comm_dim', dict(B=0, dim_c=-1), 0, None),
+    ('fg_update_comm_dim', dict(N=0), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm_dim', dict(N=5000), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm_dim', dict(action_c=None), -1, 'fg_update_comm_dim: a required pointer is NULL'),
+    ('fg_update_comm_dim', dict(comm_state=None), -1, 'fg_update_comm_dim: a required pointer is NULL'),
+    ('fg_update_comm_dim', dict(action_c=4098), -3, 'action_c and comm_state must be 4-byte aligned'),
+    ('fg_update_comm_dim', dict(comm_state=4097), -3, 'action_c and comm_state must be 4-byte aligned'),
+    ('fg_update_comm_dim', dict(action_c=None, comm_state=4098), -1, 'fg_update_comm_dim: a required pointer is NULL'),
+    ('fg_update_comm_dim', dict(N=0, action_c=None), -2, 'N must be in [1, 1024]'),
+    ('fg_update_comm_dim', dict(dim_c=-1, N=0), -1, 'B >= 0 and 0 <= dim_c <= 4096 required'),
+    ('fg_policy_bfs', dict(B=0, N=2, act=None), 0, None),
+    ('fg_policy_bfs', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_policy_bfs', dict(B=-1, N=2), -1, 'B must be >= 0'),
+    ('fg_policy_bfs', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs', dict(N=2, per=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs', dict(N=10), -2, 'fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs', dict(N=81, per=9), -2, 'fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs', dict(per=1), -2, 'fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs', dict(N=10, act=None), -2, 'fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs', dict(act=None), -1, 'fg_policy_bfs: a required pointer is NULL'),
+    ('fg_policy_bfs', dict(act=4100), -3, 'obs and act must be 8-byte aligned'),
+    ('fg_policy_bfs', dict(N=10, act=4100), -2, 'fg_policy_bfs: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs_state', dict(B=0, N=2, act=None), 0, None),
+    ('fg_policy_bfs_state', dict(B=-1), -1, 'B must be >= 0'),
+    ('fg_policy_bfs_state', dict(B=-1, N=2), -1, 'B must be >= 0'),
+    ('fg_policy_bfs_state', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs_state', dict(N=2, per=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs_state', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_policy_bfs_state', dict(N=10), -2, 'fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs_state', dict(N=81, per=9), -2, 'fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs_state', dict(per=1), -2, 'fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs_state', dict(N=10, act=None), -2, 'fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs_state', dict(act=None), -1, 'fg_policy_bfs_state: a required pointer is NULL'),
+    ('fg_policy_bfs_state', dict(act=4100), -3, 'ideal_shape, ideal_vel and act must be 8-byte aligned'),
+    ('fg_policy_bfs_state', dict(N=10, act=4100), -2, 'fg_policy_bfs_state: N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_policy_bfs', dict(obs=None), -1, 'fg_policy_bfs: a required pointer is NULL'),
+    ('fg_policy_bfs', dict(obs=None, act=4100), -1, 'fg_policy_bfs: a required pointer is NULL'),
+    ('fg_policy_bfs', dict(obs_env_stride=7), -1, 'fg_policy_bfs: obs_env_stride must be even and >= 6 N'),
+    ('fg_policy_bfs', dict(obs_env_stride=52), -1, 'fg_policy_bfs: obs_env_stride must be even and >= 6 N'),
+    ('fg_policy_bfs', dict(obs_env_stride=7, obs=4100), -1, 'fg_policy_bfs: obs_env_stride must be even and >= 6 N'),
+    ('fg_policy_bfs', dict(obs=4100), -3, 'obs and act must be 8-byte aligned'),
+    ('fg_policy_bfs', dict(obs=None, obs_env_stride=7), -1, 'fg_policy_bfs: a required pointer is NULL'),
+    ('fg_policy_bfs_state', dict(pos_x=None), -1, 'fg_policy_bfs_state: a required pointer is NULL'),
+    ('fg_policy_bfs_state', dict(ideal_vel=None), -1, 'fg_policy_bfs_state: a required pointer is NULL'),
+    ('fg_policy_bfs_state', dict(ideal_shape=4100), -3, 'ideal_shape, ideal_vel and act must be 8-byte aligned'),
+    ('fg_policy_bfs_state', dict(ideal_vel=4100), -3, 'ideal_shape, ideal_vel and act must be 8-byte aligned'),
+    ('fg_policy_bfs_state', dict(pos_x=None, act=4100), -1, 'fg_policy_bfs_state: a required pointer is NULL'),
+    ('fg_decode_actions', dict(mode=0), -1, 'fg_decode_actions: unknown mode'),
+    ('fg_decode_actions', dict(mode=4), -1, 'fg_decode_actions: unknown mode'),
+    ('fg_decode_actions', dict(mode=0, count=0), -1, 'fg_decode_actions: unknown mode'),
+    ('fg_decode_actions', dict(mode=0, count=-3), -1, 'fg_decode_actions: unknown mode'),
+    ('fg_decode_actions', dict(count=0, action=None, u_out=4100), 0, None),
+    ('fg_decode_actions', dict(count=-3), -1, 'fg_decode_actions: count out of range'),
+    ('fg_decode_actions', dict(count=274877906945), -1, 'fg_decode_actions: count out of range'),
+    ('fg_decode_actions', dict(count=-3, action=None), -1, 'fg_decode_actions: count out of range'),
+    ('fg_decode_actions', dict(action=None), -1, 'fg_decode_actions: a required pointer is NULL'),
+    ('fg_decode_actions', dict(u_out=None), -1, 'fg_decode_actions: a required pointer is NULL'),
+    ('fg_decode_actions', dict(u_out=4100), -3, 'fg_decode_actions: buffers must be 8-byte aligned'),
+    ('fg_decode_actions', dict(action=4100), -3, 'fg_decode_actions: buffers must be 8-byte aligned'),
+    ('fg_decode_actions', dict(action=4100, mode=2, u_out=4100), -3, 'fg_decode_actions: buffers must be 8-byte aligned'),
+    ('fg_decode_actions', dict(action=None, u_out=4100), -1, 'fg_decode_actions: a required pointer is NULL'),
+    ('fg_actor_noise', dict(B=-1), -1, 'fg_actor_noise: B >= 0 and 1 <= N < 2^29 required'),
+    ('fg_actor_noise', dict(N=0), -1, 'fg_actor_noise: B >= 0 and 1 <= N < 2^29 required'),
+    ('fg_actor_noise', dict(N=536870912), -1, 'fg_actor_noise: B >= 0 and 1 <= N < 2^29 required'),
+    ('fg_actor_noise', dict(B=-1, eps=None), -1, 'fg_actor_noise: B >= 0 and 1 <= N < 2^29 required'),
+    ('fg_actor_noise', dict(eps=None), -1, 'fg_actor_noise: eps is NULL'),
+    ('fg_actor_noise', dict(eps=4100), -3, 'fg_actor_noise: eps must be 8-byte aligned'),
+    ('fg_actor_noise', dict(B=0, eps=None), -1, 'fg_actor_noise: eps is NULL'),
+    ('fg_actor_noise', dict(B=0, eps=4100), -3, 'fg_actor_noise: eps must be 8-byte aligned'),
+    ('fg_actor_noise', dict(B=0), 0, None),
+    ('fg_actor_noise', dict(params=None, B=-1, eps=None), -1, 'params is NULL'),
+    ('fg_kernel_config', dict(N=1), -2, 'N must be in [2, 1024]'),
+    ('fg_kernel_config', dict(N=1025), -2, 'N must be in [2, 1024]'),
+    ('fg_describe_launch', dict(out=None), -1, 'fg_describe_launch: out buffer required'),
+    ('fg_describe_launch', dict(out=None, params=None), -1, 'fg_describe_launch: out buffer required'),
+    ('fg_describe_launch', dict(params=None, B=0), -1, 'params is NULL'),
+    ('fg_describe_launch', dict(B=0), -1, 'fg_describe_launch: B > 0 and K >= 0 required'),
+    ('fg_describe_launch', dict(K=-1), -1, 'fg_describe_launch: B > 0 and K >= 0 required'),
+    ('fg_describe_launch', dict(B=0, N=2), -1, 'fg_describe_launch: B > 0 and K >= 0 required'),
+    ('fg_describe_launch', dict(N=2), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_describe_launch', dict(N=1025), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_describe_launch', dict(N=2, per=3), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_describe_launch', dict(N=2, params={'obs_env_pitch': 7}), -2, 'formation_hd_env needs 3 <= N <= 1024'),
+    ('fg_describe_launch', dict(params={'obs_env_pitch': 7}), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_describe_launch', dict(params={'obs_env_pitch': 7}, N=10, per=3), -1, 'params: obs_env_pitch must be 0 or an even number of floats >= 6 N^2'),
+    ('fg_describe_launch', dict(N=10, per=3), -2, 'N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_describe_launch', dict(N=81, per=9), -2, 'N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_describe_launch', dict(per=1), -2, 'N must be per_layer^L with 2 <= per_layer <= 8'),
+    ('fg_describe_launch', dict(B=0, scenario={}), -1, 'fg_describe_launch: B > 0 and K >= 0 required'),
+    ('fg_describe_launch', dict(scenario={'kind': 9}), -1, 'unknown scenario kind'),
+    ('fg_describe_launch', dict(scenario={'kind': 9}, params={'comm_state': 4096}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_describe_launch', dict(params={'comm_state': 4096}, scenario={}), -1, 'comm_state is honoured by the formation_hd_env entry points only'),
+    ('fg_describe_launch', dict(scenario={'num_landmarks': 0}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_describe_launch', dict(scenario={'num_obstacles': -1}), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_describe_launch', dict(N=1, scenario={}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_describe_launch', dict(N=1022, scenario={}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_describe_launch', dict(scenario={'num_landmarks': 1025}), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_describe_launch', dict(scenario={'num_landmarks': 0}, N=1), -1, 'B >= 0, L > 0, M >= 0 required'),
+    ('fg_describe_launch', dict(scenario={'kind': 2, 'num_obs': -1}), -1, 'bad num_obs'),
+    ('fg_describe_launch', dict(scenario={'kind': 2, 'num_obs': 1025}, N=1022), -2, 'scenario kernel needs 2 <= N, N + M <= 1024, L <= 1024'),
+    ('fg_describe_scenario_actor_launch', dict(out=None), -1, 'fg_describe_scenario_actor_launch: out buffer required'),
+    ('fg_describe_scenario_actor_launch', dict(out=None, params=None), -1, 'fg_describe_scenario_actor_launch: out buffer required'),
+    ('fg_rollout_scenario_actor', dict(scenario=None), -1, 'fg_rollout_scenario_actor: scenario descriptor is NULL'),
+    ('fg_rollout_scenario_actor', dict(scenario=None, actor=None, B=-1), -1, 'fg_rollout_scenario_actor: scenario descriptor is NULL'),
+    ('fg_rollout_scenario_actor', dict(B=-1), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_rollout_scenario_actor', dict(K=0), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_rollout_scenario_actor', dict(B=-1, scenario={'kind': 9}), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_rollout_scenario_actor', dict(scenario={'kind': 9}), -1, 'fg_rollout_scenario_actor: unknown scenario kind'),
+    ('fg_rollout_scenario_actor', dict(scenario={'kind': 9}, actor=None), -1, 'fg_rollout_scenario_actor: unknown scenario kind'),
+    ('fg_rollout_scenario_actor', dict(actor=None), -1, 'fg_rollout_scenario_actor: actor is NULL'),
+    ('fg_rollout_scenario_actor', dict(actor={'hidden': 128}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_rollout_scenario_actor', dict(actor={'hidden': 48}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_rollout_scenario_actor', dict(actor={'w2': None}), -1, 'fg_rollout_scenario_actor: a weight pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(actor={'b3': 4098}), -3, 'fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(log_std=4098), -3, 'fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(actor={'w2': None, 'b3': 4098}), -1, 'fg_rollout_scenario_actor: a weight pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(actor={'hidden': 48}, params={'comm_state': 4096}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_rollout_scenario_actor', dict(params={'agent_props': 4096}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_rollout_scenario_actor', dict(params={'comm_state': 4096}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_rollout_scenario_actor', dict(scenario={'variant': 1}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_rollout_scenario_actor', dict(N=5), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_rollout_scenario_actor', dict(scenario={'num_landmarks': 5}), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_rollout_scenario_actor', dict(N=5, scenario={'variant': 1}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_describe_scenario_actor_launch', dict(scenario=None), -1, 'fg_rollout_scenario_actor: scenario descriptor is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(scenario=None, actor=None, B=-1), -1, 'fg_rollout_scenario_actor: scenario descriptor is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(B=-1), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_describe_scenario_actor_launch', dict(K=0), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_describe_scenario_actor_launch', dict(B=-1, scenario={'kind': 9}), -1, 'fg_rollout_scenario_actor: B >= 0 and K >= 1 required'),
+    ('fg_describe_scenario_actor_launch', dict(scenario={'kind': 9}), -1, 'fg_rollout_scenario_actor: unknown scenario kind'),
+    ('fg_describe_scenario_actor_launch', dict(scenario={'kind': 9}, actor=None), -1, 'fg_rollout_scenario_actor: unknown scenario kind'),
+    ('fg_describe_scenario_actor_launch', dict(actor=None), -1, 'fg_rollout_scenario_actor: actor is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'hidden': 128}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'hidden': 48}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'w2': None}), -1, 'fg_rollout_scenario_actor: a weight pointer is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'b3': 4098}), -3, 'fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned'),
+    ('fg_describe_scenario_actor_launch', dict(log_std=4098), -3, 'fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'w2': None, 'b3': 4098}), -1, 'fg_rollout_scenario_actor: a weight pointer is NULL'),
+    ('fg_describe_scenario_actor_launch', dict(actor={'hidden': 48}, params={'comm_state': 4096}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_describe_scenario_actor_launch', dict(params={'agent_props': 4096}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_describe_scenario_actor_launch', dict(params={'comm_state': 4096}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_describe_scenario_actor_launch', dict(scenario={'variant': 1}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_describe_scenario_actor_launch', dict(N=5), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_describe_scenario_actor_launch', dict(scenario={'num_landmarks': 5}), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_describe_scenario_actor_launch', dict(N=5, scenario={'variant': 1}), -1, 'fg_rollout_scenario_actor: per-agent properties, communication and variant 1 are not supported'),
+    ('fg_rollout_scenario_actor', dict(logp=4098), -3, 'fg_rollout_scenario_actor: weights, log_std and logp must be 4-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(log_std=None), -1, 'fg_rollout_scenario_actor: logp without log_std'),
+    ('fg_rollout_scenario_actor', dict(log_std=None, actor={'hidden': 48}), -1, 'fg_rollout_scenario_actor: hidden must be 32 or 64'),
+    ('fg_rollout_scenario_actor', dict(log_std=None, pos_x=None), -1, 'fg_rollout_scenario_actor: logp without log_std'),
+    ('fg_rollout_scenario_actor', dict(pos_x=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(step=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(reward=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(act_out=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(obst_pos=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(obs=4100), -3, 'fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(act_out=4100), -3, 'fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(obst_vel=4100), -3, 'fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(pos_x=None, obs=4100), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(N=5, pos_x=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(N=5, obs=4100), -3, 'fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(B=0), 0, None),
+    ('fg_rollout_scenario_actor', dict(B=0, N=5), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_rollout_scenario_actor', dict(B=0, pos_x=None), -1, 'fg_rollout_scenario_actor: a required pointer is NULL'),
+    ('fg_rollout_scenario_actor', dict(B=0, obs=4100), -3, 'fg_rollout_scenario_actor: obs/landmarks/act_out/obstacle buffers must be 8-byte aligned'),
+    ('fg_rollout_scenario_actor', dict(scenario={'num_obstacles': 0}, obst_pos=None, obst_vel=None, N=5), -2, 'fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes'),
+    ('fg_describe_scenario_actor_launch', dict(B=0), -1, 'fg_describe_scenario_actor_launch: B > 0 required'),
+    ('fg_describe_scenario_actor_launch', dict(B=0, N=5), -1, 'fg_describe_scenario_actor_launch: B > 0 required'),
+    ('fg_describe_scenario_actor_launch', dict(B=0, actor=None), -1, 'fg_rollout_scenario_actor: actor is NULL'),
+]
+
+
+def test_entries_fail_in_their_own_order_with_their_own_text(lib):
+    seen = set()
+    for entry, wrong, status, text in CABI_BAD_CALLS:
+        assert (status == 0) == (text is None), (entry, wrong)
+        rc, got = _cabi_call(lib, entry, **wrong)
+        assert rc == status and (text is None or got == text), (entry, wrong, rc, got)
+        seen.add(entry)
+    assert seen == set(CABI_ENTRIES)
+
+
 def test_no_cpu_fallback(monkeypatch):
     import formation_gym
     import torch
