@@ -13,6 +13,8 @@
 // `ls1` for gauss_logp(n, ls0, ls1).  The body stores them - each to its own place - and ends the pass with a WaveSync.
 // `constexpr bool LNORM` (with `nw`): a LayerNorm over each row of the tile after either ReLU hand-over (actor_row_norm on
 // gamma | beta at wsm + WS + 4, fg_actor_mlp_preload.inc), with a WaveSync of its own before the next layer reads the tile.
+// `constexpr bool GRU` (with `gw`, `gsm`, `hst`; formation_hd_env's body only): the recurrent layer on the tile between the
+// second hidden norm and layer 3 (fg_actor_gru.inc), which leaves LayerNorm(h') in the tile for layer 3.
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
             if constexpr (LNORM) {
@@ -45,6 +47,9 @@
             if constexpr (LNORM) {
                 actor_row_norm<H>(hb, HS, wsm + WS + 4 + 2 * H, nw.eps2, lane);
                 WaveSync()();
+            }
+            if constexpr (GRU) {
+#include "fg_actor_gru.inc"
             }
             // ---- layer 3 on the VALU: lane = (row of the pass, output), an ascending fmaf chain ----
             const int row = lane >> 1, o = lane & 1;

@@ -1,11 +1,16 @@
-// fg_actor_rollout_body.inc - the one body of the six formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
-// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel and ln_sample_kernel (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
+// fg_actor_rollout_body.inc - the one body of the eight formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
+// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel and gru_sample_kernel
+// (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
 // (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
 // (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;
 // LNORM = false: an empty constant) selects ln_actor_kernel / ln_sample_kernel: the hidden LayerNorms are fg_actor_mlp.inc's,
 // the input LayerNorm (nw.in_norm, wave-uniform) is here - row statistics from the tables, then layer 1 over the whole k range
-// on the normalised operand.  Not a header: no guard.
+// on the normalised operand.  `constexpr bool GRU` with `gw` (ActorGruW; GRU = false: an empty constant) selects
+// gru_actor_kernel / gru_sample_kernel, an LNORM body whose pass runs fg_actor_gru.inc between the second hidden norm and layer 3
+// (fg_actor_mlp.inc); here are the hidden state's block in LDS - loaded from gw.state before the first pass, its done envs' rows
+// zeroed by the physics phase, stored back after the last step - and the preload of the layer's biases and norm.
+// Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
 // scenarios' body, as is the LDS preload (fg_actor_mlp_preload.inc).  The per-agent branches stay here.
@@ -28,13 +33,17 @@
     static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
     constexpr int LNS = actor_norm_floats(N, H, LNORM), DP = actor_in_pad(N);   // LNORM: gamma / beta of the three norms in LDS
     static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
+    static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm body");
+    constexpr int GS = actor_gru_floats(H, GRU);        // GRU: the gates' biases and the post-GRU norm in LDS
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
     float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
     float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + 4 + LNS;
+    float* const hbuf = wsm + WS + 4 + LNS + GS;
+    float* const gsm = wsm + WS + 4 + LNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
+    float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
     const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -64,6 +73,22 @@
                 lnp[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
             }
         }
+    }
+
+    if constexpr (GRU) {
+        for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
+            gsm[q] = gw.b_ih[q] + gw.b_hh[q];
+            gsm[H + q] = gw.b_ih[H + q] + gw.b_hh[H + q];
+            gsm[2 * H + q] = gw.b_ih[2 * H + q];
+            gsm[3 * H + q] = gw.b_hh[2 * H + q];
+            gsm[4 * H + q] = gw.g3 ? gw.g3[q] : 1.f;
+            gsm[5 * H + q] = gw.be3 ? gw.be3[q] : 0.f;
+        }
+        // the state of this workgroup's rows (env-major, contiguous in gw.state); rows past them start at zero
+        const float* const hsrc = gw.state + (size_t)b0 * N * H;
+        const int live = El * N * H;
+        for (int idx = tid; idx < actor_state_rows(N) * H; idx += FG_ACTOR_THREADS)
+            hst[(idx / H) * HS + idx % H] = idx < live ? hsrc[idx] : 0.f;
     }
 
     const float one_minus_damp = 1.0f - a.p.damping;
@@ -352,6 +377,13 @@
             if (a.indiv) a.indiv[o] = (-Hd - velterm) - (float)cnt;
             if (a.done) a.done[o] = is_done ? 1 : 0;
         }
+        if constexpr (GRU) {                           // h = h * ~done: the episode's memory ends with it
+            if (is_done && valid) {
+                float* const hr = hst + (e * N + i) * HS;
+#pragma unroll 8
+                for (int c = 0; c < H; ++c) hr[c] = 0.f;
+            }
+        }
         if (a.p.auto_reset) {
             const bool mine = is_done && env_ok;
             if (__any(mine) != 0) {
@@ -396,3 +428,7 @@
         a.px[sidx] = p.x; a.py[sidx] = p.y; a.vx[sidx] = v.x; a.vy[sidx] = v.y;
     }
     if (a.step && env_ok && i == 0) a.step[b] = t_step;
+    if constexpr (GRU) {                               // (the loop's last barrier ordered the last pass and the last masking)
+        float* const hdst = gw.state + (size_t)b0 * N * H;
+        for (int idx = tid; idx < El * N * H; idx += FG_ACTOR_THREADS) hdst[idx] = hst[(idx / H) * HS + idx % H];
+    }

@@ -50,6 +50,22 @@
 //                 lanes (k = lane >> 4) that share a row of the A operand; layer 1 then normalises its A operand on the fly
 //                 and runs over the WHOLE k range (a normalised zero is beta - mean rstd gamma, not zero).
 // gamma / beta of the three norms sit in LDS behind b3 | log_std (fg_actor_mlp_preload.inc; the input norm's from the body).
+//
+// gru_actor_kernel<N,H> / gru_sample_kernel<N,H> (fg_rollout_hd_actor_gru, H in {32, 64}) are the LayerNorm body with the
+// recurrent layer of onpolicy's R_Actor (rMAPPO's policy, recurrent_N = 1) between the second hidden norm and the head:
+//     [LayerNorm(6N) -] Linear - ReLU - LayerNorm(H) - Linear - ReLU - LayerNorm(H) - GRU(H, H) - LayerNorm(H) - Linear(H, 2)
+//     [- Tanh]
+// selected by `constexpr bool GRU` (false in every other kernel, whose instructions it leaves as they were); the recurrent part
+// of a wave pass is fg_actor_gru.inc.  One GRU step per actor evaluation, torch.nn.GRUCell's (gate order r | z | n):
+//     r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise, n = tanh(W_in x + b_in + r (W_hn h + b_hn)), h' = (1 - z) n + z h
+// with the six products on v_mfma_f32_16x16x4_f32 - the weights as the B operand read in place, x from the wave's tile and h
+// from the state block as A operands - and the gates element-wise in the accumulator layout.  h' is the state carried on; the
+// head sees LayerNorm(h').
+//   state         every row's h [H] lives in LDS for the whole launch, one block of TILES x 32 rows at the tile's pitch H + 4
+//                 behind the activation tiles: loaded from `rnn_state` once at launch start, stored once at the end.  A row
+//                 belongs to one wave for the whole launch (tile t is wave t % 4's), so only that wave reads or writes it in
+//                 the actor phase; the physics phase zeroes the rows of an env whose step ended its episode (is_done, with
+//                 or without auto-reset), a workgroup barrier away from either neighbour.
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -78,6 +94,16 @@ struct ActorNormW {
     int in_norm;
 };
 
+// the recurrent layer of gru_*_kernel (FgActorGru): torch's GRU parameters (gate order r | z | n), the LayerNorm after it
+// (gamma / beta NULL: 1 / 0) and the hidden state, read at launch start and written back at the end
+struct ActorGruW {
+    const float* w_ih; const float* w_hh;     // [3H][H]
+    const float* b_ih; const float* b_hh;     // [3H]
+    const float* g3; const float* be3;        // [H]
+    float eps3;
+    float* state;                             // [B][N][H]
+};
+
 // one actor per agent (pa_*_kernel): agent i's parameters; entries at i >= N are never read
 constexpr int FG_ACTOR_MAX_AGENTS = 32;
 struct ActorTab {
@@ -95,16 +121,24 @@ __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // ro
 // LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
 //               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) |
 //               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
-//               activations [4][32][H + 4]
+//               (GRU: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]) |
+//               activations [4][32][H + 4] | (GRU: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32))
 // (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
 __host__ __device__ constexpr int actor_in_pad(int n) { return (6 * n + 3) / 4 * 4; }
 __host__ __device__ constexpr int actor_norm_floats(int n, int h, bool lnorm) { return lnorm ? 4 * h + 2 * actor_in_pad(n) : 0; }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false> constexpr int actor_lds_floats() {
-    return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
-           actor_norm_floats(NC, H, LNORM) + (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H);
+__host__ __device__ constexpr int actor_state_rows(int n) {
+    return (actor_envs(n) * n + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS * FG_ACTOR_ROWS;
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false> constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM>() * (int)sizeof(float);
+__host__ __device__ constexpr int actor_gru_floats(int h, bool gru) { return gru ? 6 * h : 0; }
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false>
+constexpr int actor_lds_floats() {
+    return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
+           actor_norm_floats(NC, H, LNORM) + actor_gru_floats(H, GRU) +
+           (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0);
+}
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false>
+constexpr int actor_lds_bytes() {
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -193,8 +227,9 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const Args a, const ActorW w) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = false;
+    constexpr bool LNORM = false, GRU = false;
     constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -206,8 +241,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Args a, const ActorW w, const float* log_std,
                                                                          float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = false;
+    constexpr bool LNORM = false, GRU = false;
     constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
 #include "fg_actor_rollout_body.inc"
 }
@@ -216,8 +252,9 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Ar
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_actor_kernel(const Args a, const ActorTab tab) {
     constexpr bool SAMPLE = false, PER_AGENT = true;
-    constexpr bool LNORM = false;
+    constexpr bool LNORM = false, GRU = false;
     constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -229,8 +266,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args a, const ActorTab tab, const float* log_std,
                                                                       float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = true;
-    constexpr bool LNORM = false;
+    constexpr bool LNORM = false, GRU = false;
     constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
 #include "fg_actor_rollout_body.inc"
 }
@@ -239,7 +277,8 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args 
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_actor_kernel(const Args a, const ActorW w, const ActorNormW nw) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = true;
+    constexpr bool LNORM = true, GRU = false;
+    constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -251,7 +290,30 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
                                                                       const float* log_std, float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = true;
+    constexpr bool LNORM = true, GRU = false;
+    constexpr ActorGruW gw{};
+    constexpr ActorTab tab{};
+#include "fg_actor_rollout_body.inc"
+}
+
+// GRU = true: the LayerNorm actor with the recurrent layer `gw` before its head (the deterministic actor).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_actor_kernel(const Args a, const ActorW w, const ActorNormW nw,
+                                                                      const ActorGruW gw) {
+    constexpr bool SAMPLE = false, PER_AGENT = false;
+    constexpr bool LNORM = true, GRU = true;
+    constexpr ActorTab tab{};
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// GRU = true, SAMPLE = true: the recurrent mean with actor_sample_kernel's Gaussian.
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
+                                                                       const ActorGruW gw, const float* log_std, float* logp) {
+    constexpr bool SAMPLE = true, PER_AGENT = false;
+    constexpr bool LNORM = true, GRU = true;
     constexpr ActorTab tab{};
 #include "fg_actor_rollout_body.inc"
 }

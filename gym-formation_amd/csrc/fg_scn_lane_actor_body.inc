@@ -8,6 +8,10 @@
     static_assert(!FG_F64, "the actor rollout is an fp32 kernel");
     constexpr bool LNORM = false;                       // no LayerNorm actor in the landmark scenarios' launch
     constexpr ActorNormW nw{};
+    constexpr bool GRU = false;                         // nor a recurrent one
+    constexpr ActorGruW gw{};
+    float* const gsm = nullptr;
+    float* const hst = nullptr;
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
     constexpr int NE = N + M;

@@ -937,32 +937,37 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
     return launch<Det>(grid, threads, lds, st, fail_fmt, args...);
 }
 // The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
-// per agent (pa_*_kernel) and the shared actor with LayerNorms (ln_*_kernel).  `w`: the kernel's arguments after `a` - an
-// ActorW, an ActorTab, or an ActorW and an ActorNormW.
-template <int NC, int H, bool PER_AGENT, bool LNORM, class... W>
+// per agent (pa_*_kernel), the shared actor with LayerNorms (ln_*_kernel) and the LayerNorm actor with a recurrent layer
+// (gru_*_kernel).  `w`: the kernel's arguments after `a` - an ActorW, an ActorTab, an ActorW and an ActorNormW, or those two
+// and an ActorGruW.
+template <int NC, int H, bool PER_AGENT, bool LNORM, bool GRU = false, class... W>
 static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
     static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
-    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() <= 160 * 1024, "actor rollout LDS");
-    constexpr int E = actor_envs(NC), V = LNORM ? 2 : PER_AGENT ? 1 : 0;
+    static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm actor");
+    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU>() <= 160 * 1024, "actor rollout LDS");
+    constexpr int E = actor_envs(NC), V = GRU ? 3 : LNORM ? 2 : PER_AGENT ? 1 : 0;
     constexpr auto det = [] {
-        if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
+        if constexpr (GRU) return &gru_actor_kernel<NC, H>;
+        else if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
         else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
         else return &actor_rollout_kernel<NC, H>;
     }();
     constexpr auto smp = [] {
-        if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
+        if constexpr (GRU) return &gru_sample_kernel<NC, H>;
+        else if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
         else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
         else return &actor_sample_kernel<NC, H>;
     }();
-    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel"};
-    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel"};
+    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel", "gru_actor_kernel"};
+    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel", "gru_sample_kernel"};
     static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
-                                           "LayerNorm actor rollout launch failed: %s"};
+                                           "LayerNorm actor rollout launch failed: %s",
+                                           "recurrent actor rollout launch failed: %s"};
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
     return launch_actor_pair<det, smp>(
         det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM>(),
+        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM, GRU>(),
         fail_fmt[V], st, log_std, logp, a, w...);
 }
 // The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
@@ -994,38 +999,68 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
 
 // One call of a formation_hd_env actor entry, fg_rollout_hd_actor* or its fg_describe_actor*_launch twin, as its checks
 // (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
-// host array of N members; `norm` counts for HD_ACTOR_NORM only; `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE
-// requires it); `logp`: the log-densities' destination, NULL from a describe twin.
-enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM };
+// host array of N members; `norm` counts for HD_ACTOR_NORM and HD_ACTOR_GRU only; `log_std` NULL: the deterministic actor
+// (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a describe twin; `gru` and `rnn_state`
+// (HD_ACTOR_GRU only): the recurrent layer and the hidden state [B][N][H], a stand-in address from a describe twin.
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
-                                             "fg_rollout_hd_actor_norm"};
+                                             "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru"};
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
     const FgActorNorm* norm;
     const float* log_std;
     float* logp;
+    const FgActorGru* gru = nullptr;
+    float* rnn_state = nullptr;
 };
-// FgActorNorm's checks (no device touched): hidden 32 or 64, every eps that is read positive and finite, gamma / beta 4-byte aligned
-static int actor_norm_check(const FgActor* actor, const FgActorNorm* norm) {
-    if (!norm) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: norm is NULL%s");
-    if (actor->hidden != 32 && actor->hidden != 64)
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: hidden must be 32 or 64 with LayerNorms%s");
+// FgActorNorm's checks (no device touched), in the name of the entry `who`: hidden 32 or 64, every eps that is read positive and
+// finite, gamma / beta 4-byte aligned
+static int actor_norm_check(const char* who, const FgActor* actor, const FgActorNorm* norm) {
+    char msg[160];
+    auto bad = [&](const char* what, const char* arg = "") {
+        snprintf(msg, sizeof(msg), what, who, arg);
+        return fail(FG_ERR_BAD_ARG, "%s", msg);
+    };
+    if (!norm) return bad("%s: norm is NULL");
+    if (actor->hidden != 32 && actor->hidden != 64) return bad("%s: hidden must be 32 or 64 with LayerNorms");
     auto eps_ok = [](float e) { return e > 0.0f && std::isfinite(e); };
-    if (norm->in_norm && !eps_ok(norm->in_eps))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: in_eps must be positive and finite%s");
-    if (!eps_ok(norm->h1_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h1_eps must be positive and finite%s");
-    if (!eps_ok(norm->h2_eps)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: h2_eps must be positive and finite%s");
+    if (norm->in_norm && !eps_ok(norm->in_eps)) return bad("%s: in_eps must be positive and finite");
+    if (!eps_ok(norm->h1_eps)) return bad("%s: h1_eps must be positive and finite");
+    if (!eps_ok(norm->h2_eps)) return bad("%s: h2_eps must be positive and finite");
     const struct { const float* p; const char* name; } ptrs[] = {
         {norm->in_gamma, "in_gamma"}, {norm->in_beta, "in_beta"}, {norm->h1_gamma, "h1_gamma"},
         {norm->h1_beta, "h1_beta"},   {norm->h2_gamma, "h2_gamma"}, {norm->h2_beta, "h2_beta"}};
     for (const auto& q : ptrs)
-        if ((uintptr_t)q.p & 3u) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_norm: %s must be 4-byte aligned", q.name);
+        if ((uintptr_t)q.p & 3u) return bad("%s: %s must be 4-byte aligned", q.name);
+    return FG_OK;
+}
+// FgActorGru's and the hidden state's checks (no device touched): the layer and its four parameter tensors present, the state
+// present where there are envs, norm_eps positive and finite (FG_ERR_BAD_ARG, the message naming the field); then the
+// parameters 4-byte and the state 16-byte aligned (FG_ERR_ALIGNMENT)
+static int actor_gru_check(const FgActorGru* gru, const float* rnn_state, int B) {
+    const char* const who = "fg_rollout_hd_actor_gru";
+    char msg[160];
+    auto bad = [&](int code, const char* what, const char* arg = "") {
+        snprintf(msg, sizeof(msg), what, who, arg);
+        return fail(code, "%s", msg);
+    };
+    if (!gru) return bad(FG_ERR_BAD_ARG, "%s: gru is NULL");
+    const struct { const float* p; const char* name; bool required; } ptrs[] = {
+        {gru->w_ih, "w_ih", true}, {gru->w_hh, "w_hh", true}, {gru->b_ih, "b_ih", true},
+        {gru->b_hh, "b_hh", true}, {gru->norm_gamma, "norm_gamma", false}, {gru->norm_beta, "norm_beta", false}};
+    for (const auto& q : ptrs)
+        if (q.required && !q.p) return bad(FG_ERR_BAD_ARG, "%s: %s is NULL", q.name);
+    if (!rnn_state && B > 0) return bad(FG_ERR_BAD_ARG, "%s: rnn_state is NULL");
+    if (!(gru->norm_eps > 0.0f && std::isfinite(gru->norm_eps))) return bad(FG_ERR_BAD_ARG, "%s: norm_eps must be positive and finite");
+    for (const auto& q : ptrs)
+        if ((uintptr_t)q.p & 3u) return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", q.name);
+    if ((uintptr_t)rnn_state & 15u) return bad(FG_ERR_ALIGNMENT, "%s: rnn_state must be 16-byte aligned");
     return FG_OK;
 }
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
 // this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
-// the norms, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
+// the norms, the recurrent layer with its state, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
 // log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
     const char* const who = hd_actor_entry[c.kind];
@@ -1048,7 +1083,8 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
     } else if ((rc = hd_actor_struct_check(params, c.actor)) != FG_OK) {
         return rc;
     }
-    if (c.kind == HD_ACTOR_NORM && (rc = actor_norm_check(c.actor, c.norm)) != FG_OK) return rc;
+    if ((c.kind == HD_ACTOR_NORM || c.kind == HD_ACTOR_GRU) && (rc = actor_norm_check(who, c.actor, c.norm)) != FG_OK) return rc;
+    if (c.kind == HD_ACTOR_GRU && (rc = actor_gru_check(c.gru, c.rnn_state, B)) != FG_OK) return rc;
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1089,7 +1125,7 @@ static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st
         });
     }
     const ActorW w = actor_w(*c.actor);
-    if (c.kind != HD_ACTOR_NORM)
+    if (c.kind != HD_ACTOR_NORM && c.kind != HD_ACTOR_GRU)
         return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
             return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
         });
@@ -1097,6 +1133,13 @@ static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st
     const bool in_norm = norm.in_norm != 0;
     const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
                            norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
+    if (c.kind == HD_ACTOR_GRU) {
+        const FgActorGru& g = *c.gru;
+        const ActorGruW gw = {g.w_ih, g.w_hh, g.b_ih, g.b_hh, g.norm_gamma, g.norm_beta, g.norm_eps, c.rnn_state};
+        return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true, true>(a, c.log_std, c.logp, st, w, nw, gw);
+        });
+    }
     return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
         return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true>(a, c.log_std, c.logp, st, w, nw);
     });
@@ -1772,6 +1815,17 @@ int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const
                                         obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
+int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                            const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                            float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                            float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                            float* rnn_state, int obs_every, void* stream) {
+    HdActorCall c = {HD_ACTOR_GRU, actor, norm, log_std, logp_seq, gru, rnn_state};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+}
+
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1812,6 +1866,13 @@ int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, 
                                   int B, int N, int K, int obs_every, char* out, int out_len) {
     return describe_actor_impl("fg_describe_actor_norm_launch", params, {HD_ACTOR_NORM, actor, norm, log_std, nullptr}, B, N, K,
                                obs_every, out, out_len);
+}
+
+int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                 const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // a stand-in: the dry run has no hidden state
+    return describe_actor_impl("fg_describe_actor_gru_launch", params, {HD_ACTOR_GRU, actor, norm, log_std, nullptr, gru, state},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,

@@ -115,6 +115,24 @@ def actor_norm(norms):
                        0 if n0 is None else 1)
 
 
+class FgActorGru(ctypes.Structure):
+    """Mirror of `struct FgActorGru` (include/formation_hip.h): the recurrent layer of fg_rollout_hd_actor_gru's actor and the
+    LayerNorm after it."""
+    _fields_ = [
+        ("w_ih", ctypes.c_void_p), ("w_hh", ctypes.c_void_p),
+        ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+        ("norm_gamma", ctypes.c_void_p), ("norm_beta", ctypes.c_void_p),
+        ("norm_eps", ctypes.c_float),
+    ]
+
+
+def actor_gru(gru):
+    """FgActorGru of an `actor_rollout.ActorGru`: the GRU's four parameter tensors and (weight, bias, eps) of the norm after
+    it; a None norm tensor is a NULL pointer (weight 1, bias 0)."""
+    g, b, eps = gru.norm
+    return FgActorGru(ptr(gru.w_ih), ptr(gru.w_hh), ptr(gru.b_ih), ptr(gru.b_hh), ptr(g), ptr(b), eps)
+
+
 class FormationHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libformation_hip: status %d: %s" % (code, msg))
@@ -174,6 +192,10 @@ SIGNATURES = {
                                  + [_I, _P]),
     "fg_describe_actor_norm_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), _P, _I, _I, _I, _I,
                                            ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_gru": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru), _P,
+                                     _I, _I, _I] + [_P] * 14 + [_I, _P]),
+    "fg_describe_actor_gru_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru),
+                                          _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,

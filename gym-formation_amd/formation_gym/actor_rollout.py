@@ -17,6 +17,15 @@ Host-paced: H = 128 with norms, a single hidden norm, a norm before the ReLU or 
 axis, norm parameters in another dtype, non-contiguous or off the device, PerAgentActor members with norms, and any LayerNorm
 actor in the landmark scenarios (their `actor_fused_rule` states `fused_ln_hidden=()`: no such kernel).
 
+A `RecurrentActor(base, rnn, norm, head)` is rMAPPO's policy (onpolicy's R_Actor with use_recurrent_policy, recurrent_N = 1):
+the LayerNorm body without its last Linear, one GRU step on a hidden state carried from step to step and zeroed where an episode
+ended, a LayerNorm, and the action head.  It fuses (`fg_rollout_hd_actor_gru`, gru_actor_kernel / gru_sample_kernel) under the
+LayerNorm actor's rule with H in FUSED_GRU_HIDDEN = {32, 64}, `rnn` an nn.GRUCell(H, H) or a single-layer unidirectional
+nn.GRU(H, H) with biases, `norm` a LayerNorm(H) as above and `head` Linear(H, 2) or Sequential(Linear(H, 2), Tanh()), alone or as
+a GaussianActor's mean, in formation_hd_env only.  Host-paced (the same loop in Python, with the same state handling): a base
+without norms, H = 128, a multi-layer or bidirectional GRU, a missing norm after the GRU, recurrent PerAgentActor members, and
+the landmark scenarios (`fused_gru_hidden=()`).
+
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
 
@@ -40,6 +49,7 @@ LOG_2PI = math.log(2.0 * math.pi)
 FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)
 FUSED_HIDDEN = (32, 64, 128)
 FUSED_LN_HIDDEN = (32, 64)             # hidden widths of the LayerNorm actor's kernels (ln_actor_kernel / ln_sample_kernel)
+FUSED_GRU_HIDDEN = (32, 64)            # hidden widths of the recurrent actor's kernels (gru_actor_kernel / gru_sample_kernel)
 # the landmark scenarios: (scenario kind, agents, landmarks, obstacles, neighbours observed) -> fused; kind as _native.FG_SCN_*
 LANDMARK_FUSED_SHAPES = ((1, 3, 3, 0, 2), (2, 5, 5, 0, 3), (2, 3, 5, 0, 3), (3, 4, 4, 0, 3), (3, 3, 4, 0, 2),
                          (4, 4, 4, 3, 3), (4, 3, 4, 3, 2))
@@ -58,7 +68,7 @@ def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_
 
 
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-               fused_ln_hidden=FUSED_LN_HIDDEN):
+               fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], norms) when a fused kernel can evaluate the shared actor body `actor` for
     `num_agents` agents, else None.  The two forms, each with its own kernels and so its own hidden widths:
         Sequential(Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])              H in `fused_hidden`
@@ -68,13 +78,20 @@ def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     fp32 contiguous parameters on `device` or none.  `device`: the env's device (None: not checked).  The tensors are the
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
-    are built for (None or empty: it has no kernel for that form)."""
+    are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact, not read
+    here."""
+    if type(actor) is not torch.nn.Sequential:
+        return None
+    return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden)
+
+
+def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden):
+    """`_body_spec` of the body whose modules, in order, are `mods`."""
     nn = torch.nn
-    if type(actor) is not nn.Sequential or int(num_agents) not in fused_n:
+    if int(num_agents) not in fused_n:
         return None
     if in_features is None:
         in_features = 6 * int(num_agents)
-    mods = list(actor)
     lead = bool(mods) and type(mods[0]) is nn.LayerNorm
     rest = mods[1:] if lead else mods
     kinds = [type(m) for m in rest]
@@ -156,6 +173,110 @@ def _norm_triple(m, width, device):
     return g, b, eps
 
 
+class RecurrentActor(torch.nn.Module):
+    """rMAPPO's recurrent policy (onpolicy's R_Actor with use_recurrent_policy): `forward(obs [..., D], h [..., H])` returns
+    (action [..., 2], h' [..., H]) with
+        x = base(obs);  h' = GRU(x, h);  action = head(norm(h'))
+    one step of torch.nn.GRUCell (gate order r | z | n): r = sigmoid(W_ir x + b_ir + W_hr h + b_hr), z likewise,
+    n = tanh(W_in x + b_in + r * (W_hn h + b_hn)), h' = (1 - z) * n + z * h.  The state carried on is h', before the norm
+    (as onpolicy's RNNLayer does).  `rnn`: an nn.GRUCell(H, H) or a single-layer unidirectional nn.GRU(H, H) - one parameter
+    naming (weight_ih[_l0] ...) and one function (`torch.gru_cell`) for both, so the two give the same bits; any other nn.GRU
+    is called as a module on a one-step sequence, its state [..., num_layers * directions * H] (layer-major).  `norm`:
+    nn.LayerNorm(H), or None for none.  `head`: nn.Linear(H, 2) or Sequential(Linear(H, 2), Tanh()).
+    `env.rollout_actor(K, actor, rnn_state=h)` runs the loop with it, zeroing h where a step ended an episode."""
+
+    def __init__(self, base, rnn, norm, head):
+        super().__init__()
+        self.base, self.rnn, self.norm, self.head = base, rnn, norm, head
+
+    def gru_parameters(self):
+        """(weight_ih, weight_hh, bias_ih, bias_hh) of a GRUCell or of layer 0 of a GRU (a missing bias: None); None for
+        any other module."""
+        rnn = self.rnn
+        if not isinstance(rnn, (torch.nn.GRUCell, torch.nn.GRU)):
+            return None
+        sfx = "" if isinstance(rnn, torch.nn.GRUCell) else "_l0"
+        return tuple(getattr(rnn, name + sfx, None) for name in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+    def _one_cell(self):
+        rnn = self.rnn
+        return isinstance(rnn, torch.nn.GRUCell) or (isinstance(rnn, torch.nn.GRU) and rnn.num_layers == 1
+                                                     and not rnn.bidirectional and getattr(rnn, "proj_size", 0) == 0)
+
+    @property
+    def state_size(self):
+        rnn = self.rnn
+        if self._one_cell():
+            return int(rnn.hidden_size)
+        return int(rnn.num_layers) * (2 if rnn.bidirectional else 1) * int(rnn.hidden_size)
+
+    def initial_state(self, *batch_shape):
+        """Zeros [*batch_shape, H] on the parameters' device: the state of a fresh episode."""
+        p = next(self.rnn.parameters())
+        return torch.zeros(tuple(batch_shape) + (self.state_size,), dtype=p.dtype, device=p.device)
+
+    def forward(self, obs, h):
+        x = self.base(obs)
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, x.shape[-1])
+        if self._one_cell():
+            h_new = torch.gru_cell(x2, h.reshape(-1, h.shape[-1]), *self.gru_parameters())
+            y = h_new
+        else:
+            rnn = self.rnn
+            layers = self.state_size // int(rnn.hidden_size)
+            h0 = h.reshape(-1, layers, int(rnn.hidden_size)).transpose(0, 1).contiguous()
+            out, hn = rnn(x2.unsqueeze(1) if rnn.batch_first else x2.unsqueeze(0), h0)
+            y = out.squeeze(1) if rnn.batch_first else out.squeeze(0)
+            h_new = hn.transpose(0, 1).reshape(-1, self.state_size)
+        y = y.reshape(lead + (y.shape[-1],))
+        if self.norm is not None:
+            y = self.norm(y)
+        return self.head(y), h_new.reshape(lead + (h_new.shape[-1],))
+
+
+class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
+    """The recurrent layer of a fused RecurrentActor (`_recurrent_spec`): the GRU's own parameter tensors ([3H, H], [3H, H],
+    [3H], [3H]) and `norm`, the (weight, bias, eps) triple of the LayerNorm after it (`_norm_triple`)."""
+    __slots__ = ()
+
+
+def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
+                    fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms, ActorGru) when the fused recurrent kernel can evaluate the
+    RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
+    of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
+    one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
+    parameter fp32, contiguous and on `device`."""
+    nn = torch.nn
+    if type(actor) is not RecurrentActor or type(actor.base) is not nn.Sequential:
+        return None
+    head = actor.head
+    if type(head) is nn.Linear:
+        head_mods = [head]
+    elif type(head) is nn.Sequential and [type(m) for m in head] == [nn.Linear, nn.Tanh]:
+        head_mods = list(head)
+    else:
+        return None
+    spec = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden)
+    if spec is None or spec[3] is None:
+        return None
+    H = spec[0]
+    rnn = actor.rnn
+    if type(rnn) not in (nn.GRUCell, nn.GRU) or not actor._one_cell() or (rnn.input_size, rnn.hidden_size) != (H, H):
+        return None
+    dev = None if device is None else torch.device(device)
+    params = actor.gru_parameters()
+    for t, shape in zip(params, ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
+                or not _on_device(t, dev):
+            return None
+    norm = _norm_triple(actor.norm, H, dev)
+    if norm is None:
+        return None
+    return spec + (ActorGru(*params, norm),)
+
+
 class PerAgentActor(torch.nn.Module):
     """One actor per agent (no parameter sharing): `actors[i]` maps agent i's observation rows [..., 6N] to its actions
     [..., 2].  `forward(obs [..., N, 6N])` returns [..., N, 2] with out[..., i, :] = actors[i](obs[..., i, :]), which is
@@ -196,19 +317,28 @@ class GaussianActor(torch.nn.Module):
             log_std = torch.zeros(2)
         self.log_std = log_std if isinstance(log_std, torch.nn.Parameter) else torch.nn.Parameter(torch.as_tensor(log_std))
 
-    def forward(self, obs):
-        mu = self.mean(obs)
-        return mu + torch.exp(self.log_std) * torch.randn_like(mu)
+    def _mean(self, obs, rnn_state):
+        """mean(obs), or for a RecurrentActor mean with its state the action part of mean(obs, rnn_state)."""
+        return self.mean(obs) if rnn_state is None else self.mean(obs, rnn_state)[0]
 
-    def distribution(self, obs):
-        """torch.distributions.Normal(mean(obs), exp(log_std)) of the per-component actions."""
-        mu = self.mean(obs)
+    def forward(self, obs, rnn_state=None):
+        """The sampled action; with `rnn_state` (a RecurrentActor mean's hidden state) the pair (action, new state)."""
+        if rnn_state is None:
+            mu = self.mean(obs)
+            return mu + torch.exp(self.log_std) * torch.randn_like(mu)
+        mu, h = self.mean(obs, rnn_state)
+        return mu + torch.exp(self.log_std) * torch.randn_like(mu), h
+
+    def distribution(self, obs, rnn_state=None):
+        """torch.distributions.Normal(mean(obs), exp(log_std)) of the per-component actions (`rnn_state`: a recurrent mean's
+        hidden state)."""
+        mu = self._mean(obs, rnn_state)
         return torch.distributions.Normal(mu, torch.exp(self.log_std).expand_as(mu))
 
-    def log_prob(self, obs, act):
-        """Log-density of `act` [..., 2] under the policy at `obs`, summed over the last axis (the PPO ratio's input);
-        differentiable in the mean's parameters and in log_std."""
-        z = (act - self.mean(obs)) * torch.exp(-self.log_std)
+    def log_prob(self, obs, act, rnn_state=None):
+        """Log-density of `act` [..., 2] under the policy at `obs` (`rnn_state`: a recurrent mean's hidden state), summed over
+        the last axis (the PPO ratio's input); differentiable in the mean's parameters and in log_std."""
+        z = (act - self._mean(obs, rnn_state)) * torch.exp(-self.log_std)
         return -0.5 * (z * z).sum(-1) - self.log_std.sum() - LOG_2PI
 
     def entropy(self):
@@ -249,11 +379,13 @@ def _fused_log_std(actor, device):
     return ls
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms", defaults=(None,))):
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru",
+                                        defaults=(None, None))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
     N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
-    ActorNorms of a LayerNorm actor (None: the actor has no LayerNorm)."""
+    ActorNorms of a LayerNorm actor (None: the actor has no LayerNorm), and `gru`, the ActorGru of a RecurrentActor (None: the
+    actor keeps no state), whose body is then `members[0]` with `norms` and whose head is w3, b3."""
     __slots__ = ()
 
 
@@ -267,7 +399,8 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     fused_n, fused_hidden, fused_ln_hidden), as the scenario states them.  A GaussianActor is unwrapped once, into its mean and
     its log_std; the mean - or the actor itself - is a PerAgentActor (per_agent_spec: members without LayerNorms) or a shared
     body (`_body_spec`: with LayerNorms where the scenario has such a kernel - formation_hd_env, H in {32, 64}; the landmark
-    scenarios state `fused_ln_hidden=()`)."""
+    scenarios state `fused_ln_hidden=()`) or a RecurrentActor (`_recurrent_spec`: formation_hd_env, H in {32, 64}; the landmark
+    scenarios state `fused_gru_hidden=()`)."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return None
     mean, log_std = actor, None
@@ -278,13 +411,22 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     members_own = isinstance(mean, PerAgentActor)
     if members_own:
         spec = per_agent_spec(mean, num_agents, device) if per_agent else None
-        spec = None if spec is None else spec + (None,)
+        spec = None if spec is None else spec + (None, None)
+    elif isinstance(mean, RecurrentActor):
+        spec = _recurrent_spec(mean, num_agents, device, **facts)
     else:
         spec = _body_spec(mean, num_agents, device, **facts)
+        spec = None if spec is None else spec + (None,)
     if spec is None:
         return None
-    hidden, out_tanh, weights, norms = spec
-    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms)
+    hidden, out_tanh, weights, norms, gru = spec
+    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms, gru)
+
+
+def recurrent_mean(actor):
+    """The RecurrentActor that `actor` is or, for a GaussianActor, has as its mean; else None: the actor keeps no state."""
+    mean = actor.mean if isinstance(actor, GaussianActor) else actor
+    return mean if isinstance(mean, RecurrentActor) else None
 
 
 def actor_path(actor, num_agents, device=None, **facts):

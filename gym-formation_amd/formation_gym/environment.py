@@ -384,7 +384,7 @@ class MultiAgentEnv(object):
         rule = getattr(self.scenario, "actor_fused_rule", None)
         return {} if rule is None else rule(self.world)
 
-    def rollout_actor(self, K, actor, out=None, obs_every=1):
+    def rollout_actor(self, K, actor, out=None, obs_every=1, rnn_state=None):
         """The loop of a learned actor for K steps in one call:
             act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
         from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
@@ -413,15 +413,31 @@ class MultiAgentEnv(object):
         (`fg_rollout_hd_actor_norm`), alone or as a GaussianActor's mean with the same eps draws and log_prob; its norm
         parameters are read in place like the weights.  Host-paced: H = 128 with norms, any other placement of norms, norm
         parameters in another dtype / non-contiguous / off the device, PerAgentActor members with norms, and a LayerNorm
-        actor in the landmark scenarios."""
+        actor in the landmark scenarios.
+        A `RecurrentActor(base, rnn, norm, head)` (rMAPPO's policy), alone or as a GaussianActor's mean, carries a hidden
+        state through the loop:
+            a, h = actor(obs, h); obs, rew, done, info = env.step(a); h = h * ~done[..., None]
+        (the step's own done flags, whether or not `auto_reset` is set).  `rnn_state`: a contiguous fp32 [B, N, H] tensor on
+        the env's device, read as the state step 0 acts with, updated in place to the state after step K - 1 (already masked
+        by that step's done flags) and returned as info['rnn_state']; None: a fresh zero tensor per call.  A K-step call
+        equals K one-step calls that pass the state along, bit for bit, and so does any other split of K.  It fuses
+        (`fg_rollout_hd_actor_gru`, the state on chip for the whole launch) in formation_hd_env when its base with its head
+        is the LayerNorm actor above, H in {32, 64}, `rnn` is an nn.GRUCell(H, H) or a single-layer unidirectional
+        nn.GRU(H, H) with biases and `norm` a LayerNorm(H); anything else - and the landmark scenarios - runs this loop
+        host-paced.  `rnn_state` with an actor that keeps no state raises ValueError."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
         if K < 1 or obs_every < 1:
             raise ValueError("need K >= 1 steps and obs_every >= 1")
+        recurrent = actor_rollout.recurrent_mean(actor)
+        if recurrent is None and rnn_state is not None:
+            raise ValueError("rnn_state given, but the actor is not a RecurrentActor (nor a GaussianActor with one as its mean)")
+        if recurrent is not None:
+            rnn_state = self._rnn_state(recurrent, rnn_state)
         fused = self._resolve_actor(actor)
         if fused is None:
-            return self._rollout_actor_by_steps(K, actor, obs_every)
+            return self._rollout_actor_by_steps(K, actor, obs_every, rnn_state)
         log_std = fused.log_std
         gaussian = log_std is not None
         B, N = self.num_envs, self.num_agents
@@ -450,6 +466,8 @@ class MultiAgentEnv(object):
                    0 if log_std is None else log_std.data_ptr(),
                    None if fused.norms is None else tuple(
                        None if n is None else (_native.ptr(n[0]), _native.ptr(n[1]), n[2]) for n in fused.norms),
+                   None if fused.gru is None else tuple(_native.ptr(t) for t in fused.gru[:4] + fused.gru.norm[:2])
+                   + (fused.gru.norm[2], rnn_state.data_ptr()),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))
@@ -458,8 +476,9 @@ class MultiAgentEnv(object):
             for k, shp in want.items():
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
+            extra = {} if fused.gru is None else {"rnn_state": rnn_state}
             launch = self.scenario.bind_rollout_actor(self.world, K, fused, out, obs_every=obs_every,
-                                                      auto_reset=self.auto_reset)
+                                                      auto_reset=self.auto_reset, **extra)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()
@@ -473,7 +492,21 @@ class MultiAgentEnv(object):
         info = {"individual_reward": out["indiv"], "actions": out["act"]}
         if gaussian:
             info["log_prob"] = out["log_prob"]
+        if fused.gru is not None:
+            info["rnn_state"] = rnn_state
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
+
+    def _rnn_state(self, recurrent, rnn_state):
+        """The hidden state `rollout_actor` runs the RecurrentActor `recurrent` with: the caller's tensor, checked - contiguous
+        fp32 [B, N, H] on the env's device - or, for None, fresh zeros."""
+        shape = (self.num_envs, self.num_agents, recurrent.state_size)
+        dev = self.world.device
+        if rnn_state is None:
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+        if not torch.is_tensor(rnn_state) or rnn_state.dtype != torch.float32 or tuple(rnn_state.shape) != shape \
+                or not rnn_state.is_contiguous() or not actor_rollout._on_device(rnn_state, dev):
+            raise ValueError("rnn_state must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
+        return rnn_state
 
     def actor_noise(self, out=None):
         """The exploration noise eps [B, N, 2] that a GaussianActor's next step draws (`fg_actor_noise` at the offset of the
@@ -495,12 +528,16 @@ class MultiAgentEnv(object):
                                                        _native.current_stream(self.world.device)))
         return out
 
-    def _rollout_actor_by_steps(self, K, actor, obs_every):
+    def _rollout_actor_by_steps(self, K, actor, obs_every, rnn_state=None):
         """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
         launch's (fresh tensors).  A GaussianActor: mean(obs) + exp(log_std) * eps with eps from `actor_noise`, the draws
         of the fused kernel, and the log-density from eps by the kernel's own device function (`fg_actor_log_prob`): for the
-        same eps and log_std, the fused launch's bits."""
+        same eps and log_std, the fused launch's bits.  A RecurrentActor (alone or as the mean): `rnn_state` [B, N, H] goes
+        through the loop - a, h = actor(obs, h), then h zeroed where the step's done flag is set - is updated in place at the
+        end and comes back as info['rnn_state']."""
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
+        recurrent = rnn_state is not None
+        h = rnn_state.clone() if recurrent else None
         observe = getattr(self.scenario, "observe_batch", None)
         if observe is not None:                            # the observation of the current state (a multi-step launch
             observe(self.world, {"obs": self._out["obs"]})  # leaves the env's own step buffer behind)
@@ -511,8 +548,14 @@ class MultiAgentEnv(object):
                 if gaussian:
                     eps = self.actor_noise()
                     ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
-                    act = actor.mean(obs) + torch.exp(ls) * eps
+                    if recurrent:
+                        mu, h = actor.mean(obs, h)
+                    else:
+                        mu = actor.mean(obs)
+                    act = mu + torch.exp(ls) * eps
                     res["logp"].append(self._noise_log_prob(eps, ls))
+                elif recurrent:
+                    act, h = actor(obs, h)
                 else:
                     act = actor(obs)
                 res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
@@ -520,9 +563,14 @@ class MultiAgentEnv(object):
                 if (k + 1) % obs_every == 0:
                     res["obs"].append(obs.clone())
                 res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
+                if recurrent:
+                    h = h * (~torch.as_tensor(d, device=h.device).view(torch.bool).reshape(h.shape[:-1] + (1,))).to(h.dtype)
         info = {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])}
         if gaussian:
             info["log_prob"] = torch.stack(res["logp"])
+        if recurrent:
+            rnn_state.copy_(h)
+            info["rnn_state"] = rnn_state
         return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
                 torch.stack(res["done"]), info)
 

@@ -253,19 +253,25 @@ class Scenario(BaseScenario):
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(lib.fg_rollout_hd_policy, p, *args, keep=out)
 
-    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
+    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
-        other tensors are those of `rollout_batch`.  The entry point by (norms, per_agent, log_std):
+        other tensors are those of `rollout_batch`.  The entry point by (gru, norms, per_agent, log_std):
           one shared actor                      `fg_rollout_hd_actor`
           ... with a GaussianActor's log_std    `fg_rollout_hd_actor_sample`, the log-densities in out["log_prob"] [K,B,N]
           one actor per agent                   `fg_rollout_hd_actor_per_agent` (log_std or NULL), agent i's rows through
                                                 member i's weights
-          one shared actor with LayerNorms      `fg_rollout_hd_actor_norm` (log_std or NULL), `actor.norms` as FgActorNorm"""
+          one shared actor with LayerNorms      `fg_rollout_hd_actor_norm` (log_std or NULL), `actor.norms` as FgActorNorm
+          ... with a recurrent layer            `fg_rollout_hd_actor_gru` (log_std or NULL), `actor.gru` as FgActorGru and
+                                                `rnn_state` [B,N,H], read and updated in place by every launch and kept alive
+                                                by the launcher like the GRU's tensors"""
         lib = _native.load()
         log_std = actor.log_std
         norm = None if actor.norms is None else _native.actor_norm(actor.norms)
+        gru = None if actor.gru is None else _native.actor_gru(actor.gru)
+        if gru is not None and rnn_state is None:
+            raise ValueError("a recurrent actor's launch needs its rnn_state")
         fas = (_native.FgActor * len(actor.members))(*[
             _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
         p = self.params(world, auto_reset, 0, out.get("obs"))
@@ -276,20 +282,26 @@ class Scenario(BaseScenario):
                  _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                  _native.ptr(out.get("done")))
         tail = (int(obs_every), _native.current_stream(world.device))
-        # (norms, per_agent, gaussian) -> (entry point, its arguments before the state, logp_seq follows the state)
+        # (gru, norms, per_agent, gaussian) -> (entry point, its arguments before the state, logp_seq follows the state);
+        # the recurrent entry's rnn_state follows logp_seq
         ls = _native.ptr(log_std)
         pa, ln = (lib.fg_rollout_hd_actor_per_agent, (fas, ls), True), (lib.fg_rollout_hd_actor_norm, (fas, norm, ls), True)
-        table = {(False, False, False): (lib.fg_rollout_hd_actor, (fas,), False),
-                 (False, False, True): (lib.fg_rollout_hd_actor_sample, (fas, ls), True),
-                 (False, True, False): pa, (False, True, True): pa, (True, False, False): ln, (True, False, True): ln}
-        key = (norm is not None, bool(actor.per_agent), log_std is not None)
+        gr = (lib.fg_rollout_hd_actor_gru, (fas, norm, gru, ls), True)
+        table = {(False, False, False, False): (lib.fg_rollout_hd_actor, (fas,), False),
+                 (False, False, False, True): (lib.fg_rollout_hd_actor_sample, (fas, ls), True),
+                 (False, False, True, False): pa, (False, False, True, True): pa,
+                 (False, True, False, False): ln, (False, True, False, True): ln,
+                 (True, True, False, False): gr, (True, True, False, True): gr}
+        key = (gru is not None, norm is not None, bool(actor.per_agent), log_std is not None)
         if key not in table:
-            raise NotImplementedError("PerAgentActor members with LayerNorms have no fused launch")
+            raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
         fn, lead, with_logp = table[key]
         logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
-        args = lead + state + logp + tail
+        hidden = () if gru is None else (rnn_state.data_ptr(),)
+        args = lead + state + logp + hidden + tail
         return _native.bind_launch(fn, p, *args,
-                                   keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm))
+                                   keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
+                                         actor.gru, gru, rnn_state))
 
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the

@@ -81,12 +81,13 @@ class ActorRolloutMixin(object):
         """The facts `actor_rollout.resolve_actor` needs when this world's shape has a fused actor launch - the seven shapes of
         the one-env-per-lane kernel, not the run-time-count kernel (`kernel_variant = 1`) - else None: host-paced.  (World
         options and per-agent properties are `MultiAgentEnv.actor_path`'s own checks, as for formation_hd_env.)
-        `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here."""
+        `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here;
+        `fused_gru_hidden=()`: nor a recurrent one, so a RecurrentActor does too."""
         from formation_gym import actor_rollout
         d = self._actor_descriptor(world)
         facts = actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
                                              self.obs_dim(world), d.variant)
-        return None if facts is None else dict(facts, fused_ln_hidden=())
+        return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=())
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs
@@ -99,6 +100,8 @@ class ActorRolloutMixin(object):
             raise NotImplementedError("one actor per agent has no fused launch in %s" % type(self).__name__)
         if actor.norms is not None:
             raise NotImplementedError("a LayerNorm actor has no fused launch in %s" % type(self).__name__)
+        if actor.gru is not None:
+            raise NotImplementedError("a recurrent actor has no fused launch in %s" % type(self).__name__)
         weights, log_std = actor.members[0], actor.log_std
         fa = _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in weights])
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)

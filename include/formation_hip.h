@@ -549,6 +549,46 @@ int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const
 int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
                                   int B, int N, int K, int obs_every, char* out, int out_len);
 
+/* The recurrent layer of fg_rollout_hd_actor_gru's actor (rMAPPO's policy: onpolicy's R_Actor with use_recurrent_policy and
+ * recurrent_N = 1), between the LayerNorm body and the action head:
+ *     [LayerNorm(6N) -] Linear(6N, hidden) - ReLU - LayerNorm(hidden) - Linear(hidden, hidden) - ReLU - LayerNorm(hidden) -
+ *     GRU(hidden, hidden) - LayerNorm(hidden) - Linear(hidden, 2) [- tanh]
+ * One step of torch.nn.GRUCell / a single-layer unidirectional torch.nn.GRU per actor evaluation, gate order r | z | n:
+ *     r = sigmoid(W_ir x + b_ir + W_hr h + b_hr),  z = sigmoid(W_iz x + b_iz + W_hz h + b_hz),
+ *     n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),  h' = (1 - z) * n + z * h
+ * h' is the state carried to the next step; the head sees LayerNorm(h').  All tensors fp32 in DEVICE memory, torch's layout
+ * (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0), read in place by every launch; the four of them are required.
+ * norm_gamma / norm_beta: the LayerNorm after the GRU, NULL is the identity (gamma 1, beta 0); norm_eps positive and finite. */
+typedef struct FgActorGru {
+    const float* w_ih;       /* [3 hidden][hidden] */
+    const float* w_hh;       /* [3 hidden][hidden] */
+    const float* b_ih;       /* [3 hidden] */
+    const float* b_hh;       /* [3 hidden] */
+    const float* norm_gamma; /* [hidden] or NULL */
+    const float* norm_beta;  /* [hidden] or NULL */
+    float norm_eps;
+} FgActorGru;
+
+/* fg_rollout_hd_actor_norm with the recurrent layer `gru` between the body and its last Linear (gru_actor_kernel, or
+ * gru_sample_kernel when log_std is not NULL): `actor` and `norm` describe the body, actor->w3 / b3 the head on
+ * LayerNorm(h').  The loop of the launch, for k = 0 .. K - 1:
+ *     a, h = actor(obs, h);  obs, ..., done = env.step(a);  h = 0 in every env whose step k ended its episode
+ * (the step's own done flag, whether or not params->auto_reset is set).  rnn_state [B][N][hidden], fp32, 16-byte aligned, is
+ * the state step 0 acts with and receives the state after step K - 1, already masked; in between it lives on chip.  A K-step
+ * call equals K one-step calls that pass the state along, bit for bit.  actor->hidden: 32 or 64.  Every other argument,
+ * check and status code is fg_rollout_hd_actor_norm's, in this entry's name; then FG_ERR_BAD_ARG, the message naming the
+ * field, for a NULL gru, a NULL w_ih / w_hh / b_ih / b_hh, a NULL rnn_state with B > 0, or a norm_eps that is not positive
+ * and finite, and FG_ERR_ALIGNMENT for a gru pointer that is not 4-byte or an rnn_state that is not 16-byte aligned. */
+int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                            const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                            float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                            float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                            float* rnn_state, int obs_every, void* stream);
+/* Dry run of fg_rollout_hd_actor_gru: same checks and status codes (rnn_state's apart), names the gru_actor_kernel<N,H> or
+ * gru_sample_kernel<N,H> instantiation and its launch geometry.  Touches no device. */
+int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                 const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
+
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
  * (scn_lane_actor, or scn_lane_actor_gauss when log_std is not NULL), with the actor
