@@ -30,70 +30,20 @@ import torch
 
 from formation_gym import GaussianActor, _native
 from formation_gym.actor_rollout import FUSED_N
-from tests.actor_testlib import (ACT_SCALE, B, DEV, K, Wrap as _Wrap, clone as _clone, current_obs as _current_obs, env as _env,
+from tests.actor_fidelity import EDGE_EPS, TOL, ln_actor, ln_fidelity as _fidelity, ln_ref64 as _ref64
+from tests.actor_testlib import (B, DEV, K, Wrap as _Wrap, clone as _clone, current_obs as _current_obs, env as _env,
                                  logp_formula as _logp_formula, noise_at as _noise_at, obs_before as _obs_before, state as _state)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-5
 # (N, H, input norm, tanh): every N at H = 64, alternating with and without the input norm, plus two shapes at H = 32
 CASES = [(n, 64, i % 2 == 0, i % 4 < 2) for i, n in enumerate(FUSED_N)] + [(9, 32, False, True), (27, 32, True, False)]
 nn = torch.nn
 
 
-def _ln_actor(N, H, in_norm, tanh=False, seed=0, zero_head=False, eps=1e-5):
-    torch.manual_seed(seed)
-    D = 6 * N
-    mods = [nn.LayerNorm(D, eps=eps)] if in_norm else []
-    mods += [nn.Linear(D, H), nn.ReLU(), nn.LayerNorm(H, eps=eps), nn.Linear(H, H), nn.ReLU(), nn.LayerNorm(H, eps=eps), nn.Linear(H, 2)]
-    if tanh:
-        mods.append(nn.Tanh())
-    m = nn.Sequential(*mods)
-    with torch.no_grad():
-        for mod in m:
-            if isinstance(mod, nn.Linear):                       # PyTorch's default initialisation, scaled
-                mod.weight.mul_(ACT_SCALE)
-                mod.bias.mul_(ACT_SCALE)
-            elif isinstance(mod, nn.LayerNorm):                  # gamma / beta away from 1 / 0
-                mod.weight.add_(0.25 * torch.randn_like(mod.weight))
-                mod.bias.add_(0.2 * torch.randn_like(mod.bias))
-        if zero_head:
-            head = [mod for mod in m if isinstance(mod, nn.Linear)][-1]
-            head.weight.zero_()
-            head.bias.zero_()
-    return m.to(DEV)
-
-
-def _ref64(ref, o):
-    """The fp64 actor `ref` on observations o [..., D]: (actions, r1, r2, first ReLU output), r1 / r2 the rows' rstd of the two
-    hidden LayerNorms ([..., 1])."""
-    x = o
-    rstd, relu1 = [], None
-    mods = list(ref)
-    for idx, mod in enumerate(mods):
-        if isinstance(mod, nn.LayerNorm) and idx > 0:
-            rstd.append(1.0 / torch.sqrt(x.var(-1, unbiased=False, keepdim=True) + mod.eps))
-        x = mod(x)
-        if isinstance(mod, nn.ReLU) and relu1 is None:
-            relu1 = x
-    assert len(rstd) == 2
-    return x, rstd[0], rstd[1], relu1
-
-
-def _fidelity(actor, obs_before, means, rstd_factor=True, scale=1.0):
-    """max err / bound of means [K,B,N,2] (fp64 or fp32) against the actor in fp64 on obs_before[k]; asserts nothing."""
-    ref = copy.deepcopy(actor).double()
-    worst = 0.0
-    for k in range(len(means)):
-        with torch.no_grad():
-            want, r1, r2, _ = _ref64(ref, obs_before[k].double())
-        bound = scale * TOL * torch.clamp(want.abs(), min=1.0)
-        if rstd_factor:
-            bound = bound * torch.clamp(r1, min=1.0) * torch.clamp(r2, min=1.0)
-        err = (means[k].double() - want).abs()
-        assert bool(torch.isfinite(means[k]).all()), "step %d: a non-finite action" % k
-        worst = max(worst, float((err / bound).max()))
-    return worst
+def _ln_actor(*args, **kwargs):
+    """tests/actor_fidelity.py's `ln_actor` on DEV."""
+    return ln_actor(*args, device=DEV, **kwargs)
 
 
 @pytest.mark.parametrize("N,H,in_norm,tanh", CASES)
@@ -256,7 +206,7 @@ def test_fresh_parameters_seen_by_bound_launcher(N, in_norm):
 @pytest.mark.parametrize("N,H,in_norm,gaussian", [(9, 64, True, True), (25, 32, False, False)])
 def test_c_abi_call_equals_rollout_actor(N, H, in_norm, gaussian):
     env = _env(N)
-    mean = _ln_actor(N, H, in_norm, tanh=True, eps=3e-4)
+    mean = _ln_actor(N, H, in_norm, tanh=True, eps=EDGE_EPS)             # one eps per norm: the fields cannot be permuted
     log_std = nn.Parameter(torch.tensor([0.2, -0.4], device=DEV))
     actor = GaussianActor(mean, log_std) if gaussian else mean
     assert env.actor_path(actor) == "fused"
