@@ -13,8 +13,28 @@
 // Each product is layer 2's: v_mfma_f32_16x16x4_f32 over ascending k, the weights as the B operand from global memory (three
 // gates' fragments per k chunk and column block), x / h as the A operand from LDS.  The gates are element-wise in the
 // accumulator layout (register j of lane l: row 4 (l >> 4) + j, column l & 15 of its tile), where h is read back and h' written
-// to the state and, for the norm and layer 3, over x in the tile.
+// to the state and, for the norm and layer 3, over x in the tile.  Also from the including scope: `off` and `rbase` (the step
+// is off - rbase), `M` (the workgroup's live rows) and `b0`, for the record of the states below.
                 float* const hs = hst + q0 * HS;
+                // The record of the states (gw.states, wave-uniform): hs is the state this step acts with - the physics phase
+                // has zeroed the rows whose last step ended an episode, a workgroup barrier ago - and these rows are this wave's
+                // alone, so the wave stores them itself, before the products, with no barrier of its own.  The pass's rows are one
+                // span of FG_ACTOR_ROWS H floats of entry kstep / states_every, 16 bytes per lane and store (rows stay 16-byte
+                // aligned at the pitch H + 4); rows past the workgroup's agents - a tail workgroup's, the last tile's padding - are
+                // not stored.
+                if (gw.states != nullptr) {
+                    static_assert(HS % 4 == 0 && (FG_ACTOR_ROWS * H / 4) % 64 == 0, "the state's rows are read 16 bytes at a time");
+                    const int kstep = (int)(off - rbase);
+                    if (kstep % gw.states_every == 0) {
+                        float* const dst = gw.states + (((size_t)(kstep / gw.states_every) * a.B + b0) * N + q0) * H;
+#pragma unroll
+                        for (int it = 0; it < FG_ACTOR_ROWS * H / 256; ++it) {
+                            const int idx = it * 64 + lane, srow = idx / (H / 4), c4 = idx % (H / 4);
+                            if (q0 + srow < M)
+                                reinterpret_cast<float4*>(dst)[idx] = *reinterpret_cast<const float4*>(hs + srow * HS + 4 * c4);
+                        }
+                    }
+                }
                 f32x4 az[RT][CB], an[RT][CB], ahn[RT][CB];
                 actor_bias_init(acc, gsm, col);
                 actor_bias_init(az, gsm + H, col);

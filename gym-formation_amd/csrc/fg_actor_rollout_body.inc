@@ -9,7 +9,8 @@
 // on the normalised operand.  `constexpr bool GRU` with `gw` (ActorGruW; GRU = false: an empty constant) selects
 // gru_actor_kernel / gru_sample_kernel, an LNORM body whose pass runs fg_actor_gru.inc between the second hidden norm and layer 3
 // (fg_actor_mlp.inc); here are the hidden state's block in LDS - loaded from gw.state before the first pass, its done envs' rows
-// zeroed by the physics phase, stored back after the last step - and the preload of the layer's biases and norm.
+// zeroed by the physics phase, stored back after the last step (the per-step record gw.states is fg_actor_gru.inc's) - and the
+// preload of the layer's biases and norm.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -44,6 +45,8 @@
     float* const hbuf = wsm + WS + 4 + LNS + GS;
     float* const gsm = wsm + WS + 4 + LNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
     float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
+    static_assert(!GRU || (E * env_block_floats(N) + (SAMPLE ? 3 : 2) * E * N + WS + 4 + LNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
+                  "the hidden state's block is 16-byte aligned (fg_actor_gru.inc stores its rows with 16-byte reads)");
     const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;

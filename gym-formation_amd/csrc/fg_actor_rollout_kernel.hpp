@@ -66,6 +66,10 @@
 //                 belongs to one wave for the whole launch (tile t is wave t % 4's), so only that wave reads or writes it in
 //                 the actor phase; the physics phase zeroes the rows of an env whose step ended its episode (is_done, with
 //                 or without auto-reset), a workgroup barrier away from either neighbour.
+//   kept states   fg_rollout_hd_actor_gru_states (ActorGruW::states, a run-time, wave-uniform fact of the launch): before the
+//                 six products of step k with k % states_every == 0, the wave that owns a tile stores its rows - the state the
+//                 step acts with, masking applied - to entry k / states_every of `rnn_states`, 16 bytes per lane and store.
+//                 Its own rows only, so no barrier is added; without `states` the pass takes one scalar branch.
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -95,13 +99,16 @@ struct ActorNormW {
 };
 
 // the recurrent layer of gru_*_kernel (FgActorGru): torch's GRU parameters (gate order r | z | n), the LayerNorm after it
-// (gamma / beta NULL: 1 / 0) and the hidden state, read at launch start and written back at the end
+// (gamma / beta NULL: 1 / 0) and the hidden state, read at launch start and written back at the end; `states` (NULL: none
+// kept) receives the state every states_every-th step acted with (fg_rollout_hd_actor_gru_states)
 struct ActorGruW {
     const float* w_ih; const float* w_hh;     // [3H][H]
     const float* b_ih; const float* b_hh;     // [3H]
     const float* g3; const float* be3;        // [H]
     float eps3;
     float* state;                             // [B][N][H]
+    float* states;                            // [ceil(K / states_every)][B][N][H]
+    int states_every;
 };
 
 // one actor per agent (pa_*_kernel): agent i's parameters; entries at i >= N are never read

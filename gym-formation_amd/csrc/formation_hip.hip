@@ -1001,7 +1001,8 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
 // (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
 // host array of N members; `norm` counts for HD_ACTOR_NORM and HD_ACTOR_GRU only; `log_std` NULL: the deterministic actor
 // (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a describe twin; `gru` and `rnn_state`
-// (HD_ACTOR_GRU only): the recurrent layer and the hidden state [B][N][H], a stand-in address from a describe twin.
+// (HD_ACTOR_GRU only): the recurrent layer and the hidden state [B][N][H], a stand-in address from a describe twin;
+// `states_entry` with `rnn_states` and `states_every`: the same call as fg_rollout_hd_actor_gru_states makes it.
 enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
                                              "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru"};
@@ -1013,7 +1014,15 @@ struct HdActorCall {
     float* logp;
     const FgActorGru* gru = nullptr;
     float* rnn_state = nullptr;
+    // fg_rollout_hd_actor_gru_states only (`states_entry`, which also puts its name on the recurrent entry's messages): the
+    // record of the states [ceil(K / states_every)][B][N][H]
+    bool states_entry = false;
+    float* rnn_states = nullptr;
+    int states_every = 1;
 };
+static const char* hd_actor_who(const HdActorCall& c) {
+    return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
+}
 // FgActorNorm's checks (no device touched), in the name of the entry `who`: hidden 32 or 64, every eps that is read positive and
 // finite, gamma / beta 4-byte aligned
 static int actor_norm_check(const char* who, const FgActor* actor, const FgActorNorm* norm) {
@@ -1038,8 +1047,7 @@ static int actor_norm_check(const char* who, const FgActor* actor, const FgActor
 // FgActorGru's and the hidden state's checks (no device touched): the layer and its four parameter tensors present, the state
 // present where there are envs, norm_eps positive and finite (FG_ERR_BAD_ARG, the message naming the field); then the
 // parameters 4-byte and the state 16-byte aligned (FG_ERR_ALIGNMENT)
-static int actor_gru_check(const FgActorGru* gru, const float* rnn_state, int B) {
-    const char* const who = "fg_rollout_hd_actor_gru";
+static int actor_gru_check(const char* who, const FgActorGru* gru, const float* rnn_state, int B) {
     char msg[160];
     auto bad = [&](int code, const char* what, const char* arg = "") {
         snprintf(msg, sizeof(msg), what, who, arg);
@@ -1063,7 +1071,7 @@ static int actor_gru_check(const FgActorGru* gru, const float* rnn_state, int B)
 // the norms, the recurrent layer with its state, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
 // log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
-    const char* const who = hd_actor_entry[c.kind];
+    const char* const who = hd_actor_who(c);
     const char* const shared = hd_actor_entry[c.kind == HD_ACTOR_PER_AGENT ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
     int rc = check_params(params);
     if (rc) return rc;
@@ -1084,7 +1092,7 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
         return rc;
     }
     if ((c.kind == HD_ACTOR_NORM || c.kind == HD_ACTOR_GRU) && (rc = actor_norm_check(who, c.actor, c.norm)) != FG_OK) return rc;
-    if (c.kind == HD_ACTOR_GRU && (rc = actor_gru_check(c.gru, c.rnn_state, B)) != FG_OK) return rc;
+    if (c.kind == HD_ACTOR_GRU && (rc = actor_gru_check(who, c.gru, c.rnn_state, B)) != FG_OK) return rc;
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1111,7 +1119,7 @@ static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
 }
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
 static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
-    const char* const who = hd_actor_entry[c.kind == HD_ACTOR_SAMPLE ? HD_ACTOR_SHARED : c.kind];
+    const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
     if (c.kind == HD_ACTOR_PER_AGENT) {
         ActorTab tab;
         memset(&tab, 0, sizeof(tab));
@@ -1135,7 +1143,8 @@ static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st
                            norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
     if (c.kind == HD_ACTOR_GRU) {
         const FgActorGru& g = *c.gru;
-        const ActorGruW gw = {g.w_ih, g.w_hh, g.b_ih, g.b_hh, g.norm_gamma, g.norm_beta, g.norm_eps, c.rnn_state};
+        const ActorGruW gw = {g.w_ih, g.w_hh, g.b_ih, g.b_hh, g.norm_gamma, g.norm_beta, g.norm_eps, c.rnn_state,
+                              c.states_entry ? c.rnn_states : nullptr, c.states_entry ? c.states_every : 1};
         return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
             return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true, true>(a, c.log_std, c.logp, st, w, nw, gw);
         });
@@ -1154,6 +1163,12 @@ static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int 
     int rc = rollout_buffers_check("fg_rollout_hd_actor", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq,
                                    reward_seq);
     if (rc) return rc;
+    if (c.states_entry) {                              // the record's own checks, after every one the entry inherits
+        const char* const who = hd_actor_who(c);
+        if (c.states_every < 1) return fail(FG_ERR_BAD_ARG, "%s: states_every >= 1 required", who);
+        if (!c.rnn_states && B > 0) return fail(FG_ERR_BAD_ARG, "%s: rnn_states is NULL", who);
+        if ((uintptr_t)c.rnn_states & 15u) return fail(FG_ERR_ALIGNMENT, "%s: rnn_states must be 16-byte aligned", who);
+    }
     if (B == 0) return FG_OK;
     const DeviceGuard device_guard(stream, pos_x);
     Args a;
@@ -1821,6 +1836,17 @@ int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const 
                             float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                             float* rnn_state, int obs_every, void* stream) {
     HdActorCall c = {HD_ACTOR_GRU, actor, norm, log_std, logp_seq, gru, rnn_state};
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                   const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                   float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                   float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                   float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream) {
+    HdActorCall c = {HD_ACTOR_GRU, actor, norm, log_std, logp_seq, gru, rnn_state, true, rnn_states, states_every};
     const int rc = hd_actor_check(params, c, B, N, K);
     return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
                                         obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);

@@ -194,6 +194,8 @@ SIGNATURES = {
                                            ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor_gru": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru), _P,
                                      _I, _I, _I] + [_P] * 14 + [_I, _P]),
+    "fg_rollout_hd_actor_gru_states": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm),
+                                            ctypes.POINTER(FgActorGru), _P, _I, _I, _I] + [_P] * 15 + [_I, _I, _P]),
     "fg_describe_actor_gru_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru),
                                           _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14

@@ -19,6 +19,8 @@ Two calling conventions for `step`:
 Either way ONE fused HIP launch does `_set_action` (x N), `world.step()` and the
 N observation / 2N reward / N done callbacks of environment.py:113-142.
 """
+import numbers
+
 import numpy as np
 import torch
 
@@ -384,7 +386,7 @@ class MultiAgentEnv(object):
         rule = getattr(self.scenario, "actor_fused_rule", None)
         return {} if rule is None else rule(self.world)
 
-    def rollout_actor(self, K, actor, out=None, obs_every=1, rnn_state=None):
+    def rollout_actor(self, K, actor, out=None, obs_every=1, rnn_state=None, rnn_states_every=None):
         """The loop of a learned actor for K steps in one call:
             act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
         from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
@@ -424,7 +426,16 @@ class MultiAgentEnv(object):
         (`fg_rollout_hd_actor_gru`, the state on chip for the whole launch) in formation_hd_env when its base with its head
         is the LayerNorm actor above, H in {32, 64}, `rnn` is an nn.GRUCell(H, H) or a single-layer unidirectional
         nn.GRU(H, H) with biases and `norm` a LayerNorm(H); anything else - and the landmark scenarios - runs this loop
-        host-paced.  `rnn_state` with an actor that keeps no state raises ValueError."""
+        host-paced.  `rnn_state` with an actor that keeps no state raises ValueError.
+        `rnn_states_every=S` (an integer >= 1; None: nothing kept, no such key) also keeps the states a recurrent PPO update
+        restarts from, on either path: info['rnn_states'] [ceil(K / S), B, N, state_size], fp32 and contiguous on the env's
+        device, entry j the state step j * S ACTED WITH (onpolicy's rnn_states[step]) - entry 0 is `rnn_state` as passed in,
+        entry j > 0 is already zero where step j * S - 1 ended an episode; S = data_chunk_length keeps only what the recurrent
+        generator reads, S > K entry 0 alone.  The fused launch (`fg_rollout_hd_actor_gru_states`) stores them from the chip
+        as it goes; nothing else of its results changes, and the entries of a K-step call are those of any split of K.  `out`
+        may carry 'rnn_states' of exactly that shape; with out=None the tensor is kept with this shape's env-owned buffers
+        like 'log_prob' (replaced when S or the state width changes) under the same aliasing rule - the next out=None call of
+        the shape overwrites it - and out=False gives a fresh one per call.  With an actor that keeps no state: ValueError."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
         K, obs_every = int(K), int(obs_every)
@@ -433,11 +444,25 @@ class MultiAgentEnv(object):
         recurrent = actor_rollout.recurrent_mean(actor)
         if recurrent is None and rnn_state is not None:
             raise ValueError("rnn_state given, but the actor is not a RecurrentActor (nor a GaussianActor with one as its mean)")
+        if recurrent is None and rnn_states_every is not None:
+            raise ValueError("rnn_states_every given, but the actor is not a RecurrentActor (nor a GaussianActor with one as its "
+                             "mean)")
+        S = None
+        if rnn_states_every is not None:
+            if isinstance(rnn_states_every, bool) or not isinstance(rnn_states_every, numbers.Integral) or rnn_states_every < 1:
+                raise ValueError("rnn_states_every must be an integer >= 1 (or None)")
+            S = int(rnn_states_every)
         if recurrent is not None:
             rnn_state = self._rnn_state(recurrent, rnn_state)
+        states_shape = None if S is None else ((K + S - 1) // S,) + tuple(rnn_state.shape)
         fused = self._resolve_actor(actor)
         if fused is None:
-            return self._rollout_actor_by_steps(K, actor, obs_every, rnn_state)
+            if S is not None and isinstance(out, dict) and "rnn_states" in out:
+                self._check_rnn_states(out["rnn_states"], states_shape)
+            res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S)
+            if S is not None and isinstance(out, dict) and "rnn_states" in out:
+                res[3]["rnn_states"] = out["rnn_states"].copy_(res[3]["rnn_states"])
+            return res
         log_std = fused.log_std
         gaussian = log_std is not None
         B, N = self.num_envs, self.num_agents
@@ -446,10 +471,14 @@ class MultiAgentEnv(object):
         want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
         if gaussian:
             want["log_prob"] = (K, B, N)
+        if S is not None:
+            want["rnn_states"] = states_shape
         if out is None:
             out = self._default_out(K, obs_every, True) if self.default_placed else False
             if gaussian and out is not False and "log_prob" not in out:
                 out["log_prob"] = torch.empty(want["log_prob"], **f)     # kept with this shape's buffers, same aliasing
+            if S is not None and out is not False and tuple(getattr(out.get("rnn_states"), "shape", ())) != states_shape:
+                out["rnn_states"] = torch.empty(states_shape, **f)       # likewise; another S or state width replaces it
         own_buffers = out is not False
         if out is False:
             out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
@@ -457,6 +486,11 @@ class MultiAgentEnv(object):
         elif gaussian and "log_prob" not in out:                        # the caller's buffers without one: a fresh one
             out = dict(out, log_prob=torch.empty(want["log_prob"], **f))
             own_buffers = False
+        if S is not None and "rnn_states" not in out:
+            out = dict(out, rnn_states=torch.empty(states_shape, **f))
+            own_buffers = False
+        elif S is not None:
+            self._check_rnn_states(out["rnn_states"], states_shape)
         # bound once per (buffers, weights, stream, constants), like rollout_policy: the binding holds the parameter tensors'
         # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
         key = None
@@ -467,7 +501,7 @@ class MultiAgentEnv(object):
                    None if fused.norms is None else tuple(
                        None if n is None else (_native.ptr(n[0]), _native.ptr(n[1]), n[2]) for n in fused.norms),
                    None if fused.gru is None else tuple(_native.ptr(t) for t in fused.gru[:4] + fused.gru.norm[:2])
-                   + (fused.gru.norm[2], rnn_state.data_ptr()),
+                   + (fused.gru.norm[2], rnn_state.data_ptr()), S,
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))
@@ -477,6 +511,8 @@ class MultiAgentEnv(object):
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
             extra = {} if fused.gru is None else {"rnn_state": rnn_state}
+            if S is not None:
+                extra["rnn_states_every"] = S
             launch = self.scenario.bind_rollout_actor(self.world, K, fused, out, obs_every=obs_every,
                                                       auto_reset=self.auto_reset, **extra)
             if key is not None:
@@ -494,7 +530,16 @@ class MultiAgentEnv(object):
             info["log_prob"] = out["log_prob"]
         if fused.gru is not None:
             info["rnn_state"] = rnn_state
+        if S is not None:
+            info["rnn_states"] = out["rnn_states"]
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
+
+    def _check_rnn_states(self, t, shape):
+        """out['rnn_states'] as `rollout_actor(rnn_states_every=S)` takes it: contiguous fp32 of `shape` on the env's device."""
+        dev = self.world.device
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+                or not actor_rollout._on_device(t, dev):
+            raise ValueError("out[%r] must be a contiguous float32 tensor of shape %s on %s" % ("rnn_states", tuple(shape), dev))
 
     def _rnn_state(self, recurrent, rnn_state):
         """The hidden state `rollout_actor` runs the RecurrentActor `recurrent` with: the caller's tensor, checked - contiguous
@@ -528,13 +573,14 @@ class MultiAgentEnv(object):
                                                        _native.current_stream(self.world.device)))
         return out
 
-    def _rollout_actor_by_steps(self, K, actor, obs_every, rnn_state=None):
+    def _rollout_actor_by_steps(self, K, actor, obs_every, rnn_state=None, rnn_states_every=None):
         """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
         launch's (fresh tensors).  A GaussianActor: mean(obs) + exp(log_std) * eps with eps from `actor_noise`, the draws
         of the fused kernel, and the log-density from eps by the kernel's own device function (`fg_actor_log_prob`): for the
         same eps and log_std, the fused launch's bits.  A RecurrentActor (alone or as the mean): `rnn_state` [B, N, H] goes
         through the loop - a, h = actor(obs, h), then h zeroed where the step's done flag is set - is updated in place at the
-        end and comes back as info['rnn_state']."""
+        end and comes back as info['rnn_state'].  `rnn_states_every` = S: a copy of the state before the actor call of every
+        step k with k % S == 0, stacked as info['rnn_states'] [ceil(K / S), B, N, state_size]."""
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
         recurrent = rnn_state is not None
         h = rnn_state.clone() if recurrent else None
@@ -542,9 +588,11 @@ class MultiAgentEnv(object):
         if observe is not None:                            # the observation of the current state (a multi-step launch
             observe(self.world, {"obs": self._out["obs"]})  # leaves the env's own step buffer behind)
         obs = self._out["obs"]
-        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act", "logp")}
+        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act", "logp", "states")}
         with torch.no_grad():
             for k in range(K):
+                if rnn_states_every is not None and k % rnn_states_every == 0:
+                    res["states"].append(h.clone())
                 if gaussian:
                     eps = self.actor_noise()
                     ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
@@ -571,6 +619,8 @@ class MultiAgentEnv(object):
         if recurrent:
             rnn_state.copy_(h)
             info["rnn_state"] = rnn_state
+        if rnn_states_every is not None:
+            info["rnn_states"] = torch.stack(res["states"])
         return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
                 torch.stack(res["done"]), info)
 

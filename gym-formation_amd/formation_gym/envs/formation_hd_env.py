@@ -253,7 +253,7 @@ class Scenario(BaseScenario):
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(lib.fg_rollout_hd_policy, p, *args, keep=out)
 
-    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None):
+    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
@@ -265,13 +265,17 @@ class Scenario(BaseScenario):
           one shared actor with LayerNorms      `fg_rollout_hd_actor_norm` (log_std or NULL), `actor.norms` as FgActorNorm
           ... with a recurrent layer            `fg_rollout_hd_actor_gru` (log_std or NULL), `actor.gru` as FgActorGru and
                                                 `rnn_state` [B,N,H], read and updated in place by every launch and kept alive
-                                                by the launcher like the GRU's tensors"""
+                                                by the launcher like the GRU's tensors
+          ... that keeps its states             `fg_rollout_hd_actor_gru_states` with `rnn_states_every` = S: the state every
+                                                S-th step acted with into out["rnn_states"] [ceil(K / S),B,N,H]"""
         lib = _native.load()
         log_std = actor.log_std
         norm = None if actor.norms is None else _native.actor_norm(actor.norms)
         gru = None if actor.gru is None else _native.actor_gru(actor.gru)
         if gru is not None and rnn_state is None:
             raise ValueError("a recurrent actor's launch needs its rnn_state")
+        if rnn_states_every is not None and gru is None:
+            raise ValueError("rnn_states_every needs a recurrent actor")
         fas = (_native.FgActor * len(actor.members))(*[
             _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
         p = self.params(world, auto_reset, 0, out.get("obs"))
@@ -298,6 +302,8 @@ class Scenario(BaseScenario):
         fn, lead, with_logp = table[key]
         logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
         hidden = () if gru is None else (rnn_state.data_ptr(),)
+        if rnn_states_every is not None:
+            fn, hidden = lib.fg_rollout_hd_actor_gru_states, hidden + (out["rnn_states"].data_ptr(), int(rnn_states_every))
         args = lead + state + logp + hidden + tail
         return _native.bind_launch(fn, p, *args,
                                    keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,

@@ -584,6 +584,19 @@ int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const 
                             float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                             float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                             float* rnn_state, int obs_every, void* stream);
+/* fg_rollout_hd_actor_gru that also keeps the hidden states a recurrent PPO update restarts from (onpolicy's
+ * rnn_states[step]): rnn_states [ceil(K / states_every)][B][N][hidden], fp32, 16-byte aligned, an OUTPUT.  Entry j is the state
+ * step j * states_every ACTED WITH: entry 0 is rnn_state as passed in, entry j > 0 is already zero in every env whose step
+ * j * states_every - 1 ended its episode.  states_every = 1 keeps every step's state, states_every = the update's chunk length
+ * only what its chunks start from, states_every > K entry 0 alone.  Nothing else of the launch changes: the same kernel and
+ * geometry (fg_describe_actor_gru_launch), the same bits in every other output and in rnn_state.  Every other argument, check
+ * and status code is fg_rollout_hd_actor_gru's, in this entry's name; then FG_ERR_BAD_ARG for states_every < 1 or a NULL
+ * rnn_states with B > 0, and FG_ERR_ALIGNMENT for an rnn_states that is not 16-byte aligned.  B == 0 returns FG_OK. */
+int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                   const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                   float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                   float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                   float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream);
 /* Dry run of fg_rollout_hd_actor_gru: same checks and status codes (rnn_state's apart), names the gru_actor_kernel<N,H> or
  * gru_sample_kernel<N,H> instantiation and its launch geometry.  Touches no device. */
 int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
