@@ -1,6 +1,6 @@
-// fg_actor_rollout_body.inc - the one body of the eight formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
-// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel and gru_sample_kernel
-// (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
+// fg_actor_rollout_body.inc - the one body of the twelve formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
+// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel, gru_sample_kernel, bn_actor_kernel,
+// bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
 // (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
 // (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;
@@ -10,7 +10,10 @@
 // gru_actor_kernel / gru_sample_kernel, an LNORM body whose pass runs fg_actor_gru.inc between the second hidden norm and layer 3
 // (fg_actor_mlp.inc); here are the hidden state's block in LDS - loaded from gw.state before the first pass, its done envs' rows
 // zeroed by the physics phase, stored back after the last step (the per-step record gw.states is fg_actor_gru.inc's) - and the
-// preload of the layer's biases and norm.
+// preload of the layer's biases and norm.  `constexpr bool INBN` with `bw` (ActorBnW, the shared actor) or `btab` (ActorBnTab,
+// PER_AGENT; the other an empty constant, both when INBN = false) selects bn_*_kernel / pa_bn_*_kernel: the plain body behind an
+// eval-mode input BatchNorm - layer 1's A operand through bn_apply, over the whole k range; the shared actor's tables mean |
+// istd | gamma | beta are filled here once per workgroup, the per-agent ones are read through L1 per element.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -36,18 +39,22 @@
     static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
     static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm body");
     constexpr int GS = actor_gru_floats(H, GRU);        // GRU: the gates' biases and the post-GRU norm in LDS
+    static_assert(!(INBN && LNORM), "the input BatchNorm is in front of the plain body only");
+    static_assert(!INBN || H <= 64, "the BatchNorm actor's kernels: H 32 or 64");
+    constexpr int BNS = actor_bn_floats(N, INBN, PER_AGENT);   // INBN, shared: mean | istd | gamma | beta [DP] each in LDS
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
     float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
     float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + 4 + LNS + GS;
-    float* const gsm = wsm + WS + 4 + LNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
+    float* const hbuf = wsm + WS + 4 + LNS + BNS + GS;
+    float* const gsm = wsm + WS + 4 + LNS + BNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
     float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
-    static_assert(!GRU || (E * env_block_floats(N) + (SAMPLE ? 3 : 2) * E * N + WS + 4 + LNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
+    static_assert(!GRU || (E * env_block_floats(N) + (SAMPLE ? 3 : 2) * E * N + WS + 4 + LNS + BNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
                   "the hidden state's block is 16-byte aligned (fg_actor_gru.inc stores its rows with 16-byte reads)");
     const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
+    const float* const bn0 = wsm + WS + 4 + LNS;                            // INBN, shared: the four tables, zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -75,6 +82,16 @@
                 lnp[q] = q < D ? (nw.g0 ? nw.g0[q] : 1.f) : 0.f;
                 lnp[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
             }
+        }
+    }
+    if constexpr (INBN && !PER_AGENT) {
+        float* const bnp = wsm + WS + 4 + LNS;
+        for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
+            const bool in = q < D;
+            bnp[q] = in ? bw.mean[q] : 0.f;
+            bnp[DP + q] = in ? bn_istd(bw.var[q], bw.eps) : 0.f;
+            bnp[2 * DP + q] = in ? (bw.gamma ? bw.gamma[q] : 1.f) : 0.f;
+            bnp[3 * DP + q] = (in && bw.beta) ? bw.beta[q] : 0.f;
         }
     }
 
@@ -243,6 +260,27 @@
                             xa[rt] = __builtin_fmaf((xa[rt] - xmean[rt]) * xrstd[rt], ln0[k], ln0[DP + k]);
                     }
                 }
+                if constexpr (INBN) {                  // k < DP: every operand 0 at k >= D, so x' = 0 there
+                    if constexpr (PER_AGENT) {         // the tile's agent's statistics through L1 (scalar bases)
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt) {
+                            gfloat* const bm = (gfloat*)btab.mean[ra[rt]];
+                            gfloat* const bv = (gfloat*)btab.var[ra[rt]];
+                            gfloat* const bg = (gfloat*)btab.gamma[ra[rt]];
+                            gfloat* const bb = (gfloat*)btab.beta[ra[rt]];
+                            const bool in = k < D;
+                            const float mean = in ? bm[k] : 0.f;
+                            const float istd = in ? bn_istd(bv[k], btab.eps[ra[rt]]) : 0.f;
+                            const float gamma = in ? (bg ? bg[k] : 1.f) : 0.f;
+                            const float beta = (in && bb) ? bb[k] : 0.f;
+                            xa[rt] = bn_apply(xa[rt], mean, istd, gamma, beta);
+                        }
+                    } else {
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt)
+                            xa[rt] = bn_apply(xa[rt], bn0[k], bn0[DP + k], bn0[2 * DP + k], bn0[3 * DP + k]);
+                    }
+                }
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) {
                     if constexpr (PER_AGENT) {
@@ -269,6 +307,10 @@
 #pragma unroll 2
                     for (int ks = KA; ks < KB0; ++ks) l1_chunk(ks);
                 }
+            }
+            if constexpr (INBN) {                      // an input BatchNorm likewise: beta - mean istd gamma there
+#pragma unroll 2
+                for (int ks = KA; ks < KB0; ++ks) l1_chunk(ks);
             }
 #pragma unroll 2
             for (int ks = KB0; ks < KB1; ++ks) l1_chunk(ks);

@@ -70,6 +70,22 @@
 //                 six products of step k with k % states_every == 0, the wave that owns a tile stores its rows - the state the
 //                 step acts with, masking applied - to entry k / states_every of `rnn_states`, 16 bytes per lane and store.
 //                 Its own rows only, so no barrier is added; without `states` the pass takes one scalar branch.
+//
+// bn_actor_kernel<N,H> / bn_sample_kernel<N,H> (fg_rollout_hd_actor_bn) and pa_bn_actor_kernel<N,H> / pa_bn_sample_kernel<N,H>
+// (fg_rollout_hd_actor_bn_per_agent), H in {32, 64}, are the shared and the per-agent body behind an eval-mode BatchNorm1d over
+// the actor's input (the MADDPG trainers' `in_fn`: running statistics, no batch statistics):
+//     BatchNorm1d(6N) - Linear - ReLU - Linear - ReLU - Linear(H, 2) [- Tanh]
+// selected by `constexpr bool INBN` (false in every other kernel, whose instructions it leaves as they were).  Per feature k,
+// torch's eval-mode arithmetic in one spelling for both bodies (bn_istd, bn_apply), so N identical members give the shared
+// kernel's bits:
+//     istd_k = 1 / sqrt(var_k + eps),    x'_k = fma((x_k - mean_k) istd_k, gamma_k, beta_k)      (NULL gamma / beta: 1 / 0)
+// x' is layer 1's A operand; layer 1 runs over the WHOLE k range as with the input LayerNorm (a normalised zero of the
+// communication block is beta - mean istd gamma).  Everything after layer 1 is the plain body's.
+//   shared     mean | istd | gamma | beta, each [DP] (DP = 6N rounded up to 4) with zeros at k >= 6N, are filled once per
+//              workgroup in LDS behind b3 | log_std, published by the barrier that publishes the preload.
+//   per agent  each 16-row tile's agent's four pointers and eps come from the by-value table `ActorBnTab` in the kernel
+//              arguments (wave-uniform index: scalar loads); the statistics are read through L1 like the per-agent biases, and
+//              istd is recomputed per element (the same two lines of arithmetic).
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -120,6 +136,24 @@ struct ActorTab {
     int out_tanh;
 };
 
+// the eval-mode input BatchNorm of bn_*_kernel (FgActorInBn): running mean / variance [6N], gamma / beta (NULL: 1 / 0), eps
+struct ActorBnW {
+    const float* mean; const float* var;
+    const float* gamma; const float* beta;
+    float eps;
+};
+// ... of pa_bn_*_kernel: agent i's; entries at i >= N are never read
+struct ActorBnTab {
+    const float* mean[FG_ACTOR_MAX_AGENTS]; const float* var[FG_ACTOR_MAX_AGENTS];
+    const float* gamma[FG_ACTOR_MAX_AGENTS]; const float* beta[FG_ACTOR_MAX_AGENTS];
+    float eps[FG_ACTOR_MAX_AGENTS];
+};
+// The one spelling of the input BatchNorm's arithmetic (shared and per-agent kernels):
+FG_DEV float bn_istd(float var, float eps) { return 1.0f / sqrtf(var + eps); }
+FG_DEV float bn_apply(float x, float mean, float istd, float gamma, float beta) {
+    return __builtin_fmaf((x - mean) * istd, gamma, beta);
+}
+
 constexpr int FG_ACTOR_THREADS = 256;
 constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-row MFMA tiles
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
@@ -128,6 +162,7 @@ __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // ro
 // LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
 //               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) |
 //               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
+//               (INBN, not PER_AGENT: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm) |
 //               (GRU: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]) |
 //               activations [4][32][H + 4] | (GRU: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32))
 // (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
@@ -137,15 +172,18 @@ __host__ __device__ constexpr int actor_state_rows(int n) {
     return (actor_envs(n) * n + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS * FG_ACTOR_ROWS;
 }
 __host__ __device__ constexpr int actor_gru_floats(int h, bool gru) { return gru ? 6 * h : 0; }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false>
+__host__ __device__ constexpr int actor_bn_floats(int n, bool inbn, bool per_agent) {
+    return inbn && !per_agent ? 4 * actor_in_pad(n) : 0;
+}
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false>
 constexpr int actor_lds_floats() {
     return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
-           actor_norm_floats(NC, H, LNORM) + actor_gru_floats(H, GRU) +
+           actor_norm_floats(NC, H, LNORM) + actor_bn_floats(NC, INBN, PER_AGENT) + actor_gru_floats(H, GRU) +
            (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0);
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false>
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false>
 constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU>() * (int)sizeof(float);
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -234,7 +272,9 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const Args a, const ActorW w) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false;
+    constexpr bool LNORM = false, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorNormW nw{};
     constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
@@ -248,7 +288,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Args a, const ActorW w, const float* log_std,
                                                                          float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false;
+    constexpr bool LNORM = false, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorNormW nw{};
     constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
@@ -259,7 +301,9 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Ar
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_actor_kernel(const Args a, const ActorTab tab) {
     constexpr bool SAMPLE = false, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false;
+    constexpr bool LNORM = false, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorNormW nw{};
     constexpr ActorGruW gw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
@@ -273,7 +317,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args a, const ActorTab tab, const float* log_std,
                                                                       float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false;
+    constexpr bool LNORM = false, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorNormW nw{};
     constexpr ActorGruW gw{};
     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
@@ -284,7 +330,9 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args 
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_actor_kernel(const Args a, const ActorW w, const ActorNormW nw) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = false;
+    constexpr bool LNORM = true, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
     const float* const log_std = nullptr;
@@ -297,7 +345,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
                                                                       const float* log_std, float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = false;
+    constexpr bool LNORM = true, GRU = false, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorGruW gw{};
     constexpr ActorTab tab{};
 #include "fg_actor_rollout_body.inc"
@@ -308,7 +358,9 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_actor_kernel(const Args a, const ActorW w, const ActorNormW nw,
                                                                       const ActorGruW gw) {
     constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = true;
+    constexpr bool LNORM = true, GRU = true, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorTab tab{};
     const float* const log_std = nullptr;
     float* const logp = nullptr;
@@ -320,8 +372,66 @@ template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
                                                                        const ActorGruW gw, const float* log_std, float* logp) {
     constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = true;
+    constexpr bool LNORM = true, GRU = true, INBN = false;
+    constexpr ActorBnW bw{};
+    constexpr ActorBnTab btab{};
     constexpr ActorTab tab{};
+#include "fg_actor_rollout_body.inc"
+}
+
+// INBN = true: the shared actor behind the eval-mode input BatchNorm `bw` (the deterministic actor).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void bn_actor_kernel(const Args a, const ActorW w, const ActorBnW bw) {
+    constexpr bool SAMPLE = false, PER_AGENT = false;
+    constexpr bool LNORM = false, GRU = false, INBN = true;
+    constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
+    constexpr ActorTab tab{};
+    constexpr ActorBnTab btab{};
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// INBN = true, SAMPLE = true: the BatchNorm actor's mean with actor_sample_kernel's Gaussian.
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void bn_sample_kernel(const Args a, const ActorW w, const ActorBnW bw,
+                                                                      const float* log_std, float* logp) {
+    constexpr bool SAMPLE = true, PER_AGENT = false;
+    constexpr bool LNORM = false, GRU = false, INBN = true;
+    constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
+    constexpr ActorTab tab{};
+    constexpr ActorBnTab btab{};
+#include "fg_actor_rollout_body.inc"
+}
+
+// INBN = true, PER_AGENT = true: agent i evaluates tab's actor i behind btab's BatchNorm i (the deterministic actor).
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_bn_actor_kernel(const Args a, const ActorTab tab, const ActorBnTab btab) {
+    static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
+    constexpr bool SAMPLE = false, PER_AGENT = true;
+    constexpr bool LNORM = false, GRU = false, INBN = true;
+    constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
+    constexpr ActorBnW bw{};
+    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// INBN = true, PER_AGENT = true, SAMPLE = true: the per-agent BatchNorm means with actor_sample_kernel's Gaussian.
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_bn_sample_kernel(const Args a, const ActorTab tab, const ActorBnTab btab,
+                                                                         const float* log_std, float* logp) {
+    static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
+    constexpr bool SAMPLE = true, PER_AGENT = true;
+    constexpr bool LNORM = false, GRU = false, INBN = true;
+    constexpr ActorNormW nw{};
+    constexpr ActorGruW gw{};
+    constexpr ActorBnW bw{};
+    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
 #include "fg_actor_rollout_body.inc"
 }
 

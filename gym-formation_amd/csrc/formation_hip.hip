@@ -938,36 +938,47 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
 }
 // The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
 // per agent (pa_*_kernel), the shared actor with LayerNorms (ln_*_kernel) and the LayerNorm actor with a recurrent layer
-// (gru_*_kernel).  `w`: the kernel's arguments after `a` - an ActorW, an ActorTab, an ActorW and an ActorNormW, or those two
-// and an ActorGruW.
-template <int NC, int H, bool PER_AGENT, bool LNORM, bool GRU = false, class... W>
+// (gru_*_kernel), and - INBN - the shared or the per-agent actor behind an eval-mode input BatchNorm (bn_*_kernel,
+// pa_bn_*_kernel).  `w`: the kernel's arguments after `a` - an ActorW, an ActorTab, an ActorW and an ActorNormW, those two
+// and an ActorGruW, an ActorW and an ActorBnW, or an ActorTab and an ActorBnTab.
+template <int NC, int H, bool PER_AGENT, bool LNORM, bool GRU = false, bool INBN = false, class... W>
 static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
     static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
     static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm actor");
-    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU>() <= 160 * 1024, "actor rollout LDS");
-    constexpr int E = actor_envs(NC), V = GRU ? 3 : LNORM ? 2 : PER_AGENT ? 1 : 0;
+    static_assert(!(INBN && LNORM), "the input BatchNorm is in front of the plain body only");
+    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU, INBN>() <= 160 * 1024, "actor rollout LDS");
+    constexpr int E = actor_envs(NC), V = INBN ? (PER_AGENT ? 5 : 4) : GRU ? 3 : LNORM ? 2 : PER_AGENT ? 1 : 0;
     constexpr auto det = [] {
-        if constexpr (GRU) return &gru_actor_kernel<NC, H>;
+        if constexpr (INBN && PER_AGENT) return &pa_bn_actor_kernel<NC, H>;
+        else if constexpr (INBN) return &bn_actor_kernel<NC, H>;
+        else if constexpr (GRU) return &gru_actor_kernel<NC, H>;
         else if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
         else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
         else return &actor_rollout_kernel<NC, H>;
     }();
     constexpr auto smp = [] {
-        if constexpr (GRU) return &gru_sample_kernel<NC, H>;
+        if constexpr (INBN && PER_AGENT) return &pa_bn_sample_kernel<NC, H>;
+        else if constexpr (INBN) return &bn_sample_kernel<NC, H>;
+        else if constexpr (GRU) return &gru_sample_kernel<NC, H>;
         else if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
         else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
         else return &actor_sample_kernel<NC, H>;
     }();
-    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel", "gru_actor_kernel"};
-    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel", "gru_sample_kernel"};
+    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel", "gru_actor_kernel",
+                                           "bn_actor_kernel", "pa_bn_actor_kernel"};
+    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel", "gru_sample_kernel",
+                                           "bn_sample_kernel", "pa_bn_sample_kernel"};
     static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
                                            "LayerNorm actor rollout launch failed: %s",
-                                           "recurrent actor rollout launch failed: %s"};
+                                           "recurrent actor rollout launch failed: %s",
+                                           "BatchNorm actor rollout launch failed: %s",
+                                           "per-agent BatchNorm actor rollout launch failed: %s"};
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
     return launch_actor_pair<det, smp>(
         det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU>() : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM, GRU>(),
+        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU, INBN>()
+                : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM, GRU, INBN>(),
         fail_fmt[V], st, log_std, logp, a, w...);
 }
 // The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
@@ -1002,10 +1013,14 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
 // host array of N members; `norm` counts for HD_ACTOR_NORM and HD_ACTOR_GRU only; `log_std` NULL: the deterministic actor
 // (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a describe twin; `gru` and `rnn_state`
 // (HD_ACTOR_GRU only): the recurrent layer and the hidden state [B][N][H], a stand-in address from a describe twin;
-// `states_entry` with `rnn_states` and `states_every`: the same call as fg_rollout_hd_actor_gru_states makes it.
-enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU };
+// `states_entry` with `rnn_states` and `states_every`: the same call as fg_rollout_hd_actor_gru_states makes it; `in_bn`
+// (HD_ACTOR_BN: the one input BatchNorm; HD_ACTOR_BN_PER_AGENT: a host array of N, `actor` one of N members as for
+// HD_ACTOR_PER_AGENT).
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
+                   HD_ACTOR_BN_PER_AGENT };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
-                                             "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru"};
+                                             "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
+                                             "fg_rollout_hd_actor_bn_per_agent"};
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
@@ -1019,7 +1034,9 @@ struct HdActorCall {
     bool states_entry = false;
     float* rnn_states = nullptr;
     int states_every = 1;
+    const FgActorInBn* in_bn = nullptr;
 };
+static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
 static const char* hd_actor_who(const HdActorCall& c) {
     return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
 }
@@ -1066,18 +1083,40 @@ static int actor_gru_check(const char* who, const FgActorGru* gru, const float* 
     if ((uintptr_t)rnn_state & 15u) return bad(FG_ERR_ALIGNMENT, "%s: rnn_state must be 16-byte aligned");
     return FG_OK;
 }
+// FgActorInBn's checks (no device touched), in the name of the entry `who`; `member` >= 0: the per-agent entry's member, whose
+// index the messages name.  FG_ERR_BAD_ARG for hidden = 128, a NULL mean or var, an eps that is not positive and finite;
+// FG_ERR_ALIGNMENT for a mean, var, gamma or beta that is not 4-byte aligned.
+static int actor_in_bn_check(const char* who, const FgActor& actor, const FgActorInBn& bn, int member) {
+    char msg[192], idx[24] = "";
+    if (member >= 0) snprintf(idx, sizeof(idx), "member %d: ", member);
+    auto bad = [&](int code, const char* what, const char* arg = "") {
+        char text[128];
+        snprintf(text, sizeof(text), what, arg);
+        snprintf(msg, sizeof(msg), "%s: %s%s", who, idx, text);
+        return fail(code, "%s", msg);
+    };
+    if (actor.hidden != 32 && actor.hidden != 64) return bad(FG_ERR_BAD_ARG, "hidden must be 32 or 64 with an input BatchNorm");
+    if (!bn.mean) return bad(FG_ERR_BAD_ARG, "in_bn mean is NULL");
+    if (!bn.var) return bad(FG_ERR_BAD_ARG, "in_bn var is NULL");
+    if (!(bn.eps > 0.0f && std::isfinite(bn.eps))) return bad(FG_ERR_BAD_ARG, "in_bn eps must be positive and finite");
+    const struct { const float* p; const char* name; } ptrs[] = {
+        {bn.mean, "mean"}, {bn.var, "var"}, {bn.gamma, "gamma"}, {bn.beta, "beta"}};
+    for (const auto& q : ptrs)
+        if ((uintptr_t)q.p & 3u) return bad(FG_ERR_ALIGNMENT, "in_bn %s must be 4-byte aligned", q.name);
+    return FG_OK;
+}
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
 // this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
-// the norms, the recurrent layer with its state, log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
+// the norms, the recurrent layer with its state, the input BatchNorm(s), log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
 // log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
     const char* const who = hd_actor_who(c);
-    const char* const shared = hd_actor_entry[c.kind == HD_ACTOR_PER_AGENT ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
+    const char* const shared = hd_actor_entry[hd_actor_members(c) ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
     int rc = check_params(params);
     if (rc) return rc;
     if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 1 required", shared);
     if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", shared);
-    if (c.kind == HD_ACTOR_PER_AGENT) {
+    if (hd_actor_members(c)) {
         if (!c.actor) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_per_agent: actors is NULL%s");
         char idx[16];
         for (int i = 0; i < N; ++i) {
@@ -1093,6 +1132,15 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
     }
     if ((c.kind == HD_ACTOR_NORM || c.kind == HD_ACTOR_GRU) && (rc = actor_norm_check(who, c.actor, c.norm)) != FG_OK) return rc;
     if (c.kind == HD_ACTOR_GRU && (rc = actor_gru_check(who, c.gru, c.rnn_state, B)) != FG_OK) return rc;
+    if (c.kind == HD_ACTOR_BN || c.kind == HD_ACTOR_BN_PER_AGENT) {
+        if (!c.in_bn) return fail(FG_ERR_BAD_ARG, "%s: in_bn is NULL", who);
+        if (c.kind == HD_ACTOR_BN) {
+            if ((rc = actor_in_bn_check(who, *c.actor, *c.in_bn, -1)) != FG_OK) return rc;
+        } else {
+            for (int i = 0; i < N; ++i)
+                if ((rc = actor_in_bn_check(who, c.actor[i], c.in_bn[i], i)) != FG_OK) return rc;
+        }
+    }
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1120,7 +1168,7 @@ static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
 static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
     const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
-    if (c.kind == HD_ACTOR_PER_AGENT) {
+    if (hd_actor_members(c)) {
         ActorTab tab;
         memset(&tab, 0, sizeof(tab));
         for (int i = 0; i < a.N; ++i) {
@@ -1128,11 +1176,30 @@ static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st
             tab.b2[i] = c.actor[i].b2; tab.w3[i] = c.actor[i].w3; tab.b3[i] = c.actor[i].b3;
         }
         tab.out_tanh = c.actor[0].out_tanh ? 1 : 0;
+        if (c.kind == HD_ACTOR_BN_PER_AGENT) {
+            ActorBnTab btab;
+            memset(&btab, 0, sizeof(btab));
+            for (int i = 0; i < a.N; ++i) {
+                btab.mean[i] = c.in_bn[i].mean; btab.var[i] = c.in_bn[i].var; btab.gamma[i] = c.in_bn[i].gamma;
+                btab.beta[i] = c.in_bn[i].beta; btab.eps[i] = c.in_bn[i].eps;
+            }
+            return actor_nh_dispatch<64>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
+                return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false, false, true>(a, c.log_std, c.logp, st,
+                                                                                                         tab, btab);
+            });
+        }
         return actor_nh_dispatch<128>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
             return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false>(a, c.log_std, c.logp, st, tab);
         });
     }
     const ActorW w = actor_w(*c.actor);
+    if (c.kind == HD_ACTOR_BN) {
+        const ActorBnW bw = {c.in_bn->mean, c.in_bn->var, c.in_bn->gamma, c.in_bn->beta, c.in_bn->eps};
+        return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
+            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false, false, true>(a, c.log_std, c.logp, st, w,
+                                                                                                      bw);
+        });
+    }
     if (c.kind != HD_ACTOR_NORM && c.kind != HD_ACTOR_GRU)
         return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
             return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
@@ -1852,6 +1919,30 @@ int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor,
                                         obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
 }
 
+int fg_rollout_hd_actor_bn(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
+                           int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                           float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                           float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                           int obs_every, void* stream) {
+    HdActorCall c = {HD_ACTOR_BN, actor, nullptr, log_std, logp_seq};
+    c.in_bn = in_bn;
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_bn_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                     const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                     float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                     float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                     int obs_every, void* stream) {
+    HdActorCall c = {HD_ACTOR_BN_PER_AGENT, actors, nullptr, log_std, logp_seq};
+    c.in_bn = in_bns;
+    const int rc = hd_actor_check(params, c, B, N, K);
+    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+}
+
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1905,6 +1996,20 @@ int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* ac
                                       int K, int obs_every, char* out, int out_len) {
     return describe_actor_impl("fg_describe_actor_per_agent_launch", params,
                                {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, nullptr}, B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_bn_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
+                                int B, int N, int K, int obs_every, char* out, int out_len) {
+    HdActorCall c = {HD_ACTOR_BN, actor, nullptr, log_std, nullptr};
+    c.in_bn = in_bn;
+    return describe_actor_impl("fg_describe_actor_bn_launch", params, c, B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_bn_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                          const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
+    HdActorCall c = {HD_ACTOR_BN_PER_AGENT, actors, nullptr, log_std, nullptr};
+    c.in_bn = in_bns;
+    return describe_actor_impl("fg_describe_actor_bn_per_agent_launch", params, c, B, N, K, obs_every, out, out_len);
 }
 
 int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario, const FgActor* actor, const float* log_std,

@@ -18,9 +18,9 @@ import os.path as osp
 from .environment import MultiAgentEnv
 from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
-from .actor_rollout import GaussianActor, PerAgentActor, RecurrentActor  # noqa: F401
+from .actor_rollout import GaussianActor, InputBatchNorm, PerAgentActor, RecurrentActor  # noqa: F401
 
-__all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor"]
+__all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm"]
 
 _counter = [0]
 

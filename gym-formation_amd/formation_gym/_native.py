@@ -133,6 +133,22 @@ def actor_gru(gru):
     return FgActorGru(ptr(gru.w_ih), ptr(gru.w_hh), ptr(gru.b_ih), ptr(gru.b_hh), ptr(g), ptr(b), eps)
 
 
+class FgActorInBn(ctypes.Structure):
+    """Mirror of `struct FgActorInBn` (include/formation_hip.h): the eval-mode input BatchNorm of fg_rollout_hd_actor_bn's actor."""
+    _fields_ = [
+        ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p),
+        ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+        ("eps", ctypes.c_float),
+    ]
+
+
+def actor_in_bn(bn):
+    """FgActorInBn of an `actor_rollout.ActorInBn` (running_mean, running_var, weight, bias, eps); a None weight / bias is a
+    NULL pointer (1 / 0)."""
+    mean, var, g, b, eps = bn
+    return FgActorInBn(ptr(mean), ptr(var), ptr(g), ptr(b), eps)
+
+
 class FormationHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libformation_hip: status %d: %s" % (code, msg))
@@ -198,6 +214,14 @@ SIGNATURES = {
                                             ctypes.POINTER(FgActorGru), _P, _I, _I, _I] + [_P] * 15 + [_I, _I, _P]),
     "fg_describe_actor_gru_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru),
                                           _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_bn": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _P, _I, _I, _I] + [_P] * 13
+                               + [_I, _P]),
+    "fg_rollout_hd_actor_bn_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _P, _I, _I, _I]
+                                         + [_P] * 13 + [_I, _P]),
+    "fg_describe_actor_bn_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _P, _I, _I, _I, _I,
+                                         ctypes.c_char_p, _I]),
+    "fg_describe_actor_bn_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _P, _I, _I, _I, _I,
+                                                   ctypes.c_char_p, _I]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,

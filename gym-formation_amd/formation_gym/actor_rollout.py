@@ -26,6 +26,21 @@ a GaussianActor's mean, in formation_hd_env only.  Host-paced (the same loop in 
 without norms, H = 128, a multi-layer or bidirectional GRU, a missing norm after the GRU, recurrent PerAgentActor members, and
 the landmark scenarios (`fused_gru_hidden=()`).
 
+The MADDPG trainers' actor (train/maddpg-v2's MLPNetwork with norm_in) is the plain body behind a BatchNorm over its input,
+one network per agent, in eval mode while acting: exactly
+    Sequential(BatchNorm1d(6N), Linear(6N, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])
+with H in FUSED_BN_HIDDEN = {32, 64}.  The leading module is an nn.BatchNorm1d or an `InputBatchNorm` (the same module made to
+take the env's [B, N, 6N] observations: nn.BatchNorm1d reads axis 1 of a 3-D input as its channels) in eval mode with
+track_running_stats, num_features == 6N, running_mean / running_var fp32 contiguous [6N] on the env's device, a positive finite
+eps and weight / bias fp32 contiguous [6N] on the device or none (affine=False: 1 and 0).  It fuses as a shared actor
+(`fg_rollout_hd_actor_bn`) and as the members of a PerAgentActor (`fg_rollout_hd_actor_bn_per_agent`: every member this form
+or none, each with its own statistics, eps and affine-ness), alone or as a GaussianActor's mean, in formation_hd_env only; the
+statistics are read in place like the weights, and the rule is evaluated per call, so `actor.train()` / `actor.eval()` between
+calls switch the path.  Host-paced: training mode (batch statistics are a function of the whole batch),
+track_running_stats=False, a BatchNorm anywhere but first, in front of the LayerNorm form or in a RecurrentActor's base, H = 128,
+statistics in another dtype or off the device, mixed PerAgentActor members, and the landmark scenarios
+(`fused_bn_hidden=()`).  Out of scope: MADDPG's post-noise clamp(-1, 1) and OU noise - a GaussianActor stays "no clipping".
+
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
 
@@ -50,6 +65,7 @@ FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)
 FUSED_HIDDEN = (32, 64, 128)
 FUSED_LN_HIDDEN = (32, 64)             # hidden widths of the LayerNorm actor's kernels (ln_actor_kernel / ln_sample_kernel)
 FUSED_GRU_HIDDEN = (32, 64)            # hidden widths of the recurrent actor's kernels (gru_actor_kernel / gru_sample_kernel)
+FUSED_BN_HIDDEN = (32, 64)             # hidden widths of the BatchNorm actor's kernels (bn_*_kernel / pa_bn_*_kernel)
 # the landmark scenarios: (scenario kind, agents, landmarks, obstacles, neighbours observed) -> fused; kind as _native.FG_SCN_*
 LANDMARK_FUSED_SHAPES = ((1, 3, 3, 0, 2), (2, 5, 5, 0, 3), (2, 3, 5, 0, 3), (3, 4, 4, 0, 3), (3, 3, 4, 0, 2),
                          (4, 4, 4, 3, 3), (4, 3, 4, 3, 2))
@@ -67,14 +83,53 @@ def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_
     return dict(in_features=int(obs_dim), fused_n=(N,), fused_hidden=LANDMARK_FUSED_HIDDEN, per_agent=False)
 
 
+class InputBatchNorm(torch.nn.BatchNorm1d):
+    """nn.BatchNorm1d over the LAST axis of an input of any rank: `forward` flattens every leading axis to [-1, D], applies
+    BatchNorm1d's forward (train or eval mode, the running statistics updated as BatchNorm1d updates them) and restores the
+    shape.  A shared actor's input norm on the env's [B, N, D] observations, where nn.BatchNorm1d takes axis 1 for its channels.
+    Same parameter and buffer names as nn.BatchNorm1d, so a trainer's `in_fn` state dict loads into it."""
+
+    def forward(self, input):
+        if input.dim() < 1 or input.shape[-1] != self.num_features:
+            raise ValueError("expected [..., %d] input (got %s)" % (self.num_features, tuple(input.shape)))
+        return super().forward(input.reshape(-1, input.shape[-1])).reshape(input.shape)
+
+
+class ActorInBn(collections.namedtuple("ActorInBn", "running_mean running_var weight bias eps")):
+    """The eval-mode input BatchNorm of a fused BatchNorm actor (`_body_spec`): the module's own running_mean / running_var
+    buffers and weight / bias parameters (None with affine=False: 1 and 0), read in place by every launch, and its eps as a
+    float."""
+    __slots__ = ()
+
+
+def _in_bn(m, width, device):
+    """The ActorInBn of the leading module `m` over `width` features as the fused kernel can read it, else None: an
+    nn.BatchNorm1d or InputBatchNorm in eval mode that tracks running statistics."""
+    if type(m) not in (torch.nn.BatchNorm1d, InputBatchNorm) or m.training or not m.track_running_stats \
+            or int(m.num_features) != int(width):
+        return None
+    eps = float(m.eps)
+    if not (eps > 0.0 and math.isfinite(eps)):
+        return None
+    for t, required in ((m.running_mean, True), (m.running_var, True), (m.weight, False), (m.bias, False)):
+        if t is None and not required:
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (int(width),) or not t.is_contiguous() \
+                or not _on_device(t, device):
+            return None
+    return ActorInBn(m.running_mean, m.running_var, m.weight, m.bias, eps)
+
+
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-               fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN):
+               fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], norms) when a fused kernel can evaluate the shared actor body `actor` for
     `num_agents` agents, else None.  The two forms, each with its own kernels and so its own hidden widths:
         Sequential(Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])              H in `fused_hidden`
         Sequential([LayerNorm(D),] Linear(D, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2)
                    [, Tanh()])                                                                       H in `fused_ln_hidden`
-    `norms` is None for the first and the ActorNorms of the second, whose every LayerNorm is over its last axis alone with
+        Sequential(BatchNorm1d(D), Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])  H in `fused_bn_hidden`
+    `norms` is None for the first, the ActorInBn of the third (`_in_bn`: eval mode, running statistics) and the ActorNorms of
+    the second, whose every LayerNorm is over its last axis alone with
     fp32 contiguous parameters on `device` or none.  `device`: the env's device (None: not checked).  The tensors are the
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
@@ -82,16 +137,24 @@ def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     here."""
     if type(actor) is not torch.nn.Sequential:
         return None
-    return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden)
+    return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden)
 
 
-def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden):
+def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden=()):
     """`_body_spec` of the body whose modules, in order, are `mods`."""
     nn = torch.nn
     if int(num_agents) not in fused_n:
         return None
     if in_features is None:
         in_features = 6 * int(num_agents)
+    if mods and type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm):     # in front of the plain form only
+        kinds = [type(m) for m in mods[1:]]
+        out_tanh = kinds[-1:] == [nn.Tanh]
+        if kinds[:5] != [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] or len(kinds) != 5 + out_tanh:
+            return None
+        spec = _linears_spec(mods[1], mods[3], mods[5], out_tanh, in_features, device, fused_bn_hidden)
+        bn = None if spec is None else _in_bn(mods[0], in_features, None if device is None else torch.device(device))
+        return None if bn is None else spec + (bn,)
     lead = bool(mods) and type(mods[0]) is nn.LayerNorm
     rest = mods[1:] if lead else mods
     kinds = [type(m) for m in rest]
@@ -127,7 +190,14 @@ def layernorm_spec(actor, num_agents, device=None, **facts):
     `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its second form.  An actor without
     LayerNorms is `actor_spec`'s, not this function's."""
     spec = _body_spec(actor, num_agents, device, **facts)
-    return spec if spec is not None and spec[3] is not None else None
+    return spec if spec is not None and isinstance(spec[3], ActorNorms) else None
+
+
+def batchnorm_spec(actor, num_agents, device=None, **facts):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorInBn) when the fused BatchNorm kernel can evaluate `actor` for
+    `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its third form."""
+    spec = _body_spec(actor, num_agents, device, **facts)
+    return spec if spec is not None and isinstance(spec[3], ActorInBn) else None
 
 
 def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
@@ -242,12 +312,13 @@ class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
 
 
 def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-                    fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN):
+                    fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms, ActorGru) when the fused recurrent kernel can evaluate the
     RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
     of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
     one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
-    parameter fp32, contiguous and on `device`."""
+    parameter fp32, contiguous and on `device`.  `fused_bn_hidden` is `_body_spec`'s fact, not read here: a base that starts
+    with a BatchNorm has no recurrent kernel."""
     nn = torch.nn
     if type(actor) is not RecurrentActor or type(actor.base) is not nn.Sequential:
         return None
@@ -259,7 +330,7 @@ def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FU
     else:
         return None
     spec = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden)
-    if spec is None or spec[3] is None:
+    if spec is None or not isinstance(spec[3], ActorNorms):
         return None
     H = spec[0]
     rnn = actor.rnn
@@ -301,6 +372,19 @@ def per_agent_spec(actor, num_agents, device=None):
     if any(s is None for s in specs) or len({(s[0], s[1]) for s in specs}) != 1:
         return None
     return specs[0][0], specs[0][1], [s[2] for s in specs]
+
+
+def per_agent_bn_spec(actor, num_agents, device=None):
+    """(hidden, out_tanh, [[w1, b1, w2, b2, w3, b3] per agent], [ActorInBn per agent]) when the fused kernel can evaluate the
+    PerAgentActor `actor` for `num_agents` agents with every member behind its own eval-mode input BatchNorm, else None: N
+    members, each passing batchnorm_spec (nn.BatchNorm1d is fine here: members see 2-D rows), all with the same H and tanh
+    flag; statistics, eps and affine-ness are each member's own.  Members of which only some have the BatchNorm: None."""
+    if not isinstance(actor, PerAgentActor) or len(actor.actors) != int(num_agents):
+        return None
+    specs = [batchnorm_spec(a, num_agents, device) for a in actor.actors]
+    if any(s is None for s in specs) or len({(s[0], s[1]) for s in specs}) != 1:
+        return None
+    return specs[0][0], specs[0][1], [s[2] for s in specs], [s[3] for s in specs]
 
 
 class GaussianActor(torch.nn.Module):
@@ -379,13 +463,15 @@ def _fused_log_std(actor, device):
     return ls
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru",
-                                        defaults=(None, None))):
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn",
+                                        defaults=(None, None, None))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
     N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
     ActorNorms of a LayerNorm actor (None: the actor has no LayerNorm), and `gru`, the ActorGru of a RecurrentActor (None: the
-    actor keeps no state), whose body is then `members[0]` with `norms` and whose head is w3, b3."""
+    actor keeps no state), whose body is then `members[0]` with `norms` and whose head is w3, b3.  `in_bn`: the eval-mode
+    input BatchNorm in front of the plain body - the (running_mean, running_var, weight, bias, eps) tuple (ActorInBn) of a
+    shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own."""
     __slots__ = ()
 
 
@@ -400,7 +486,9 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     its log_std; the mean - or the actor itself - is a PerAgentActor (per_agent_spec: members without LayerNorms) or a shared
     body (`_body_spec`: with LayerNorms where the scenario has such a kernel - formation_hd_env, H in {32, 64}; the landmark
     scenarios state `fused_ln_hidden=()`) or a RecurrentActor (`_recurrent_spec`: formation_hd_env, H in {32, 64}; the landmark
-    scenarios state `fused_gru_hidden=()`)."""
+    scenarios state `fused_gru_hidden=()`).  A leading eval-mode BatchNorm in front of the plain body - shared, or in every
+    member of a PerAgentActor (per_agent_bn_spec) - fuses in formation_hd_env with H in {32, 64}; the landmark scenarios state
+    `fused_bn_hidden=()`."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return None
     mean, log_std = actor, None
@@ -412,6 +500,9 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     if members_own:
         spec = per_agent_spec(mean, num_agents, device) if per_agent else None
         spec = None if spec is None else spec + (None, None)
+        if spec is None and per_agent and tuple(facts.get("fused_bn_hidden", FUSED_BN_HIDDEN) or ()):
+            spec = per_agent_bn_spec(mean, num_agents, device)
+            spec = None if spec is None else spec + (None,)
     elif isinstance(mean, RecurrentActor):
         spec = _recurrent_spec(mean, num_agents, device, **facts)
     else:
@@ -420,7 +511,10 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     if spec is None:
         return None
     hidden, out_tanh, weights, norms, gru = spec
-    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms, gru)
+    in_bn = None
+    if isinstance(norms, ActorInBn) or isinstance(norms, list):
+        in_bn, norms = norms, None
+    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms, gru, in_bn)
 
 
 def recurrent_mean(actor):

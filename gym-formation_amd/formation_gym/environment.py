@@ -416,6 +416,12 @@ class MultiAgentEnv(object):
         parameters are read in place like the weights.  Host-paced: H = 128 with norms, any other placement of norms, norm
         parameters in another dtype / non-contiguous / off the device, PerAgentActor members with norms, and a LayerNorm
         actor in the landmark scenarios.
+        The MADDPG trainers' BatchNorm actor - Sequential(BatchNorm1d(6N), Linear(6N, H), ReLU, Linear(H, H), ReLU,
+        Linear(H, 2) [, Tanh]) in eval mode, H in {32, 64} - fuses in formation_hd_env shared (`fg_rollout_hd_actor_bn`; the
+        leading module an `InputBatchNorm`, which takes [B, N, 6N]) or as every member of a PerAgentActor
+        (`fg_rollout_hd_actor_bn_per_agent`), alone or as a GaussianActor's mean; the running statistics are read in place,
+        and `actor.train()` / `actor.eval()` between calls switch the path.  Host-paced: training mode, a BatchNorm anywhere
+        but first, mixed members, H = 128, the landmark scenarios.  No clamp after the noise, no OU noise.
         A `RecurrentActor(base, rnn, norm, head)` (rMAPPO's policy), alone or as a GaussianActor's mean, carries a hidden
         state through the loop:
             a, h = actor(obs, h); obs, rew, done, info = env.step(a); h = h * ~done[..., None]
@@ -502,6 +508,9 @@ class MultiAgentEnv(object):
                        None if n is None else (_native.ptr(n[0]), _native.ptr(n[1]), n[2]) for n in fused.norms),
                    None if fused.gru is None else tuple(_native.ptr(t) for t in fused.gru[:4] + fused.gru.norm[:2])
                    + (fused.gru.norm[2], rnn_state.data_ptr()), S,
+                   None if fused.in_bn is None else tuple(
+                       tuple(_native.ptr(t) for t in bn[:4]) + (bn[4],)
+                       for bn in (fused.in_bn if fused.per_agent else [fused.in_bn])),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))

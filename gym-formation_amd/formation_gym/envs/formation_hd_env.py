@@ -267,7 +267,10 @@ class Scenario(BaseScenario):
                                                 `rnn_state` [B,N,H], read and updated in place by every launch and kept alive
                                                 by the launcher like the GRU's tensors
           ... that keeps its states             `fg_rollout_hd_actor_gru_states` with `rnn_states_every` = S: the state every
-                                                S-th step acted with into out["rnn_states"] [ceil(K / S),B,N,H]"""
+                                                S-th step acted with into out["rnn_states"] [ceil(K / S),B,N,H]
+          an eval-mode input BatchNorm          `fg_rollout_hd_actor_bn` (shared) / `fg_rollout_hd_actor_bn_per_agent` (log_std or
+                                                NULL), `actor.in_bn` as one FgActorInBn or a host array of N; the running
+                                                statistics are read in place and kept alive like the weights"""
         lib = _native.load()
         log_std = actor.log_std
         norm = None if actor.norms is None else _native.actor_norm(actor.norms)
@@ -278,6 +281,13 @@ class Scenario(BaseScenario):
             raise ValueError("rnn_states_every needs a recurrent actor")
         fas = (_native.FgActor * len(actor.members))(*[
             _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
+        in_bn = actor.in_bn
+        bns = None
+        if in_bn is not None:
+            if norm is not None or gru is not None:
+                raise NotImplementedError("an input BatchNorm fuses in front of the plain body only")
+            members = list(in_bn) if actor.per_agent else [in_bn]
+            bns = (_native.FgActorInBn * len(members))(*[_native.actor_in_bn(m) for m in members])
         p = self.params(world, auto_reset, 0, out.get("obs"))
         state = (world.num_envs, len(world.agents), int(K),
                  world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
@@ -300,6 +310,9 @@ class Scenario(BaseScenario):
         if key not in table:
             raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
         fn, lead, with_logp = table[key]
+        if bns is not None:
+            fn = lib.fg_rollout_hd_actor_bn_per_agent if actor.per_agent else lib.fg_rollout_hd_actor_bn
+            lead, with_logp = (fas, bns, ls), True
         logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
         hidden = () if gru is None else (rnn_state.data_ptr(),)
         if rnn_states_every is not None:
@@ -307,7 +320,7 @@ class Scenario(BaseScenario):
         args = lead + state + logp + hidden + tail
         return _native.bind_launch(fn, p, *args,
                                    keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
-                                         actor.gru, gru, rnn_state))
+                                         actor.gru, gru, rnn_state, in_bn, bns))
 
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the

@@ -602,6 +602,51 @@ int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor,
 int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
                                  const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
 
+/* The eval-mode input BatchNorm of fg_rollout_hd_actor_bn's actor (the MADDPG trainers' MLPNetwork with norm_in: `in_fn`, one
+ * network per agent, `policy.eval()` while acting):
+ *     BatchNorm1d(6N) - Linear(6N, hidden) - ReLU - Linear(hidden, hidden) - ReLU - Linear(hidden, 2) [- tanh]
+ * torch.nn.BatchNorm1d on its running statistics, per feature k:
+ *     y_k = (x_k - mean_k) / sqrt(var_k + eps) * gamma_k + beta_k
+ * All tensors fp32 [6N] in DEVICE memory, read in place by every launch like the weights (a changed statistic is seen by the
+ * next launch).  Batch statistics (training mode) are a function of the whole batch and have no fused launch.  Out of scope:
+ * hidden = 128, a BatchNorm anywhere but first or with the LayerNorm / GRU bodies, the landmark scenarios, and MADDPG's
+ * post-noise clamp(-1, 1) and OU noise. */
+typedef struct FgActorInBn {
+    const float* mean;    /* [6N] running mean */
+    const float* var;     /* [6N] running variance */
+    const float* gamma;   /* [6N] or NULL: 1 */
+    const float* beta;    /* [6N] or NULL: 0 */
+    float eps;            /* positive, finite */
+} FgActorInBn;
+
+/* fg_rollout_hd_actor (log_std == NULL; logp_seq ignored) or fg_rollout_hd_actor_sample (log_std [2] and logp_seq as there, the
+ * same eps draws) with the actor `actor` behind the input BatchNorm `in_bn`, shared by every agent (bn_actor_kernel /
+ * bn_sample_kernel).  actor->hidden: 32 or 64.  Every other argument, check and status code is fg_rollout_hd_actor_sample's; then
+ * FG_ERR_BAD_ARG, the message naming the field, for a NULL in_bn, a NULL mean or var, an eps that is not positive and finite,
+ * or hidden = 128, and FG_ERR_ALIGNMENT for a mean, var, gamma or beta that is not 4-byte aligned.  Two launches from one
+ * state give the same bits, and fg_rollout_hd driven by the recorded act_seq returns the same results bit for bit. */
+int fg_rollout_hd_actor_bn(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
+                           int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                           float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                           float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                           int obs_every, void* stream);
+/* fg_rollout_hd_actor_per_agent with member i's network behind its own input BatchNorm in_bns[i] (pa_bn_actor_kernel /
+ * pa_bn_sample_kernel): `actors` and `in_bns` are HOST arrays of N entries, the tables of pointers and the eps values are copied
+ * into the launch (both may be freed when the call returns), the tensors are read in place.  Every check of
+ * fg_rollout_hd_actor_per_agent, then fg_rollout_hd_actor_bn's for every member, the message naming the member's index.
+ * N identical members give the results of fg_rollout_hd_actor_bn with that member bit for bit. */
+int fg_rollout_hd_actor_bn_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                     const float* log_std, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                     float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                     float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                                     int obs_every, void* stream);
+/* Dry runs of the two: same checks and status codes, name the bn_actor_kernel<N,H> / bn_sample_kernel<N,H> or
+ * pa_bn_actor_kernel<N,H> / pa_bn_sample_kernel<N,H> instantiation and its launch geometry.  Touch no device. */
+int fg_describe_actor_bn_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
+                                int B, int N, int K, int obs_every, char* out, int out_len);
+int fg_describe_actor_bn_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                          const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
+
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
  * (scn_lane_actor, or scn_lane_actor_gauss when log_std is not NULL), with the actor
