@@ -64,13 +64,17 @@ FG_DEV double hw_exp(double a) { return exp(a); }
 // World / scenario constants as the kernels read them: the C ABI's FgParams (fp32 fields), or the same names in fp64
 // for the parity build (0.1f is not the reference's 0.1)
 #if FG_F64
+struct KWall {                 // FgWall with its lengths in double (0.9f is not the reference's 0.9)
+    int32_t vertical, soft;
+    double axis_pos, end0, end1, width;
+};
 struct KParams {
     double dt, damping, contact_force, contact_margin, sensitivity, mass, dist_min, collide_thresh;
     int32_t world_length, auto_reset;
     uint64_t seed, rng_offset;
     double accel, max_speed, u_noise;
     int32_t num_walls;
-    FgWall walls[FG_MAX_WALLS];
+    KWall walls[FG_MAX_WALLS];
     int32_t obs_env_pitch, env_index_base;
     const uint64_t* rng_offset_dev;
     const double* agent_props;
@@ -79,6 +83,7 @@ struct KParams {
 };
 #else
 typedef FgParams KParams;
+typedef FgWall KWall;
 #endif
 // per-launch offset of the counter RNG: by-value part + the caller's optional device counter (FgParams.rng_offset_dev)
 FG_DEV uint64_t rng_base(const KParams& p) { return p.rng_offset + (p.rng_offset_dev ? *p.rng_offset_dev : 0ull); }
@@ -96,6 +101,11 @@ FG_DEV real2* env_tables(real2* smem, int ee, int n) {
 }
 FG_DEV const real2* env_tables(const real2* smem, int ee, int n) {
     return reinterpret_cast<const real2*>(reinterpret_cast<const real*>(smem) + ee * env_block_floats(n));
+}
+// Dynamic LDS of one step_kernel workgroup of E envs: the env blocks, the 72 scratch values (16 x 4 reduction partials, the reset
+// flags) and - OPTS - the per-agent mass | size | flags tables at npad(N) each and the communication states of E x N agents
+__host__ __device__ constexpr int step_lds_bytes(int n, int e, bool opts) {
+    return (e * env_block_floats(n) + 72 + (opts ? 3 * npad(n) + 2 * e * n : 0)) * (int)sizeof(real);
 }
 constexpr real FAR_AWAY = 1.0e18f;   // sentinel coordinate: squared distances stay finite (2e36)
 
@@ -239,7 +249,7 @@ FG_DEV void wall_forces(const KParams& P, real2 p, real size, real& fx, real& fy
 #pragma unroll 1
     for (int w = 0; w < FG_MAX_WALLS; ++w) {                                   // static indices: no scratch copy
         if (w >= P.num_walls) break;
-        const FgWall wl = P.walls[w];
+        const KWall wl = P.walls[w];
         if (ghost && wl.soft) continue;
         const real prll = wl.vertical ? p.y : p.x;
         const real perp = wl.vertical ? p.x : p.y;

@@ -237,7 +237,7 @@ static bool geometry_for(int N, Geometry* g, int B = 0, bool need_full = false, 
     const Variant* v = variant_for(N, B, need_full, generic);
     if (!v) return false;
     g->G = v->G; g->T = v->T; g->E = v->E;
-    g->lds = v->E * env_block_floats(N) * (int)sizeof(float) + 72 * (int)sizeof(float);
+    g->lds = step_lds_bytes(N, v->E, false);
     return true;
 }
 
@@ -261,7 +261,7 @@ static int launch_step(Args a, hipStream_t st) {
     if (const int rc = generic_n_check(a.N)) return rc;
     const Variant* v = variant_for(a.N, a.B, opts || idx, generic);      // (never NULL: the run-time-N entries cover every N in range)
     geometry_for(a.N, &g, a.B, opts || idx, generic);
-    if (opts) g.lds += (3 * npad(a.N) + 2 * g.E * a.N) * (int)sizeof(float);    // per-agent mass / size / flags, per-env comm states
+    if (opts) g.lds = step_lds_bytes(a.N, g.E, true);    // + per-agent mass / size / flags, per-env comm states
     a.coll_scale = (float)((double)a.p.collide_thresh / (double)a.p.dist_min);
     const int grid = (a.B + g.E - 1) / g.E;
     // Split step: more than 64 agents (one env per workgroup) and fewer envs than half the chip's CUs.  One workgroup per

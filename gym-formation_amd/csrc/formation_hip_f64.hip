@@ -6,6 +6,10 @@
 // (/root/reference/formation_gym/core.py:206-225, :289-322; environment.py:113-142) over whole fixtures, which an
 // fp32 run cannot do beyond ~10 steps because stiff contacts amplify rounding chaotically.  Not shipped in the
 // product path: formation_gym never loads it.
+// Both halves of step_kernel are built: OPTS = false (fg64_step_hd) and OPTS = true (fg64_step_hd_opts: accel, max_speed, walls
+// with corner rounding / soft walls / ghosts, the per-agent table with its mass ratio, per-pair contact and penalty distances,
+// immovable / non-colliding / scripted agents, the communication block of the flat writer, the 1024-thread re-fetch of the
+// properties, the K-loop), each free-running on the reference's option fixtures (tests/test_gpu_f64_options.py).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=on -DFG_F64=1 -fPIC -shared -Iinclude
 //         -o lib/libformation_hip_f64.so csrc/formation_hip_f64.hip          (no -fapprox-func: full-precision libm)
@@ -40,14 +44,36 @@ static hipError_t launch_wide64(Args a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int G, int T, int E, bool IDX>
-static hipError_t launch64(const Args& a, hipStream_t st) {
+constexpr int FG64_LDS_LIMIT = 160 * 1024;      // LDS one gfx950 workgroup can have
+
+// -2: the workgroup's LDS does not fit (OPTS from ~970 agents up: 8-byte tables); -4: the runtime refused; 0: launched
+template <int G, int T, int E, bool IDX, bool OPTS>
+static int launch64(const Args& a, hipStream_t st) {
     const int grid = (a.B + E - 1) / E;
-    const int lds = (E * env_block_floats(a.N) + 72) * (int)sizeof(real);
-    hipLaunchKernelGGL((step_kernel<0, G, T, E, IDX, false>), dim3(grid), dim3(T), lds, st,
+    const int lds = step_lds_bytes(a.N, E, OPTS);           // the product host side's arithmetic (fg_common.hpp), sizeof(real) = 8
+    if (lds > FG64_LDS_LIMIT) return -2;
+    const auto kernel = &step_kernel<0, G, T, E, IDX, OPTS>;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -4;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(T), lds, st,
                        a.B, a.N, (const real*)a.px, (const real*)a.py, (const real*)a.vx, (const real*)a.vy,
                        (const real*)a.shape, (const real*)a.ivel, (const int32_t*)a.step, a);
-    return hipGetLastError();
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// The geometry table of the run-time-N step kernel: lanes per env, threads and envs per workgroup by agent count
+// (the product's NC = 0 variants, formation_hip.hip kVariants).  OPTS always carries the index outputs, as in the product.
+static int launch_step64(const Args& a, bool idx, bool opts, hipStream_t st) {
+    int G = 4; while (G < a.N) G <<= 1;
+    if (G > 64 && G < 128) G = 128;
+#define FG64(GG, TT, EE) return opts ? launch64<GG, TT, EE, true, true>(a, st) \
+                              : idx ? launch64<GG, TT, EE, true, false>(a, st) : launch64<GG, TT, EE, false, false>(a, st)
+    switch (G) {
+        case 4: FG64(4, 64, 16);      case 8: FG64(8, 64, 8);       case 16: FG64(16, 64, 4);
+        case 32: FG64(32, 128, 4);    case 64: FG64(64, 128, 2);    case 128: FG64(128, 128, 1);
+        case 256: FG64(256, 256, 1);  case 512: FG64(512, 512, 1);  default: FG64(1024, 1024, 1);
+    }
+#undef FG64
 }
 
 }  // namespace fg
@@ -59,6 +85,28 @@ struct Fg64Params {
     double dt, damping, contact_force, contact_margin, sensitivity, mass, dist_min, collide_thresh;
     int32_t world_length, reserved;
 };
+
+// The World options of FgParams in double (u_noise stays 0: its draws are fp32 by design, distributional parity only)
+struct Fg64Wall {
+    int32_t vertical, soft;                 // FgWall.vertical / .soft
+    double axis_pos, end0, end1, width;
+};
+struct Fg64Options {
+    double accel, max_speed;                // 0 = None
+    int32_t num_walls, reserved;
+    Fg64Wall walls[FG_MAX_WALLS];
+    const double* agent_props;              // DEVICE double [N][FG_AGENT_PROPS] (columns as FgParams.agent_props) or NULL
+    const double* comm_state;               // DEVICE double [B][N][2] or NULL
+};
+
+static void fg64_args(fg::Args& a, const Fg64Params* params, int B, int N, int K) {
+    memset(&a, 0, sizeof(a));
+    a.p.dt = params->dt; a.p.damping = params->damping; a.p.contact_force = params->contact_force;
+    a.p.contact_margin = params->contact_margin; a.p.sensitivity = params->sensitivity; a.p.mass = params->mass;
+    a.p.dist_min = params->dist_min; a.p.collide_thresh = params->collide_thresh; a.p.world_length = params->world_length;
+    a.B = B; a.N = N; a.inv_n = 1.0 / (double)N; a.K = K; a.obs_every = 1; a.do_phys = 1; a.do_post = 1;
+    a.obs_pitch = 3LL * N * N;
+}
 
 // fg_step_hd in fp64: state, actions, formation and every output are double arrays of the fp32 entry point's shapes.
 // Returns 0 or a negative code (-1 bad argument, -2 unsupported N, -4 HIP error).
@@ -72,29 +120,45 @@ int fg64_step_hd(const Fg64Params* params, int B, int N,
         return -1;
     if (N < 3 || N > 1024) return -2;
     if (B == 0) return 0;
-    Args a; memset(&a, 0, sizeof(a));
-    a.p.dt = params->dt; a.p.damping = params->damping; a.p.contact_force = params->contact_force;
-    a.p.contact_margin = params->contact_margin; a.p.sensitivity = params->sensitivity; a.p.mass = params->mass;
-    a.p.dist_min = params->dist_min; a.p.collide_thresh = params->collide_thresh; a.p.world_length = params->world_length;
-    a.B = B; a.N = N; a.inv_n = 1.0 / (double)N; a.K = 1; a.obs_every = 1; a.do_phys = 1; a.do_post = 1;
-    a.obs_pitch = 3LL * N * N;
+    Args a; fg64_args(a, params, B, N, 1);
     a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act;
     a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
     a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
     a.near_lm = near_lm; a.near_ag = near_ag; a.hd_idx = hd_idx;
-    hipStream_t st = (hipStream_t)stream;
-    const bool idx = near_lm || near_ag || hd_idx;
-    int G = 4; while (G < N) G <<= 1;
-    if (G > 64 && G < 128) G = 128;
-    hipError_t err;
-#define FG64(GG, TT, EE) err = idx ? launch64<GG, TT, EE, true>(a, st) : launch64<GG, TT, EE, false>(a, st)
-    switch (G) {
-        case 4: FG64(4, 64, 16); break;      case 8: FG64(8, 64, 8); break;       case 16: FG64(16, 64, 4); break;
-        case 32: FG64(32, 128, 4); break;    case 64: FG64(64, 128, 2); break;    case 128: FG64(128, 128, 1); break;
-        case 256: FG64(256, 256, 1); break;  case 512: FG64(512, 512, 1); break;  default: FG64(1024, 1024, 1); break;
+    return launch_step64(a, near_lm || near_ag || hd_idx, false, (hipStream_t)stream);
+}
+
+// fg_step_hd / the K-loop rollout of the World options in fp64: step_kernel's OPTS instantiation, K steps in ONE launch as the
+// product runs option rollouts.  act [K][B][N][2], obs [K][B][N][6N], reward / indiv_reward / done [K][B][N]; the index outputs
+// hold the last step's.  comm_state is read once per launch.  Returns 0, -1 bad argument, -2 unsupported N or a workgroup whose
+// LDS does not fit the device, -4 HIP error.
+int fg64_step_hd_opts(const Fg64Params* params, const Fg64Options* opts, int B, int N, int K,
+                      double* pos_x, double* pos_y, double* vel_x, double* vel_y,
+                      const double* act, double* ideal_shape, double* ideal_vel, int32_t* step,
+                      double* obs, double* reward, double* indiv_reward, uint8_t* done,
+                      int32_t* near_lm, int32_t* near_ag, int32_t* hd_idx, void* stream) {
+    using namespace fg;
+    if (!params || !opts || B < 0 || K < 1 || !pos_x || !pos_y || !vel_x || !vel_y || !act || !ideal_shape || !ideal_vel || !step ||
+        !obs || !reward)
+        return -1;
+    if (opts->num_walls < 0 || opts->num_walls > FG_MAX_WALLS || opts->accel < 0 || opts->max_speed < 0) return -1;
+    if (N < 3 || N > 1024) return -2;
+    if (B == 0) return 0;
+    Args a; fg64_args(a, params, B, N, K);
+    a.p.accel = opts->accel; a.p.max_speed = opts->max_speed; a.p.u_noise = 0.0;
+    a.p.num_walls = opts->num_walls;
+    for (int w = 0; w < opts->num_walls; ++w) {
+        const Fg64Wall& s = opts->walls[w];
+        a.p.walls[w].vertical = s.vertical; a.p.walls[w].soft = s.soft;
+        a.p.walls[w].axis_pos = s.axis_pos; a.p.walls[w].end0 = s.end0; a.p.walls[w].end1 = s.end1; a.p.walls[w].width = s.width;
     }
-#undef FG64
-    return err == hipSuccess ? 0 : -4;
+    a.p.agent_props = opts->agent_props; a.p.comm_state = opts->comm_state;
+    a.coll_scale = params->collide_thresh / params->dist_min;           // divided in double
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act;
+    a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
+    a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;
+    a.near_lm = near_lm; a.near_ag = near_ag; a.hd_idx = hd_idx;
+    return launch_step64(a, true, true, (hipStream_t)stream);
 }
 
 // fg_rollout_hd in fp64 for 9, 27, 81 and 243 agents (the reference's own hierarchy sizes): K steps in ONE launch of the pipelined kernel; act [K][B][N][2], obs [K][B][N][6N],
@@ -108,12 +172,7 @@ int fg64_rollout_hd(const Fg64Params* params, int B, int N, int K,
         return -1;
     if (N != 9 && N != 27 && N != 81 && N != 243) return -2;
     if (B == 0) return 0;
-    Args a; memset(&a, 0, sizeof(a));
-    a.p.dt = params->dt; a.p.damping = params->damping; a.p.contact_force = params->contact_force;
-    a.p.contact_margin = params->contact_margin; a.p.sensitivity = params->sensitivity; a.p.mass = params->mass;
-    a.p.dist_min = params->dist_min; a.p.collide_thresh = params->collide_thresh; a.p.world_length = params->world_length;
-    a.B = B; a.N = N; a.inv_n = 1.0 / (double)N; a.K = K; a.obs_every = 1; a.do_phys = 1; a.do_post = 1;
-    a.obs_pitch = 3LL * N * N;
+    Args a; fg64_args(a, params, B, N, K);
     a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act;
     a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
     a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done;

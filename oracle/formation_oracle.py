@@ -137,15 +137,21 @@ GOLDEN_WALLS = [("V", -0.9, (-1.0, 1.0), 0.1), ("V", 0.9, (-0.6, 0.6), 0.1), ("H
 GOLDEN_SOFT_WALLS = [("H", -0.05, (-0.4, 0.4), 0.1)]    # the soft wall of fixture hd_n9_flags (tests/golden/make_golden.py SOFT_WALLS)
 
 
-def wall_force(pos, size, wall, P, dtype=np.float64, ghost=None):
+BLINDABLE = ("corner", "mass_ratio", "immovable_partner", "pair_distance")
+
+
+def wall_force(pos, size, wall, P, dtype=np.float64, ghost=None, blind=()):
     """core.py:325-362 get_wall_collision_force for every entity [B,N,2] against one wall
-    (orient, axis_pos, endpoints, width[, hard]); a ghost entity passes through a soft wall (:326-327)."""
+    (orient, axis_pos, endpoints, width[, hard]); a ghost entity passes through a soft wall (:326-327).
+    blind: see physics_step."""
     orient, axis_pos, ep, width = wall[:4]
     hard = wall[4] if len(wall) > 4 else True
     prll, perp = (0, 1) if orient == "H" else (1, 0)
     x = pos[..., prll]
     beyond = (x < ep[0] - size) | (x > ep[1] + size)
     partial = ~beyond & ((x < ep[0]) | (x > ep[1]))
+    if "corner" in blind:
+        partial = np.zeros_like(partial)
     past = np.where(x < ep[0], x - ep[0], x - ep[1])
     with np.errstate(invalid="ignore"):
         theta = np.where(partial, np.arcsin(np.clip(past / size, -1, 1)), 0.0)
@@ -164,7 +170,7 @@ def wall_force(pos, size, wall, P, dtype=np.float64, ghost=None):
 
 
 def physics_step(pos, vel, act, P, dtype=np.float64, max_speed=None, accel=None, walls=None, mass=None, size=None,
-                 movable=None, collide=None, ghost=None, scripted=None):
+                 movable=None, collide=None, ghost=None, scripted=None, blind=()):
     """World.step for agent-only colliders (core.py:206-322 with the early-outs
     of :292-297 applied: landmarks have collide=False, so only agent-agent
     pairs survive).  pos, vel, act: [B,N,2].  Returns new (pos, vel).
@@ -180,6 +186,10 @@ def physics_step(pos, vel, act, P, dtype=np.float64, max_speed=None, accel=None,
     takes no action force (:231) and is not integrated (:266-267); a ghost passes through soft walls (:326-327).
     scripted: per-agent booleans [N]: `act` of such an agent is a scripted agent's `action.u` (core.py:210-211), used as it
     is - the sensitivity of environment.py:216-221 scales policy agents' actions only.
+    blind: names from BLINDABLE of branches to leave OUT, for tests that prove that an input takes a branch (the blind
+    oracle then leaves the trajectory): "corner" = an entity past a wall's endpoint is treated as beside the wall (:345-352),
+    "mass_ratio" = movable pairs exchange the unscaled force (:314-317), "immovable_partner" = the mass ratio also scales
+    the force an immovable partner exerts (:319-321), "pair_distance" (reward_hd) = one penalty distance for every pair.
     """
     pos = np.asarray(pos, dtype=dtype); vel = np.asarray(vel, dtype=dtype)
     act = np.asarray(act, dtype=dtype)
@@ -202,13 +212,16 @@ def physics_step(pos, vel, act, P, dtype=np.float64, max_speed=None, accel=None,
     mov = np.ones(N, dtype=bool) if movable is None else np.asarray(movable, dtype=bool)
     col = np.ones(N, dtype=bool) if collide is None else np.asarray(collide, dtype=bool)
     both = mov[:, None] & mov[None, :]
-    ratio = np.where(both, m[None, :] / m[:, None], 1.0).astype(dtype)   # core.py:314-321: agent i receives (m_j / m_i) f, or f
+    assert set(blind) <= set(BLINDABLE), blind
+    ratio = np.where(both | ("immovable_partner" in blind), m[None, :] / m[:, None], 1.0).astype(dtype)   # core.py:314-321: agent i receives (m_j / m_i) f, or f
+    if "mass_ratio" in blind:
+        ratio = np.where(both, dtype(1), ratio)
     f = ratio[None, :, :, None] * f
     pair = col[:, None] & col[None, :] & (mov[:, None] | mov[None, :]) & ~np.eye(N, dtype=bool)   # :292-297
     f = np.where(pair[None, :, :, None], f, dtype(0))
     F = np.where(mov[None, :, None], F, dtype(0)) + f.sum(2)   # :231 an immovable agent takes no action force
     for w in (walls or []):                                    # core.py:255-261
-        F = F + wall_force(pos, sz[None, :], w, P, dtype, ghost=ghost)
+        F = F + wall_force(pos, sz[None, :], w, P, dtype, ghost=ghost, blind=blind)
     new_vel = vel * dtype(1 - P.damping) + (F / m[None, :, None]) * dtype(P.dt)
     if max_speed is not None:                                  # core.py:271-276
         ms = np.broadcast_to(np.asarray(max_speed, dtype=np.float64), (N,))[None, :, None]
@@ -272,7 +285,7 @@ def observation_hd(pos, vel, ideal_shape, ideal_vel, dtype=np.float64, comm=None
     return obs
 
 
-def reward_hd(pos, vel, ideal_shape, ideal_vel, P, dtype=np.float64, size=None, collide=None):
+def reward_hd(pos, vel, ideal_shape, ideal_vel, P, dtype=np.float64, size=None, collide=None, blind=()):
     """formation_hd_env.py:61-75 for every agent + the integer by-products.
     Returns dict(indiv[B,N], shared[B], hd[B,2], hd_idx[B,4], near_lm[B,N],
     near_ag[B,N], cnt[B,N], gap_lm, gap_ag, cnt_margin)."""
@@ -286,7 +299,7 @@ def reward_hd(pos, vel, ideal_shape, ideal_vel, P, dtype=np.float64, size=None, 
     H = np.maximum(h1, h2)                                     # :66
     velterm = np.sqrt(((iv - vel.mean(1)) ** 2).sum(-1))       # :68-69
     PD = np.sqrt(((pos[:, :, None, :] - pos[:, None, :, :]) ** 2).sum(-1))
-    if size is None:
+    if size is None or "pair_distance" in blind:
         thr = dtype(P.collide_thresh)
     else:                                                      # :119-121 per pair: (size_a + size_b) / 2, scaled like P's
         sz = np.asarray(size, dtype=dtype)
@@ -322,10 +335,11 @@ def step_hd(state, act, P=None, dtype=np.float64, **world_options):
     (new_state, out) with out = dict(obs, reward[B,N,1], done[B,N], indiv, ...)."""
     P = P or HdParams()
     comm = world_options.pop("comm", None)                     # AgentState.c [B,N,2] of non-silent agents
+    blind = world_options.get("blind", ())
     pos, vel = physics_step(state["pos"], state["vel"], act, P, dtype, **world_options)
     step = np.asarray(state["step"]) + 1                       # environment.py:114
     out = reward_hd(pos, vel, state["ideal_shape"], state["ideal_vel"], P, dtype, size=world_options.get("size"),
-                    collide=world_options.get("collide"))
+                    collide=world_options.get("collide"), blind=blind)
     out["obs"] = observation_hd(pos, vel, state["ideal_shape"], state["ideal_vel"], dtype, comm=comm)
     N = pos.shape[1]
     out["reward"] = np.repeat(out["shared"][:, None], N, 1)[..., None]    # :136-138

@@ -17,6 +17,21 @@ class Fg64Params(ctypes.Structure):
                [("world_length", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+MAX_WALLS, AGENT_PROPS = 4, 8                                            # FG_MAX_WALLS, FG_AGENT_PROPS (include/formation_hip.h)
+AGENT_IMMOVABLE, AGENT_NO_COLLIDE, AGENT_GHOST, AGENT_SCRIPTED = 1, 2, 4, 8
+
+
+class Fg64Wall(ctypes.Structure):
+    _fields_ = [("vertical", ctypes.c_int32), ("soft", ctypes.c_int32)] + \
+               [(k, ctypes.c_double) for k in ("axis_pos", "end0", "end1", "width")]
+
+
+class Fg64Options(ctypes.Structure):
+    _fields_ = [("accel", ctypes.c_double), ("max_speed", ctypes.c_double), ("num_walls", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("walls", Fg64Wall * MAX_WALLS), ("agent_props", ctypes.c_void_p),
+                ("comm_state", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -26,6 +41,9 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         lib.fg64_step_hd.restype = ctypes.c_int
         lib.fg64_step_hd.argtypes = [ctypes.POINTER(Fg64Params), ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 16
+        lib.fg64_step_hd_opts.restype = ctypes.c_int
+        lib.fg64_step_hd_opts.argtypes = [ctypes.POINTER(Fg64Params), ctypes.POINTER(Fg64Options)] + [ctypes.c_int] * 3 + \
+                                         [ctypes.c_void_p] * 16
         lib.fg64_rollout_hd.restype = ctypes.c_int
         lib.fg64_rollout_hd.argtypes = [ctypes.POINTER(Fg64Params), ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 13
         _lib = lib
@@ -40,10 +58,51 @@ def default_params(**kw):
     return Fg64Params(**d)
 
 
-class Env64(object):
-    """B envs of N agents held in fp64 device tensors; `step(act)` = one fg64_step_hd launch."""
+def params_of(P):
+    """Fg64Params of an oracle parameter object (oracle.formation_oracle.HdParams): the same doubles"""
+    return default_params(dt=P.dt, damping=P.damping, contact_force=P.contact_force, contact_margin=P.contact_margin,
+                          sensitivity=P.sensitivity, mass=P.mass, dist_min=P.dist_min, collide_thresh=P.collide_thresh,
+                          world_length=P.world_length)
 
-    def __init__(self, pos, vel, ideal_shape, ideal_vel, step=None, params=None, indices=True):
+
+def kernel_options(N, P, mass=None, size=None, accel=None, max_speed=None, walls=None, movable=None, collide=None, ghost=None,
+                   scripted=None):
+    """The oracle's World options (keyword arguments of O.physics_step) as the kernel takes them:
+    dict(accel, max_speed, walls, agent_props[, sensitivity]).  accel / max_speed given as one number stay the World-wide scalars; anything per
+    agent makes the [N][8] table (NaN = None = 0), whose columns are FgParams.agent_props'."""
+    per_agent = any(x is not None for x in (mass, size, movable, collide, ghost, scripted)) or \
+        any(x is not None and np.ndim(x) > 0 for x in (accel, max_speed))
+    o = dict(accel=0.0, max_speed=0.0, agent_props=None, walls=[])
+    for w in walls or []:
+        o["walls"].append(dict(vertical=int(w[0] == "V"), axis_pos=float(w[1]), end0=float(w[2][0]), end1=float(w[2][1]),
+                               width=float(w[3]), soft=int(len(w) > 4 and not w[4])))
+    if not per_agent:
+        o["accel"] = 0.0 if accel is None else float(accel)
+        # FgParams' contract for a World-wide accel: `sensitivity` carries it too (environment.py:218-220; the product's
+        # World.native_params and INTEGRATION.md's example fill it so) - the kernel multiplies mass * accel * (sensitivity * u)
+        o["sensitivity"] = None if accel is None else float(accel)
+        o["max_speed"] = 0.0 if max_speed is None else float(max_speed)
+        return o
+    col = lambda x, default: np.broadcast_to(np.asarray(default if x is None else x, dtype=np.float64), (N,))
+    t = np.zeros((N, AGENT_PROPS))
+    t[:, 0] = col(mass, P.mass)
+    t[:, 1] = col(size, P.agent_size)
+    t[:, 2] = np.nan_to_num(col(accel, np.nan), nan=0.0)
+    t[:, 3] = np.nan_to_num(col(max_speed, np.nan), nan=0.0)
+    flag = lambda x, default: np.broadcast_to(np.asarray(default if x is None else x, dtype=bool), (N,))
+    t[:, 6] = (AGENT_IMMOVABLE * ~flag(movable, True) + AGENT_NO_COLLIDE * ~flag(collide, True) + AGENT_GHOST * flag(ghost, False) +
+               AGENT_SCRIPTED * flag(scripted, False))
+    o["agent_props"] = t
+    return o
+
+
+class Env64(object):
+    """B envs of N agents held in fp64 device tensors; `step(act)` = one fg64_step_hd launch.
+    options: dict(accel, max_speed, walls, agent_props) as kernel_options() makes it -> every launch goes through
+    fg64_step_hd_opts (step_kernel's OPTS instantiation): `step(act, comm)` with that step's communication states [B,N,2], or
+    `rollout(acts)`, K steps in ONE launch through the kernel's own K-loop."""
+
+    def __init__(self, pos, vel, ideal_shape, ideal_vel, step=None, params=None, indices=True, options=None):
         f = dict(dtype=torch.float64, device="cuda")
         pos = np.asarray(pos, dtype=np.float64)
         self.B, self.N = pos.shape[:2]
@@ -64,10 +123,58 @@ class Env64(object):
         self.near_ag = torch.zeros((B, N), dtype=torch.int32, device="cuda") if indices else None
         self.hd_idx = torch.zeros((B, 4), dtype=torch.int32, device="cuda") if indices else None
         self.params = params or default_params()
+        self.options = None
+        if options is not None:
+            o = Fg64Options(accel=options.get("accel", 0.0), max_speed=options.get("max_speed", 0.0),
+                            num_walls=len(options.get("walls") or []))
+            assert o.num_walls <= MAX_WALLS
+            for k, w in enumerate(options.get("walls") or []):
+                o.walls[k] = Fg64Wall(**w)
+            self.props = None
+            if options.get("agent_props") is not None:
+                t = np.ascontiguousarray(options["agent_props"], dtype=np.float64)
+                assert t.shape == (N, AGENT_PROPS)
+                self.props = torch.as_tensor(t, **f)
+                o.agent_props = self.props.data_ptr()
+            self.options = o
+            if options.get("sensitivity") is not None:
+                self.params = Fg64Params.from_buffer_copy(self.params)
+                self.params.sensitivity = options["sensitivity"]
 
-    def step(self, act):
+    def _launch_opts(self, act, K, obs, reward, indiv, done, comm):
+        """fg64_step_hd_opts over act [K,B,N,2] into obs [K,B,N,6N], reward / indiv / done [K,B,N]"""
+        f = dict(dtype=torch.float64, device="cuda")
+        p = lambda t: None if t is None else t.data_ptr()
+        self.comm = None if comm is None else torch.as_tensor(np.ascontiguousarray(comm, dtype=np.float64), **f)
+        assert self.comm is None or tuple(self.comm.shape) == (self.B, self.N, 2)
+        self.options.comm_state = p(self.comm)
+        rc = load().fg64_step_hd_opts(self.params, self.options, self.B, self.N, K, p(self.px), p(self.py), p(self.vx), p(self.vy),
+                                      p(act), p(self.shape), p(self.ivel), p(self.step_count), p(obs), p(reward), p(indiv), p(done),
+                                      p(self.near_lm), p(self.near_ag), p(self.hd_idx), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, "fg64_step_hd_opts returned %d" % rc
+        torch.cuda.synchronize()
+
+    def rollout(self, acts):
+        """K = len(acts) steps in ONE fg64_step_hd_opts launch.  Returns dict(obs [K,B,N,6N], reward, indiv, done [K,B,N])."""
+        f = dict(dtype=torch.float64, device="cuda")
+        acts = torch.as_tensor(np.ascontiguousarray(np.asarray(acts, dtype=np.float64)), **f)
+        K, B, N = acts.shape[0], self.B, self.N
+        assert tuple(acts.shape) == (K, B, N, 2)
+        obs = torch.full((K, B, N, 6 * N), float("nan"), **f)
+        rew = torch.full((K, B, N), float("nan"), **f)
+        indiv = torch.full((K, B, N), float("nan"), **f)
+        done = torch.full((K, B, N), 7, dtype=torch.uint8, device="cuda")
+        self._launch_opts(acts, K, obs, rew, indiv, done, None)
+        return dict(obs=obs.cpu().numpy(), reward=rew.cpu().numpy(), indiv=indiv.cpu().numpy(), done=done.cpu().numpy())
+
+    def step(self, act, comm=None):
         act = torch.as_tensor(np.ascontiguousarray(np.asarray(act, dtype=np.float64)), dtype=torch.float64, device="cuda")
         p = lambda t: None if t is None else t.data_ptr()
+        if self.options is not None:
+            assert tuple(act.shape) == (self.B, self.N, 2)
+            self._launch_opts(act, 1, self.obs, self.reward, self.indiv, self.done, comm)
+            return self
+        assert comm is None, "communication states need the options entry"
         rc = load().fg64_step_hd(self.params, self.B, self.N, p(self.px), p(self.py), p(self.vx), p(self.vy), p(act),
                                  p(self.shape), p(self.ivel), p(self.step_count), p(self.obs), p(self.reward),
                                  p(self.indiv), p(self.done), p(self.near_lm), p(self.near_ag), p(self.hd_idx),

@@ -2,6 +2,7 @@
 (asserts the bounds) and profiles/parity_errors.py (writes the committed table profiles/r02_parity_errors.md).
 
   free_running_f64(g)     the fp64 parity build free-runs over ALL recorded steps from the fixture's initial state
+                          (P / options / comm: through the World-option instantiation, tests/option_cases.py fixture_case)
   teacher_forced_f32(g)   the product (fp32) library, state re-seeded from the reference before every step
 Both return {quantity: max abs error over all steps / envs / agents} (+ bookkeeping)."""
 import numpy as np
@@ -12,6 +13,8 @@ from tests import f64_parity
 
 HD_CASES = ["hd_n3", "hd_n4", "hd_n5", "hd_n9", "hd_n10", "hd_n27", "hd_n50", "hd_n81", "hd_n243", "hd_n6_crowd", "hd_n9_crowd", "hd_n16_crowd", "hd_n27_crowd",
             "hd_n81_crowd", "hd_n100_crowd"]
+# the fixtures with non-default World constants: Fg64Params carries them, no option needed (P = option_cases.fixture_case's)
+HD_CONSTANTS_CASES = ["hd_n9_constants", "hd_n27_constants"]
 
 
 def _mx(a, b, mask=None):
@@ -21,14 +24,22 @@ def _mx(a, b, mask=None):
     return float(d.max()) if d.size else 0.0
 
 
-def free_running_f64(g, excuse_margin=1e-9):
+def free_running_f64(g, excuse_margin=1e-9, P=None, options=None, comm=None):
+    """g: a fixture in the multi-env layout.  P: the oracle's parameter object when the constants are not the defaults.
+    options: the oracle's World options (keyword arguments of O.physics_step; {} = none set) - not None sends every step through
+    fg64_step_hd_opts, step_kernel's OPTS instantiation.  comm [T,B,N,2]: the communication states of every step."""
     T, B, N = g["acts"].shape[:3]
-    env = f64_parity.Env64(g["pos0"], g["vel0"], g["ideal_shape"], g["ideal_vel"])
+    params = None if P is None else f64_parity.params_of(P)
+    kopts = None if options is None else f64_parity.kernel_options(N, P or O.HdParams(), **options)
+    env = f64_parity.Env64(g["pos0"], g["vel0"], g["ideal_shape"], g["ideal_vel"], params=params, options=kopts)
     err = dict(pos=0.0, vel=0.0, indiv=0.0, shared_rel=0.0, obs=0.0)
     idx_bad = dict(near_lm=0, near_ag=0, hd_idx=0, done=0, cnt_excused=0)
     per_step_pos = []
     for t in range(T):
-        env.step(g["acts"][t].astype(np.float64))                   # fp32-representable actions, as the reference got them
+        if options is None:
+            env.step(g["acts"][t].astype(np.float64))               # fp32-representable actions, as the reference got them
+        else:
+            env.step(g["acts"][t].astype(np.float64), None if comm is None else comm[t])
         err["pos"] = max(err["pos"], _mx(env.pos(), g["pos"][t]))
         err["vel"] = max(err["vel"], _mx(env.vel(), g["vel"][t]))
         per_step_pos.append(_mx(env.pos(), g["pos"][t]))

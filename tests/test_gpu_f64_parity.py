@@ -17,10 +17,13 @@ from tests import parity_errors as PE
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("name", PE.HD_CASES)
+@pytest.mark.parametrize("name", PE.HD_CASES + PE.HD_CONSTANTS_CASES)
 def test_f64_kernel_free_runs_on_the_reference_trajectory(golden, name):
+    """(hd_n*_constants: dt, damping, contact force / margin, mass, size and episode length away from the defaults, carried by
+    Fg64Params; the World-option instantiation has its own file, tests/test_gpu_f64_options.py)"""
+    from tests import option_cases
     g = golden(name)
-    r = PE.free_running_f64(g)
+    r = PE.free_running_f64(g, P=option_cases.fixture_case(name, g)["P"] if name in PE.HD_CONSTANTS_CASES else None)
     tol = 1e-9
     for k, v in r["err"].items():
         assert v <= tol, "%s: %s error %.3g over %d free-running steps (bound %.0e)" % (name, k, v, r["steps"], tol)

@@ -707,7 +707,8 @@ def test_demo_driver_runs():
 @pytest.mark.parametrize("name,opts", [("hd_n9_options", dict(max_speed=0.6, accel=3.0, walls=True)),
                                         ("hd_n27_walls", dict(walls=True))])
 def test_world_options_teacher_forced(golden, name, opts):
-    """max_speed, accel and walls (World features the reference scenarios leave off)."""
+    """max_speed, accel and walls (World features the reference scenarios leave off): state, rewards, done flags and the
+    recorded observations of every teacher-forced step."""
     from formation_gym.core import Wall
     g = golden(name)
     T, B, N = g["acts"].shape[:3]
@@ -724,6 +725,12 @@ def test_world_options_teacher_forced(golden, name, opts):
         pos, vel = env.world.get_state()
         np.testing.assert_allclose(_np(pos), g["pos"][t], rtol=0, atol=ATOL)
         np.testing.assert_allclose(_np(vel), g["vel"][t], rtol=0, atol=ATOL)
+        ok = g["cnt_margin"][t] > 1e-5
+        np.testing.assert_allclose(_np(info["individual_reward"])[ok], g["indiv"][t][ok], rtol=0, atol=ATOL)
+        np.testing.assert_allclose(_np(rew)[ok, :, 0], g["shared"][t][ok], rtol=2e-6, atol=ATOL)
+        np.testing.assert_array_equal(done.cpu().numpy(), g["done"][t])
+        if (t + 1) in g["obs_steps"]:
+            np.testing.assert_allclose(_np(obs), g["obs_t%d" % (t + 1)], rtol=0, atol=ATOL)
         prev_pos, prev_vel = g["pos"][t], g["vel"][t]
     if opts.get("max_speed"):
         assert float(torch.stack(env.world.get_state()[1:]).norm(dim=-1).max()) <= opts["max_speed"] * (1 + 1e-5)
