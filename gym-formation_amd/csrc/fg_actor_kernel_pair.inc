@@ -1,0 +1,32 @@
+// fg_actor_kernel_pair.inc - the two kernels of one formation_hd_env actor family (fg_actor_rollout_kernel.hpp): the
+// deterministic actor and its Gaussian twin, which takes (log_std, logp) after the family's operands.  The family block
+// that includes this file defines
+//     FG_ACTOR_DET, FG_ACTOR_SMP   the two kernel names
+//     FG_ACTOR_FLAGS               `PER_AGENT = .., LNORM = .., GRU = .., INBN = ..` (the declarators after SAMPLE)
+//     FG_ACTOR_OPERANDS            the kernel parameters after `a`
+//     FG_ACTOR_ABSENT              the FG_ACTOR_NO_* constants of the operands the family does not take
+// and they are undefined again here.  Not a header: no guard.  The body stays a textual include in each kernel
+// (fg_actor_rollout_body.inc says why), so a kernel's token stream is what its hand-written wrapper was.
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, FG_ACTOR_OPERANDS) {
+    constexpr bool SAMPLE = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+
+// log_std [2] read in place, log-probs to logp [K][B][N] when it is not NULL
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP(const Args a, FG_ACTOR_OPERANDS, const float* log_std,
+                                                                 float* logp) {
+    constexpr bool SAMPLE = true, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT
+#include "fg_actor_rollout_body.inc"
+}
+
+#undef FG_ACTOR_DET
+#undef FG_ACTOR_SMP
+#undef FG_ACTOR_FLAGS
+#undef FG_ACTOR_OPERANDS
+#undef FG_ACTOR_ABSENT

@@ -1,7 +1,8 @@
-// fg_actor_rollout_body.inc - the one body of the twelve formation_hd_env actor kernels: actor_rollout_kernel, actor_sample_kernel,
-// pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel, gru_sample_kernel, bn_actor_kernel,
-// bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel (fg_actor_rollout_kernel.hpp).  Included inside each kernel, whose scope provides the kernel arguments `a` (Args), `w`
-// (ActorW: the shared actor) and `tab` (ActorTab: one actor per agent), the template parameters NC and H,
+// fg_actor_rollout_body.inc - the one body of the twelve formation_hd_env actor kernels: actor_rollout_kernel,
+// actor_sample_kernel, pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel,
+// gru_sample_kernel, bn_actor_kernel, bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel (the family blocks of
+// fg_actor_rollout_kernel.hpp).  Included inside each kernel (fg_actor_kernel_pair.inc), whose scope provides the kernel
+// arguments `a` (Args), `w` (ActorW: the shared actor) and `tab` (ActorTab: one per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
 // (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;
 // LNORM = false: an empty constant) selects ln_actor_kernel / ln_sample_kernel: the hidden LayerNorms are fg_actor_mlp.inc's,

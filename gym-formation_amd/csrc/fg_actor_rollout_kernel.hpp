@@ -86,6 +86,12 @@
 //   per agent  each 16-row tile's agent's four pointers and eps come from the by-value table `ActorBnTab` in the kernel
 //              arguments (wave-uniform index: scalar loads); the statistics are read through L1 like the per-agent biases, and
 //              istd is recomputed per element (the same two lines of arithmetic).
+//
+// How a family is wired up: the twelve kernels are six family blocks at the end of this file, each the two kernel names, the
+// four flags, the operands the family takes and the ones it does not, around fg_actor_kernel_pair.inc, which emits the
+// deterministic / Gaussian pair with fg_actor_rollout_body.inc as a textual include.  The host's side of the same table is
+// HdActorFamily in formation_hip.hip.  Adding a family: its operand struct here, an FG_ACTOR_NO_* constant for the blocks that
+// do not take it, its block, its `if constexpr` branches in the body; then the host's row (DESIGN.md lists the places).
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -268,172 +274,72 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
     logp[t] = gauss_logp(eps[t], log_std[0], log_std[1]);
 }
 
-// SAMPLE = false: the deterministic actor.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_rollout_kernel(const Args a, const ActorW w) {
-    constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
+// ---- the twelve kernels: one block per family, each the deterministic / Gaussian pair of fg_actor_kernel_pair.inc around
+// fg_actor_rollout_body.inc.  A family is its two names, its four flags, the operands it takes as kernel arguments and the
+// ones it does not; the body names all of `w tab nw gw bw btab`, and an operand a family does not take is the empty constant
+// below (`w` of a per-agent family: only tab's tanh flag), so that no kernel carries an argument it never reads.
+#define FG_ACTOR_NO_W    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
+#define FG_ACTOR_NO_TAB  constexpr ActorTab tab{};
+#define FG_ACTOR_NO_NW   constexpr ActorNormW nw{};
+#define FG_ACTOR_NO_GW   constexpr ActorGruW gw{};
+#define FG_ACTOR_NO_BW   constexpr ActorBnW bw{};
+#define FG_ACTOR_NO_BTAB constexpr ActorBnTab btab{};
 
-// SAMPLE = true: the Gaussian actor, log_std [2] read in place, log-probs to logp [K][B][N] when it is not NULL.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void actor_sample_kernel(const Args a, const ActorW w, const float* log_std,
-                                                                         float* logp) {
-    constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-#include "fg_actor_rollout_body.inc"
-}
+// the shared actor
+#define FG_ACTOR_DET      actor_rollout_kernel
+#define FG_ACTOR_SMP      actor_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = false
+#define FG_ACTOR_OPERANDS const ActorW w
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
+#include "fg_actor_kernel_pair.inc"
 
-// PER_AGENT = true: agent i evaluates tab's actor i (the deterministic actor).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_actor_kernel(const Args a, const ActorTab tab) {
-    constexpr bool SAMPLE = false, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
+// PER_AGENT: agent i evaluates tab's actor i; the Gaussian twin has one log_std [2] for all agents
+#define FG_ACTOR_DET      pa_actor_kernel
+#define FG_ACTOR_SMP      pa_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = false
+#define FG_ACTOR_OPERANDS const ActorTab tab
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_W
+#include "fg_actor_kernel_pair.inc"
 
-// PER_AGENT = true, SAMPLE = true: the per-agent means with actor_sample_kernel's Gaussian (one log_std [2] for all agents).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_sample_kernel(const Args a, const ActorTab tab, const float* log_std,
-                                                                      float* logp) {
-    constexpr bool SAMPLE = true, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
-#include "fg_actor_rollout_body.inc"
-}
+// LNORM: the shared actor with LayerNorms `nw`
+#define FG_ACTOR_DET      ln_actor_kernel
+#define FG_ACTOR_SMP      ln_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = false, INBN = false
+#define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
+#include "fg_actor_kernel_pair.inc"
 
-// LNORM = true: the shared actor with LayerNorms `nw` (the deterministic actor).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_actor_kernel(const Args a, const ActorW w, const ActorNormW nw) {
-    constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
+// GRU: the LayerNorm actor with the recurrent layer `gw` before its head
+#define FG_ACTOR_DET      gru_actor_kernel
+#define FG_ACTOR_SMP      gru_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = true, INBN = false
+#define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw, const ActorGruW gw
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_TAB
+#include "fg_actor_kernel_pair.inc"
 
-// LNORM = true, SAMPLE = true: the LayerNorm mean with actor_sample_kernel's Gaussian.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void ln_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
-                                                                      const float* log_std, float* logp) {
-    constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = false, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-#include "fg_actor_rollout_body.inc"
-}
+// INBN: the shared actor behind the eval-mode input BatchNorm `bw`
+#define FG_ACTOR_DET      bn_actor_kernel
+#define FG_ACTOR_SMP      bn_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = true
+#define FG_ACTOR_OPERANDS const ActorW w, const ActorBnW bw
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_TAB FG_ACTOR_NO_BTAB
+#include "fg_actor_kernel_pair.inc"
 
-// GRU = true: the LayerNorm actor with the recurrent layer `gw` before its head (the deterministic actor).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_actor_kernel(const Args a, const ActorW w, const ActorNormW nw,
-                                                                      const ActorGruW gw) {
-    constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = true, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorTab tab{};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
+// INBN, PER_AGENT: agent i evaluates tab's actor i behind btab's BatchNorm i
+static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
+#define FG_ACTOR_DET      pa_bn_actor_kernel
+#define FG_ACTOR_SMP      pa_bn_sample_kernel
+#define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = true
+#define FG_ACTOR_OPERANDS const ActorTab tab, const ActorBnTab btab
+#define FG_ACTOR_ABSENT   FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_BW FG_ACTOR_NO_W
+#include "fg_actor_kernel_pair.inc"
 
-// GRU = true, SAMPLE = true: the recurrent mean with actor_sample_kernel's Gaussian.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void gru_sample_kernel(const Args a, const ActorW w, const ActorNormW nw,
-                                                                       const ActorGruW gw, const float* log_std, float* logp) {
-    constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = true, GRU = true, INBN = false;
-    constexpr ActorBnW bw{};
-    constexpr ActorBnTab btab{};
-    constexpr ActorTab tab{};
-#include "fg_actor_rollout_body.inc"
-}
-
-// INBN = true: the shared actor behind the eval-mode input BatchNorm `bw` (the deterministic actor).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void bn_actor_kernel(const Args a, const ActorW w, const ActorBnW bw) {
-    constexpr bool SAMPLE = false, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false, INBN = true;
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-    constexpr ActorBnTab btab{};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
-
-// INBN = true, SAMPLE = true: the BatchNorm actor's mean with actor_sample_kernel's Gaussian.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void bn_sample_kernel(const Args a, const ActorW w, const ActorBnW bw,
-                                                                      const float* log_std, float* logp) {
-    constexpr bool SAMPLE = true, PER_AGENT = false;
-    constexpr bool LNORM = false, GRU = false, INBN = true;
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorTab tab{};
-    constexpr ActorBnTab btab{};
-#include "fg_actor_rollout_body.inc"
-}
-
-// INBN = true, PER_AGENT = true: agent i evaluates tab's actor i behind btab's BatchNorm i (the deterministic actor).
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_bn_actor_kernel(const Args a, const ActorTab tab, const ActorBnTab btab) {
-    static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
-    constexpr bool SAMPLE = false, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false, INBN = true;
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorBnW bw{};
-    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
-    const float* const log_std = nullptr;
-    float* const logp = nullptr;
-#include "fg_actor_rollout_body.inc"
-}
-
-// INBN = true, PER_AGENT = true, SAMPLE = true: the per-agent BatchNorm means with actor_sample_kernel's Gaussian.
-template <int NC, int H>
-__global__ __launch_bounds__(FG_ACTOR_THREADS) void pa_bn_sample_kernel(const Args a, const ActorTab tab, const ActorBnTab btab,
-                                                                         const float* log_std, float* logp) {
-    static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
-    constexpr bool SAMPLE = true, PER_AGENT = true;
-    constexpr bool LNORM = false, GRU = false, INBN = true;
-    constexpr ActorNormW nw{};
-    constexpr ActorGruW gw{};
-    constexpr ActorBnW bw{};
-    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
-#include "fg_actor_rollout_body.inc"
-}
+#undef FG_ACTOR_NO_W
+#undef FG_ACTOR_NO_TAB
+#undef FG_ACTOR_NO_NW
+#undef FG_ACTOR_NO_GW
+#undef FG_ACTOR_NO_BW
+#undef FG_ACTOR_NO_BTAB
 
 }  // namespace fg
 

@@ -619,12 +619,18 @@ static int check_params(const FgParams* p) {
 // not agree on the order (fg_step_hd checks N before it looks at an empty batch, the rollouts after), and the order is ABI.
 static int null_pointer(const char* who) { return fail(FG_ERR_BAD_ARG, "%s: a required pointer is NULL", who); }
 
-// the buffers of a K-step formation_hd_env rollout: fg_rollout_hd, fg_rollout_hd_policy and the fused-actor entries, as `who`
-static int rollout_buffers_check(const char* who, const float* px, const float* py, const float* vx, const float* vy,
-                                 const float* act_seq, const float* shape, const float* ivel, const int32_t* step,
-                                 const float* obs_seq, const float* reward_seq) {
-    if (!px || !py || !vx || !vy || !act_seq || !shape || !ivel || !step || !reward_seq) return null_pointer(who);
-    if (((uintptr_t)obs_seq & 15u) || ((uintptr_t)act_seq & 7u) || ((uintptr_t)shape & 7u) || ((uintptr_t)ivel & 7u))
+// the buffers of a K-step formation_hd_env rollout - fg_rollout_hd, fg_rollout_hd_policy and the fused-actor entries - in the
+// order in which those entries take them (act_seq: read by fg_rollout_hd, written by the others), and their checks as `who`
+struct HdRollout {
+    float *pos_x, *pos_y, *vel_x, *vel_y, *act_seq, *ideal_shape, *ideal_vel;
+    int32_t* step;
+    float *obs_seq, *reward_seq, *indiv_seq;
+    uint8_t* done_seq;
+};
+static int rollout_buffers_check(const char* who, const HdRollout& r) {
+    if (!r.pos_x || !r.pos_y || !r.vel_x || !r.vel_y || !r.act_seq || !r.ideal_shape || !r.ideal_vel || !r.step || !r.reward_seq)
+        return null_pointer(who);
+    if (((uintptr_t)r.obs_seq & 15u) || ((uintptr_t)r.act_seq & 7u) || ((uintptr_t)r.ideal_shape & 7u) || ((uintptr_t)r.ideal_vel & 7u))
         return fail(FG_ERR_ALIGNMENT, "obs_seq must be 16-byte, act_seq/ideal_shape/ideal_vel 8-byte aligned%s");
     return FG_OK;
 }
@@ -646,6 +652,9 @@ static void hd_buffers(Args* a, float* px, float* py, float* vx, float* vy, floa
                        float* obs, float* rew, float* indiv, uint8_t* done) {
     a->px = px; a->py = py; a->vx = vx; a->vy = vy; a->shape = shape; a->ivel = ivel; a->step = step;
     a->obs = obs; a->rew = rew; a->indiv = indiv; a->done = done;
+}
+static void hd_buffers(Args* a, const HdRollout& r) {
+    hd_buffers(a, r.pos_x, r.pos_y, r.vel_x, r.vel_y, r.ideal_shape, r.ideal_vel, r.step, r.obs_seq, r.reward_seq, r.indiv_seq, r.done_seq);
 }
 
 // ---- the reference's demo controller (fg_policy_kernels.hpp): one launch geometry and one PER switch for both of its kernels
@@ -920,9 +929,6 @@ static int launch_scenario(const FgParams* params, const FgScenario* sc, int B, 
 static bool actor_n_supported(int N) {
     return N == 3 || N == 4 || N == 8 || N == 9 || N == 16 || N == 25 || N == 27 || N == 32;
 }
-static ActorW actor_w(const FgActor& actor) {
-    return {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
-}
 // Describe-or-launch of an actor kernel: Det (the deterministic actor; log_std == NULL) or its sampling twin Smp (the Gaussian
 // actor), which takes (log_std, logp) after Det's arguments `args`.  `targs` spells the template arguments and `unit` the word
 // before the thread count in the describe string; `lds` is the chosen kernel's.
@@ -936,68 +942,84 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
     if (sample) return launch<Smp>(grid, threads, lds, st, fail_fmt, args..., log_std, logp);
     return launch<Det>(grid, threads, lds, st, fail_fmt, args...);
 }
-// The formation_hd_env actor kernels by their flags: the shared actor (actor_rollout_kernel / actor_sample_kernel), one actor
-// per agent (pa_*_kernel), the shared actor with LayerNorms (ln_*_kernel) and the LayerNorm actor with a recurrent layer
-// (gru_*_kernel), and - INBN - the shared or the per-agent actor behind an eval-mode input BatchNorm (bn_*_kernel,
-// pa_bn_*_kernel).  `w`: the kernel's arguments after `a` - an ActorW, an ActorTab, an ActorW and an ActorNormW, those two
-// and an ActorGruW, an ActorW and an ActorBnW, or an ActorTab and an ActorBnTab.
-template <int NC, int H, bool PER_AGENT, bool LNORM, bool GRU = false, bool INBN = false, class... W>
+
+// The formation_hd_env actor families, one kind per entry point fg_rollout_hd_actor* (in hd_actor_entry's order) and one
+// record per kind: the flags of its kernel pair (fg_actor_rollout_kernel.hpp), the widest H the pair is built for, the pair
+// itself, its names in the describe strings and what a failed launch is called.  HD_ACTOR_SAMPLE is a kind of its own for the
+// messages only: its kernels are the shared family's.  The kernels' operands after `a`, as hd_actor_dispatch builds them:
+//     HD_ACTOR_SHARED        ActorW                          HD_ACTOR_GRU           ActorW, ActorNormW, ActorGruW
+//     HD_ACTOR_PER_AGENT     ActorTab                        HD_ACTOR_BN            ActorW, ActorBnW
+//     HD_ACTOR_NORM          ActorW, ActorNormW              HD_ACTOR_BN_PER_AGENT  ActorTab, ActorBnTab
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
+                   HD_ACTOR_BN_PER_AGENT };
+static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
+                                             "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
+                                             "fg_rollout_hd_actor_bn_per_agent"};
+template <HdActorKind> struct HdActorFamily;
+#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, WHAT)                                             \
+    template <> struct HdActorFamily<KIND> {                                                                      \
+        static constexpr bool per_agent = PA, lnorm = LN, gru = GR, in_bn = BN;                                   \
+        static constexpr int max_h = MAXH;                                                                        \
+        template <int NC, int H> static constexpr auto det = &DET<NC, H>;                                         \
+        template <int NC, int H> static constexpr auto smp = &SMP<NC, H>;                                         \
+        static constexpr const char* det_name = #DET;                                                             \
+        static constexpr const char* smp_name = #SMP;                                                             \
+        static constexpr const char* fail_fmt = WHAT "actor rollout launch failed: %s";                           \
+        static_assert(!(PA && LN), "no per-agent actor kernel with LayerNorms");                                  \
+        static_assert(!GR || LN, "the recurrent actor's base is the LayerNorm actor");                            \
+        static_assert(!(BN && LN), "the input BatchNorm is in front of the plain body only");                     \
+        template <int NC, int H, bool SAMPLE> static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN>(); \
+    };
+//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian
+FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, "")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    "per-agent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    "LayerNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   "recurrent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    "BatchNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, "per-agent BatchNorm ")
+#undef FG_HD_ACTOR_FAMILY
+template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
+
+// one kernel pair of the family F at <NC, H>; `w`: the family's operands
+template <int NC, int H, class F, class... W>
 static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
-    static_assert(!(PER_AGENT && LNORM), "no per-agent actor kernel with LayerNorms");
-    static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm actor");
-    static_assert(!(INBN && LNORM), "the input BatchNorm is in front of the plain body only");
-    static_assert(actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU, INBN>() <= 160 * 1024, "actor rollout LDS");
-    constexpr int E = actor_envs(NC), V = INBN ? (PER_AGENT ? 5 : 4) : GRU ? 3 : LNORM ? 2 : PER_AGENT ? 1 : 0;
-    constexpr auto det = [] {
-        if constexpr (INBN && PER_AGENT) return &pa_bn_actor_kernel<NC, H>;
-        else if constexpr (INBN) return &bn_actor_kernel<NC, H>;
-        else if constexpr (GRU) return &gru_actor_kernel<NC, H>;
-        else if constexpr (LNORM) return &ln_actor_kernel<NC, H>;
-        else if constexpr (PER_AGENT) return &pa_actor_kernel<NC, H>;
-        else return &actor_rollout_kernel<NC, H>;
-    }();
-    constexpr auto smp = [] {
-        if constexpr (INBN && PER_AGENT) return &pa_bn_sample_kernel<NC, H>;
-        else if constexpr (INBN) return &bn_sample_kernel<NC, H>;
-        else if constexpr (GRU) return &gru_sample_kernel<NC, H>;
-        else if constexpr (LNORM) return &ln_sample_kernel<NC, H>;
-        else if constexpr (PER_AGENT) return &pa_sample_kernel<NC, H>;
-        else return &actor_sample_kernel<NC, H>;
-    }();
-    static const char* const det_name[] = {"actor_rollout_kernel", "pa_actor_kernel", "ln_actor_kernel", "gru_actor_kernel",
-                                           "bn_actor_kernel", "pa_bn_actor_kernel"};
-    static const char* const smp_name[] = {"actor_sample_kernel", "pa_sample_kernel", "ln_sample_kernel", "gru_sample_kernel",
-                                           "bn_sample_kernel", "pa_bn_sample_kernel"};
-    static const char* const fail_fmt[] = {"actor rollout launch failed: %s", "per-agent actor rollout launch failed: %s",
-                                           "LayerNorm actor rollout launch failed: %s",
-                                           "recurrent actor rollout launch failed: %s",
-                                           "BatchNorm actor rollout launch failed: %s",
-                                           "per-agent BatchNorm actor rollout launch failed: %s"};
+    static_assert(F::template lds_bytes<NC, H, true> <= 160 * 1024, "actor rollout LDS");
+    constexpr int E = actor_envs(NC);
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    return launch_actor_pair<det, smp>(
-        det_name[V], smp_name[V], targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? actor_lds_bytes<NC, H, true, PER_AGENT, LNORM, GRU, INBN>()
-                : actor_lds_bytes<NC, H, false, PER_AGENT, LNORM, GRU, INBN>(),
-        fail_fmt[V], st, log_std, logp, a, w...);
+    return launch_actor_pair<F::template det<NC, H>, F::template smp<NC, H>>(
+        F::det_name, F::smp_name, targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
+        log_std ? F::template lds_bytes<NC, H, true> : F::template lds_bytes<NC, H, false>, F::fail_fmt, st, log_std, logp, a, w...);
 }
+
+// A failed check of an actor description, in the name of the entry `who` [and of the per-agent entry's member `member`]:
+// "<who>: [member <i>: ]<what, with arg>" as the error text, `code` as the status.
+struct ActorComplaint {
+    const char* who;
+    int member = -1;
+    int operator()(int code, const char* what, const char* arg = "") const {
+        char text[128], idx[24] = "", msg[192];
+        snprintf(text, sizeof(text), what, arg);
+        if (member >= 0) snprintf(idx, sizeof(idx), "member %d: ", member);
+        snprintf(msg, sizeof(msg), "%s: %s%s", who, idx, text);
+        return fail(code, "%s", msg);
+    }
+};
+static bool actor_eps_ok(float e) { return e > 0.0f && std::isfinite(e); }
+
 // The checks of one FgActor (no device touched): FG_OK, or the status of the first one that fails.  `who` is the entry point
 // the messages name, `max_hidden` / `widths` its admissible hidden widths (32, 64 and up to max_hidden), `also` further
 // pointers that share the weights' 4-byte alignment check and `aligned` what the alignment message calls them all.
 static int actor_struct_check(const FgActor* actor, const char* who, int max_hidden, const char* widths, uintptr_t also,
                               const char* aligned) {
-    char msg[160];
-    auto bad = [&](int code, const char* what, const char* arg = "") {
-        snprintf(msg, sizeof(msg), what, who, arg);
-        return fail(code, "%s", msg);
-    };
-    if (!actor) return bad(FG_ERR_BAD_ARG, "%s: actor is NULL");
+    const ActorComplaint bad{who};
+    if (!actor) return bad(FG_ERR_BAD_ARG, "actor is NULL");
     if (actor->hidden != 32 && actor->hidden != 64 && !(actor->hidden == 128 && max_hidden == 128))
-        return bad(FG_ERR_BAD_ARG, "%s: hidden must be %s", widths);
-    if (!actor->w1 || !actor->w2 || !actor->w3) return bad(FG_ERR_BAD_ARG, "%s: a weight pointer is NULL");
+        return bad(FG_ERR_BAD_ARG, "hidden must be %s", widths);
+    if (!actor->w1 || !actor->w2 || !actor->w3) return bad(FG_ERR_BAD_ARG, "a weight pointer is NULL");
     if (((uintptr_t)actor->w1 | (uintptr_t)actor->w2 | (uintptr_t)actor->w3 | (uintptr_t)actor->b1 | (uintptr_t)actor->b2 |
          (uintptr_t)actor->b3 | also) & 3u)
-        return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", aligned);
+        return bad(FG_ERR_ALIGNMENT, "%s must be 4-byte aligned", aligned);
     return FG_OK;
 }
 static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
@@ -1009,24 +1031,19 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
 }
 
 // One call of a formation_hd_env actor entry, fg_rollout_hd_actor* or its fg_describe_actor*_launch twin, as its checks
-// (hd_actor_check) and its dispatch (hd_actor_dispatch) take it.  `actor`: the one shared actor, or for HD_ACTOR_PER_AGENT a
-// host array of N members; `norm` counts for HD_ACTOR_NORM and HD_ACTOR_GRU only; `log_std` NULL: the deterministic actor
-// (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a describe twin; `gru` and `rnn_state`
-// (HD_ACTOR_GRU only): the recurrent layer and the hidden state [B][N][H], a stand-in address from a describe twin;
-// `states_entry` with `rnn_states` and `states_every`: the same call as fg_rollout_hd_actor_gru_states makes it; `in_bn`
-// (HD_ACTOR_BN: the one input BatchNorm; HD_ACTOR_BN_PER_AGENT: a host array of N, `actor` one of N members as for
-// HD_ACTOR_PER_AGENT).
-enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
-                   HD_ACTOR_BN_PER_AGENT };
-static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
-                                             "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
-                                             "fg_rollout_hd_actor_bn_per_agent"};
+// (hd_actor_check) and its dispatch (hd_actor_dispatch) take it; the fields in the order in which the kinds add them, so that
+// every entry is one brace initialiser.  `actor`: the one shared actor, or for the per-agent kinds a host array of N members;
+// `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a
+// describe twin; `in_bn` (HD_ACTOR_BN: the one input BatchNorm; HD_ACTOR_BN_PER_AGENT: a host array of N); `norm` counts for
+// HD_ACTOR_NORM and HD_ACTOR_GRU only; `gru` and `rnn_state` (HD_ACTOR_GRU only): the recurrent layer and the hidden state
+// [B][N][H], a stand-in address from a describe twin.
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
-    const FgActorNorm* norm;
-    const float* log_std;
-    float* logp;
+    const float* log_std = nullptr;
+    float* logp = nullptr;
+    const FgActorInBn* in_bn = nullptr;
+    const FgActorNorm* norm = nullptr;
     const FgActorGru* gru = nullptr;
     float* rnn_state = nullptr;
     // fg_rollout_hd_actor_gru_states only (`states_entry`, which also puts its name on the recurrent entry's messages): the
@@ -1034,7 +1051,6 @@ struct HdActorCall {
     bool states_entry = false;
     float* rnn_states = nullptr;
     int states_every = 1;
-    const FgActorInBn* in_bn = nullptr;
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
 static const char* hd_actor_who(const HdActorCall& c) {
@@ -1043,62 +1059,46 @@ static const char* hd_actor_who(const HdActorCall& c) {
 // FgActorNorm's checks (no device touched), in the name of the entry `who`: hidden 32 or 64, every eps that is read positive and
 // finite, gamma / beta 4-byte aligned
 static int actor_norm_check(const char* who, const FgActor* actor, const FgActorNorm* norm) {
-    char msg[160];
-    auto bad = [&](const char* what, const char* arg = "") {
-        snprintf(msg, sizeof(msg), what, who, arg);
-        return fail(FG_ERR_BAD_ARG, "%s", msg);
-    };
-    if (!norm) return bad("%s: norm is NULL");
-    if (actor->hidden != 32 && actor->hidden != 64) return bad("%s: hidden must be 32 or 64 with LayerNorms");
-    auto eps_ok = [](float e) { return e > 0.0f && std::isfinite(e); };
-    if (norm->in_norm && !eps_ok(norm->in_eps)) return bad("%s: in_eps must be positive and finite");
-    if (!eps_ok(norm->h1_eps)) return bad("%s: h1_eps must be positive and finite");
-    if (!eps_ok(norm->h2_eps)) return bad("%s: h2_eps must be positive and finite");
+    const ActorComplaint bad{who};
+    if (!norm) return bad(FG_ERR_BAD_ARG, "norm is NULL");
+    if (actor->hidden != 32 && actor->hidden != 64) return bad(FG_ERR_BAD_ARG, "hidden must be 32 or 64 with LayerNorms");
+    if (norm->in_norm && !actor_eps_ok(norm->in_eps)) return bad(FG_ERR_BAD_ARG, "in_eps must be positive and finite");
+    if (!actor_eps_ok(norm->h1_eps)) return bad(FG_ERR_BAD_ARG, "h1_eps must be positive and finite");
+    if (!actor_eps_ok(norm->h2_eps)) return bad(FG_ERR_BAD_ARG, "h2_eps must be positive and finite");
     const struct { const float* p; const char* name; } ptrs[] = {
         {norm->in_gamma, "in_gamma"}, {norm->in_beta, "in_beta"}, {norm->h1_gamma, "h1_gamma"},
         {norm->h1_beta, "h1_beta"},   {norm->h2_gamma, "h2_gamma"}, {norm->h2_beta, "h2_beta"}};
     for (const auto& q : ptrs)
-        if ((uintptr_t)q.p & 3u) return bad("%s: %s must be 4-byte aligned", q.name);
+        if ((uintptr_t)q.p & 3u) return bad(FG_ERR_BAD_ARG, "%s must be 4-byte aligned", q.name);
     return FG_OK;
 }
 // FgActorGru's and the hidden state's checks (no device touched): the layer and its four parameter tensors present, the state
 // present where there are envs, norm_eps positive and finite (FG_ERR_BAD_ARG, the message naming the field); then the
 // parameters 4-byte and the state 16-byte aligned (FG_ERR_ALIGNMENT)
 static int actor_gru_check(const char* who, const FgActorGru* gru, const float* rnn_state, int B) {
-    char msg[160];
-    auto bad = [&](int code, const char* what, const char* arg = "") {
-        snprintf(msg, sizeof(msg), what, who, arg);
-        return fail(code, "%s", msg);
-    };
-    if (!gru) return bad(FG_ERR_BAD_ARG, "%s: gru is NULL");
+    const ActorComplaint bad{who};
+    if (!gru) return bad(FG_ERR_BAD_ARG, "gru is NULL");
     const struct { const float* p; const char* name; bool required; } ptrs[] = {
         {gru->w_ih, "w_ih", true}, {gru->w_hh, "w_hh", true}, {gru->b_ih, "b_ih", true},
         {gru->b_hh, "b_hh", true}, {gru->norm_gamma, "norm_gamma", false}, {gru->norm_beta, "norm_beta", false}};
     for (const auto& q : ptrs)
-        if (q.required && !q.p) return bad(FG_ERR_BAD_ARG, "%s: %s is NULL", q.name);
-    if (!rnn_state && B > 0) return bad(FG_ERR_BAD_ARG, "%s: rnn_state is NULL");
-    if (!(gru->norm_eps > 0.0f && std::isfinite(gru->norm_eps))) return bad(FG_ERR_BAD_ARG, "%s: norm_eps must be positive and finite");
+        if (q.required && !q.p) return bad(FG_ERR_BAD_ARG, "%s is NULL", q.name);
+    if (!rnn_state && B > 0) return bad(FG_ERR_BAD_ARG, "rnn_state is NULL");
+    if (!actor_eps_ok(gru->norm_eps)) return bad(FG_ERR_BAD_ARG, "norm_eps must be positive and finite");
     for (const auto& q : ptrs)
-        if ((uintptr_t)q.p & 3u) return bad(FG_ERR_ALIGNMENT, "%s: %s must be 4-byte aligned", q.name);
-    if ((uintptr_t)rnn_state & 15u) return bad(FG_ERR_ALIGNMENT, "%s: rnn_state must be 16-byte aligned");
+        if ((uintptr_t)q.p & 3u) return bad(FG_ERR_ALIGNMENT, "%s must be 4-byte aligned", q.name);
+    if ((uintptr_t)rnn_state & 15u) return bad(FG_ERR_ALIGNMENT, "rnn_state must be 16-byte aligned");
     return FG_OK;
 }
 // FgActorInBn's checks (no device touched), in the name of the entry `who`; `member` >= 0: the per-agent entry's member, whose
 // index the messages name.  FG_ERR_BAD_ARG for hidden = 128, a NULL mean or var, an eps that is not positive and finite;
 // FG_ERR_ALIGNMENT for a mean, var, gamma or beta that is not 4-byte aligned.
 static int actor_in_bn_check(const char* who, const FgActor& actor, const FgActorInBn& bn, int member) {
-    char msg[192], idx[24] = "";
-    if (member >= 0) snprintf(idx, sizeof(idx), "member %d: ", member);
-    auto bad = [&](int code, const char* what, const char* arg = "") {
-        char text[128];
-        snprintf(text, sizeof(text), what, arg);
-        snprintf(msg, sizeof(msg), "%s: %s%s", who, idx, text);
-        return fail(code, "%s", msg);
-    };
+    const ActorComplaint bad{who, member};
     if (actor.hidden != 32 && actor.hidden != 64) return bad(FG_ERR_BAD_ARG, "hidden must be 32 or 64 with an input BatchNorm");
     if (!bn.mean) return bad(FG_ERR_BAD_ARG, "in_bn mean is NULL");
     if (!bn.var) return bad(FG_ERR_BAD_ARG, "in_bn var is NULL");
-    if (!(bn.eps > 0.0f && std::isfinite(bn.eps))) return bad(FG_ERR_BAD_ARG, "in_bn eps must be positive and finite");
+    if (!actor_eps_ok(bn.eps)) return bad(FG_ERR_BAD_ARG, "in_bn eps must be positive and finite");
     const struct { const float* p; const char* name; } ptrs[] = {
         {bn.mean, "mean"}, {bn.var, "var"}, {bn.gamma, "gamma"}, {bn.beta, "beta"}};
     for (const auto& q : ptrs)
@@ -1106,9 +1106,10 @@ static int actor_in_bn_check(const char* who, const FgActor& actor, const FgActo
     return FG_OK;
 }
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
-// this order - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width and tanh flag),
-// the norms, the recurrent layer with its state, the input BatchNorm(s), log_std, logp.  The shared actor's checks name fg_rollout_hd_actor through the sample and norm entries too, the
-// log_std checks fg_rollout_hd_actor_sample.  Without log_std (the deterministic actor) `logp` is set to NULL.
+// this order, which is ABI - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
+// and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), log_std, logp.  The shared actor's
+// checks name fg_rollout_hd_actor through the sample and norm entries too, the log_std checks fg_rollout_hd_actor_sample.
+// Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
     const char* const who = hd_actor_who(c);
     const char* const shared = hd_actor_entry[hd_actor_members(c) ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
@@ -1150,6 +1151,42 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
     if ((uintptr_t)c.logp & 3u) return fail(FG_ERR_ALIGNMENT, "%s: logp_seq must be 4-byte aligned", who);
     return FG_OK;
 }
+
+// The kernels' operands from the caller's descriptions (checked: hd_actor_check).  The per-agent tables are zero past member N.
+static ActorW actor_w(const FgActor& actor) {
+    return {actor.w1, actor.b1, actor.w2, actor.b2, actor.w3, actor.b3, actor.out_tanh ? 1 : 0};
+}
+static ActorTab actor_tab(const FgActor* actors, int N) {
+    ActorTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int i = 0; i < N; ++i) {
+        tab.w1[i] = actors[i].w1; tab.b1[i] = actors[i].b1; tab.w2[i] = actors[i].w2;
+        tab.b2[i] = actors[i].b2; tab.w3[i] = actors[i].w3; tab.b3[i] = actors[i].b3;
+    }
+    tab.out_tanh = actors[0].out_tanh ? 1 : 0;
+    return tab;
+}
+static ActorBnW actor_bn_w(const FgActorInBn& bn) { return {bn.mean, bn.var, bn.gamma, bn.beta, bn.eps}; }
+static ActorBnTab actor_bn_tab(const FgActorInBn* bns, int N) {
+    ActorBnTab btab;
+    memset(&btab, 0, sizeof(btab));
+    for (int i = 0; i < N; ++i) {
+        btab.mean[i] = bns[i].mean; btab.var[i] = bns[i].var; btab.gamma[i] = bns[i].gamma;
+        btab.beta[i] = bns[i].beta; btab.eps[i] = bns[i].eps;
+    }
+    return btab;
+}
+static ActorNormW actor_norm_w(const FgActorNorm& norm) {
+    const bool in_norm = norm.in_norm != 0;
+    return {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
+            norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
+}
+static ActorGruW actor_gru_w(const HdActorCall& c) {
+    const FgActorGru& g = *c.gru;
+    return {g.w_ih, g.w_hh, g.b_ih, g.b_hh, g.norm_gamma, g.norm_beta, g.norm_eps, c.rnn_state,
+            c.states_entry ? c.rnn_states : nullptr, c.states_entry ? c.states_every : 1};
+}
+
 // The one N x H grid of the formation_hd_env actor kernels: launch(n, h) with N and H as the `value` of the arguments' types,
 // or UNSUPPORTED_N in `who`'s name when N is not in the list.  MAXH is the widest H of the caller's kernels: `hidden` is 32,
 // 64 or - MAXH == 128 only - 128 (actor_struct_check, actor_norm_check), and no launch(n, 128) is instantiated below that.
@@ -1165,71 +1202,32 @@ static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
 #undef FG_ACTOR
     return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
 }
-// a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
-static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
+// the family KIND's kernel for the call's (N, hidden), with the family's operands `w`
+template <HdActorKind KIND, class... W>
+static int hd_actor_run(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
     const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
-    if (hd_actor_members(c)) {
-        ActorTab tab;
-        memset(&tab, 0, sizeof(tab));
-        for (int i = 0; i < a.N; ++i) {
-            tab.w1[i] = c.actor[i].w1; tab.b1[i] = c.actor[i].b1; tab.w2[i] = c.actor[i].w2;
-            tab.b2[i] = c.actor[i].b2; tab.w3[i] = c.actor[i].w3; tab.b3[i] = c.actor[i].b3;
-        }
-        tab.out_tanh = c.actor[0].out_tanh ? 1 : 0;
-        if (c.kind == HD_ACTOR_BN_PER_AGENT) {
-            ActorBnTab btab;
-            memset(&btab, 0, sizeof(btab));
-            for (int i = 0; i < a.N; ++i) {
-                btab.mean[i] = c.in_bn[i].mean; btab.var[i] = c.in_bn[i].var; btab.gamma[i] = c.in_bn[i].gamma;
-                btab.beta[i] = c.in_bn[i].beta; btab.eps[i] = c.in_bn[i].eps;
-            }
-            return actor_nh_dispatch<64>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-                return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false, false, true>(a, c.log_std, c.logp, st,
-                                                                                                         tab, btab);
-            });
-        }
-        return actor_nh_dispatch<128>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, true, false>(a, c.log_std, c.logp, st, tab);
-        });
-    }
-    const ActorW w = actor_w(*c.actor);
-    if (c.kind == HD_ACTOR_BN) {
-        const ActorBnW bw = {c.in_bn->mean, c.in_bn->var, c.in_bn->gamma, c.in_bn->beta, c.in_bn->eps};
-        return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false, false, true>(a, c.log_std, c.logp, st, w,
-                                                                                                      bw);
-        });
-    }
-    if (c.kind != HD_ACTOR_NORM && c.kind != HD_ACTOR_GRU)
-        return actor_nh_dispatch<128>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, false>(a, c.log_std, c.logp, st, w);
-        });
-    const FgActorNorm& norm = *c.norm;
-    const bool in_norm = norm.in_norm != 0;
-    const ActorNormW nw = {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
-                           norm.h2_gamma, norm.h2_beta, in_norm ? norm.in_eps : 1.0f, norm.h1_eps, norm.h2_eps, in_norm ? 1 : 0};
-    if (c.kind == HD_ACTOR_GRU) {
-        const FgActorGru& g = *c.gru;
-        const ActorGruW gw = {g.w_ih, g.w_hh, g.b_ih, g.b_hh, g.norm_gamma, g.norm_beta, g.norm_eps, c.rnn_state,
-                              c.states_entry ? c.rnn_states : nullptr, c.states_entry ? c.states_every : 1};
-        return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-            return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true, true>(a, c.log_std, c.logp, st, w, nw, gw);
-        });
-    }
-    return actor_nh_dispatch<64>(a.N, c.actor->hidden, who, [&](auto n, auto h) {
-        return launch_hd_actor<decltype(n)::value, decltype(h)::value, false, true>(a, c.log_std, c.logp, st, w, nw);
+    return actor_nh_dispatch<HdActorFamily<KIND>::max_h>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(a, c.log_std, c.logp, st, w...);
     });
 }
+// a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
+static int hd_actor_dispatch(const Args& a, const HdActorCall& c, hipStream_t st) {
+    switch (c.kind) {
+    case HD_ACTOR_PER_AGENT: return hd_actor_run<HD_ACTOR_PER_AGENT>(a, c, st, actor_tab(c.actor, a.N));
+    case HD_ACTOR_NORM: return hd_actor_run<HD_ACTOR_NORM>(a, c, st, actor_w(*c.actor), actor_norm_w(*c.norm));
+    case HD_ACTOR_GRU: return hd_actor_run<HD_ACTOR_GRU>(a, c, st, actor_w(*c.actor), actor_norm_w(*c.norm), actor_gru_w(c));
+    case HD_ACTOR_BN: return hd_actor_run<HD_ACTOR_BN>(a, c, st, actor_w(*c.actor), actor_bn_w(*c.in_bn));
+    case HD_ACTOR_BN_PER_AGENT:
+        return hd_actor_run<HD_ACTOR_BN_PER_AGENT>(a, c, st, actor_tab(c.actor, a.N), actor_bn_tab(c.in_bn, a.N));
+    default: return hd_actor_run<HD_ACTOR_SHARED>(a, c, st, actor_w(*c.actor));        // HD_ACTOR_SHARED, HD_ACTOR_SAMPLE
+    }
+}
 
-// the buffers' checks and the launch of a call that has passed hd_actor_check
-static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int B, int N, int K,
-                              float* pos_x, float* pos_y, float* vel_x, float* vel_y,
-                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
-                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
-                              int obs_every, void* stream) {
-    int rc = rollout_buffers_check("fg_rollout_hd_actor", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq,
-                                   reward_seq);
-    if (rc) return rc;
+// An fg_rollout_hd_actor* entry: the call's checks, the buffers', then the launch
+static int rollout_actor_impl(const FgParams* params, HdActorCall c, int B, int N, int K, const HdRollout& r, int obs_every,
+                              void* stream) {
+    int rc = hd_actor_check(params, c, B, N, K);
+    if (rc || (rc = rollout_buffers_check("fg_rollout_hd_actor", r))) return rc;
     if (c.states_entry) {                              // the record's own checks, after every one the entry inherits
         const char* const who = hd_actor_who(c);
         if (c.states_every < 1) return fail(FG_ERR_BAD_ARG, "%s: states_every >= 1 required", who);
@@ -1237,11 +1235,11 @@ static int rollout_actor_impl(const FgParams* params, const HdActorCall& c, int 
         if ((uintptr_t)c.rnn_states & 15u) return fail(FG_ERR_ALIGNMENT, "%s: rnn_states must be 16-byte aligned", who);
     }
     if (B == 0) return FG_OK;
-    const DeviceGuard device_guard(stream, pos_x);
+    const DeviceGuard device_guard(stream, r.pos_x);
     Args a;
     if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
-    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
-    a.act_out = act_seq;
+    hd_buffers(&a, r);
+    a.act_out = r.act_seq;
     return hd_actor_dispatch(a, c, (hipStream_t)stream);
 }
 
@@ -1634,12 +1632,12 @@ int fg_rollout_hd(const FgParams* params, int B, int N, int K,
     if (B == 0 || K == 0) return FG_OK;               // empty batch / zero steps: nothing to do
     if (B < 0 || K < 0) return fail(FG_ERR_BAD_ARG, "B and K must be >= 0%s");
     if ((rc = hd_n_check(N))) return rc;
-    if ((rc = rollout_buffers_check("fg_rollout_hd", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq,
-                                    reward_seq)))
-        return rc;
+    const HdRollout r = {pos_x, pos_y, vel_x, vel_y, const_cast<float*>(act_seq), ideal_shape, ideal_vel, step,
+                         obs_seq, reward_seq, indiv_seq, done_seq};
+    if ((rc = rollout_buffers_check("fg_rollout_hd", r))) return rc;
     Args a;
     if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
-    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
+    hd_buffers(&a, r);
     a.act = act_seq;
     return rollout_hd_dispatch(a, (hipStream_t)stream);
 }
@@ -1657,12 +1655,11 @@ int fg_rollout_hd_policy(const FgParams* params, int B, int N, int K, int per_la
     if ((rc = hd_n_check(N))) return rc;
     FgPolicyLevels pl;
     if ((rc = policy_levels_check("fg_rollout_hd_policy", N, per_layer, &pl))) return rc;
-    if ((rc = rollout_buffers_check("fg_rollout_hd_policy", pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                    obs_seq, reward_seq)))
-        return rc;
+    const HdRollout r = {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq};
+    if ((rc = rollout_buffers_check("fg_rollout_hd_policy", r))) return rc;
     Args a;
     if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
-    hd_buffers(&a, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq, done_seq);
+    hd_buffers(&a, r);
     a.pl = pl; a.act_out = act_seq;
     return rollout_hd_policy_dispatch(a, per_layer, (hipStream_t)stream);
 }
@@ -1858,10 +1855,9 @@ int fg_rollout_hd_actor(const FgParams* params, const FgActor* actor, int B, int
                         float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
                         int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_SHARED, actor, nullptr, nullptr, nullptr};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_SHARED, actor}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
@@ -1869,10 +1865,9 @@ int fg_rollout_hd_actor_sample(const FgParams* params, const FgActor* actor, con
                                float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_SAMPLE, actor, nullptr, log_std, logp_seq};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_SAMPLE, actor, log_std, logp_seq}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N, int K,
@@ -1880,10 +1875,9 @@ int fg_rollout_hd_actor_per_agent(const FgParams* params, const FgActor* actors,
                                   float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                   float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                   int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, logp_seq};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_PER_AGENT, actors, log_std, logp_seq}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
@@ -1891,10 +1885,9 @@ int fg_rollout_hd_actor_norm(const FgParams* params, const FgActor* actor, const
                              float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                              float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                              int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_NORM, actor, norm, log_std, logp_seq};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_NORM, actor, log_std, logp_seq, nullptr, norm}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
@@ -1902,10 +1895,9 @@ int fg_rollout_hd_actor_gru(const FgParams* params, const FgActor* actor, const 
                             float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                             float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                             float* rnn_state, int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_GRU, actor, norm, log_std, logp_seq, gru, rnn_state};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_GRU, actor, log_std, logp_seq, nullptr, norm, gru, rnn_state}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
@@ -1913,10 +1905,10 @@ int fg_rollout_hd_actor_gru_states(const FgParams* params, const FgActor* actor,
                                    float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                    float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                    float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_GRU, actor, norm, log_std, logp_seq, gru, rnn_state, true, rnn_states, states_every};
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params,
+                              {HD_ACTOR_GRU, actor, log_std, logp_seq, nullptr, norm, gru, rnn_state, true, rnn_states, states_every}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_bn(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
@@ -1924,11 +1916,9 @@ int fg_rollout_hd_actor_bn(const FgParams* params, const FgActor* actor, const F
                            float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                            float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                            int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_BN, actor, nullptr, log_std, logp_seq};
-    c.in_bn = in_bn;
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_BN, actor, log_std, logp_seq, in_bn}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_rollout_hd_actor_bn_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
@@ -1936,11 +1926,9 @@ int fg_rollout_hd_actor_bn_per_agent(const FgParams* params, const FgActor* acto
                                      float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
                                      float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
                                      int obs_every, void* stream) {
-    HdActorCall c = {HD_ACTOR_BN_PER_AGENT, actors, nullptr, log_std, logp_seq};
-    c.in_bn = in_bns;
-    const int rc = hd_actor_check(params, c, B, N, K);
-    return rc ? rc : rollout_actor_impl(params, c, B, N, K, pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
-                                        obs_seq, reward_seq, indiv_seq, done_seq, obs_every, stream);
+    return rollout_actor_impl(params, {HD_ACTOR_BN_PER_AGENT, actors, log_std, logp_seq, in_bns}, B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
 }
 
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
@@ -1969,47 +1957,45 @@ int fg_actor_log_prob(const float* eps, const float* log_std, int64_t count, flo
 
 int fg_describe_actor_launch(const FgParams* params, const FgActor* actor, int B, int N, int K, int obs_every,
                              char* out, int out_len) {
-    return describe_actor_impl("fg_describe_actor_launch", params, {HD_ACTOR_SHARED, actor, nullptr, nullptr, nullptr}, B, N, K,
-                               obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_launch", params, {HD_ACTOR_SHARED, actor},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_sample_launch(const FgParams* params, const FgActor* actor, const float* log_std, int B, int N, int K,
                                     int obs_every, char* out, int out_len) {
-    return describe_actor_impl("fg_describe_actor_sample_launch", params, {HD_ACTOR_SAMPLE, actor, nullptr, log_std, nullptr},
+    return describe_actor_impl("fg_describe_actor_sample_launch", params, {HD_ACTOR_SAMPLE, actor, log_std},
                                B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_norm_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const float* log_std,
                                   int B, int N, int K, int obs_every, char* out, int out_len) {
-    return describe_actor_impl("fg_describe_actor_norm_launch", params, {HD_ACTOR_NORM, actor, norm, log_std, nullptr}, B, N, K,
-                               obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_norm_launch", params, {HD_ACTOR_NORM, actor, log_std, nullptr, nullptr, norm},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
                                  const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
     float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // a stand-in: the dry run has no hidden state
-    return describe_actor_impl("fg_describe_actor_gru_launch", params, {HD_ACTOR_GRU, actor, norm, log_std, nullptr, gru, state},
+    return describe_actor_impl("fg_describe_actor_gru_launch", params, {HD_ACTOR_GRU, actor, log_std, nullptr, nullptr, norm, gru, state},
                                B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_per_agent_launch(const FgParams* params, const FgActor* actors, const float* log_std, int B, int N,
                                       int K, int obs_every, char* out, int out_len) {
-    return describe_actor_impl("fg_describe_actor_per_agent_launch", params,
-                               {HD_ACTOR_PER_AGENT, actors, nullptr, log_std, nullptr}, B, N, K, obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_per_agent_launch", params, {HD_ACTOR_PER_AGENT, actors, log_std},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_bn_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const float* log_std,
                                 int B, int N, int K, int obs_every, char* out, int out_len) {
-    HdActorCall c = {HD_ACTOR_BN, actor, nullptr, log_std, nullptr};
-    c.in_bn = in_bn;
-    return describe_actor_impl("fg_describe_actor_bn_launch", params, c, B, N, K, obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_bn_launch", params, {HD_ACTOR_BN, actor, log_std, nullptr, in_bn},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_bn_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
                                           const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
-    HdActorCall c = {HD_ACTOR_BN_PER_AGENT, actors, nullptr, log_std, nullptr};
-    c.in_bn = in_bns;
-    return describe_actor_impl("fg_describe_actor_bn_per_agent_launch", params, c, B, N, K, obs_every, out, out_len);
+    return describe_actor_impl("fg_describe_actor_bn_per_agent_launch", params, {HD_ACTOR_BN_PER_AGENT, actors, log_std, nullptr, in_bns},
+                               B, N, K, obs_every, out, out_len);
 }
 
 int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario, const FgActor* actor, const float* log_std,

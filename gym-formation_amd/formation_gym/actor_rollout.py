@@ -102,6 +102,13 @@ class ActorInBn(collections.namedtuple("ActorInBn", "running_mean running_var we
     __slots__ = ()
 
 
+def _param_ok(t, shape, device):
+    """Whether the fused kernels can read the tensor `t` in place: fp32, contiguous, of `shape` (None: the module that owns it
+    guarantees the shape) and on `device` (None: not checked)."""
+    return torch.is_tensor(t) and t.dtype == torch.float32 and (shape is None or tuple(t.shape) == tuple(shape)) \
+        and t.is_contiguous() and _on_device(t, device)
+
+
 def _in_bn(m, width, device):
     """The ActorInBn of the leading module `m` over `width` features as the fused kernel can read it, else None: an
     nn.BatchNorm1d or InputBatchNorm in eval mode that tracks running statistics."""
@@ -112,25 +119,23 @@ def _in_bn(m, width, device):
     if not (eps > 0.0 and math.isfinite(eps)):
         return None
     for t, required in ((m.running_mean, True), (m.running_var, True), (m.weight, False), (m.bias, False)):
-        if t is None and not required:
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (int(width),) or not t.is_contiguous() \
-                or not _on_device(t, device):
+        if (t is not None or required) and not _param_ok(t, (int(width),), device):
             return None
     return ActorInBn(m.running_mean, m.running_var, m.weight, m.bias, eps)
 
 
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], norms) when a fused kernel can evaluate the shared actor body `actor` for
-    `num_agents` agents, else None.  The two forms, each with its own kernels and so its own hidden widths:
+    """The FusedActor fields hidden, out_tanh, members = [[w1, b1, w2, b2, w3, b3]] and the form's own (below) when a fused kernel
+    can evaluate the shared actor body `actor` for `num_agents` agents, else None.  The three forms, each with its own kernels
+    and so its own hidden widths:
         Sequential(Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])              H in `fused_hidden`
         Sequential([LayerNorm(D),] Linear(D, H), ReLU(), LayerNorm(H), Linear(H, H), ReLU(), LayerNorm(H), Linear(H, 2)
                    [, Tanh()])                                                                       H in `fused_ln_hidden`
         Sequential(BatchNorm1d(D), Linear(D, H), ReLU(), Linear(H, H), ReLU(), Linear(H, 2) [, Tanh()])  H in `fused_bn_hidden`
-    `norms` is None for the first, the ActorInBn of the third (`_in_bn`: eval mode, running statistics) and the ActorNorms of
-    the second, whose every LayerNorm is over its last axis alone with
-    fp32 contiguous parameters on `device` or none.  `device`: the env's device (None: not checked).  The tensors are the
+    The first adds no field, the second `norms` - its ActorNorms, every LayerNorm over its last axis alone with fp32 contiguous
+    parameters on `device` or none - and the third `in_bn`, its ActorInBn (`_in_bn`: eval mode, running statistics).
+    `device`: the env's device (None: not checked).  The tensors are the
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
     are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact, not read
@@ -152,9 +157,9 @@ def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, 
         out_tanh = kinds[-1:] == [nn.Tanh]
         if kinds[:5] != [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] or len(kinds) != 5 + out_tanh:
             return None
-        spec = _linears_spec(mods[1], mods[3], mods[5], out_tanh, in_features, device, fused_bn_hidden)
-        bn = None if spec is None else _in_bn(mods[0], in_features, None if device is None else torch.device(device))
-        return None if bn is None else spec + (bn,)
+        fields = _linears_spec(mods[1], mods[3], mods[5], out_tanh, in_features, device, fused_bn_hidden)
+        bn = None if fields is None else _in_bn(mods[0], in_features, device)
+        return None if bn is None else dict(fields, in_bn=bn)
     lead = bool(mods) and type(mods[0]) is nn.LayerNorm
     rest = mods[1:] if lead else mods
     kinds = [type(m) for m in rest]
@@ -162,61 +167,61 @@ def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, 
     if out_tanh:
         kinds.pop()
     if kinds == [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] and not lead:
-        spec = _linears_spec(rest[0], rest[2], rest[4], out_tanh, in_features, device, fused_hidden)
-        return None if spec is None else spec + (None,)
+        return _linears_spec(rest[0], rest[2], rest[4], out_tanh, in_features, device, fused_hidden)
     if kinds != [nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear]:
         return None
-    spec = _linears_spec(rest[0], rest[3], rest[6], out_tanh, in_features, device, fused_ln_hidden)
-    if spec is None:
+    fields = _linears_spec(rest[0], rest[3], rest[6], out_tanh, in_features, device, fused_ln_hidden)
+    if fields is None:
         return None
-    dev = None if device is None else torch.device(device)
-    n0 = _norm_triple(mods[0], rest[0].in_features, dev) if lead else None
-    n1, n2 = _norm_triple(rest[2], spec[0], dev), _norm_triple(rest[5], spec[0], dev)
+    H = fields["hidden"]
+    n0 = _norm_triple(mods[0], rest[0].in_features, device) if lead else None
+    n1, n2 = _norm_triple(rest[2], H, device), _norm_triple(rest[5], H, device)
     if (lead and n0 is None) or n1 is None or n2 is None:
         return None
-    return spec + (ActorNorms(n0, n1, n2),)
+    return dict(fields, norms=ActorNorms(n0, n1, n2))
 
 
 def actor_spec(actor, num_agents, device=None, **facts):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) when the fused kernel can evaluate the actor without LayerNorms `actor`
     for `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its first form.  This function never
     accepts a LayerNorm."""
-    spec = _body_spec(actor, num_agents, device, **facts)
-    return spec[:3] if spec is not None and spec[3] is None else None
+    f = _body_spec(actor, num_agents, device, **facts)
+    return _shared_triple(f) if f is not None and len(f) == 3 else None
 
 
 def layernorm_spec(actor, num_agents, device=None, **facts):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms) when the fused LayerNorm kernel can evaluate `actor` for
     `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its second form.  An actor without
     LayerNorms is `actor_spec`'s, not this function's."""
-    spec = _body_spec(actor, num_agents, device, **facts)
-    return spec if spec is not None and isinstance(spec[3], ActorNorms) else None
+    f = _body_spec(actor, num_agents, device, **facts)
+    return _shared_triple(f) + (f["norms"],) if f is not None and "norms" in f else None
 
 
 def batchnorm_spec(actor, num_agents, device=None, **facts):
     """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorInBn) when the fused BatchNorm kernel can evaluate `actor` for
     `num_agents` agents, else None: `_body_spec`'s answer (same arguments) for its third form."""
-    spec = _body_spec(actor, num_agents, device, **facts)
-    return spec if spec is not None and isinstance(spec[3], ActorInBn) else None
+    f = _body_spec(actor, num_agents, device, **facts)
+    return _shared_triple(f) + (f["in_bn"],) if f is not None and "in_bn" in f else None
+
+
+def _shared_triple(fields):
+    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) of a shared body's FusedActor fields: what the public spec functions start
+    with."""
+    return fields["hidden"], fields["out_tanh"], fields["members"][0]
 
 
 def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3]) of the three Linears of a body whose module kinds have been checked, else
-    None.  `fused_hidden`: the hidden widths of that body's kernels (None or empty: none)."""
+    """The FusedActor fields hidden, out_tanh and members = [[w1, b1, w2, b2, w3, b3]] of the three Linears of a body whose
+    module kinds have been checked, else None.  `fused_hidden`: the hidden widths of that body's kernels (None or empty:
+    none)."""
     H = l1.out_features
     if H not in tuple(fused_hidden or ()) or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
             or (l3.in_features, l3.out_features) != (H, 2):
         return None
     params = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
-    dev = None if device is None else torch.device(device)
-    for t in params:
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            return None
-        if not _on_device(t, dev):
-            return None
-    return H, out_tanh, params
+    if not all(t is None or _param_ok(t, None, device) for t in params):
+        return None
+    return dict(hidden=H, out_tanh=bool(out_tanh), members=[params])
 
 
 class ActorNorms(collections.namedtuple("ActorNorms", "input hidden1 hidden2")):
@@ -234,12 +239,8 @@ def _norm_triple(m, width, device):
     if not (eps > 0.0 and math.isfinite(eps)):
         return None
     g, b = m.weight, getattr(m, "bias", None)
-    for t in (g, b):
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (int(width),) or not t.is_contiguous() \
-                or not _on_device(t, device):
-            return None
+    if not all(t is None or _param_ok(t, (int(width),), device) for t in (g, b)):
+        return None
     return g, b, eps
 
 
@@ -313,8 +314,8 @@ class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
 
 def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                     fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
-    """(hidden, out_tanh, [w1, b1, w2, b2, w3, b3], ActorNorms, ActorGru) when the fused recurrent kernel can evaluate the
-    RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
+    """The FusedActor fields of `_body_spec`'s LayerNorm form and `gru`, the ActorGru, when the fused recurrent kernel can evaluate
+    the RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
     of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
     one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
     parameter fp32, contiguous and on `device`.  `fused_bn_hidden` is `_body_spec`'s fact, not read here: a base that starts
@@ -329,23 +330,20 @@ def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FU
         head_mods = list(head)
     else:
         return None
-    spec = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden)
-    if spec is None or not isinstance(spec[3], ActorNorms):
+    fields = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden)
+    if fields is None or "norms" not in fields:
         return None
-    H = spec[0]
+    H = fields["hidden"]
     rnn = actor.rnn
     if type(rnn) not in (nn.GRUCell, nn.GRU) or not actor._one_cell() or (rnn.input_size, rnn.hidden_size) != (H, H):
         return None
-    dev = None if device is None else torch.device(device)
     params = actor.gru_parameters()
-    for t, shape in zip(params, ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,))):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
-                or not _on_device(t, dev):
-            return None
-    norm = _norm_triple(actor.norm, H, dev)
+    if not all(_param_ok(t, shape, device) for t, shape in zip(params, ((3 * H, H), (3 * H, H), (3 * H,), (3 * H,)))):
+        return None
+    norm = _norm_triple(actor.norm, H, device)
     if norm is None:
         return None
-    return spec + (ActorGru(*params, norm),)
+    return dict(fields, gru=ActorGru(*params, norm))
 
 
 class PerAgentActor(torch.nn.Module):
@@ -456,11 +454,7 @@ def sample_spec(actor, num_agents, device=None, **facts):
 
 def _fused_log_std(actor, device):
     """The GaussianActor's log_std when the fused launch can read it in place (contiguous fp32 [2] on `device`), else None."""
-    ls = actor.log_std
-    if not torch.is_tensor(ls) or ls.dtype != torch.float32 or tuple(ls.shape) != (2,) or not ls.is_contiguous() \
-            or not _on_device(ls, device):
-        return None
-    return ls
+    return actor.log_std if _param_ok(actor.log_std, (2,), device) else None
 
 
 class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn",
@@ -498,23 +492,15 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
             return None
     members_own = isinstance(mean, PerAgentActor)
     if members_own:
-        spec = per_agent_spec(mean, num_agents, device) if per_agent else None
-        spec = None if spec is None else spec + (None, None)
+        spec, names = per_agent_spec(mean, num_agents, device) if per_agent else None, ("hidden", "out_tanh", "members")
         if spec is None and per_agent and tuple(facts.get("fused_bn_hidden", FUSED_BN_HIDDEN) or ()):
-            spec = per_agent_bn_spec(mean, num_agents, device)
-            spec = None if spec is None else spec + (None,)
+            spec, names = per_agent_bn_spec(mean, num_agents, device), names + ("in_bn",)
+        fields = None if spec is None else dict(zip(names, spec))
     elif isinstance(mean, RecurrentActor):
-        spec = _recurrent_spec(mean, num_agents, device, **facts)
+        fields = _recurrent_spec(mean, num_agents, device, **facts)
     else:
-        spec = _body_spec(mean, num_agents, device, **facts)
-        spec = None if spec is None else spec + (None,)
-    if spec is None:
-        return None
-    hidden, out_tanh, weights, norms, gru = spec
-    in_bn = None
-    if isinstance(norms, ActorInBn) or isinstance(norms, list):
-        in_bn, norms = norms, None
-    return FusedActor(hidden, bool(out_tanh), weights if members_own else [weights], members_own, log_std, norms, gru, in_bn)
+        fields = _body_spec(mean, num_agents, device, **facts)
+    return None if fields is None else FusedActor(per_agent=members_own, log_std=log_std, **fields)
 
 
 def recurrent_mean(actor):

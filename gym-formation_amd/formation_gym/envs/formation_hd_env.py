@@ -257,7 +257,7 @@ class Scenario(BaseScenario):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
-        other tensors are those of `rollout_batch`.  The entry point by (gru, norms, per_agent, log_std):
+        other tensors are those of `rollout_batch`.  The entry points (the `families` list below, last row first):
           one shared actor                      `fg_rollout_hd_actor`
           ... with a GaussianActor's log_std    `fg_rollout_hd_actor_sample`, the log-densities in out["log_prob"] [K,B,N]
           one actor per agent                   `fg_rollout_hd_actor_per_agent` (log_std or NULL), agent i's rows through
@@ -296,29 +296,27 @@ class Scenario(BaseScenario):
                  _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                  _native.ptr(out.get("done")))
         tail = (int(obs_every), _native.current_stream(world.device))
-        # (gru, norms, per_agent, gaussian) -> (entry point, its arguments before the state, logp_seq follows the state);
-        # the recurrent entry's rnn_state follows logp_seq
-        ls = _native.ptr(log_std)
-        pa, ln = (lib.fg_rollout_hd_actor_per_agent, (fas, ls), True), (lib.fg_rollout_hd_actor_norm, (fas, norm, ls), True)
-        gr = (lib.fg_rollout_hd_actor_gru, (fas, norm, gru, ls), True)
-        table = {(False, False, False, False): (lib.fg_rollout_hd_actor, (fas,), False),
-                 (False, False, False, True): (lib.fg_rollout_hd_actor_sample, (fas, ls), True),
-                 (False, False, True, False): pa, (False, False, True, True): pa,
-                 (False, True, False, False): ln, (False, True, False, True): ln,
-                 (True, True, False, False): gr, (True, True, False, True): gr}
-        key = (gru is not None, norm is not None, bool(actor.per_agent), log_std is not None)
-        if key not in table:
+        if (gru is not None and norm is None) or (norm is not None and actor.per_agent):
             raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
-        fn, lead, with_logp = table[key]
-        if bns is not None:
-            fn = lib.fg_rollout_hd_actor_bn_per_agent if actor.per_agent else lib.fg_rollout_hd_actor_bn
-            lead, with_logp = (fas, bns, ls), True
+        # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, and
+        # what follows the state: logp_seq, rnn_state, (rnn_states, states_every))
+        ls = _native.ptr(log_std)
+        families = (
+            (bns is not None and actor.per_agent, "fg_rollout_hd_actor_bn_per_agent", (fas, bns, ls), True, False, False),
+            (bns is not None, "fg_rollout_hd_actor_bn", (fas, bns, ls), True, False, False),
+            (rnn_states_every is not None, "fg_rollout_hd_actor_gru_states", (fas, norm, gru, ls), True, True, True),
+            (gru is not None, "fg_rollout_hd_actor_gru", (fas, norm, gru, ls), True, True, False),
+            (norm is not None, "fg_rollout_hd_actor_norm", (fas, norm, ls), True, False, False),
+            (actor.per_agent, "fg_rollout_hd_actor_per_agent", (fas, ls), True, False, False),
+            (log_std is not None, "fg_rollout_hd_actor_sample", (fas, ls), True, False, False),
+            (True, "fg_rollout_hd_actor", (fas,), False, False, False))
+        entry, lead, with_logp, with_state, with_states = next(row[1:] for row in families if row[0])
         logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
-        hidden = () if gru is None else (rnn_state.data_ptr(),)
-        if rnn_states_every is not None:
-            fn, hidden = lib.fg_rollout_hd_actor_gru_states, hidden + (out["rnn_states"].data_ptr(), int(rnn_states_every))
+        hidden = (rnn_state.data_ptr(),) if with_state else ()
+        if with_states:
+            hidden += (out["rnn_states"].data_ptr(), int(rnn_states_every))
         args = lead + state + logp + hidden + tail
-        return _native.bind_launch(fn, p, *args,
+        return _native.bind_launch(getattr(lib, entry), p, *args,
                                    keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
                                          actor.gru, gru, rnn_state, in_bn, bns))
 

@@ -3,8 +3,9 @@ libformation_hip.so, for the kernels whose demangled name contains one of the gi
 
     python profiles/kernel_metadata_diff.py OLD.so NEW.so [substring ...]
 
-Default substrings: the six formation_hd_env actor kernel families.  Prints one line per family - kernels compared, kernels that
-differ - then every differing kernel with both records, and exits 1 if any differ or a kernel is missing on either side."""
+Default substrings: the twelve formation_hd_env actor kernels (six families, each deterministic and Gaussian).  Prints one
+line per substring - kernels compared, kernels that differ - then every differing kernel with both records, and exits 1 if any
+differ or a kernel is missing on either side."""
 import os
 import sys
 
@@ -12,7 +13,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.isa_scan import kernel_resources  # noqa: E402
 
 FAMILIES = ("actor_rollout_kernel<", "actor_sample_kernel<", "pa_actor_kernel<", "pa_sample_kernel<", "ln_actor_kernel<",
-            "ln_sample_kernel<")
+            "ln_sample_kernel<", "gru_actor_kernel<", "gru_sample_kernel<", "::bn_actor_kernel<", "::bn_sample_kernel<",
+            "pa_bn_actor_kernel<", "pa_bn_sample_kernel<")
 
 
 def main(argv):
