@@ -1,7 +1,7 @@
 // fg_scn_lane_kernel.hpp - The landmark scenarios at their reference shapes: ONE ENVIRONMENT PER LANE, every count a
 // compile-time constant.  Part of libformation_hip (gfx950); included by formation_hip.hip, one translation unit.
 //
-// fg::scn_kernel (fg_aux_kernels.hpp) gives one lane to every movable entity and walks run-time loops over 3-7 entities:
+// fg::scn_kernel (fg_scn_kernel.hpp) gives one lane to every movable entity and walks run-time loops over 3-7 entities:
 // at 3 agents 3 of 4 lanes work, the loops cost as many scalar and branch instructions as vector ones, and the kernel
 // runs at 0.3-0.4 of the HBM rate (profiles/r03_scn_pmc.txt).  Here a lane owns a whole environment: agents, obstacles
 // and landmarks live in its registers, every pair loop is unrolled, nothing is reduced across lanes, and the 64
@@ -49,14 +49,6 @@ template <int G> FG_DEV float lane_group_sum(const float (&x)[G]) {
     return t[0];
 }
 
-__host__ __device__ constexpr int scn_group_lanes(int entities) {     // scn_kernel's G: pow2 >= N + M, at least 4
-    int g = 4;
-    while (g < entities) g <<= 1;
-    return g;
-}
-__host__ __device__ constexpr int scn_obs_dim(int kind, int n, int l, int m, int nbr) {
-    return 2 + (kind == FG_SCN_BASIC ? 2 : 0) + 2 * l + 2 * m + 2 * nbr + 2 * (n - 1);
-}
 // LDS pitch (float2 units) of one env's [N][D] block: odd, so that the lanes' ds_write_b64 fall on distinct banks
 __host__ __device__ constexpr int scn_lane_pitch(int units) { return units | 1; }
 

@@ -24,9 +24,9 @@
 //
 // Source layout: fg_common.hpp (arguments, LDS layout, reductions, RNG, World options),
 // fg_pair_loops.hpp, fg_obs_writers.hpp, fg_step_kernel.hpp, fg_rollout_kernels.hpp,
-// fg_policy_kernels.hpp (the reference's demo controller), fg_aux_kernels.hpp (resets, landmark
+// fg_policy_kernels.hpp (the reference's demo controller), fg_aux_kernels.hpp (resets) with fg_scn_kernel.hpp (landmark
 // scenarios); this file holds the host side: variant tables, dispatch and the extern "C" entry
-// points.  formation_hip_f64.hip builds the step kernel's source in double (tests only).
+// points.  formation_hip_f64.hip builds the step, rollout and scenario kernels' source in double (tests only).
 
 #include <atomic>
 #include <cmath>
@@ -893,16 +893,14 @@ static int scenario_dispatch(ScnArgs a, hipStream_t st) {
         FG_SCN_SHAPES(FG_SCN_LANE)
 #undef FG_SCN_LANE
     }
-    constexpr int FG_SCN_T = 64;      // threads per workgroup of the scenario kernel up to 64 entities per env
-    const int G = pow2ceil(N + M) < 4 ? 4 : pow2ceil(N + M);
-    const int E = G <= 64 ? FG_SCN_T / G : 1;         // more than 64 entities: one env per workgroup of G threads
+    const int G = scn_group_lanes(N + M);
+    const int E = scn_envs_per_group(G);              // more than 64 entities: one env per workgroup of G threads
     const int grid = (B + E - 1) / E;
-    int lds = (E * (2 * (N + M) + L) + (G > 64 ? 32 : 0)) * (int)sizeof(float2);
+    int lds = (int)scn_lds_bytes(G, N, L, M, 0);
     {   // observation rows composed in LDS and streamed out contiguously when the workgroup's block fits
-        const long long D = 2 + (a.sc.kind == FG_SCN_BASIC ? 2 : 0) + 2LL * L + 2LL * M + 2LL * nbr + 2LL * (N - 1);
-        const long long stage = (long long)E * N * D * (long long)sizeof(float);
-        a.stage = (lds + stage <= 48 * 1024) ? 1 : 0;
-        if (a.stage) lds += (int)stage;
+        const long long staged = scn_lds_bytes(G, N, L, M, scn_obs_dim(a.sc.kind, N, L, M, nbr));
+        a.stage = (staged <= 48 * 1024) ? 1 : 0;
+        if (a.stage) lds = (int)staged;
     }
     if (describe("scn_kernel<%d,%d> grid %d lds %d stage %d; ", G, G <= 64 ? FG_SCN_T : G, grid, lds, a.stage)) return FG_OK;
     return pow2_dispatch(G, [&](auto g, auto t) {

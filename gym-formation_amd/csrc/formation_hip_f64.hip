@@ -10,6 +10,9 @@
 // with corner rounding / soft walls / ghosts, the per-agent table with its mass ratio, per-pair contact and penalty distances,
 // immovable / non-colliding / scripted agents, the communication block of the flat writer, the 1024-thread re-fetch of the
 // properties, the K-loop), each free-running on the reference's option fixtures (tests/test_gpu_f64_options.py).
+// fg64_rollout_scenario is the run-time-count kernel of the four landmark scenarios (fg_scn_kernel.hpp: scn_kernel<G, T> at every
+// lane-group width 4 ... 64 and every whole-workgroup size 128 ... 1024, both observation writers, the K-loop, per-agent tables and
+// walls), free-running on the 14 landmark fixtures (tests/test_gpu_f64_scenarios.py).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=on -DFG_F64=1 -fPIC -shared -Iinclude
 //         -o lib/libformation_hip_f64.so csrc/formation_hip_f64.hip          (no -fapprox-func: full-precision libm)
@@ -18,6 +21,7 @@
 #include "fg_pair_loops.hpp"
 #include "fg_step_kernel.hpp"
 #include "fg_rollout_kernels.hpp"
+#include "fg_scn_kernel.hpp"
 
 namespace fg {
 
@@ -74,6 +78,23 @@ static int launch_step64(const Args& a, bool idx, bool opts, hipStream_t st) {
         case 256: FG64(256, 256, 1);  case 512: FG64(512, 512, 1);  default: FG64(1024, 1024, 1);
     }
 #undef FG64
+}
+
+// scn_kernel<G, T> as scenario_dispatch (formation_hip.hip) chooses it: G = pow2 >= N + M lanes per env in workgroups of 64 threads,
+// one env per workgroup of G threads beyond 64 entities; LDS by scn_lds_bytes.  a.stage = 1: the staged observation writer.
+// -2: the workgroup's LDS (with the image, if asked for) does not fit; -4: the runtime refused; 0: launched
+template <int G, int T>
+static int launch_scn64(const ScnArgs& a, int obs_dim, hipStream_t st) {
+    constexpr int E = scn_envs_per_group(G);
+    static_assert(E == T / G, "the kernel's envs per workgroup");
+    const int grid = (a.B + E - 1) / E;
+    const long long lds = scn_lds_bytes(G, a.N, a.sc.num_landmarks, a.sc.num_obstacles, a.stage ? obs_dim : 0);
+    if (lds > FG64_LDS_LIMIT) return -2;
+    const auto kernel = &scn_kernel<G, T>;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -4;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(T), (size_t)lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 }  // namespace fg
@@ -180,6 +201,65 @@ int fg64_rollout_hd(const Fg64Params* params, int B, int N, int K,
     const hipError_t err = N == 9 ? launch_roll64<9, 16, 64, 128, 4>(a, st) : N == 27 ? launch_roll64<27, 32, 128, 256, 4>(a, st)
                          : N == 81 ? launch_wide64<81, 2, 2, 128>(a, st) : launch_wide64<243, 4, 1, 256>(a, st);
     return err == hipSuccess ? 0 : -4;
+}
+
+// The landmark scenarios' constants in double, field for field what FgScenario holds (kind: FG_SCN_BASIC ... FG_SCN_OBSTACLE)
+struct Fg64Scenario {
+    int32_t kind, num_landmarks, num_obstacles, num_obs;
+    double obs_range, obstacle_size, obstacle_vx, obstacle_vy, obstacle_floor, penalty;
+};
+
+// fg_step_scenario / fg_step_basic / fg_rollout_scenario in fp64: K steps in ONE launch of scn_kernel through its own K-loop (K = 1:
+// a single step; do_physics = 0: the observation and rewards of the state as it is).  opts: accel, max_speed, walls and the per-agent
+// table (comm_state must be NULL).  act [K][B][N][2], landmarks [B][L][2], obst_pos / obst_vel [B][M][2], obs [K / obs_every][B][N][D],
+// reward / indiv_reward / done [K][B][N], near_ag [K][B][L] (basic; may be NULL).  stage: 0 = every lane writes its row straight to
+// memory, 1 = the rows are composed in LDS and streamed out (the product picks this where the image fits 48 KB).  auto_reset, u_noise
+// and comm_state stay off.  Returns 0, -1 bad argument, -2 unsupported count or a workgroup whose LDS does not fit (stage = 1 with
+// an image that does not fit included), -4 HIP error.
+int fg64_rollout_scenario(const Fg64Params* params, const Fg64Scenario* sc, const Fg64Options* opts, int B, int N, int K,
+                          int do_physics, int obs_every, int stage,
+                          double* pos_x, double* pos_y, double* vel_x, double* vel_y, const double* act, double* landmarks,
+                          double* obst_pos, double* obst_vel, int32_t* step,
+                          double* obs, double* reward, double* indiv_reward, uint8_t* done, int32_t* near_ag, void* stream) {
+    using namespace fg;
+    if (!params || !sc || !opts || B < 0 || K < 1 || obs_every < 1 || (K > 1 && !do_physics) || (stage != 0 && stage != 1)) return -1;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !landmarks || !obs || (do_physics && (!act || !reward))) return -1;
+    if (sc->kind < FG_SCN_BASIC || sc->kind > FG_SCN_OBSTACLE || sc->num_landmarks < 1 || sc->num_obstacles < 0) return -1;
+    if ((sc->kind == FG_SCN_OBSTACLE) != (sc->num_obstacles > 0) || (sc->num_obstacles > 0 && (!obst_pos || !obst_vel))) return -1;
+    if (opts->num_walls < 0 || opts->num_walls > FG_MAX_WALLS || opts->accel < 0 || opts->max_speed < 0 || opts->comm_state) return -1;
+    if (sc->kind == FG_SCN_PARTIAL && (sc->num_obs < 0 || sc->num_obs > 1024)) return -1;
+    if (N < 1 || N + sc->num_obstacles > 1024 || sc->num_landmarks > 1024) return -2;
+    if (B == 0) return 0;
+    ScnArgs a; memset(&a, 0, sizeof(a));
+    a.p.dt = params->dt; a.p.damping = params->damping; a.p.contact_force = params->contact_force;
+    a.p.contact_margin = params->contact_margin; a.p.sensitivity = params->sensitivity; a.p.mass = params->mass;
+    a.p.dist_min = params->dist_min; a.p.collide_thresh = params->collide_thresh; a.p.world_length = params->world_length;
+    a.p.accel = opts->accel; a.p.max_speed = opts->max_speed; a.p.u_noise = 0.0;
+    a.p.num_walls = opts->num_walls;
+    for (int w = 0; w < opts->num_walls; ++w) {
+        const Fg64Wall& s = opts->walls[w];
+        a.p.walls[w].vertical = s.vertical; a.p.walls[w].soft = s.soft;
+        a.p.walls[w].axis_pos = s.axis_pos; a.p.walls[w].end0 = s.end0; a.p.walls[w].end1 = s.end1; a.p.walls[w].width = s.width;
+    }
+    a.p.agent_props = opts->agent_props;
+    a.sc.kind = sc->kind; a.sc.num_landmarks = sc->num_landmarks; a.sc.num_obstacles = sc->num_obstacles; a.sc.num_obs = sc->num_obs;
+    a.sc.obs_range = sc->obs_range; a.sc.obstacle_size = sc->obstacle_size; a.sc.obstacle_vx = sc->obstacle_vx;
+    a.sc.obstacle_vy = sc->obstacle_vy; a.sc.obstacle_floor = sc->obstacle_floor; a.sc.penalty = sc->penalty;
+    a.B = B; a.N = N; a.do_phys = do_physics ? 1 : 0; a.K = K; a.obs_every = obs_every; a.stage = stage;
+    a.inv_n = 1.0 / (double)N; a.inv_l = 1.0 / (double)sc->num_landmarks;
+    a.coll_scale = params->collide_thresh / params->dist_min;           // divided in double
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.act = act; a.lm = landmarks; a.opos = obst_pos; a.ovel = obst_vel;
+    a.step = step; a.obs = obs; a.rew = reward; a.indiv = indiv_reward; a.done = done; a.near_ag = near_ag;
+    const int nbr = sc->kind == FG_SCN_PARTIAL ? sc->num_obs : N - 1;
+    const int D = scn_obs_dim(sc->kind, N, sc->num_landmarks, sc->num_obstacles, nbr);
+    hipStream_t st = (hipStream_t)stream;
+    switch (scn_group_lanes(N + sc->num_obstacles)) {
+        case 4: return launch_scn64<4, FG_SCN_T>(a, D, st);       case 8: return launch_scn64<8, FG_SCN_T>(a, D, st);
+        case 16: return launch_scn64<16, FG_SCN_T>(a, D, st);     case 32: return launch_scn64<32, FG_SCN_T>(a, D, st);
+        case 64: return launch_scn64<64, FG_SCN_T>(a, D, st);     case 128: return launch_scn64<128, 128>(a, D, st);
+        case 256: return launch_scn64<256, 256>(a, D, st);        case 512: return launch_scn64<512, 512>(a, D, st);
+        default: return launch_scn64<1024, 1024>(a, D, st);
+    }
 }
 
 }  // extern "C"

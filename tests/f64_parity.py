@@ -32,6 +32,13 @@ class Fg64Options(ctypes.Structure):
                 ("comm_state", ctypes.c_void_p)]
 
 
+class Fg64Scenario(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "num_landmarks", "num_obstacles", "num_obs")] + \
+               [(k, ctypes.c_double) for k in ("obs_range", "obstacle_size", "obstacle_vx", "obstacle_vy", "obstacle_floor", "penalty")]
+
+
+SCN_KINDS = {"basic": 1, "partial": 2, "range": 3, "obstacle": 4}            # FgScenarioKind (include/formation_hip.h)
+
 _lib = None
 
 
@@ -46,6 +53,9 @@ def load():
                                          [ctypes.c_void_p] * 16
         lib.fg64_rollout_hd.restype = ctypes.c_int
         lib.fg64_rollout_hd.argtypes = [ctypes.POINTER(Fg64Params), ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 13
+        lib.fg64_rollout_scenario.restype = ctypes.c_int
+        lib.fg64_rollout_scenario.argtypes = [ctypes.POINTER(Fg64Params), ctypes.POINTER(Fg64Scenario), ctypes.POINTER(Fg64Options)] + \
+                                             [ctypes.c_int] * 6 + [ctypes.c_void_p] * 15
         _lib = lib
     return _lib
 
@@ -188,6 +198,92 @@ class Env64(object):
 
     def vel(self):
         return torch.stack((self.vx, self.vy), -1).cpu().numpy()
+
+
+def scenario_of(kind, P):
+    """Fg64Scenario of an oracle parameter object (O.BasicParams / O.ScnParams): the same doubles"""
+    if kind == "basic":
+        return Fg64Scenario(kind=SCN_KINDS[kind], num_landmarks=P.num_landmarks, num_obstacles=0, num_obs=0, obs_range=0.0,
+                            obstacle_size=0.0, obstacle_vx=0.0, obstacle_vy=0.0, obstacle_floor=0.0, penalty=1.0)
+    return Fg64Scenario(kind=SCN_KINDS[kind], num_landmarks=P.num_landmarks, num_obstacles=P.num_obstacles, num_obs=P.num_obs,
+                        obs_range=P.obs_range, obstacle_size=P.obstacle_size, obstacle_vx=P.obstacle_vel[0],
+                        obstacle_vy=P.obstacle_vel[1], obstacle_floor=P.obstacle_floor, penalty=P.penalty)
+
+
+SENTINEL = -7.5e33          # fill of every float output before a launch: a value no scenario produces
+
+
+class Scn64(object):
+    """B envs of a landmark scenario (kind: basic / partial / range / obstacle) held in fp64 device tensors; `rollout(acts)` = ONE
+    fg64_rollout_scenario launch of K = len(acts) steps through scn_kernel's own K-loop, `step(act)` = a launch with K = 1.
+    state: dict(pos, vel [B,N,2], landmarks [B,L,2], obst_pos, obst_vel [B,M,2] (obstacle), step [B]); P: the oracle's parameter
+    object; options: as kernel_options() makes them; stage: which observation writer (0 straight to memory, 1 through LDS)."""
+
+    def __init__(self, kind, state, P, options=None, stage=0):
+        f = dict(dtype=torch.float64, device="cuda")
+        dev = lambda x: torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float64)), **f)
+        pos, vel = np.asarray(state["pos"], dtype=np.float64), np.asarray(state["vel"], dtype=np.float64)
+        self.kind, self.stage = kind, int(stage)
+        self.B, self.N = pos.shape[:2]
+        self.px, self.py, self.vx, self.vy = dev(pos[..., 0]), dev(pos[..., 1]), dev(vel[..., 0]), dev(vel[..., 1])
+        self.lm = dev(state["landmarks"])
+        self.L = self.lm.shape[1]
+        self.M = P.num_obstacles if kind == "obstacle" else 0
+        self.opos = dev(state["obst_pos"]) if self.M else None
+        self.ovel = dev(state["obst_vel"]) if self.M else None
+        assert tuple(self.lm.shape) == (self.B, self.L, 2) and (not self.M or tuple(self.opos.shape) == (self.B, self.M, 2))
+        self.step_count = torch.as_tensor(np.ascontiguousarray(np.asarray(state["step"], dtype=np.int32))).cuda()
+        self.params = params_of(P)
+        self.scenario = scenario_of(kind, P)
+        nbr = P.num_obs if kind == "partial" else self.N - 1
+        self.D = 2 + (2 if kind == "basic" else 0) + 2 * self.L + 2 * self.M + 2 * nbr + 2 * (self.N - 1)
+        options = options or {}
+        o = Fg64Options(accel=options.get("accel", 0.0), max_speed=options.get("max_speed", 0.0), num_walls=len(options.get("walls") or []))
+        assert o.num_walls <= MAX_WALLS
+        for k, w in enumerate(options.get("walls") or []):
+            o.walls[k] = Fg64Wall(**w)
+        self.props = None
+        if options.get("agent_props") is not None:
+            t = np.ascontiguousarray(options["agent_props"], dtype=np.float64)
+            assert t.shape == (self.N, AGENT_PROPS)
+            self.props = torch.as_tensor(t, **f)
+            o.agent_props = self.props.data_ptr()
+        self.options = o
+        if options.get("sensitivity") is not None:
+            self.params.sensitivity = options["sensitivity"]
+
+    def launch(self, acts, obs_every=1, do_physics=1):
+        """The raw return code and the outputs of one launch over acts [K,B,N,2]: (rc, dict(obs [K / obs_every,B,N,D], reward, indiv,
+        done [K,B,N], near_ag [K,B,L] for basic)).  Every output is filled with a sentinel (SENTINEL / 7 / -1) beforehand."""
+        f = dict(dtype=torch.float64, device="cuda")
+        acts = torch.as_tensor(np.ascontiguousarray(np.asarray(acts, dtype=np.float64)), **f)
+        K, B, N = acts.shape[0], self.B, self.N
+        assert tuple(acts.shape) == (K, B, N, 2)
+        out = dict(obs=torch.full((K // max(obs_every, 1), B, N, self.D), SENTINEL, **f), reward=torch.full((K, B, N), SENTINEL, **f),
+                   indiv=torch.full((K, B, N), SENTINEL, **f), done=torch.full((K, B, N), 7, dtype=torch.uint8, device="cuda"))
+        if self.kind == "basic":
+            out["near_ag"] = torch.full((K, B, self.L), -1, dtype=torch.int32, device="cuda")
+        p = lambda t: None if t is None else t.data_ptr()
+        rc = load().fg64_rollout_scenario(self.params, self.scenario, self.options, B, N, K, do_physics, obs_every, self.stage,
+                                          p(self.px), p(self.py), p(self.vx), p(self.vy), p(acts), p(self.lm), p(self.opos),
+                                          p(self.ovel), p(self.step_count), p(out["obs"]), p(out["reward"]), p(out["indiv"]),
+                                          p(out["done"]), p(out.get("near_ag")), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return rc, {k: v.cpu().numpy() for k, v in out.items()}
+
+    def rollout(self, acts, obs_every=1):
+        rc, out = self.launch(acts, obs_every)
+        assert rc == 0, "fg64_rollout_scenario returned %d" % rc
+        return out
+
+    def step(self, act):
+        return {k: v[0] for k, v in self.rollout(np.asarray(act)[None]).items()}
+
+    def state(self):
+        """dict(pos, vel [B,N,2], obst_pos, obst_vel [B,M,2] or None, step [B]) as the device holds them now"""
+        st = lambda a, b: None if a is None else torch.stack((a, b), -1).cpu().numpy()
+        return dict(pos=st(self.px, self.py), vel=st(self.vx, self.vy), obst_pos=None if self.opos is None else self.opos.cpu().numpy(),
+                    obst_vel=None if self.ovel is None else self.ovel.cpu().numpy(), step=self.step_count.cpu().numpy())
 
 
 def rollout64(g, params=None):

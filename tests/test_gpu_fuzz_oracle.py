@@ -136,3 +136,49 @@ def test_random_landmark_scenario_step_equals_oracle(seed):
         if M:
             state["obst_pos"] = f32(new["obst_pos"]); state["obst_vel"] = f32(new["obst_vel"])
         state["step"] = np.minimum(new["step"], P.world_length - 1).astype(np.int32)
+
+
+@pytest.mark.parametrize("N,B", [(4, 16), (70, 4)])
+@pytest.mark.parametrize("seed", range(3))
+def test_landmark_scenario_step_at_the_obstacle_floor_equals_oracle(seed, N, B):
+    """formation_hd_obs_env.py:84-89 where the draws above never go (their obstacles lie within +-0.8, the floor is at -2.2): one
+    obstacle 0.05 ... 0.2 above obstacle_floor (it crosses within the two steps in part of the envs), one below it with velocity 0
+    and an agent pushing it from underneath, one far above, agents in contact with each (tests/scenario_cases.py floor_case); two
+    steps of fg_step_scenario teacher-forced from the same fp32 state.  The velocity an obstacle is left with is decided by
+    y > floor: compared exactly except where y is within 1e-5 of the floor."""
+    import formation_gym
+    from tests import scenario_cases as SC
+    c = SC.floor_case(N, B, steps=2, seed=9500 + 10 * seed + N)
+    P, kind = c["P"], "obstacle"
+    env = formation_gym.make_env("formation_hd_obs_env", False, N, num_envs=B, device="cuda:0")
+    f32 = lambda x: np.asarray(x, dtype=np.float32).astype(np.float64)
+    state = dict(c["state"], **{k: f32(c["state"][k]) for k in ("pos", "vel", "landmarks", "obst_pos", "obst_vel")})
+    tag = "seed %d: floor N=%d B=%d" % (seed, N, B)
+    crossed = moved = 0
+    for t in range(2):
+        env.world.set_state(state["pos"], state["vel"])
+        env.world.landmark_pos.copy_(torch.as_tensor(state["landmarks"], dtype=torch.float32))
+        env.world.obstacle_pos.copy_(torch.as_tensor(state["obst_pos"], dtype=torch.float32))
+        env.world.obstacle_vel.copy_(torch.as_tensor(state["obst_vel"], dtype=torch.float32))
+        env.world.step_count.copy_(torch.as_tensor(state["step"], dtype=torch.int32))
+        act = c["acts"][t]
+        obs, rew, done, info = env.step(torch.as_tensor(act, dtype=torch.float32).cuda())
+        new, out = O.step_scn(kind, state, act, P)
+        pos, vel = env.world.get_state()
+        np.testing.assert_allclose(_np(pos), new["pos"], rtol=0, atol=ATOL, err_msg=tag)
+        np.testing.assert_allclose(_np(vel), new["vel"], rtol=0, atol=ATOL, err_msg=tag)
+        np.testing.assert_allclose(_np(obs), out["obs"], rtol=0, atol=ATOL, err_msg=tag)
+        np.testing.assert_array_equal(done.cpu().numpy(), out["done"], err_msg=tag)
+        np.testing.assert_allclose(_np(env.world.obstacle_pos), new["obst_pos"], rtol=0, atol=ATOL, err_msg=tag)
+        clear = np.abs(new["obst_pos"][..., 1] - P.obstacle_floor) > 1e-5
+        assert clear.mean() >= 0.9
+        np.testing.assert_array_equal(_np(env.world.obstacle_vel)[clear], new["obst_vel"][clear], err_msg=tag)
+        ok = SC.threshold_margin(kind, new["pos"], new["obst_pos"], P, {}) > 1e-5
+        scale = np.maximum(1.0, np.abs(out["indiv"][ok]) / 16.0)
+        assert (np.abs(_np(info["individual_reward"])[ok] - out["indiv"][ok]) <= ATOL * scale).all(), tag
+        np.testing.assert_allclose(_np(rew)[ok][..., 0], np.repeat(out["shared"][:, None], N, 1)[ok], rtol=2e-6, atol=ATOL, err_msg=tag)
+        crossed += int(((state["obst_pos"][:, 0, 1] > P.obstacle_floor) & (new["obst_pos"][:, 0, 1] <= P.obstacle_floor)).sum())
+        moved += int((np.abs(new["obst_pos"][:, 1] - state["obst_pos"][:, 1]).max(-1) > 1e-4).sum())
+        assert (new["obst_vel"][:, 2, 1] == -1.0).all()
+        state = dict(new, **{k: f32(new[k]) for k in ("pos", "vel", "obst_pos", "obst_vel")})
+    assert crossed > 0 and moved > 0, tag

@@ -156,3 +156,44 @@ def test_lane_kernel_observation_only_and_world_options(shape):
     _same(s0, s1, "%s with World options" % kind)
     speed = (s0["vx"] ** 2 + s0["vy"] ** 2).sqrt()
     assert float(speed.max()) <= 0.4 * (1 + 1e-5)
+
+
+@pytest.mark.parametrize("shape", [SHAPES[3], SHAPES[6]], ids=lambda s: "%s-%d-%d-%d" % s[:4])
+def test_lane_kernel_equals_the_runtime_count_kernel_at_the_obstacle_floor(shape):
+    """formation_hd_obs_env.py:84-89 (`falling ? ... : 0` in both kernels) where no other test goes: obstacle 0 starts 0.05 ... 0.2
+    above obstacle_floor and crosses it inside the launch, obstacle 1 lies below it with velocity 0 and is pushed by the agent
+    under it, obstacle 2 keeps falling far above; agent k starts within contact distance of obstacle k."""
+    import math
+    kind, N, L, M = shape[:4]
+    B, K, floor, reach = 200, 9, -2.2, 0.1 + 0.15
+    st, p, sc, D = _setup(*shape, B=B, crowd=1.0, seed=70 + N, auto_reset=False)
+    gen = torch.Generator(device="cuda"); gen.manual_seed(700 + N)
+    r = lambda lo, hi, *s: lo + (hi - lo) * torch.rand(s, generator=gen, device="cuda")
+    opos = torch.empty((B, M, 2), device="cuda")
+    opos[:, :, 0] = torch.tensor([-1.2, 0.0, 1.2], device="cuda") + r(-0.1, 0.1, B, M)
+    opos[:, 0, 1] = floor + r(0.05, 0.2, B)
+    opos[:, 1, 1] = floor - r(0.005, 0.08, B)
+    opos[:, 2, 1] = floor + r(1.5, 2.0, B)
+    ovel = torch.tensor([[0.0, -1.0], [0.0, 0.0], [0.0, -1.0]], device="cuda").expand(B, M, 2).contiguous()
+    st["px"] = r(-2.0, 2.0, B, N); st["py"] = floor + r(0.6, 1.2, B, N)
+    for k in range(min(N, M)):                                            # above, below, above its obstacle
+        ang = r(-2.2, -0.9, B) if k == 1 else r(0.3, math.pi - 0.3, B)
+        d = reach * (r(0.6, 0.85, B) if k == 1 else r(0.8, 0.97, B))
+        st["px"][:, k] = opos[:, k, 0] + d * torch.cos(ang)
+        st["py"][:, k] = opos[:, k, 1] + d * torch.sin(ang)
+    st["opos"], st["ovel"] = opos.contiguous(), ovel
+    st["vx"] *= 0.3; st["vy"] *= 0.3
+    acts = (torch.rand((K, B, N, 2), generator=gen, device="cuda") * 2 - 1).contiguous()
+    s0, o0 = _rollout(st, p, sc, B, N, D, acts, 1, 0)
+    s1, o1 = _rollout(st, p, sc, B, N, D, acts, 1, 1)
+    what = "%s N=%d at the obstacle floor" % (kind, N)
+    _same(o0, o1, what)
+    _same(s0, s1, what)
+    assert torch.isfinite(o0["obs"]).all() and not (o0["rew"] == 7.0).any()
+    # the three obstacle states occurred: crossed and stopped, stopped but moved (re-armed where lifted above the floor), falling
+    assert (s0["opos"][:, 0, 1] <= floor).all() and (s0["ovel"][:, 0] == 0).all()
+    assert ((s0["opos"][:, 1] - st["opos"][:, 1]).abs().amax(-1) > 1e-3).all()
+    lifted = s0["opos"][:, 1, 1] > floor
+    assert lifted.any() and (~lifted).any()
+    assert (s0["ovel"][lifted, 1, 1] == -1.0).all() and (s0["ovel"][~lifted, 1] == 0).all()
+    assert (s0["opos"][:, 2, 1] > floor).all() and (s0["ovel"][:, 2, 1] == -1.0).all()
