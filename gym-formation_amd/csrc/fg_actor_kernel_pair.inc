@@ -5,12 +5,14 @@
 //     FG_ACTOR_FLAGS               `PER_AGENT = .., LNORM = .., GRU = .., INBN = ..` (the declarators after SAMPLE)
 //     FG_ACTOR_OPERANDS            the kernel parameters after `a`
 //     FG_ACTOR_ABSENT              the FG_ACTOR_NO_* constants of the operands the family does not take
+//     FG_ACTOR_OUK (optional)      the name of the family's third member, the OU-noise actor: the deterministic kernel with
+//                                  `constexpr bool OU = true`, which takes `ow` (ActorOuW) after the family's operands
 // and they are undefined again here.  Not a header: no guard.  The body stays a textual include in each kernel
 // (fg_actor_rollout_body.inc says why), so a kernel's token stream is what its hand-written wrapper was.
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, FG_ACTOR_OPERANDS) {
-    constexpr bool SAMPLE = false, FG_ACTOR_FLAGS;
-    FG_ACTOR_ABSENT
+    constexpr bool SAMPLE = false, OU = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_OW
     const float* const log_std = nullptr;
     float* const logp = nullptr;
 #include "fg_actor_rollout_body.inc"
@@ -20,10 +22,23 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, F
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP(const Args a, FG_ACTOR_OPERANDS, const float* log_std,
                                                                  float* logp) {
-    constexpr bool SAMPLE = true, FG_ACTOR_FLAGS;
-    FG_ACTOR_ABSENT
+    constexpr bool SAMPLE = true, OU = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_OW
 #include "fg_actor_rollout_body.inc"
 }
+
+// the OU-noise actor: no log_std, no log-probs; the noise state ow.state [B][N][2] read at launch start, written at the end
+#ifdef FG_ACTOR_OUK
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_OUK(const Args a, FG_ACTOR_OPERANDS, const ActorOuW ow) {
+    constexpr bool SAMPLE = false, OU = true, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+#undef FG_ACTOR_OUK
+#endif
 
 #undef FG_ACTOR_DET
 #undef FG_ACTOR_SMP

@@ -15,6 +15,8 @@
 // gamma | beta at wsm + WS + 4, fg_actor_mlp_preload.inc), with a WaveSync of its own before the next layer reads the tile.
 // `constexpr bool GRU` (with `gw`, `gsm`, `hst`; formation_hd_env's body only): the recurrent layer on the tile between the
 // second hidden norm and layer 3 (fg_actor_gru.inc), which leaves LayerNorm(h') in the tile for layer 3.
+// `constexpr bool OU` (with `ow`, `oust`, `El`; formation_hd_env's body only): the row's noise state at oust + 2 q steps with
+// the row's draw (ou_step) and `y` becomes clamp(y + scale x, -clip, clip) (ou_action).
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
             if constexpr (LNORM) {
@@ -69,4 +71,14 @@
                 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
                 ls0 = wsm[WS + 2]; ls1 = wsm[WS + 3];
                 y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
+            }
+            if constexpr (OU) {
+                const int ee = q / N;
+                // the Gaussian kernels' draw of (env, agent) at `off`; lane o steps component o of its own row's state
+                n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(q - ee * N), off);
+                if (q < El * N) {
+                    const float x = ou_step(oust[2 * q + o], o ? n.y : n.x, ow.theta, ow.mu, ow.sigma);
+                    oust[2 * q + o] = x;
+                    y = ou_action(y, x, ow.scale, ow.clip);
+                }
             }

@@ -1,6 +1,7 @@
 // fg_actor_rollout_body.inc - the one body of the twelve formation_hd_env actor kernels: actor_rollout_kernel,
 // actor_sample_kernel, pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel,
-// gru_sample_kernel, bn_actor_kernel, bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel (the family blocks of
+// gru_sample_kernel, bn_actor_kernel, bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel, and of the four OU members
+// ou_actor_kernel, pa_ou_actor_kernel, bn_ou_actor_kernel and pa_bn_ou_actor_kernel (the family blocks of
 // fg_actor_rollout_kernel.hpp).  Included inside each kernel (fg_actor_kernel_pair.inc), whose scope provides the kernel
 // arguments `a` (Args), `w` (ActorW: the shared actor) and `tab` (ActorTab: one per agent), the template parameters NC and H,
 // `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
@@ -15,6 +16,10 @@
 // PER_AGENT; the other an empty constant, both when INBN = false) selects bn_*_kernel / pa_bn_*_kernel: the plain body behind an
 // eval-mode input BatchNorm - layer 1's A operand through bn_apply, over the whole k range; the shared actor's tables mean |
 // istd | gamma | beta are filled here once per workgroup, the per-agent ones are read through L1 per element.
+// `constexpr bool OU` with `ow` (ActorOuW; OU = false: an empty constant) selects the families' *ou_actor_kernel: the
+// deterministic body with the noise state's block in LDS - loaded from ow.state before the first pass, stepped by layer 3's lanes
+// (fg_actor_mlp.inc; the per-agent branch here), its done envs' rows set to mu by the physics phase, stored back after the last
+// step.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -43,6 +48,7 @@
     static_assert(!(INBN && LNORM), "the input BatchNorm is in front of the plain body only");
     static_assert(!INBN || H <= 64, "the BatchNorm actor's kernels: H 32 or 64");
     constexpr int BNS = actor_bn_floats(N, INBN, PER_AGENT);   // INBN, shared: mean | istd | gamma | beta [DP] each in LDS
+    static_assert(!OU || (!SAMPLE && !LNORM && !GRU), "the OU-noise actor: a deterministic body without LayerNorms");
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
@@ -54,6 +60,7 @@
     float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
     static_assert(!GRU || (E * env_block_floats(N) + (SAMPLE ? 3 : 2) * E * N + WS + 4 + LNS + BNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
                   "the hidden state's block is 16-byte aligned (fg_actor_gru.inc stores its rows with 16-byte reads)");
+    float* const oust = hbuf + NW * FG_ACTOR_ROWS * HS; // OU: the noise state, component o of env-major slot q at oust + 2 q + o
     const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
     const float* const bn0 = wsm + WS + 4 + LNS;                            // INBN, shared: the four tables, zeros at k >= D
 
@@ -110,6 +117,11 @@
         const int live = El * N * H;
         for (int idx = tid; idx < actor_state_rows(N) * H; idx += FG_ACTOR_THREADS)
             hst[(idx / H) * HS + idx % H] = idx < live ? hsrc[idx] : 0.f;
+    }
+
+    if constexpr (OU) {                                // the state of this workgroup's rows (env-major, contiguous in ow.state)
+        const float* const xsrc = ow.state + (size_t)b0 * N * 2;
+        for (int idx = tid; idx < E * N * 2; idx += FG_ACTOR_THREADS) oust[idx] = idx < El * N * 2 ? xsrc[idx] : ow.mu;
     }
 
     const float one_minus_damp = 1.0f - a.p.damping;
@@ -363,6 +375,14 @@
                     y += __expf(o ? ls1 : ls0) * (o ? n.y : n.x);
                     if (ok && o == 0) logp_lds[slot] = gauss_logp(n, ls0, ls1);
                 }
+                if constexpr (OU) {                    // ou_actor_kernel's step of (env, agent): the same draw, the state's slot
+                    const float2 n = actor_eps(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)r, off);
+                    if (ok) {
+                        const float x = ou_step(oust[2 * slot + o], o ? n.y : n.x, ow.theta, ow.mu, ow.sigma);
+                        oust[2 * slot + o] = x;
+                        y = ou_action(y, x, ow.scale, ow.clip);
+                    }
+                }
                 if (ok) reinterpret_cast<float*>(act_lds)[2 * slot + o] = y;
             } else {
 #include "fg_actor_mlp.inc"
@@ -430,6 +450,9 @@
                 for (int c = 0; c < H; ++c) hr[c] = 0.f;
             }
         }
+        if constexpr (OU) {                            // reset_noise(): the next episode starts from mu
+            if (is_done && valid) { oust[2 * (e * N + i)] = ow.mu; oust[2 * (e * N + i) + 1] = ow.mu; }
+        }
         if (a.p.auto_reset) {
             const bool mine = is_done && env_ok;
             if (__any(mine) != 0) {
@@ -477,4 +500,8 @@
     if constexpr (GRU) {                               // (the loop's last barrier ordered the last pass and the last masking)
         float* const hdst = gw.state + (size_t)b0 * N * H;
         for (int idx = tid; idx < El * N * H; idx += FG_ACTOR_THREADS) hdst[idx] = hst[(idx / H) * HS + idx % H];
+    }
+    if constexpr (OU) {                                // (likewise: the last pass's steps and the last step's resets)
+        float* const xdst = ow.state + (size_t)b0 * N * 2;
+        for (int idx = tid; idx < El * N * 2; idx += FG_ACTOR_THREADS) xdst[idx] = oust[idx];
     }

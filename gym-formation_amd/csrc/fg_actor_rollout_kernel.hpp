@@ -87,9 +87,24 @@
 //              arguments (wave-uniform index: scalar loads); the statistics are read through L1 like the per-agent biases, and
 //              istd is recomputed per element (the same two lines of arithmetic).
 //
-// How a family is wired up: the twelve kernels are six family blocks at the end of this file, each the two kernel names, the
+// ou_actor_kernel<N,H>, pa_ou_actor_kernel<N,H>, bn_ou_actor_kernel<N,H> and pa_bn_ou_actor_kernel<N,H> (fg_rollout_hd_actor_ou,
+// fg_rollout_hd_actor_ou_per_agent) are the third member of the four families without LayerNorms: the deterministic body with
+// the MADDPG trainers' exploration on top, selected by `constexpr bool OU` (false in every other kernel, whose instructions it
+// leaves as they were).  Per (env, agent) a noise state x [2] is carried from step to step; the step that takes an action does
+//     x <- ou_step(x, eps)  =  x + theta (mu - x) + sigma eps,         a = clamp(actor(o) + scale x, -clip, clip)
+// (ou_step, ou_action below: the one spelling for every kernel and for the host-paced loop's actor_ou_step_kernel), eps the
+// Gaussian kernels' actor_eps at the same counter offsets, clip = +inf for no clamp; there is no log_std and no log-density.
+//   state      x lives in LDS for the whole launch, one block [E N][2] behind the activation tiles, indexed by the env-major
+//              slot e N + i in the shared and in the agent-major per-agent body alike: loaded from ActorOuW::state at launch
+//              start, stored back after the last step.  Lane (row, o) of layer 3 updates component o of its row; a row belongs
+//              to one wave for the whole launch, so the actor phase adds no barrier.  The physics phase writes mu into the rows
+//              of an env whose step ended its episode (is_done, with or without auto-reset), a workgroup barrier away from
+//              either neighbour - the convention of the GRU state's masking.
+//
+// How a family is wired up: the twelve kernels (sixteen with the OU members) are six family blocks at the end of this file, each the two kernel names, the
 // four flags, the operands the family takes and the ones it does not, around fg_actor_kernel_pair.inc, which emits the
-// deterministic / Gaussian pair with fg_actor_rollout_body.inc as a textual include.  The host's side of the same table is
+// deterministic / Gaussian pair - and, where the block names one (FG_ACTOR_OUK), the OU member - with
+// fg_actor_rollout_body.inc as a textual include.  The host's side of the same table is
 // HdActorFamily in formation_hip.hip.  Adding a family: its operand struct here, an FG_ACTOR_NO_* constant for the blocks that
 // do not take it, its block, its `if constexpr` branches in the body; then the host's row (DESIGN.md lists the places).
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
@@ -160,6 +175,26 @@ FG_DEV float bn_apply(float x, float mean, float istd, float gamma, float beta) 
     return __builtin_fmaf((x - mean) * istd, gamma, beta);
 }
 
+// the Ornstein-Uhlenbeck exploration of *ou_actor_kernel (FgActorOu) and the noise state [B][N][2], read at launch start and
+// written back at the end
+struct ActorOuW {
+    float theta, mu, sigma, scale, clip;
+    float* state;
+};
+// The one spelling of the noise state's update, x + theta (mu - x) + sigma eps, per component: three roundings (the
+// difference and the two fmas).  theta = 1, mu = 0: fma(1, -x, x) = 0 exactly, so x' = fl(sigma eps) - i.i.d. noise.
+FG_DEV float ou_step(float x, float eps, float theta, float mu, float sigma) {
+    return __builtin_fmaf(sigma, eps, __builtin_fmaf(theta, mu - x, x));
+}
+// ... and of the action, clamp(mean + scale x, -clip, clip): a product, then a sum (never contracted), then max / min, which is
+// torch's fp32 clamp(mean + scale * x, -clip, clip) bit for bit; clip = +inf leaves the sum as it is.
+FG_DEV float ou_action(float mean, float x, float scale, float clip) {
+#pragma clang fp contract(off)
+    const float noise = scale * x;
+    const float v = mean + noise;
+    return fminf(fmaxf(v, -clip), clip);
+}
+
 constexpr int FG_ACTOR_THREADS = 256;
 constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-row MFMA tiles
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
@@ -170,7 +205,8 @@ __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // ro
 //               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
 //               (INBN, not PER_AGENT: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm) |
 //               (GRU: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]) |
-//               activations [4][32][H + 4] | (GRU: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32))
+//               activations [4][32][H + 4] | (GRU: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32)) |
+//               (OU: noise state [E N][2])
 // (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
 __host__ __device__ constexpr int actor_in_pad(int n) { return (6 * n + 3) / 4 * 4; }
 __host__ __device__ constexpr int actor_norm_floats(int n, int h, bool lnorm) { return lnorm ? 4 * h + 2 * actor_in_pad(n) : 0; }
@@ -181,15 +217,19 @@ __host__ __device__ constexpr int actor_gru_floats(int h, bool gru) { return gru
 __host__ __device__ constexpr int actor_bn_floats(int n, bool inbn, bool per_agent) {
     return inbn && !per_agent ? 4 * actor_in_pad(n) : 0;
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false>
+__host__ __device__ constexpr int actor_ou_floats(int n, bool ou) { return ou ? 2 * actor_envs(n) * n : 0; }
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
+          bool OU = false>
 constexpr int actor_lds_floats() {
     return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
            actor_norm_floats(NC, H, LNORM) + actor_bn_floats(NC, INBN, PER_AGENT) + actor_gru_floats(H, GRU) +
-           (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0);
+           (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0) +
+           actor_ou_floats(NC, OU);
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false>
+template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
+          bool OU = false>
 constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN>() * (int)sizeof(float);
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN, OU>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -274,9 +314,20 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
     logp[t] = gauss_logp(eps[t], log_std[0], log_std[1]);
 }
 
+// ou_step on each of `count` (env, agent) pairs in place (fg_actor_ou_step): the host-paced loop of an OUNoiseActor carries
+// the state the fused kernels carry, from the same eps.
+__global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, float theta, float mu, float sigma,
+                                                            const float2* __restrict__ eps, float2* __restrict__ state) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const float2 x = state[t], n = eps[t];
+    state[t] = make_float2(ou_step(x.x, n.x, theta, mu, sigma), ou_step(x.y, n.y, theta, mu, sigma));
+}
+
 // ---- the twelve kernels: one block per family, each the deterministic / Gaussian pair of fg_actor_kernel_pair.inc around
 // fg_actor_rollout_body.inc.  A family is its two names, its four flags, the operands it takes as kernel arguments and the
-// ones it does not; the body names all of `w tab nw gw bw btab`, and an operand a family does not take is the empty constant
+// ones it does not, and - the four families without LayerNorms - the name of its OU member, which takes `ow` (ActorOuW)
+// after them; the body names all of `w tab nw gw bw btab ow`, and an operand a family does not take is the empty constant
 // below (`w` of a per-agent family: only tab's tanh flag), so that no kernel carries an argument it never reads.
 #define FG_ACTOR_NO_W    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
 #define FG_ACTOR_NO_TAB  constexpr ActorTab tab{};
@@ -284,9 +335,11 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 #define FG_ACTOR_NO_GW   constexpr ActorGruW gw{};
 #define FG_ACTOR_NO_BW   constexpr ActorBnW bw{};
 #define FG_ACTOR_NO_BTAB constexpr ActorBnTab btab{};
+#define FG_ACTOR_NO_OW   constexpr ActorOuW ow{};
 
 // the shared actor
 #define FG_ACTOR_DET      actor_rollout_kernel
+#define FG_ACTOR_OUK      ou_actor_kernel
 #define FG_ACTOR_SMP      actor_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w
@@ -295,6 +348,7 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 
 // PER_AGENT: agent i evaluates tab's actor i; the Gaussian twin has one log_std [2] for all agents
 #define FG_ACTOR_DET      pa_actor_kernel
+#define FG_ACTOR_OUK      pa_ou_actor_kernel
 #define FG_ACTOR_SMP      pa_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorTab tab
@@ -319,6 +373,7 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 
 // INBN: the shared actor behind the eval-mode input BatchNorm `bw`
 #define FG_ACTOR_DET      bn_actor_kernel
+#define FG_ACTOR_OUK      bn_ou_actor_kernel
 #define FG_ACTOR_SMP      bn_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = true
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorBnW bw
@@ -327,7 +382,9 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
 
 // INBN, PER_AGENT: agent i evaluates tab's actor i behind btab's BatchNorm i
 static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
+static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(ActorOuW) <= 4096, "kernel arguments: 4 KiB");
 #define FG_ACTOR_DET      pa_bn_actor_kernel
+#define FG_ACTOR_OUK      pa_bn_ou_actor_kernel
 #define FG_ACTOR_SMP      pa_bn_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = true
 #define FG_ACTOR_OPERANDS const ActorTab tab, const ActorBnTab btab
@@ -340,6 +397,7 @@ static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(
 #undef FG_ACTOR_NO_GW
 #undef FG_ACTOR_NO_BW
 #undef FG_ACTOR_NO_BTAB
+#undef FG_ACTOR_NO_OW
 
 }  // namespace fg
 

@@ -12,6 +12,9 @@
     constexpr ActorGruW gw{};
     float* const gsm = nullptr;
     float* const hst = nullptr;
+    constexpr bool OU = false;                          // nor one with OU noise
+    constexpr ActorOuW ow{};
+    float* const oust = nullptr;
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
     constexpr int NE = N + M;

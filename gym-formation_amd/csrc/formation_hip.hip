@@ -948,43 +948,59 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
 //     HD_ACTOR_SHARED        ActorW                          HD_ACTOR_GRU           ActorW, ActorNormW, ActorGruW
 //     HD_ACTOR_PER_AGENT     ActorTab                        HD_ACTOR_BN            ActorW, ActorBnW
 //     HD_ACTOR_NORM          ActorW, ActorNormW              HD_ACTOR_BN_PER_AGENT  ActorTab, ActorBnTab
+// The OU column is the family's third member (fg_rollout_hd_actor_ou*: a call with `noise` set), which takes an ActorOuW after
+// those operands; the LayerNorm families have none (hd_no_ou_kernel, never instantiated: no entry builds such a call).
 enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
                    HD_ACTOR_BN_PER_AGENT };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
                                              "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
                                              "fg_rollout_hd_actor_bn_per_agent"};
+template <int NC, int H> constexpr std::nullptr_t hd_no_ou_kernel = nullptr;
 template <HdActorKind> struct HdActorFamily;
-#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, WHAT)                                             \
+#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, WHAT)                                            \
     template <> struct HdActorFamily<KIND> {                                                                      \
         static constexpr bool per_agent = PA, lnorm = LN, gru = GR, in_bn = BN;                                   \
         static constexpr int max_h = MAXH;                                                                        \
         template <int NC, int H> static constexpr auto det = &DET<NC, H>;                                         \
         template <int NC, int H> static constexpr auto smp = &SMP<NC, H>;                                         \
+        static constexpr bool has_ou = !LN;                                                                       \
+        template <int NC, int H> static constexpr auto ou = OUK<NC, H>;                                           \
         static constexpr const char* det_name = #DET;                                                             \
         static constexpr const char* smp_name = #SMP;                                                             \
+        static constexpr const char* ou_name = #OUK;                                                              \
         static constexpr const char* fail_fmt = WHAT "actor rollout launch failed: %s";                           \
         static_assert(!(PA && LN), "no per-agent actor kernel with LayerNorms");                                  \
         static_assert(!GR || LN, "the recurrent actor's base is the LayerNorm actor");                            \
         static_assert(!(BN && LN), "the input BatchNorm is in front of the plain body only");                     \
-        template <int NC, int H, bool SAMPLE> static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN>(); \
+        template <int NC, int H, bool SAMPLE, bool OU = false>                                                    \
+        static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN, OU>();                    \
     };
-//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian
-FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, "")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    "per-agent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    "LayerNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   "recurrent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    "BatchNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, "per-agent BatchNorm ")
+//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise
+FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       "")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    "per-agent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       "LayerNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       "recurrent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    "BatchNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, "per-agent BatchNorm ")
 #undef FG_HD_ACTOR_FAMILY
 template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
 
-// one kernel pair of the family F at <NC, H>; `w`: the family's operands
+// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member; `w`: the family's operands
 template <int NC, int H, class F, class... W>
-static int launch_hd_actor(const Args& a, const float* log_std, float* logp, hipStream_t st, const W&... w) {
+static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, hipStream_t st, const W&... w) {
     static_assert(F::template lds_bytes<NC, H, true> <= 160 * 1024, "actor rollout LDS");
     constexpr int E = actor_envs(NC);
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    if constexpr (F::has_ou) {
+        if (ow) {
+            constexpr int lds = F::template lds_bytes<NC, H, false, true>;
+            static_assert(lds <= 160 * 1024, "actor rollout LDS");
+            const int grid = (a.B + E - 1) / E;
+            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::ou_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
+            return launch<F::template ou<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *ow);
+        }
+    }
     return launch_actor_pair<F::template det<NC, H>, F::template smp<NC, H>>(
         F::det_name, F::smp_name, targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
         log_std ? F::template lds_bytes<NC, H, true> : F::template lds_bytes<NC, H, false>, F::fail_fmt, st, log_std, logp, a, w...);
@@ -1034,7 +1050,12 @@ static int hd_actor_struct_check(const FgParams* params, const FgActor* actor) {
 // `log_std` NULL: the deterministic actor (HD_ACTOR_SAMPLE requires it); `logp`: the log-densities' destination, NULL from a
 // describe twin; `in_bn` (HD_ACTOR_BN: the one input BatchNorm; HD_ACTOR_BN_PER_AGENT: a host array of N); `norm` counts for
 // HD_ACTOR_NORM and HD_ACTOR_GRU only; `gru` and `rnn_state` (HD_ACTOR_GRU only): the recurrent layer and the hidden state
-// [B][N][H], a stand-in address from a describe twin.
+// [B][N][H], a stand-in address from a describe twin; `noise`: the OU entries' parameters and state, likewise.
+struct HdActorNoise {                                  // fg_rollout_hd_actor_ou*: the OU parameters and the noise state [B][N][2]
+    bool on = false;
+    const FgActorOu* ou = nullptr;
+    float* state = nullptr;
+};
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
@@ -1049,9 +1070,13 @@ struct HdActorCall {
     bool states_entry = false;
     float* rnn_states = nullptr;
     int states_every = 1;
+    // fg_rollout_hd_actor_ou and fg_rollout_hd_actor_ou_per_agent only (`noise.on`, which also puts their names on the messages):
+    // the kind is the inner actor's family - shared or per-agent, with `in_bn` the BatchNorm one - whose OU member runs
+    HdActorNoise noise = {};
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
 static const char* hd_actor_who(const HdActorCall& c) {
+    if (c.noise.on) return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
     return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
 }
 // FgActorNorm's checks (no device touched), in the name of the entry `who`: hidden 32 or 64, every eps that is read positive and
@@ -1103,9 +1128,26 @@ static int actor_in_bn_check(const char* who, const FgActor& actor, const FgActo
         if ((uintptr_t)q.p & 3u) return bad(FG_ERR_ALIGNMENT, "in_bn %s must be 4-byte aligned", q.name);
     return FG_OK;
 }
+// FgActorOu's and the noise state's checks (no device touched), in the name of the entry `who`: FG_ERR_BAD_ARG naming the field
+// for a NULL ou, a theta that is not finite or outside [0, 1], a mu, sigma or scale that is not finite, a negative sigma, a clip
+// that is NaN or not positive (+inf: no clamp), a NULL state where there are envs; FG_ERR_ALIGNMENT for a state that is not
+// 8-byte aligned.
+static int actor_ou_check(const char* who, const FgActorOu* ou, const float* state, int B) {
+    const ActorComplaint bad{who};
+    if (!ou) return bad(FG_ERR_BAD_ARG, "ou is NULL");
+    if (!(ou->theta >= 0.0f && ou->theta <= 1.0f)) return bad(FG_ERR_BAD_ARG, "theta must be in [0, 1]");
+    if (!std::isfinite(ou->mu)) return bad(FG_ERR_BAD_ARG, "mu must be finite");
+    if (!(ou->sigma >= 0.0f) || !std::isfinite(ou->sigma)) return bad(FG_ERR_BAD_ARG, "sigma must be finite and not negative");
+    if (!std::isfinite(ou->scale)) return bad(FG_ERR_BAD_ARG, "scale must be finite");
+    if (!(ou->clip > 0.0f)) return bad(FG_ERR_BAD_ARG, "clip must be positive (+inf: no clamp)");
+    if (!state && B > 0) return bad(FG_ERR_BAD_ARG, "noise_state is NULL");
+    if ((uintptr_t)state & 7u) return bad(FG_ERR_ALIGNMENT, "noise_state must be 8-byte aligned");
+    return FG_OK;
+}
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
 // this order, which is ABI - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
-// and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), log_std, logp.  The shared actor's
+// and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), the OU noise with its state, log_std,
+// logp.  The shared actor's
 // checks name fg_rollout_hd_actor through the sample and norm entries too, the log_std checks fg_rollout_hd_actor_sample.
 // Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
@@ -1140,6 +1182,7 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
                 if ((rc = actor_in_bn_check(who, c.actor[i], c.in_bn[i], i)) != FG_OK) return rc;
         }
     }
+    if (c.noise.on && (rc = actor_ou_check(who, c.noise.ou, c.noise.state, B)) != FG_OK) return rc;
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1174,6 +1217,9 @@ static ActorBnTab actor_bn_tab(const FgActorInBn* bns, int N) {
     }
     return btab;
 }
+static ActorOuW actor_ou_w(const HdActorNoise& n) {
+    return {n.ou->theta, n.ou->mu, n.ou->sigma, n.ou->scale, n.ou->clip, n.state};
+}
 static ActorNormW actor_norm_w(const FgActorNorm& norm) {
     const bool in_norm = norm.in_norm != 0;
     return {in_norm ? norm.in_gamma : nullptr, in_norm ? norm.in_beta : nullptr, norm.h1_gamma, norm.h1_beta,
@@ -1204,8 +1250,10 @@ static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
 template <HdActorKind KIND, class... W>
 static int hd_actor_run(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
     const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
+    const ActorOuW ow = c.noise.on ? actor_ou_w(c.noise) : ActorOuW{};
     return actor_nh_dispatch<HdActorFamily<KIND>::max_h>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(a, c.log_std, c.logp, st, w...);
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(a, c.log_std, c.logp,
+                                                                                           c.noise.on ? &ow : nullptr, st, w...);
     });
 }
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
@@ -1929,6 +1977,46 @@ int fg_rollout_hd_actor_bn_per_agent(const FgParams* params, const FgActor* acto
                                done_seq}, obs_every, stream);
 }
 
+// the OU entries' call: the inner actor's family with `noise` set (no log_std, no logp)
+static HdActorCall hd_actor_ou_call(bool members, const FgActor* actor, const FgActorInBn* in_bn, const FgActorOu* ou, float* state) {
+    HdActorCall c{members ? (in_bn ? HD_ACTOR_BN_PER_AGENT : HD_ACTOR_PER_AGENT) : (in_bn ? HD_ACTOR_BN : HD_ACTOR_SHARED), actor};
+    c.in_bn = in_bn;
+    c.noise = {true, ou, state};
+    return c;
+}
+
+int fg_rollout_hd_actor_ou(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const FgActorOu* ou,
+                           float* noise_state, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                           float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                           float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int obs_every, void* stream) {
+    return rollout_actor_impl(params, hd_actor_ou_call(false, actor, in_bn, ou, noise_state), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_ou_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns, const FgActorOu* ou,
+                                     float* noise_state, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                     float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                     float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int obs_every,
+                                     void* stream) {
+    return rollout_actor_impl(params, hd_actor_ou_call(true, actors, in_bns, ou, noise_state), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
+}
+
+int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream) {
+    if (count < 0) return fail(FG_ERR_BAD_ARG, "fg_actor_ou_step: count >= 0 required%s");
+    const int rc = actor_ou_check("fg_actor_ou_step", ou, state, count > 0 ? 1 : 0);
+    if (rc) return rc;
+    if (count == 0) return FG_OK;
+    if (!eps) return fail(FG_ERR_BAD_ARG, "fg_actor_ou_step: eps is NULL%s");
+    if ((uintptr_t)eps & 7u) return fail(FG_ERR_ALIGNMENT, "fg_actor_ou_step: eps must be 8-byte aligned%s");
+    const DeviceGuard device_guard(stream, state);
+    return launch<&actor_ou_step_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream, "actor OU step launch failed: %s",
+                                         (long long)count, ou->theta, ou->mu, ou->sigma, reinterpret_cast<const float2*>(eps),
+                                         reinterpret_cast<float2*>(state));
+}
+
 int fg_actor_noise(const FgParams* params, int B, int N, float* eps, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -1993,6 +2081,20 @@ int fg_describe_actor_bn_launch(const FgParams* params, const FgActor* actor, co
 int fg_describe_actor_bn_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
                                           const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len) {
     return describe_actor_impl("fg_describe_actor_bn_per_agent_launch", params, {HD_ACTOR_BN_PER_AGENT, actors, log_std, nullptr, in_bns},
+                               B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_ou_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const FgActorOu* ou,
+                                int B, int N, int K, int obs_every, char* out, int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // a stand-in: the dry run has no noise state
+    return describe_actor_impl("fg_describe_actor_ou_launch", params, hd_actor_ou_call(false, actor, in_bn, ou, state),
+                               B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                          const FgActorOu* ou, int B, int N, int K, int obs_every, char* out, int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);
+    return describe_actor_impl("fg_describe_actor_ou_per_agent_launch", params, hd_actor_ou_call(true, actors, in_bns, ou, state),
                                B, N, K, obs_every, out, out_len);
 }
 

@@ -18,9 +18,10 @@ import os.path as osp
 from .environment import MultiAgentEnv
 from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
-from .actor_rollout import GaussianActor, InputBatchNorm, PerAgentActor, RecurrentActor  # noqa: F401
+from .actor_rollout import GaussianActor, InputBatchNorm, OUNoiseActor, PerAgentActor, RecurrentActor  # noqa: F401
 
-__all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm"]
+__all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm",
+           "OUNoiseActor"]
 
 _counter = [0]
 

@@ -149,6 +149,21 @@ def actor_in_bn(bn):
     return FgActorInBn(ptr(mean), ptr(var), ptr(g), ptr(b), eps)
 
 
+class FgActorOu(ctypes.Structure):
+    """Mirror of `struct FgActorOu` (include/formation_hip.h): the OU exploration of fg_rollout_hd_actor_ou's actor."""
+    _fields_ = [("theta", ctypes.c_float), ("mu", ctypes.c_float), ("sigma", ctypes.c_float), ("scale", ctypes.c_float),
+                ("clip", ctypes.c_float)]
+
+
+def actor_ou(ou, into=None):
+    """FgActorOu of an `actor_rollout.OUNoiseActor`'s five scalars as they are now (clip None: +inf, no clamp); `into`: the
+    struct to update in place - a bound launcher's, so that an annealed scale is seen by its next launch."""
+    s = FgActorOu() if into is None else into
+    s.theta, s.mu, s.sigma, s.scale = float(ou.theta), float(ou.mu), float(ou.sigma), float(ou.scale)
+    s.clip = float("inf") if ou.clip is None else float(ou.clip)
+    return s
+
+
 class FormationHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libformation_hip: status %d: %s" % (code, msg))
@@ -222,6 +237,15 @@ SIGNATURES = {
                                          ctypes.c_char_p, _I]),
     "fg_describe_actor_bn_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _P, _I, _I, _I, _I,
                                                    ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_ou": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), ctypes.POINTER(FgActorOu), _P,
+                                    _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_rollout_hd_actor_ou_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn),
+                                              ctypes.POINTER(FgActorOu), _P, _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_describe_actor_ou_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), ctypes.POINTER(FgActorOu),
+                                         _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_describe_actor_ou_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn),
+                                                   ctypes.POINTER(FgActorOu), _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_actor_ou_step": (_I, [ctypes.POINTER(FgActorOu), ctypes.c_int64, _P, _P, _P]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,

@@ -39,7 +39,16 @@ statistics are read in place like the weights, and the rule is evaluated per cal
 calls switch the path.  Host-paced: training mode (batch statistics are a function of the whole batch),
 track_running_stats=False, a BatchNorm anywhere but first, in front of the LayerNorm form or in a RecurrentActor's base, H = 128,
 statistics in another dtype or off the device, mixed PerAgentActor members, and the landmark scenarios
-(`fused_bn_hidden=()`).  Out of scope: MADDPG's post-noise clamp(-1, 1) and OU noise - a GaussianActor stays "no clipping".
+(`fused_bn_hidden=()`).
+
+An `OUNoiseActor(actor, theta, sigma, scale, mu, clip)` is the MADDPG trainers' exploration on a deterministic actor:
+    x <- x + theta * (mu - x) + sigma * eps;   a = clamp(actor(o) + scale * x, -clip, clip)
+with the Ornstein-Uhlenbeck state x [B, N, 2] carried from step to step, set back to mu where a step ended an episode, and eps
+the env's counter stream (a GaussianActor's draws).  It fuses (`fg_rollout_hd_actor_ou`, `fg_rollout_hd_actor_ou_per_agent`) in
+formation_hd_env when its inner actor resolves to the plain or the BatchNorm form above, shared or as a PerAgentActor; the five
+scalars are plain Python numbers read at every call.  Host-paced (the same loop in Python, the state stepped by the kernels' own
+device function): a LayerNorm inner actor, any inner actor that would run host-paced itself, the landmark scenarios
+(`fused_ou=False`) and World options.  A GaussianActor stays "no clipping".
 
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
@@ -125,7 +134,8 @@ def _in_bn(m, width, device):
 
 
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-               fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
+               fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
+               fused_ou=True):
     """The FusedActor fields hidden, out_tanh, members = [[w1, b1, w2, b2, w3, b3]] and the form's own (below) when a fused kernel
     can evaluate the shared actor body `actor` for `num_agents` agents, else None.  The three forms, each with its own kernels
     and so its own hidden widths:
@@ -138,8 +148,8 @@ def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     `device`: the env's device (None: not checked).  The tensors are the
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
-    are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact, not read
-    here."""
+    are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact and
+    `fused_ou` (whether the scenario's launch has OU members) `resolve_actor`'s, neither read here."""
     if type(actor) is not torch.nn.Sequential:
         return None
     return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden)
@@ -313,13 +323,14 @@ class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
 
 
 def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
-                    fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN):
+                    fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
+               fused_ou=True):
     """The FusedActor fields of `_body_spec`'s LayerNorm form and `gru`, the ActorGru, when the fused recurrent kernel can evaluate
     the RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
     of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
     one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
     parameter fp32, contiguous and on `device`.  `fused_bn_hidden` is `_body_spec`'s fact, not read here: a base that starts
-    with a BatchNorm has no recurrent kernel."""
+    with a BatchNorm has no recurrent kernel; nor is `fused_ou`, `resolve_actor`'s fact."""
     nn = torch.nn
     if type(actor) is not RecurrentActor or type(actor.base) is not nn.Sequential:
         return None
@@ -457,15 +468,69 @@ def _fused_log_std(actor, device):
     return actor.log_std if _param_ok(actor.log_std, (2,), device) else None
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn",
-                                        defaults=(None, None, None))):
+class OUNoiseActor(torch.nn.Module):
+    """MADDPG's exploration on a deterministic actor (train/maddpg-v2's OUNoise with its `scale`, and the clamp after it):
+        x <- x + theta * (mu - x) + sigma * eps,  eps ~ N(0, I);   a = clamp(actor(obs) + scale * x, -clip, clip)
+    x [..., 2] is the Ornstein-Uhlenbeck state, carried from step to step and set back to `mu` at every episode start
+    (`reset_noise()`); `scale` is what the trainers anneal between episodes - the attributes are plain numbers, read anew by
+    every `env.rollout_actor` call.  `clip=None`: no clamp.  With theta = 1 and mu = 0 the state has no memory, x = sigma * eps:
+    i.i.d. Gaussian noise and a clip, which is maddpg-v1's exploration.
+    `forward(obs, noise_state=None)` draws eps with torch.randn and returns (action, new state) - the action alone when no
+    state is passed (a fresh `initial_state`) - and is meant for use outside the env: inside
+    `env.rollout_actor(K, ou, noise_state=x)` the env's counter stream supplies eps (`fg_actor_noise`) and x is reset where
+    a step's done flag is set.  The inner actor is deterministic: a GaussianActor, a RecurrentActor or another OUNoiseActor
+    raises ValueError."""
+
+    def __init__(self, actor, theta=0.15, sigma=0.2, scale=0.1, mu=0.0, clip=1.0):
+        super().__init__()
+        if isinstance(actor, (GaussianActor, RecurrentActor, OUNoiseActor)):
+            raise ValueError("OUNoiseActor wraps a deterministic, stateless actor (got a %s)" % type(actor).__name__)
+        self.actor = actor
+        self.theta, self.sigma, self.scale, self.mu = float(theta), float(sigma), float(scale), float(mu)
+        self.clip = None if clip is None else float(clip)
+
+    def initial_state(self, *batch_shape, device=None):
+        """[*batch_shape, 2] full of mu (fp32; on `device`, default the inner actor's parameters'): a fresh episode's state."""
+        if device is None:
+            p = next(iter(self.actor.parameters()), None) if isinstance(self.actor, torch.nn.Module) else None
+            device = None if p is None else p.device
+        return torch.full(tuple(batch_shape) + (2,), self.mu, dtype=torch.float32, device=device)
+
+    def noise_step(self, noise_state, eps):
+        """x + theta * (mu - x) + sigma * eps (a new tensor)."""
+        return noise_state + self.theta * (self.mu - noise_state) + self.sigma * eps
+
+    def explore(self, mean, noise_state):
+        """clamp(mean + scale * x, -clip, clip): a product, a sum and the clamp, as the fused kernels evaluate it."""
+        act = mean + self.scale * noise_state
+        return act if self.clip is None else act.clamp(-self.clip, self.clip)
+
+    def reset(self, noise_state, done):
+        """`noise_state` with mu where `done` [...] (bool, one flag per state row or per env) is set, in place."""
+        d = torch.as_tensor(done, device=noise_state.device).to(torch.bool)
+        while d.dim() < noise_state.dim():
+            d = d.unsqueeze(-1)
+        noise_state.masked_fill_(d, self.mu)
+        return noise_state
+
+    def forward(self, obs, noise_state=None):
+        mean = self.actor(obs)
+        x = self.initial_state(*mean.shape[:-1], device=mean.device) if noise_state is None else noise_state
+        x = self.noise_step(x, torch.randn_like(x))
+        act = self.explore(mean, x)
+        return act if noise_state is None else (act, x)
+
+
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn ou",
+                                        defaults=(None, None, None, None))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
     N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
     ActorNorms of a LayerNorm actor (None: the actor has no LayerNorm), and `gru`, the ActorGru of a RecurrentActor (None: the
     actor keeps no state), whose body is then `members[0]` with `norms` and whose head is w3, b3.  `in_bn`: the eval-mode
     input BatchNorm in front of the plain body - the (running_mean, running_var, weight, bias, eps) tuple (ActorInBn) of a
-    shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own."""
+    shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own.  `ou`: the
+    OUNoiseActor whose exploration runs on top of the actor (None: none) - the module itself, whose scalars every launch reads."""
     __slots__ = ()
 
 
@@ -482,9 +547,17 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     scenarios state `fused_ln_hidden=()`) or a RecurrentActor (`_recurrent_spec`: formation_hd_env, H in {32, 64}; the landmark
     scenarios state `fused_gru_hidden=()`).  A leading eval-mode BatchNorm in front of the plain body - shared, or in every
     member of a PerAgentActor (per_agent_bn_spec) - fuses in formation_hd_env with H in {32, 64}; the landmark scenarios state
-    `fused_bn_hidden=()`."""
+    `fused_bn_hidden=()`.  An OUNoiseActor is unwrapped likewise, into its inner actor and itself (`FusedActor.ou`): it fuses
+    where the fact `fused_ou` holds (the scenario's launch has OU members: formation_hd_env's; the landmark scenarios state
+    False) and the
+    inner actor resolves to a form without LayerNorms - plain or BatchNorm, shared or per-agent."""
     if not (fused_scenario and continuous and silent) or world_options or callback:
         return None
+    ou = None
+    if isinstance(actor, OUNoiseActor):
+        if not facts.get("fused_ou", True):
+            return None
+        ou, actor = actor, actor.actor
     mean, log_std = actor, None
     if isinstance(actor, GaussianActor):
         mean, log_std = actor.mean, _fused_log_std(actor, device)
@@ -500,7 +573,9 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
         fields = _recurrent_spec(mean, num_agents, device, **facts)
     else:
         fields = _body_spec(mean, num_agents, device, **facts)
-    return None if fields is None else FusedActor(per_agent=members_own, log_std=log_std, **fields)
+    if fields is None or (ou is not None and ("norms" in fields or "gru" in fields)):
+        return None
+    return FusedActor(per_agent=members_own, log_std=log_std, ou=ou, **fields)
 
 
 def recurrent_mean(actor):

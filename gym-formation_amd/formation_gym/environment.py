@@ -386,7 +386,7 @@ class MultiAgentEnv(object):
         rule = getattr(self.scenario, "actor_fused_rule", None)
         return {} if rule is None else rule(self.world)
 
-    def rollout_actor(self, K, actor, out=None, obs_every=1, rnn_state=None, rnn_states_every=None):
+    def rollout_actor(self, K, actor, out=None, obs_every=1, noise_state=None, rnn_state=None, rnn_states_every=None):
         """The loop of a learned actor for K steps in one call:
             act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
         from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
@@ -421,7 +421,20 @@ class MultiAgentEnv(object):
         leading module an `InputBatchNorm`, which takes [B, N, 6N]) or as every member of a PerAgentActor
         (`fg_rollout_hd_actor_bn_per_agent`), alone or as a GaussianActor's mean; the running statistics are read in place,
         and `actor.train()` / `actor.eval()` between calls switch the path.  Host-paced: training mode, a BatchNorm anywhere
-        but first, mixed members, H = 128, the landmark scenarios.  No clamp after the noise, no OU noise.
+        but first, mixed members, H = 128, the landmark scenarios.
+        An `OUNoiseActor(actor, theta, sigma, scale, mu, clip)` is the MADDPG trainers' exploration: step k takes
+            x = x + theta * (mu - x) + sigma * eps;  a = clamp(actor(o) + scale * x, -clip, clip)
+        with eps the GaussianActor's draws (`fg_actor_noise`: the same on either path and for a shard as for its slice of the
+        full batch), and x is set to mu where the step's done flag is set, whether or not `auto_reset` is set (the trainers'
+        `reset_noise()`).  `noise_state`: a contiguous fp32 [B, N, 2] tensor on the env's device, read as the state step 0
+        starts from, updated in place to the state after step K - 1 and returned as info['noise_state']; None: a fresh
+        `initial_state` (all mu) per call.  A K-step call equals K one-step calls that pass the state along, bit for bit.  The
+        five scalars are read from the module at every call, so `ou.scale = ...` between calls is seen by the next one.  It
+        fuses (`fg_rollout_hd_actor_ou`, `fg_rollout_hd_actor_ou_per_agent`; the state on chip for the whole launch) in
+        formation_hd_env when its inner actor is the plain or the BatchNorm actor above, shared or a PerAgentActor; a
+        LayerNorm inner actor, the landmark scenarios and World options run this loop host-paced, the state stepped by the
+        kernels' own device function (`fg_actor_ou_step`).  There is no info['log_prob'] (a GaussianActor's noise stays
+        unclipped); `noise_state` with any other actor raises ValueError.
         A `RecurrentActor(base, rnn, norm, head)` (rMAPPO's policy), alone or as a GaussianActor's mean, carries a hidden
         state through the loop:
             a, h = actor(obs, h); obs, rew, done, info = env.step(a); h = h * ~done[..., None]
@@ -453,6 +466,11 @@ class MultiAgentEnv(object):
         if recurrent is None and rnn_states_every is not None:
             raise ValueError("rnn_states_every given, but the actor is not a RecurrentActor (nor a GaussianActor with one as its "
                              "mean)")
+        ou = actor if isinstance(actor, actor_rollout.OUNoiseActor) else None
+        if ou is None and noise_state is not None:
+            raise ValueError("noise_state given, but the actor is not an OUNoiseActor")
+        if ou is not None:
+            noise_state = self._noise_state(ou, noise_state)
         S = None
         if rnn_states_every is not None:
             if isinstance(rnn_states_every, bool) or not isinstance(rnn_states_every, numbers.Integral) or rnn_states_every < 1:
@@ -465,7 +483,7 @@ class MultiAgentEnv(object):
         if fused is None:
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 self._check_rnn_states(out["rnn_states"], states_shape)
-            res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S)
+            res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S, noise_state)
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 res[3]["rnn_states"] = out["rnn_states"].copy_(res[3]["rnn_states"])
             return res
@@ -511,6 +529,7 @@ class MultiAgentEnv(object):
                    None if fused.in_bn is None else tuple(
                        tuple(_native.ptr(t) for t in bn[:4]) + (bn[4],)
                        for bn in (fused.in_bn if fused.per_agent else [fused.in_bn])),
+                   None if fused.ou is None else (id(fused.ou), noise_state.data_ptr()),
                    tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
                    getattr(self.scenario, "_seed", 0))
@@ -522,6 +541,8 @@ class MultiAgentEnv(object):
             extra = {} if fused.gru is None else {"rnn_state": rnn_state}
             if S is not None:
                 extra["rnn_states_every"] = S
+            if fused.ou is not None:
+                extra["noise_state"] = noise_state
             launch = self.scenario.bind_rollout_actor(self.world, K, fused, out, obs_every=obs_every,
                                                       auto_reset=self.auto_reset, **extra)
             if key is not None:
@@ -541,6 +562,8 @@ class MultiAgentEnv(object):
             info["rnn_state"] = rnn_state
         if S is not None:
             info["rnn_states"] = out["rnn_states"]
+        if fused.ou is not None:
+            info["noise_state"] = noise_state
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
 
     def _check_rnn_states(self, t, shape):
@@ -562,6 +585,24 @@ class MultiAgentEnv(object):
             raise ValueError("rnn_state must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
         return rnn_state
 
+    def _noise_state(self, ou, noise_state):
+        """The OU state `rollout_actor` runs the OUNoiseActor `ou` with: the caller's tensor, checked - contiguous fp32
+        [B, N, 2] on the env's device - or, for None, a fresh `initial_state`."""
+        shape = (self.num_envs, self.num_agents, 2)
+        dev = self.world.device
+        if noise_state is None:
+            return ou.initial_state(*shape[:2], device=dev)
+        if not torch.is_tensor(noise_state) or noise_state.dtype != torch.float32 or tuple(noise_state.shape) != shape \
+                or not noise_state.is_contiguous() or not actor_rollout._on_device(noise_state, dev):
+            raise ValueError("noise_state must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
+        return noise_state
+
+    def _ou_step(self, ou, eps, x):
+        """x <- x + theta * (mu - x) + sigma * eps in place (`fg_actor_ou_step`: the fused kernels' device function)."""
+        _native.check(_native.load().fg_actor_ou_step(_native.actor_ou(ou), x.numel() // 2, eps.data_ptr(), x.data_ptr(),
+                                                      _native.current_stream(self.world.device)))
+        return x
+
     def actor_noise(self, out=None):
         """The exploration noise eps [B, N, 2] that a GaussianActor's next step draws (`fg_actor_noise` at the offset of the
         next launch): what `rollout_actor` adds, scaled by exp(log_std), to the mean action of that step."""
@@ -582,14 +623,19 @@ class MultiAgentEnv(object):
                                                        _native.current_stream(self.world.device)))
         return out
 
-    def _rollout_actor_by_steps(self, K, actor, obs_every, rnn_state=None, rnn_states_every=None):
+    def _rollout_actor_by_steps(self, K, actor, obs_every, rnn_state=None, rnn_states_every=None, noise_state=None):
         """`rollout_actor` host-paced: `actor(obs)` and `step` K times under torch.no_grad(), results stacked like the fused
         launch's (fresh tensors).  A GaussianActor: mean(obs) + exp(log_std) * eps with eps from `actor_noise`, the draws
         of the fused kernel, and the log-density from eps by the kernel's own device function (`fg_actor_log_prob`): for the
         same eps and log_std, the fused launch's bits.  A RecurrentActor (alone or as the mean): `rnn_state` [B, N, H] goes
         through the loop - a, h = actor(obs, h), then h zeroed where the step's done flag is set - is updated in place at the
         end and comes back as info['rnn_state'].  `rnn_states_every` = S: a copy of the state before the actor call of every
-        step k with k % S == 0, stacked as info['rnn_states'] [ceil(K / S), B, N, state_size]."""
+        step k with k % S == 0, stacked as info['rnn_states'] [ceil(K / S), B, N, state_size].  An OUNoiseActor: `noise_state`
+        [B, N, 2] steps with eps from `actor_noise` by the kernels' device function (`fg_actor_ou_step`: for the same eps the
+        fused launch's state bits), the action is clamp(inner(obs) + scale * x, -clip, clip), x goes back to mu where the
+        step's done flag is set, is updated in place at the end and comes back as info['noise_state']."""
+        ou = actor if noise_state is not None else None
+        x = noise_state.clone() if ou is not None else None
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
         recurrent = rnn_state is not None
         h = rnn_state.clone() if recurrent else None
@@ -613,6 +659,9 @@ class MultiAgentEnv(object):
                     res["logp"].append(self._noise_log_prob(eps, ls))
                 elif recurrent:
                     act, h = actor(obs, h)
+                elif ou is not None:
+                    self._ou_step(ou, self.actor_noise(), x)
+                    act = ou.explore(ou.actor(obs), x)
                 else:
                     act = actor(obs)
                 res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
@@ -620,6 +669,8 @@ class MultiAgentEnv(object):
                 if (k + 1) % obs_every == 0:
                     res["obs"].append(obs.clone())
                 res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
+                if ou is not None:
+                    ou.reset(x, torch.as_tensor(d, device=x.device).view(torch.bool).reshape(x.shape[:-1]))
                 if recurrent:
                     h = h * (~torch.as_tensor(d, device=h.device).view(torch.bool).reshape(h.shape[:-1] + (1,))).to(h.dtype)
         info = {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])}
@@ -630,6 +681,9 @@ class MultiAgentEnv(object):
             info["rnn_state"] = rnn_state
         if rnn_states_every is not None:
             info["rnn_states"] = torch.stack(res["states"])
+        if ou is not None:
+            noise_state.copy_(x)
+            info["noise_state"] = noise_state
         return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
                 torch.stack(res["done"]), info)
 

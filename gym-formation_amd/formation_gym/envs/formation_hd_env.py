@@ -253,7 +253,8 @@ class Scenario(BaseScenario):
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(lib.fg_rollout_hd_policy, p, *args, keep=out)
 
-    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None):
+    def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None,
+                           noise_state=None):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
@@ -270,7 +271,11 @@ class Scenario(BaseScenario):
                                                 S-th step acted with into out["rnn_states"] [ceil(K / S),B,N,H]
           an eval-mode input BatchNorm          `fg_rollout_hd_actor_bn` (shared) / `fg_rollout_hd_actor_bn_per_agent` (log_std or
                                                 NULL), `actor.in_bn` as one FgActorInBn or a host array of N; the running
-                                                statistics are read in place and kept alive like the weights"""
+                                                statistics are read in place and kept alive like the weights
+          an OUNoiseActor (`actor.ou`)          `fg_rollout_hd_actor_ou` / `fg_rollout_hd_actor_ou_per_agent` on the plain or the
+                                                BatchNorm actor (in_bn or NULL), `noise_state` [B,N,2] read and updated in place
+                                                like `rnn_state`; the FgActorOu struct is filled from the module's scalars
+                                                before every launch, so a scale annealed between calls needs no new binding"""
         lib = _native.load()
         log_std = actor.log_std
         norm = None if actor.norms is None else _native.actor_norm(actor.norms)
@@ -288,6 +293,12 @@ class Scenario(BaseScenario):
                 raise NotImplementedError("an input BatchNorm fuses in front of the plain body only")
             members = list(in_bn) if actor.per_agent else [in_bn]
             bns = (_native.FgActorInBn * len(members))(*[_native.actor_in_bn(m) for m in members])
+        ou = actor.ou
+        if ou is not None and (norm is not None or gru is not None or log_std is not None):
+            raise NotImplementedError("OU noise fuses on a deterministic actor without LayerNorms only")
+        if ou is not None and noise_state is None:
+            raise ValueError("an OUNoiseActor's launch needs its noise_state")
+        fou = None if ou is None else _native.actor_ou(ou)
         p = self.params(world, auto_reset, 0, out.get("obs"))
         state = (world.num_envs, len(world.agents), int(K),
                  world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
@@ -300,8 +311,10 @@ class Scenario(BaseScenario):
             raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
         # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, and
         # what follows the state: logp_seq, rnn_state, (rnn_states, states_every))
-        ls = _native.ptr(log_std)
+        ls, nst = _native.ptr(log_std), _native.ptr(noise_state)
         families = (
+            (ou is not None and actor.per_agent, "fg_rollout_hd_actor_ou_per_agent", (fas, bns, fou, nst), False, False, False),
+            (ou is not None, "fg_rollout_hd_actor_ou", (fas, bns, fou, nst), False, False, False),
             (bns is not None and actor.per_agent, "fg_rollout_hd_actor_bn_per_agent", (fas, bns, ls), True, False, False),
             (bns is not None, "fg_rollout_hd_actor_bn", (fas, bns, ls), True, False, False),
             (rnn_states_every is not None, "fg_rollout_hd_actor_gru_states", (fas, norm, gru, ls), True, True, True),
@@ -316,9 +329,16 @@ class Scenario(BaseScenario):
         if with_states:
             hidden += (out["rnn_states"].data_ptr(), int(rnn_states_every))
         args = lead + state + logp + hidden + tail
-        return _native.bind_launch(getattr(lib, entry), p, *args,
-                                   keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
-                                         actor.gru, gru, rnn_state, in_bn, bns))
+        launch = _native.bind_launch(getattr(lib, entry), p, *args,
+                                     keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
+                                           actor.gru, gru, rnn_state, in_bn, bns, fou, noise_state))
+        if ou is None:
+            return launch
+
+        def launch_ou(rng_offset=0):                   # the module's scalars as they are now, into the struct the launch reads
+            _native.actor_ou(ou, fou)
+            return launch(rng_offset)
+        return launch_ou
 
     def policy_actions(self, world, per_layer, out=None):
         """get_action_BFS(ezpolicy, obs, per_layer) for the CURRENT state of every env, straight from the

@@ -83,12 +83,13 @@ class ActorRolloutMixin(object):
         options and per-agent properties are `MultiAgentEnv.actor_path`'s own checks, as for formation_hd_env.)
         `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here;
         `fused_gru_hidden=()`: nor a recurrent one, so a RecurrentActor does too; `fused_bn_hidden=()`: nor one with an input
-        BatchNorm, so the MADDPG trainers' BatchNorm actor does too."""
+        BatchNorm, so the MADDPG trainers' BatchNorm actor does too; `fused_ou=False`: no OU kernel, so an OUNoiseActor does
+        too."""
         from formation_gym import actor_rollout
         d = self._actor_descriptor(world)
         facts = actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
                                              self.obs_dim(world), d.variant)
-        return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=(), fused_bn_hidden=())
+        return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=(), fused_bn_hidden=(), fused_ou=False)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs
@@ -105,6 +106,8 @@ class ActorRolloutMixin(object):
             raise NotImplementedError("a recurrent actor has no fused launch in %s" % type(self).__name__)
         if actor.in_bn is not None:
             raise NotImplementedError("a BatchNorm actor has no fused launch in %s" % type(self).__name__)
+        if actor.ou is not None:
+            raise NotImplementedError("an OUNoiseActor has no fused launch in %s" % type(self).__name__)
         weights, log_std = actor.members[0], actor.log_std
         fa = _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in weights])
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)

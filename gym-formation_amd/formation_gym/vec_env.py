@@ -130,14 +130,14 @@ class FormationVecEnv(object):
         self._ts_synced = False
         return self.env.rollout_policy(K, num_agents_per_layer, out=out, obs_every=obs_every)
 
-    def rollout_actor(self, K, actor, out=None, obs_every=1, rnn_state=None, rnn_states_every=None):
+    def rollout_actor(self, K, actor, out=None, obs_every=1, noise_state=None, rnn_state=None, rnn_states_every=None):
         """K vec-env steps driven by the caller's actor (`env.rollout_actor`): `actor(obs); step` K times, in one launch
         when `env.actor_path(actor)` is 'fused'; infos carries the actions taken ('device' reset mode only)."""
         if self.reset_mode != "device":
             raise NotImplementedError("multi-step launches reset on the device: use reset_mode='device' or call step()")
         self._ts_synced = False
         return self.env.rollout_actor(K, actor, out=out, obs_every=obs_every, rnn_state=rnn_state,
-                                      rnn_states_every=rnn_states_every)
+                                      rnn_states_every=rnn_states_every, noise_state=noise_state)
 
     def capture(self, policy_fn, steps_per_replay):
         """The caller's step loop (train/maddpg-v2/main.py:77-91: policy forward -> env.step, K times) captured ONCE

@@ -609,8 +609,9 @@ int fg_describe_actor_gru_launch(const FgParams* params, const FgActor* actor, c
  *     y_k = (x_k - mean_k) / sqrt(var_k + eps) * gamma_k + beta_k
  * All tensors fp32 [6N] in DEVICE memory, read in place by every launch like the weights (a changed statistic is seen by the
  * next launch).  Batch statistics (training mode) are a function of the whole batch and have no fused launch.  Out of scope:
- * hidden = 128, a BatchNorm anywhere but first or with the LayerNorm / GRU bodies, the landmark scenarios, and MADDPG's
- * post-noise clamp(-1, 1) and OU noise. */
+ * hidden = 128, a BatchNorm anywhere but first or with the LayerNorm / GRU bodies, and the landmark scenarios.  MADDPG's
+ * exploration on top of it - OU noise and the clamp after it - is fg_rollout_hd_actor_ou's; fg_rollout_hd_actor_sample's Gaussian
+ * noise stays unclipped. */
 typedef struct FgActorInBn {
     const float* mean;    /* [6N] running mean */
     const float* var;     /* [6N] running variance */
@@ -646,6 +647,54 @@ int fg_describe_actor_bn_launch(const FgParams* params, const FgActor* actor, co
                                 int B, int N, int K, int obs_every, char* out, int out_len);
 int fg_describe_actor_bn_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
                                           const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
+
+/* MADDPG's exploration on top of a deterministic actor (train/maddpg-v2: OUNoise, `scale`, the clamp after it).  Per
+ * (env, agent) a noise state x [2] is carried from step to step; the step that takes an action does, per component,
+ *     x <- x + theta (mu - x) + sigma eps          evaluated fma(sigma, eps, fma(theta, mu - x, x))
+ *     a  = clamp(actor(o) + scale x, -clip, clip)  a product, a sum, max, min - torch's fp32 bits; clip = +inf: no clamp
+ * with eps fg_actor_noise's draw at the step's counter offset (the draws of fg_rollout_hd_actor_sample: the same on either path
+ * and under any sharding), and after a step whose done flag is set for the env - with or without auto_reset - x <- mu
+ * (reset_noise(); the convention of fg_rollout_hd_actor_gru's state).  theta = 1, mu = 0 is the memoryless special case,
+ * x = sigma eps: maddpg-v1's Gaussian noise and clip.  There is no log_std and no log-density. */
+typedef struct FgActorOu {
+    float theta;   /* in [0, 1] */
+    float mu;      /* finite */
+    float sigma;   /* finite, >= 0 */
+    float scale;   /* finite */
+    float clip;    /* > 0; +inf: no clamp */
+} FgActorOu;
+
+/* fg_rollout_hd_actor (in_bn == NULL) or fg_rollout_hd_actor_bn (in_bn: the input BatchNorm) with the exploration `ou` on the
+ * actor's output (ou_actor_kernel / bn_ou_actor_kernel), hidden as there.  noise_state [B][N][2], fp32 in DEVICE memory, 8-byte
+ * aligned: read as the state step 0 starts from, kept on chip for the launch, written back as the state after step K - 1
+ * (already mu where that step ended an episode).  act_seq receives the clamped actions.  Every other argument, check and
+ * status code is the inner entry's; then FG_ERR_BAD_ARG, the message naming the field, for a NULL ou, a theta outside [0, 1],
+ * a negative sigma, a theta / mu / sigma / scale that is not finite, a clip that is NaN or not positive, a NULL noise_state
+ * with B > 0, and FG_ERR_ALIGNMENT for a noise_state that is not 8-byte aligned.  B == 0 returns FG_OK.  A K-step launch equals
+ * K one-step launches that pass noise_state along, bit for bit; two launches from one state give the same bits, and
+ * fg_rollout_hd driven by the recorded act_seq returns the same results bit for bit. */
+int fg_rollout_hd_actor_ou(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const FgActorOu* ou,
+                           float* noise_state, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                           float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                           float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int obs_every, void* stream);
+/* ... with one actor per agent: fg_rollout_hd_actor_per_agent (in_bns == NULL) or fg_rollout_hd_actor_bn_per_agent (in_bns: a
+ * HOST array of N) under the one `ou` (pa_ou_actor_kernel / pa_bn_ou_actor_kernel). */
+int fg_rollout_hd_actor_ou_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns, const FgActorOu* ou,
+                                     float* noise_state, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                     float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                     float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int obs_every,
+                                     void* stream);
+/* Dry runs of the two: same checks and status codes (noise_state's apart), name the ou_actor_kernel<N,H> / bn_ou_actor_kernel<N,H>
+ * or pa_ou_actor_kernel<N,H> / pa_bn_ou_actor_kernel<N,H> instantiation and its launch geometry.  Touch no device. */
+int fg_describe_actor_ou_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, const FgActorOu* ou,
+                                int B, int N, int K, int obs_every, char* out, int out_len);
+int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                          const FgActorOu* ou, int B, int N, int K, int obs_every, char* out, int out_len);
+/* The state update alone, x <- x + theta (mu - x) + sigma eps, on `count` (env, agent) pairs in place - eps and state
+ * [count][2], fp32 in DEVICE memory, 8-byte aligned - by the device function the fused kernels use: the host-paced loop calls
+ * it once per step on fg_actor_noise's draw and carries the fused launch's state bits.  ou's checks as above; count == 0 is a
+ * no-op. */
+int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream);
 
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch

@@ -14,7 +14,8 @@ from tests.isa_scan import kernel_resources  # noqa: E402
 
 FAMILIES = ("actor_rollout_kernel<", "actor_sample_kernel<", "pa_actor_kernel<", "pa_sample_kernel<", "ln_actor_kernel<",
             "ln_sample_kernel<", "gru_actor_kernel<", "gru_sample_kernel<", "::bn_actor_kernel<", "::bn_sample_kernel<",
-            "pa_bn_actor_kernel<", "pa_bn_sample_kernel<")
+            "pa_bn_actor_kernel<", "pa_bn_sample_kernel<", "::ou_actor_kernel<", "::pa_ou_actor_kernel<", "::bn_ou_actor_kernel<",
+            "pa_bn_ou_actor_kernel<")
 
 
 def main(argv):
