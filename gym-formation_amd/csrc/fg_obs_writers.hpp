@@ -1,4 +1,5 @@
-// fg_obs_writers.hpp - Observation writers: register-cached rows, LDS tiles, and the table-driven gather writer (8 / 9 agents).
+// fg_obs_writers.hpp - Observation writers: register-cached rows, LDS tiles, the table-driven gather writer (8 / 9 agents), and the
+// 16-bit (fp16 / bf16) tile writer.
 // Part of libformation_hip (gfx950); included by formation_hip.hip, one translation unit.
 #ifndef FG_OBS_WRITERS_HPP_
 #define FG_OBS_WRITERS_HPP_
@@ -493,6 +494,129 @@ template <int NC, int NW, int E, int CHMAX = 4> struct SpanGather {
         }
     }
 };
+
+// ---------------------------------------------------------------------------
+// 16-bit observation writer (fg_rollout_hd_obs16: fp16 or bf16 observations out of the rollout launch itself).  A unit - one
+// (x, y) pair of the [N][6N] block - becomes ONE 32-bit word, x in the low half, each half the round-to-nearest-even conversion
+// of the fp32 value the other writers store (v_cvt_f16_f32 / v_cvt_pk_bf16_f32: what torch's .to(dtype) computes, overflow to
+// inf, fp16 subnormals and signed zeros included).  The values are the same subtractions on the same table entries as in
+// write_obs_tiled, whose shape this is: a wave composes a tile in its own LDS (register-cached rows, ds_write_b32 per unit) and
+// streams it out as ONE contiguous span with ds_read_b128 + global_store_dwordx4, lanes consecutive - 16 bytes per lane, because
+// a 4-byte-per-lane store costs several times as much per byte and would give back what the halved bytes buy.
+//   tile   27 agents: 9 rows of one env (729 units, 2 916 B), the wave's envs w, w + NW, ...;
+//          3 / 9 agents: the E / NW consecutive envs of the wave, whole (at 3 agents an env is 108 B: eight of them make a
+//          span worth a wide store).
+// An env block is 3 N^2 units = 12 N^2 bytes, no multiple of 16 at an odd N: consecutive tiles start at different 16-byte
+// phases.  The tile sits in LDS at the phase of its destination, so both sides of the copy are naturally aligned; the up to 3
+// units in front of the first 16-byte boundary and behind the last are stored as single words by lanes 0 ... 2 (the plain tile
+// writer's odd unit).  Contiguous observation tensors only (the host refuses a padded env pitch); two tiles per wave, tile
+// t + 1 composed while tile t drains; only the issuing wave touches its tiles, so no barrier is needed.
+// ---------------------------------------------------------------------------
+constexpr int FG_WR_OBS_F16 = 65, FG_WR_OBS_BF16 = 66;                  // rollout_kernel's WR values for this writer, one per format
+constexpr bool roll_writer_obs16(int wr) { return wr == FG_WR_OBS_F16 || wr == FG_WR_OBS_BF16; }
+template <int NC> constexpr int obs16_rows() { return NC > 9 ? 9 : NC; }                                  // rows of an env per tile
+template <int NC, int NW, int E> constexpr int obs16_envs() { return NC <= 9 ? E / NW : 1; }                // envs per tile
+// 32-bit words of one tile: its units, the 16-byte phase in front, rounded up to whole 16-byte pieces
+template <int NC, int NW, int E> constexpr int obs16_tile_words() { return (obs16_envs<NC, NW, E>() * obs16_rows<NC>() * 3 * NC + 3 + 3) & ~3; }
+
+#if !FG_F64
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <int FMT> FG_DEV uint32_t obs16_pack(float x, float y) {
+    if constexpr (FMT == FG_WR_OBS_F16) {
+        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+        const h2 v = {(_Float16)x, (_Float16)y};
+        return __builtin_bit_cast(uint32_t, v);
+    } else {
+        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+        const b2 v = {(__bf16)x, (__bf16)y};
+        return __builtin_bit_cast(uint32_t, v);
+    }
+}
+
+// tables0 / env_stride: as write_obs_rows; tiles: 2 * NW tiles of obs16_tile_words (16-byte aligned); span: the workgroup's
+// first unit in the observation tensor, unit0 its index there (the tensor's base is 16-byte aligned); El envs, 3 N^2 units apart
+template <int NC, int NW, int E, int FMT>
+FG_DEV void write_obs16(const float2* __restrict__ tables0, int env_stride, int w, uint32_t* __restrict__ tiles,
+                        uint32_t* __restrict__ span, size_t unit0, int El) {
+    constexpr int N = NC, RT = obs16_rows<NC>(), ET = obs16_envs<NC, NW, E>(), WORDS = obs16_tile_words<NC, NW, E>();
+    static_assert(N <= 32 && N % RT == 0 && E >= NW && E % NW == 0, "16-bit writer: N <= 32, whole rows per tile, whole envs per wave");
+    static_assert(ET == 1 || RT == N, "a tile of several envs holds them whole");
+    constexpr unsigned ROWU = 3u * N, ENVU = ROWU * N, TU = ROWU * RT;    // units per row, per env, per env's share of a tile
+    constexpr int TILES_ENV = N / RT;
+    const int lane = threadIdx.x & 63;
+    uint32_t* const tile0 = tiles + w * 2 * WORDS;
+    constexpr int RW = 64 / N;
+    const int rsub = lane / N, u = lane - rsub * N;
+    const bool act = rsub < RW;
+    const int xoff = (u == 0) ? 4 * N : 0;                                 // lane u = 0 reads -v_row (NV = A + 4N)
+    constexpr int RS = 64 / (2 * N);
+    const int ssub = lane / (2 * N), sidx = lane - ssub * 2 * N;
+    // the wave's tiles of this step: ET == 1: envs w, w + NW, ... by TILES_ENV tiles; else ONE tile of the envs w ET ... w ET + ET - 1
+    const int n_env = (El > w) ? (El - w + NW - 1) / NW : 0;
+    const int total = ET == 1 ? n_env * TILES_ENV : (w * ET < El ? 1 : 0);
+    auto locate = [&](int t, int& ee, int& r0, int& ne) {                  // first env, first row, envs of the wave's t-th tile
+        if constexpr (ET == 1) {
+            const int ie = t / TILES_ENV;
+            ee = w + ie * NW; r0 = (t - ie * TILES_ENV) * RT; ne = 1;
+        } else {
+            ee = w * ET; r0 = 0; ne = min(ET, El - ee);
+        }
+    };
+    auto compose = [&](int t) {
+        int ee, r0, ne; locate(t, ee, r0, ne);
+        const unsigned par = (unsigned)((unit0 + (size_t)ee * ENVU + (size_t)r0 * ROWU) & 3);
+        uint32_t* img = tile0 + (t & 1) * WORDS + par;                    // no restrict: the two tiles alternate
+        for (int j = 0; j < ne; ++j, img += TU) {
+            const float2* __restrict__ AA = tables0 + (size_t)(ee + j) * env_stride;
+            const float2 Pm = lds_if(act && u >= 1, AA, u - 1);           // per-env register cache, as write_obs_rows
+            const float2 Pu = lds_if(act && u >= 1, AA, u);
+            const float2 sv = lds_if(ssub < RS, AA, N + sidx);
+#pragma unroll
+            for (int rb = 0; rb < RT; rb += RW) {
+                const int rl = rb + rsub;
+                if (act && rl < RT) {
+                    const int r = r0 + rl;
+                    const float2 x = AA[xoff + r];
+                    const float2 c = (u - 1 >= r) ? Pu : Pm;
+                    img[(unsigned)rl * ROWU + (unsigned)u] = obs16_pack<FMT>(c.x - x.x, c.y - x.y);
+                }
+            }
+            const uint32_t svp = obs16_pack<FMT>(sv.x, sv.y);             // zeros | ideal shape | ideal velocity: entry - 0
+#pragma unroll
+            for (int rb = 0; rb < RT; rb += RS) {
+                const int rl = rb + ssub;
+                if (ssub < RS && rl < RT) img[(unsigned)rl * ROWU + (unsigned)(N + sidx)] = svp;
+            }
+        }
+    };
+    auto stream = [&](int t) {
+        int ee, r0, ne; locate(t, ee, r0, ne);
+        const size_t first = (size_t)ee * ENVU + (size_t)r0 * ROWU;
+        const unsigned par = (unsigned)((unit0 + first) & 3);
+        const uint32_t* img = tile0 + (t & 1) * WORDS + par;
+        uint32_t* __restrict__ out = span + first;
+        const unsigned n = (unsigned)ne * TU;                             // units of this tile (>= 27: more than a head)
+        const unsigned head = (4u - par) & 3u;                            // single words up to the first 16-byte boundary
+        if ((unsigned)lane < head) out[lane] = img[lane];
+        const unsigned nq = (n - head) >> 2;
+        const u32x4* src4 = reinterpret_cast<const u32x4*>(img + head);
+        u32x4* __restrict__ dst4 = reinterpret_cast<u32x4*>(out + head);
+        constexpr unsigned NQMAX = ((unsigned)ET * TU) >> 2;
+#pragma unroll
+        for (unsigned q0 = 0; q0 < NQMAX; q0 += 64) {
+            const unsigned q = q0 + lane;
+            if (q < nq) dst4[q] = src4[q];
+        }
+        const unsigned tail = (n - head) & 3u, t0 = head + 4u * nq;       // ... and behind the last one
+        if ((unsigned)lane < tail) out[t0 + lane] = img[t0 + lane];
+    };
+    if (total > 0) compose(0);
+    for (int t = 0; t < total; ++t) {
+        if (t + 1 < total) compose(t + 1);
+        stream(t);
+    }
+}
+#endif  // !FG_F64
 
 }  // namespace fg
 

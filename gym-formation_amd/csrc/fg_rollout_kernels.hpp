@@ -25,9 +25,11 @@ namespace fg {
 // ---------------------------------------------------------------------------
 __host__ __device__ constexpr int roll_block_floats(int n) { return 20 * n + 6 * npad(n); }
 // LDS of the writer waves behind the env blocks, in float2 units: two tiles per wave (WR = 1 + rows per tile), the gather
-// writer's table (WR = FG_WR_GATHER), nothing for the rows writer (WR = 0)
+// writer's table (WR = FG_WR_GATHER), two tiles of 32-bit units per wave for the 16-bit writer (WR = FG_WR_OBS_F16 / _BF16),
+// nothing for the rows writer (WR = 0)
 template <int NC, int WR, int NWW, int E> constexpr int roll_writer_units() {
     if constexpr (WR == 0) return 0;
+    else if constexpr (roll_writer_obs16(WR)) return 2 * NWW * obs16_tile_words<NC, NWW, E>() / 2;
     else if constexpr (WR == FG_WR_GATHER)                                     // the per-env table or the span table (one entry per piece)
         return gather_lut_units<NC>() > E * 3 * NC * NC / 2 ? gather_lut_units<NC>() : E * 3 * NC * NC / 2;
     else return 2 * NWW * tile_units<NC, WR - 1>();
@@ -62,7 +64,8 @@ template <int NC, int G, int TP, int TW, int E, int WR, int PER = 0, bool STREAM
 __global__ __launch_bounds__(TP + TW) __attribute__((amdgpu_waves_per_eu((TP + TW) <= 512 && PER < 8 ? 4 : 3)))
 void rollout_kernel(const Args a) {
     constexpr bool POLICY = PER > 0;
-    // WR: observation writer of the writer waves, 0 = register-cached rows, 1 + RT = LDS tiles of RT rows
+    // WR: observation writer of the writer waves, 0 = register-cached rows, 1 + RT = LDS tiles of RT rows, FG_WR_GATHER,
+    //     FG_WR_OBS_F16 / FG_WR_OBS_BF16 = the 16-bit writer (a.obs then holds 32-bit units, a.obs_pitch counts them)
     // STREAM: HBM-streaming form of the LDS-tile writer (fg_obs_writers.hpp)
     // PER > 0: closed loop - the action of step k is the demo controller (PER-ary hierarchy, N = PER^L) on the state
     //         step k-1 left, evaluated by the env's own lane group; a.act is not read, a.act_out records the actions
@@ -317,6 +320,14 @@ void rollout_kernel(const Args a) {
                                                  reinterpret_cast<real2*>(a.obs) + unit0, unit0, env_units, El, gather_entries);
                   }
                 }
+#if !FG_F64
+                else if constexpr (roll_writer_obs16(WR)) {
+                    static_assert((E * roll_block_floats(NC)) % 4 == 0, "the 16-bit writer's tiles start on a 16-byte boundary");
+                    write_obs16<NC, NWW, E, WR>(tables0, roll_block_floats(N) / 2, (tid - TP) >> 6,
+                                                reinterpret_cast<uint32_t*>(smemf + E * roll_block_floats(N)),
+                                                reinterpret_cast<uint32_t*>(a.obs) + unit0, unit0, El);
+                }
+#endif
                 else
                     write_obs_tiled<NC, NWW, E, WR - 1, STREAM>(tables0, roll_block_floats(N) / 2, (tid - TP) >> 6,
                                                                 reinterpret_cast<real2*>(smemf + E * roll_block_floats(N)),

@@ -803,6 +803,56 @@ static int rollout_hd_policy_dispatch(const Args& a, int per_layer, hipStream_t 
     return FG_OK;
 }
 
+// ---- 16-bit observations out of the rollout launch (fg_rollout_hd_obs16, fg_rollout_hd_policy_obs16) ----
+// A dispatch of its own, reached only from those entries and their dry run: ONE instantiation per (agents, loop, format) with the
+// geometry of the fp32 default of its class (the last rule of launch_roll_8 / _16 / _32) and the 16-bit writer of
+// fg_obs_writers.hpp as WR.  The fp32 rule tables above never name these kernels.
+template <int WR>
+static int obs16_launch(const Args& a, int per, hipStream_t st) {
+#define FG_OBS16(NN, G, TP, TW, E)                                                                               \
+    if (a.N == NN) {                                                                                             \
+        static_assert(roll_lds_bytes<NN, TW, E, WR, 3>() <= 160 * 1024, "16-bit rollout LDS");                  \
+        return per ? launch_roll_v<NN, G, TP, TW, E, WR, 3>(a, st) : launch_roll_v<NN, G, TP, TW, E, WR, 0>(a, st); \
+    }
+    FG_OBS16(27, 32, 512, 256, 16) FG_OBS16(9, 16, 64, 128, 4) FG_OBS16(3, 4, 64, 128, 16)
+#undef FG_OBS16
+    return fail(FG_ERR_UNSUPPORTED_N, "16-bit observations: no fused launch for this agent count%s");   // (unreachable after obs16_check)
+}
+static int obs16_dispatch(const Args& a, int obs_format, int per, hipStream_t st) {
+    return obs_format == FG_OBS_F16 ? obs16_launch<FG_WR_OBS_F16>(a, per, st) : obs16_launch<FG_WR_OBS_BF16>(a, per, st);
+}
+// The checks the two entries and their dry run share, before the buffers: FG_OK, or the status of the first that fails.
+// per_layer 0: open loop; `pl` receives the controller's constants otherwise.
+static int obs16_check(const char* who, const FgParams* params, int obs_format, int B, int N, int K, int per_layer, FgPolicyLevels* pl) {
+    if (const int rc = check_params(params)) return rc;
+    if (obs_format != FG_OBS_F16 && obs_format != FG_OBS_BF16) return fail(FG_ERR_BAD_ARG, "%s: obs_format must be FG_OBS_F16 or FG_OBS_BF16", who);
+    if (B < 0 || K < 2) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 2 required", who);
+    if (world_options_set(*params))
+        return fail(FG_ERR_BAD_ARG, "%s: World options (walls, noise, max_speed, accel, agent_props, comm_state) have no 16-bit launch", who);
+    if (params->obs_env_pitch != 0) return fail(FG_ERR_BAD_ARG, "%s: a padded env pitch (obs_env_pitch) is not supported", who);
+    if (N != 3 && N != 9 && N != 27) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 9 or 27", who);
+    if (per_layer != 0 && (per_layer != 3 || !policy_levels_for(N, per_layer, pl)))
+        return fail(FG_ERR_UNSUPPORTED_N, "%s: the closed loop needs per_layer = 3", who);
+    return FG_OK;
+}
+// ... and the rest of an entry: buffers, launch description (fg_rollout_hd's builder), dispatch.  r.obs_seq holds 32-bit units.
+static int obs16_rollout(const char* who, const FgParams* params, int obs_format, int B, int N, int K, int per_layer,
+                         const HdRollout& r, int obs_every, void* stream) {
+    FgPolicyLevels pl;
+    int rc = obs16_check(who, params, obs_format, B, N, K, per_layer, &pl);
+    if (rc) return rc;
+    if (B == 0) return FG_OK;                         // an empty batch is a no-op (e.g. a rank that owns no envs)
+    if (obs_every < 1) return fail(FG_ERR_BAD_ARG, "%s: obs_every >= 1 required", who);
+    if (!r.obs_seq) return null_pointer(who);
+    if ((rc = rollout_buffers_check(who, r))) return rc;
+    const DeviceGuard device_guard(stream, r.pos_x);
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    hd_buffers(&a, r);
+    if (per_layer) { a.pl = pl; a.act_out = r.act_seq; } else a.act = r.act_seq;
+    return obs16_dispatch(a, obs_format, per_layer, (hipStream_t)stream);
+}
+
 static int launch_mt_reset(int B, int N, const uint8_t* mask, uint32_t* mt_state,
                            float* pos_x, float* pos_y, float* vel_x, float* vel_y,
                            float* ideal_shape, float* ideal_vel, float* landmark_pos, int32_t* step,
@@ -2167,6 +2217,43 @@ int fg_describe_launch(const FgParams* params, const FgScenario* scenario, int B
         return rollout_hd_policy_dispatch(a, per_layer, nullptr);
     }
     return K == 0 ? step_hd_dispatch(a, nullptr) : rollout_hd_dispatch(a, nullptr);   // fg_step_hd : fg_rollout_hd with K steps
+}
+
+int fg_rollout_hd_obs16(const FgParams* params, int obs_format, int B, int N, int K,
+                        float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                        const float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                        void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                        int obs_every, void* stream) {
+    const HdRollout r = {pos_x, pos_y, vel_x, vel_y, const_cast<float*>(act_seq), ideal_shape, ideal_vel, step,
+                         static_cast<float*>(obs_seq), reward_seq, indiv_seq, done_seq};
+    return obs16_rollout("fg_rollout_hd_obs16", params, obs_format, B, N, K, 0, r, obs_every, stream);
+}
+
+int fg_rollout_hd_policy_obs16(const FgParams* params, int obs_format, int B, int N, int K, int per_layer,
+                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                               int obs_every, void* stream) {
+    if (per_layer == 0) return fail(FG_ERR_UNSUPPORTED_N, "%s: the closed loop needs per_layer = 3", "fg_rollout_hd_policy_obs16");
+    const HdRollout r = {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step,
+                         static_cast<float*>(obs_seq), reward_seq, indiv_seq, done_seq};
+    return obs16_rollout("fg_rollout_hd_policy_obs16", params, obs_format, B, N, K, per_layer, r, obs_every, stream);
+}
+
+// The dry run of fg_rollout_hd_obs16 (per_layer 0) / fg_rollout_hd_policy_obs16 (per_layer 3): their checks before the buffers,
+// then their dispatch.  Touches no device.
+int fg_describe_obs16_launch(const FgParams* params, int obs_format, int B, int N, int K, int per_layer, int obs_every,
+                             char* out, int out_len) {
+    if (!out || out_len < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_obs16_launch: out buffer required%s");
+    out[0] = 0;
+    FgPolicyLevels pl;
+    int rc = obs16_check("fg_describe_obs16_launch", params, obs_format, B, N, K, per_layer, &pl);
+    if (rc) return rc;
+    if (B <= 0) return fail(FG_ERR_BAD_ARG, "fg_describe_obs16_launch: B > 0 required%s");
+    Args a;
+    if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
+    const DescribeScope describing(out, out_len);
+    return obs16_dispatch(a, obs_format, per_layer, nullptr);
 }
 
 }  // extern "C"

@@ -64,6 +64,19 @@ class FgParams(ctypes.Structure):
 
 FG_SCN_BASIC, FG_SCN_PARTIAL, FG_SCN_RANGE, FG_SCN_OBSTACLE = 1, 2, 3, 4
 FG_ACT_ONEHOT5, FG_ACT_INDEX, FG_ACT_ARGMAX = 1, 2, 3          # fg_decode_actions modes
+FG_OBS_F16, FG_OBS_BF16 = 1, 2                                 # obs_format of fg_rollout_hd_obs16 / fg_rollout_hd_policy_obs16
+
+
+def obs_format(dtype):
+    """FG_OBS_* of a torch 16-bit float dtype; 0 for None (fp32 observations); ValueError for anything else."""
+    import torch
+    if dtype is None:
+        return 0
+    if dtype == torch.float16:
+        return FG_OBS_F16
+    if dtype == torch.bfloat16:
+        return FG_OBS_BF16
+    raise ValueError("obs_dtype must be None, torch.float16 or torch.bfloat16; got %r" % (dtype,))
 
 
 class FgScenario(ctypes.Structure):
@@ -211,6 +224,9 @@ SIGNATURES = {
     "fg_policy_bfs": (_I, [_I, _I, _I, _P, ctypes.c_int64, _P, _P]),
     "fg_policy_bfs_state": (_I, [_I, _I, _I] + [_P] * 6),
     "fg_rollout_hd_policy": (_I, [_PP, _I, _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_rollout_hd_obs16": (_I, [_PP, _I, _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_rollout_hd_policy_obs16": (_I, [_PP, _I, _I, _I, _I, _I] + [_P] * 12 + [_I, _P]),
+    "fg_describe_obs16_launch": (_I, [_PP, _I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor": (_I, [_PP, ctypes.POINTER(FgActor), _I, _I, _I] + [_P] * 12 + [_I, _P]),
     "fg_describe_actor_launch": (_I, [_PP, ctypes.POINTER(FgActor), _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_rollout_hd_actor_sample": (_I, [_PP, ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 13 + [_I, _P]),

@@ -169,7 +169,7 @@ class MultiAgentEnv(object):
             return self._batched_result()
         return self._reference_result()
 
-    def rollout(self, action_seq, out=None, obs_every=1):
+    def rollout(self, action_seq, out=None, obs_every=1, obs_dtype=None):
         """K consecutive `step` calls in ONE launch (`fg_rollout_hd`): for policies that hand over a
         whole action sequence (open-loop / pre-staged random policies, model-predictive candidates).
         `action_seq` is a [K, B, N, 2] tensor of raw continuous actions.  Results are bit-identical to
@@ -184,7 +184,18 @@ class MultiAgentEnv(object):
         arenas) and re-used by every later call.  LIKE `step`, THE RESULTS ARE VIEWS OF ENV-OWNED BUFFERS THAT THE NEXT
         `rollout` OF THE SAME SHAPE OVERWRITES: `traj.append(env.rollout(a))` aliases - clone what must outlive the next
         call, or pass out=False (fresh, ordinary tensors on every call) or your own `out`.  The four most recently used
-        (K, obs_every, policy) shapes keep their buffers; `env.default_placed = False` makes out=None mean out=False."""
+        (K, obs_every, policy) shapes keep their buffers; `env.default_placed = False` makes out=None mean out=False.
+        `obs_dtype` = torch.float16 or torch.bfloat16: the returned obs has that dtype and holds, bit for bit, what
+        `.to(obs_dtype)` of the fp32 launch's observations holds (round to nearest even); everything else, the state left
+        behind and the RNG counter are the fp32 launch's.  `obs_path(obs_dtype)` tells how: 'fused' - the launch itself stores
+        16-bit units (`fg_rollout_hd_obs16`: half the observation bytes, no second pass) - or 'cast' - the fp32 launch into
+        the env's usual buffers, then a cast.  With `obs_dtype`, `out` is a caller's dict whose out["obs"] is a CONTIGUOUS
+        tensor of that dtype (a padded env pitch raises ValueError), and out=None means out=False: fresh, ordinary tensors per
+        call - the placement probe is not extended to 16-bit buffers."""
+        fmt = _native.obs_format(obs_dtype)
+        if fmt and (len(action_seq) < 2 or self.obs_path(obs_dtype) == "cast"):
+            return self._rollout_cast(obs_dtype, out, len(action_seq), int(obs_every), False,
+                                      lambda o: self.rollout(action_seq, o, obs_every))
         roll = getattr(self.scenario, "rollout_batch", None)
         if roll is None or self.post_step_callback is not None:
             # no multi-step launch (a reference-style Scenario file: its callbacks run on the host), or a post_step_callback
@@ -209,11 +220,12 @@ class MultiAgentEnv(object):
         B, N = self.num_envs, self.num_agents
         D = self._out["obs"].shape[-1]
         if out is None:
-            out = self._default_out(K, obs_every, False) if self.default_placed else False
+            out = self._default_out(K, obs_every, False) if self.default_placed and not fmt else False
         own_buffers = out is not False
         if out is False:
             f = dict(dtype=torch.float32, device=self._act.device)
-            out = dict(obs=torch.empty((K // obs_every, B, N, D), **f), reward=torch.empty((K, B, N), **f),
+            out = dict(obs=torch.empty((K // obs_every, B, N, D), dtype=obs_dtype or torch.float32, device=self._act.device),
+                       reward=torch.empty((K, B, N), **f),
                        indiv=torch.empty((K, B, N), **f),
                        done=torch.zeros((K, B, N), dtype=torch.uint8, device=self._act.device))
         # launches into CALLER-OWNED buffers are bound once per (actions, buffers, stream, constants): a training
@@ -225,23 +237,26 @@ class MultiAgentEnv(object):
             key = ("roll", act.data_ptr(), K, out["obs"].data_ptr(), tuple(out["obs"].stride()), out["reward"].data_ptr(),
                    out["indiv"].data_ptr(), out["done"].data_ptr(), obs_every, self.auto_reset,
                    _native.current_stream_fast(self.world.device),
-                   self.world.params_signature(), getattr(self.scenario, "_seed", 0))
+                   self.world.params_signature(), getattr(self.scenario, "_seed", 0), obs_dtype)
         launch = self._roll_launchers.get(key) if key is not None else None
+        fmt_kw = dict(obs_format=fmt) if fmt else {}
         if launch is None:
             want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
             for k, shp in want.items():
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
+            self._check_obs_dtype(out, obs_dtype)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()
                 launch = self._roll_launchers[key] = bind(self.world, act, out, obs_every=obs_every,
-                                                          auto_reset=self.auto_reset)
+                                                          auto_reset=self.auto_reset, **fmt_kw)
         if launch is not None:
             launch(self._launch_rng_offset())
             self.scenario._cache = None
         else:
-            roll(self.world, act, out, obs_every=obs_every, auto_reset=self.auto_reset, rng_offset=self._launch_rng_offset())
+            roll(self.world, act, out, obs_every=obs_every, auto_reset=self.auto_reset, rng_offset=self._launch_rng_offset(),
+                 **fmt_kw)
         self._advance_rng(K)
         self.current_step += K
         self.world.world_step += K
@@ -280,18 +295,23 @@ class MultiAgentEnv(object):
         rew = out["reward"] if self.shared_reward else first
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), {"individual_reward": out["indiv"]}
 
-    def rollout_policy(self, K, num_agents_per_layer=3, out=None, obs_every=1):
+    def rollout_policy(self, K, num_agents_per_layer=3, out=None, obs_every=1, obs_dtype=None):
         """The reference's demo loop (test.py:17-27) for K steps in one call:
             act_n = get_action_BFS(ezpolicy, obs_n, num_agents_per_layer); obs_n, ... = env.step(act_n)
         starting from the current state (`fg_rollout_hd_policy`; ONE launch at 3, 9, 27, 81 or 243 agents with
         3 agents per layer).  Results equal K x (`get_action_BFS` on the last observation, `step`) bit for bit and
-        come back like `rollout`'s, with the actions taken under info['actions'] [K, B, N, 2]."""
+        come back like `rollout`'s, with the actions taken under info['actions'] [K, B, N, 2].  `obs_dtype`: as `rollout`'s
+        (`obs_path(obs_dtype, policy=True)`; the fused launch is `fg_rollout_hd_policy_obs16`, 3 agents per layer)."""
         roll = getattr(self.scenario, "rollout_policy_batch", None)
         if roll is None:
             raise NotImplementedError("%s has no built-in controller" % type(self.scenario).__name__)
         if self._action_mode():
             raise NotImplementedError("the built-in controller emits raw continuous actions")
         K, obs_every = int(K), int(obs_every)
+        fmt = _native.obs_format(obs_dtype)
+        if fmt and (K < 2 or int(num_agents_per_layer) != 3 or self.obs_path(obs_dtype, policy=True) == "cast"):
+            return self._rollout_cast(obs_dtype, out, K, obs_every, True,
+                                      lambda o: self.rollout_policy(K, num_agents_per_layer, o, obs_every))
         if self.post_step_callback is not None:
             # a host function after every step (environment.py:140-141): the demo loop itself, launch by launch
             from .policy_bfs import ezpolicy, get_action_BFS
@@ -315,11 +335,13 @@ class MultiAgentEnv(object):
         f = dict(dtype=torch.float32, device=self._act.device)
         want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
         if out is None:
-            out = self._default_out(K, obs_every, True) if self.default_placed else False
+            out = self._default_out(K, obs_every, True) if self.default_placed and not fmt else False
         own_buffers = out is not False
         if out is False:
             out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
                        else torch.empty(shp, **f)) for k, shp in want.items()}
+            if fmt:
+                out["obs"] = torch.empty(want["obs"], dtype=obs_dtype, device=self._act.device)
         # launches into CALLER-OWNED buffers are bound once (cf. rollout): a loop that steps K = 1 at a time pays one
         # ctypes call per launch
         bind = getattr(self.scenario, "bind_rollout_policy", None)
@@ -328,29 +350,78 @@ class MultiAgentEnv(object):
             key = ("pol", K, int(num_agents_per_layer), tuple(out[k].data_ptr() for k in sorted(want)),
                    tuple(out["obs"].stride()), obs_every,
                    self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
-                   getattr(self.scenario, "_seed", 0))
+                   getattr(self.scenario, "_seed", 0), obs_dtype)
         launch = self._roll_launchers.get(key) if key is not None else None
+        fmt_kw = dict(obs_format=fmt) if fmt else {}
         if launch is None:
             for k, shp in want.items():
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
+            self._check_obs_dtype(out, obs_dtype)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()
                 launch = self._roll_launchers[key] = bind(self.world, K, num_agents_per_layer, out, obs_every=obs_every,
-                                                          auto_reset=self.auto_reset)
+                                                          auto_reset=self.auto_reset, **fmt_kw)
         if launch is not None:
             launch(self._launch_rng_offset())
             self.scenario._cache = None
         else:
             roll(self.world, K, num_agents_per_layer, out, obs_every=obs_every, auto_reset=self.auto_reset,
-                 rng_offset=self._launch_rng_offset())
+                 rng_offset=self._launch_rng_offset(), **fmt_kw)
         self._advance_rng(K)
         self.current_step += K
         self.world.world_step += K
         rew = out["reward"] if self.shared_reward else out["indiv"]
         return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), \
             {"individual_reward": out["indiv"], "actions": out["act"]}
+
+    def obs_path(self, obs_dtype, policy=False):
+        """How `rollout(..., obs_dtype=obs_dtype)` (policy=True: `rollout_policy`, 3 agents per layer) produces its 16-bit
+        observations: 'fused' - the launch itself stores fp16 / bf16 units (`fg_rollout_hd_obs16`; formation_hd_env at 3, 9
+        or 27 agents without World options) - or 'cast' - the fp32 launch runs into the env's usual buffers and the result
+        is cast, which is the same bits by definition and works for every scenario, agent count and option.  Decided without
+        touching the device: the scenario asks the library (`obs16_supported`, `fg_describe_obs16_launch`); a scenario that
+        does not define it (the landmark scenarios, plugin scenarios) runs 'cast', and so does a single step (K = 1)."""
+        if not _native.obs_format(obs_dtype):
+            raise ValueError("obs_dtype must be torch.float16 or torch.bfloat16")
+        sc = self.scenario
+        supported = getattr(sc, "obs16_supported", None)
+        launch = getattr(sc, "rollout_policy_batch" if policy else "rollout_batch", None)
+        if supported is None or launch is None or self.post_step_callback is not None:
+            return "cast"
+        return "fused" if supported(self.world, 2, 3 if policy else 0) else "cast"
+
+    @staticmethod
+    def _check_obs_dtype(out, obs_dtype):
+        """A launch with `obs_dtype` writes a contiguous out["obs"] of that dtype (obs_dtype None: nothing to check here)."""
+        if obs_dtype is None:
+            return
+        obs = out["obs"]
+        if obs.dtype != obs_dtype:
+            raise ValueError("out['obs'] must have dtype %s, got %s" % (obs_dtype, obs.dtype))
+        if not obs.is_contiguous():
+            raise ValueError("a padded env pitch is not supported with obs_dtype: out['obs'] must be contiguous")
+
+    def _rollout_cast(self, obs_dtype, out, K, obs_every, policy, run_fp32):
+        """The 'cast' route of `rollout` / `rollout_policy`.  `run_fp32(out)` is the fp32 call.  Without a caller's `out` it
+        runs into the env's usual buffers (out=None) and everything comes back as fresh tensors, the observations cast.  With
+        one, the launch fills the caller's tensors itself, except that its observations go to the env's usual fp32 buffer
+        and are cast into out["obs"] from there."""
+        if not isinstance(out, dict):
+            obs, rew, done, info = run_fp32(None)
+            return obs.to(obs_dtype), rew.clone(), done.clone(), {k: v.clone() for k, v in info.items()}
+        if "obs" not in out:
+            raise ValueError("out['obs'] must be a contiguous tensor of dtype %s" % obs_dtype)
+        self._check_obs_dtype(out, obs_dtype)
+        launches = getattr(self.scenario, "rollout_batch", None) is not None and self.post_step_callback is None
+        if launches and self.default_placed and K >= 1 and obs_every >= 1:
+            obs32 = self._default_out(K, obs_every, policy)["obs"]
+        else:
+            obs32 = torch.empty(tuple(out["obs"].shape), dtype=torch.float32, device=self._act.device)
+        obs, rew, done, info = run_fp32(dict(out, obs=obs32))
+        out["obs"].copy_(obs)                              # the cast: round to nearest even, as .to(obs_dtype)
+        return out["obs"], rew, done, info
 
     def actor_path(self, actor):
         """'fused' when `rollout_actor(K, actor)` runs as ONE launch with the actor inside the rollout kernel

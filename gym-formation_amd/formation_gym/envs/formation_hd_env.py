@@ -214,12 +214,31 @@ class Scenario(BaseScenario):
             _native.ptr(out.get("hd_idx")), _native.current_stream(world.device)))
         self._cache = out
 
-    def rollout_batch(self, world, act_seq, out, obs_every=1, auto_reset=False, rng_offset=0):
-        """K steps in one launch; act_seq [K,B,N,2], out tensors carry a leading K."""
+    def obs16_supported(self, world, K, per_layer=0):
+        """Whether a K-step launch (per_layer 0: `rollout_batch`, else `rollout_policy_batch`) of this world can store its
+        observations in fp16 / bf16 itself (`obs_format`): the library's own answer (`fg_describe_obs16_launch`, which touches
+        no device).  False: the caller runs the fp32 launch and casts."""
+        try:
+            p = self.params(world)
+        except NotImplementedError:                        # scripted agents: only the World API drives them
+            return False
+        buf = ctypes.create_string_buffer(256)
+        return _native.load().fg_describe_obs16_launch(p, _native.FG_OBS_F16, world.num_envs, len(world.agents), int(K),
+                                                       int(per_layer), 1, buf, len(buf)) == _native.FG_OK
+
+    @staticmethod
+    def _rollout_entry(lib, name, obs_format):
+        """(C entry, its arguments between params and B) of a K-step launch: `name`, or its 16-bit twin with the format."""
+        return (getattr(lib, name + "_obs16"), (int(obs_format),)) if obs_format else (getattr(lib, name), ())
+
+    def rollout_batch(self, world, act_seq, out, obs_every=1, auto_reset=False, rng_offset=0, obs_format=0):
+        """K steps in one launch; act_seq [K,B,N,2], out tensors carry a leading K.  obs_format (_native.FG_OBS_F16 / _BF16):
+        out["obs"] is a contiguous tensor of that 16-bit dtype, written by the launch itself (`fg_rollout_hd_obs16`)."""
         lib = _native.load()
         K = act_seq.shape[0]
-        _native.check(lib.fg_rollout_hd(
-            self.params(world, auto_reset, rng_offset, out.get("obs")), world.num_envs, len(world.agents), K,
+        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd", obs_format)
+        _native.check(fn(
+            self.params(world, auto_reset, rng_offset, out.get("obs")), *fmt, world.num_envs, len(world.agents), K,
             world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
             act_seq.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
             world.step_count.data_ptr(),
@@ -227,12 +246,13 @@ class Scenario(BaseScenario):
             _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device)))
         self._cache = None
 
-    def rollout_policy_batch(self, world, K, per_layer, out, obs_every=1, auto_reset=False, rng_offset=0):
+    def rollout_policy_batch(self, world, K, per_layer, out, obs_every=1, auto_reset=False, rng_offset=0, obs_format=0):
         """K closed-loop steps with the built-in controller (`fg_rollout_hd_policy`): out["act"] [K,B,N,2]
-        receives the actions taken, the other tensors are those of `rollout_batch`."""
+        receives the actions taken, the other tensors (and obs_format) are those of `rollout_batch`."""
         lib = _native.load()
-        _native.check(lib.fg_rollout_hd_policy(
-            self.params(world, auto_reset, rng_offset, out.get("obs")), world.num_envs, len(world.agents), int(K), int(per_layer),
+        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_policy", obs_format)
+        _native.check(fn(
+            self.params(world, auto_reset, rng_offset, out.get("obs")), *fmt, world.num_envs, len(world.agents), int(K), int(per_layer),
             world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
             out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
             world.step_count.data_ptr(),
@@ -240,18 +260,19 @@ class Scenario(BaseScenario):
             _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device)))
         self._cache = None
 
-    def bind_rollout_policy(self, world, K, per_layer, out, obs_every=1, auto_reset=False):
+    def bind_rollout_policy(self, world, K, per_layer, out, obs_every=1, auto_reset=False, obs_format=0):
         """`rollout_policy_batch` with every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`, one ctypes call per closed-loop launch."""
         lib = _native.load()
         p = self.params(world, auto_reset, 0, out.get("obs"))
-        args = (world.num_envs, len(world.agents), int(K), int(per_layer),
+        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_policy", obs_format)
+        args = fmt + (world.num_envs, len(world.agents), int(K), int(per_layer),
                 world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
                 out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
                 world.step_count.data_ptr(),
                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
-        return _native.bind_launch(lib.fg_rollout_hd_policy, p, *args, keep=out)
+        return _native.bind_launch(fn, p, *args, keep=out)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None,
                            noise_state=None):
@@ -352,19 +373,20 @@ class Scenario(BaseScenario):
             _native.current_stream(world.device)))
         return out
 
-    def bind_rollout(self, world, act_seq, out, obs_every=1, auto_reset=False):
+    def bind_rollout(self, world, act_seq, out, obs_every=1, auto_reset=False, obs_format=0):
         """`rollout_batch` with every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`, one ctypes call per K-step launch (a 9 x 4096 launch lasts ~35 us on the GPU,
         less than the generic path spends in Python)."""
         lib = _native.load()
         p = self.params(world, auto_reset, 0, out.get("obs"))
-        args = (world.num_envs, len(world.agents), int(act_seq.shape[0]),
+        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd", obs_format)
+        args = fmt + (world.num_envs, len(world.agents), int(act_seq.shape[0]),
                 world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
                 act_seq.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
                 world.step_count.data_ptr(),
                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
-        return _native.bind_launch(lib.fg_rollout_hd, p, *args, keep=(act_seq, out))
+        return _native.bind_launch(fn, p, *args, keep=(act_seq, out))
 
     def upload_mt_streams(self, world):
         """Copy every env's legacy MT19937 state (RandomState(seed + 1000 b), at its CURRENT

@@ -434,6 +434,39 @@ int fg_rollout_hd_policy(const FgParams* params, int B, int N, int K, int per_la
                          float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
                          int obs_every, void* stream);
 
+/* 16-bit observations out of the rollout launch itself.  obs_format: */
+#define FG_OBS_F16 1     /* IEEE binary16 (torch.float16) */
+#define FG_OBS_BF16 2    /* bfloat16 */
+/* fg_rollout_hd with obs_seq [K / obs_every][B][N][6N] in `obs_format` (2 bytes per element; 16-byte aligned, required,
+ * contiguous): every element is the round-to-nearest-even conversion of the fp32 value fg_rollout_hd stores there - what a
+ * second pass `obs.to(dtype)` over the fp32 tensor gives, bit for bit (fp16: overflow to inf, subnormals kept; signed zeros
+ * kept) - written by the rollout kernel's writer waves as 16-byte stores, so that the launch moves half the observation bytes
+ * and the caller's cast pass (read 4 B, write 2 B per element) goes away.  Everything else - state, reward_seq, indiv_seq,
+ * done_seq, the RNG counter - is fg_rollout_hd's, bit for bit.
+ * Fused support: formation_hd_env at N in {3, 9, 27} (the reference's hierarchy counts rollout_kernel serves), K >= 2.
+ * Status: FG_ERR_UNSUPPORTED_N for any other N; FG_ERR_BAD_ARG for an unknown obs_format, K < 2, a padded env pitch
+ * (params->obs_env_pitch != 0) or anything fg_rollout_hd would not run in the pipelined rollout kernel (walls, u_noise,
+ * max_speed, accel, agent_props, comm_state); FG_ERR_ALIGNMENT for an obs_seq that is not 16-byte aligned.  There is no
+ * fall-back inside the library: a caller that gets one of these runs fg_rollout_hd and casts.  B == 0 returns FG_OK without
+ * a launch. */
+int fg_rollout_hd_obs16(const FgParams* params, int obs_format, int B, int N, int K,
+                        float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                        const float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                        void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                        int obs_every, void* stream);
+/* ... and fg_rollout_hd_policy likewise (act_seq is an OUTPUT); per_layer must be 3 (else FG_ERR_UNSUPPORTED_N). */
+int fg_rollout_hd_policy_obs16(const FgParams* params, int obs_format, int B, int N, int K, int per_layer,
+                               float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq,
+                               int obs_every, void* stream);
+/* Dry run of fg_rollout_hd_obs16 (per_layer = 0) or fg_rollout_hd_policy_obs16 (per_layer = 3): the same checks and status
+ * codes (those on the buffers apart; B > 0 required), then "rollout_kernel<NC,G,TP,TW,E,WR,PER,STREAM> grid G lds L; " in
+ * `out` as fg_describe_launch writes it, WR being the 16-bit writer of the format (65: fp16, 66: bf16).  Touches no device:
+ * this is how a caller decides between the fused launch and fg_rollout_hd + cast. */
+int fg_describe_obs16_launch(const FgParams* params, int obs_format, int B, int N, int K, int per_layer, int obs_every,
+                             char* out, int out_len);
+
 /* The caller's MLP actor for fg_rollout_hd_actor: Linear(6N, hidden) - ReLU - Linear(hidden, hidden) - ReLU -
  * Linear(hidden, 2) [- tanh], one actor shared by every agent.  Weights in the torch Linear layout [out][in], fp32, in
  * DEVICE memory, read in place by every launch (an optimizer step between two launches is seen by the next one); a NULL
