@@ -71,7 +71,22 @@ typedef enum FgStatus {
  *                      (when done: re-initialise the env on device and return the RESET
  *                      observation together with the pre-reset reward/done)
  *   seed, rng_offset  counter-RNG key / per-call offset for the device-side reset
- *                   (distributional parity with formation_hd_env.py:77-95 only)
+ *                   (distributional parity with formation_hd_env.py:77-95 only).
+ *                   The contract, pinned draw by draw by tests/test_gpu_counter_rng.py against tests/counter_rng.py:
+ *                   every draw is ONE Philox4x32-10 block with key {lo32(seed), hi32(seed)} and counter
+ *                   {env_index_base + b, stream code, lo32(off), hi32(off)}, off = rng_offset + *rng_offset_dev (+ k at
+ *                   step k of a K-step launch, a 64-bit sum).  Stream codes (counter word 1) and the words used:
+ *                     formation_hd_env reset, agent i     i                      c0,c1 -> position; c2,c3 -> ideal shape
+ *                                                                                 before centring (shape = raw - sum / N)
+ *                     ... its ideal velocity              0xFFFFFFFF             c0,c1
+ *                     landmark-scenario reset: agent i    i                      c0,c1
+ *                                  landmark l / obstacle k  0x10000000 | l / 0x20000000 | k     c0,c1
+ *                     motor noise (u_noise), agent i      i ^ 0x80000000         c0,c1 -> Box-Muller
+ *                     comm noise (c_noise), agent i,      (i | 0x40000000 | q << 12) ^ 0x80000000   c0,c1 -> Box-Muller
+ *                       components 2q, 2q + 1
+ *                     actor exploration, agent i          (i | 0x20000000) ^ 0x80000000             c0,c1 -> Box-Muller
+ *                   uniform: u = (c >> 8) * 2^-23 - 1 in [-1, 1), exact in fp32; Box-Muller: r = sqrt(-2 ln(((c0 >> 8) + 1)
+ *                   / 2^24)), a = 6.2831853f * (c1 >> 8) / 2^24, (r cos a, r sin a).  Disjoint for i, l, k < 1024, q < 2^16.
  * World options that no reference scenario switches on (0 = None, the reference default):
  *   accel           core.py:236 + environment.py:219-220: force = mass*accel*(accel*action)
  *   max_speed       core.py:271-276 speed clamp after the velocity update

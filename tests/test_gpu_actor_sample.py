@@ -1,14 +1,13 @@
 """GPU tests of the Gaussian actor rollout: `env.rollout_actor(K, GaussianActor(mean, log_std))`, fused
 (`fg_rollout_hd_actor_sample`, actor_sample_kernel) and host-paced (`fg_actor_noise` once per step).
 
-Noise reference bound.  eps = (r cos a, r sin a), r = sqrt(-2 ln u), u = ((c0 >> 8) + 1) / 2^24, a = 6.2831853f (c1 >> 8) / 2^24,
-c = Philox4x32-10 (below, in NumPy).  u is exact in fp32 and a carries one rounding (2^-24 relative), so the error is that of
-the fp32 transcendentals.  __logf is v_log_f32 (log2, ~1 ulp) times ln 2 (0.5 ulp): ln u to ~2^-22 relative; the square root
-halves that and adds 0.5 ulp: r to ~2.5e-7 relative.  __cosf / __sinf scale a by 1 / 2 pi (0.5 ulp of a revolution < 1) and
-take v_cos_f32 / v_sin_f32 (~2^-22 absolute): cos a, sin a to ~4e-7 absolute.  Per component
-    |eps - eps64| <= r (2.5e-7 |cos a| + 4e-7) + 0.5 ulp(eps) <= 7e-7 r + 1e-7,
-which is below 2e-6 for r <= 2.7 (97 % of the draws) and grows in the tail: at this test's ~1e5 draws r reaches ~4.8.  A flat
-2e-6 does not hold there - the measured maximum is 2.2-2.3e-6 - so the test enforces the per-draw bound.
+Noise reference bound.  eps = (r cos a, r sin a) is Box-Muller of a Philox4x32-10 block; the NumPy reference (`_philox`, `_eps_ref`)
+and the derivation of the per-draw bound
+    |eps - eps64| <= 7e-7 r + 1e-7
+live in tests/counter_rng.py, which holds every other consumer of the device counter RNG to the same reference
+(tests/test_gpu_counter_rng.py).  The bound is below 2e-6 for r <= 2.7 (97 % of the draws) and grows in the tail: at this test's
+~1e5 draws r reaches ~4.8.  A flat 2e-6 does not hold there - the measured maximum is 2.2-2.3e-6 - so the test enforces the
+per-draw bound.
 
 Log-prob fidelity bound.  The kernel's log_prob is -|eps|^2 / 2 - sum(log_std) - log(2 pi) of its own eps; the fp64 reference
 is Normal(mean64(o), std).log_prob(a).sum(-1) at the recorded fp32 action a.  With z = (a - mean64) / std the two differ by
@@ -26,6 +25,7 @@ from formation_gym import GaussianActor
 from formation_gym.actor_rollout import FUSED_N
 from tests.actor_testlib import (ACT_SCALE, B, DEV, K, Wrap as _Wrap, clone as _clone, env as _env, logp_formula as _logp_formula,
                                  noise_at as _noise_at, scaled_mlp, state as _state)
+from tests.counter_rng import _eps_ref, _philox  # noqa: F401  (the NumPy Philox4x32-10 and fp64 Box-Muller reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,33 +38,6 @@ def _mlp(N, H, tanh=False, seed=0, zero=False):
 
 def _zero_actor(N, H=64):
     return GaussianActor(_mlp(N, H, zero=True), torch.nn.Parameter(torch.zeros(2, device=DEV)))
-
-
-# ---- NumPy Philox4x32-10 and fp64 Box-Muller ----
-def _philox(c0, c1, c2, c3, seed):
-    M = np.uint64(0xFFFFFFFF)
-    c = [np.asarray(x, dtype=np.uint64) & M for x in (c0, c1, c2, c3)]
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        m0 = np.uint64(0xD2511F53) * c[0]
-        m1 = np.uint64(0xCD9E8D57) * c[2]
-        n0 = (m1 >> np.uint64(32)) ^ c[1] ^ k0
-        n2 = (m0 >> np.uint64(32)) ^ c[3] ^ k1
-        c = [n0 & M, m1 & M, n2 & M, m0 & M]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    return c
-
-
-def _eps_ref(seed, Bn, N, offset, base=0):
-    g = np.arange(Bn, dtype=np.uint64)[:, None] + np.uint64(base)
-    i = np.arange(N, dtype=np.uint64)[None, :]
-    shape = (Bn, N)
-    c = _philox(np.broadcast_to(g, shape), np.broadcast_to(i ^ np.uint64(0xA0000000), shape),
-                np.full(shape, offset & 0xFFFFFFFF, np.uint64), np.full(shape, offset >> 32, np.uint64), int(seed))
-    u = ((c[0] >> np.uint64(8)).astype(np.float64) + 1.0) / 16777216.0
-    a = float(np.float32(6.2831853)) * ((c[1] >> np.uint64(8)).astype(np.float64) / 16777216.0)
-    r = np.sqrt(-2.0 * np.log(u))
-    return np.stack([r * np.cos(a), r * np.sin(a)], -1)
 
 
 @pytest.mark.parametrize("N", [9, 27])
