@@ -162,6 +162,21 @@ def actor_in_bn(bn):
     return FgActorInBn(ptr(mean), ptr(var), ptr(g), ptr(b), eps)
 
 
+def actor_structs(actor):
+    """The structs of an `actor_rollout.FusedActor`, as the actor launches take them: (FgActor[members], FgActorNorm,
+    FgActorGru, FgActorInBn[members]), None for a struct the actor has no part for.  Their non-NULL pointer fields and the
+    log_std argument are, between them, the addresses of `actor.tensors()`."""
+    fas = (FgActor * len(actor.members))(*[
+        FgActor(int(actor.hidden), int(actor.out_tanh), *[ptr(t) for t in ws]) for ws in actor.members])
+    norm = None if actor.norms is None else actor_norm(actor.norms)
+    gru = None if actor.gru is None else actor_gru(actor.gru)
+    bns = None
+    if actor.in_bn is not None:
+        members = list(actor.in_bn) if actor.per_agent else [actor.in_bn]
+        bns = (FgActorInBn * len(members))(*[actor_in_bn(m) for m in members])
+    return fas, norm, gru, bns
+
+
 class FgActorOu(ctypes.Structure):
     """Mirror of `struct FgActorOu` (include/formation_hip.h): the OU exploration of fg_rollout_hd_actor_ou's actor."""
     _fields_ = [("theta", ctypes.c_float), ("mu", ctypes.c_float), ("sigma", ctypes.c_float), ("scale", ctypes.c_float),

@@ -530,8 +530,44 @@ class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members p
     actor keeps no state), whose body is then `members[0]` with `norms` and whose head is w3, b3.  `in_bn`: the eval-mode
     input BatchNorm in front of the plain body - the (running_mean, running_var, weight, bias, eps) tuple (ActorInBn) of a
     shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own.  `ou`: the
-    OUNoiseActor whose exploration runs on top of the actor (None: none) - the module itself, whose scalars every launch reads."""
+    OUNoiseActor whose exploration runs on top of the actor (None: none) - the module itself, whose scalars every launch reads.
+    `tensors()` and `binding_key()` are the one statement of what a launch reads by address: a binder keeps the first alive
+    and a launcher cache keys on the second, so a new field is added to `_slots` and nowhere else."""
     __slots__ = ()
+
+    def _in_bns(self):
+        """The ActorInBn tuples, one per member: () without an input BatchNorm."""
+        return () if self.in_bn is None else tuple(self.in_bn) if self.per_agent else (self.in_bn,)
+
+    def _slots(self):
+        """Every tensor position of the record in a fixed order - the members' weights and biases, log_std, the norms' weight and
+        bias, the GRU's four tensors and its norm's two, every input BatchNorm's four - with None where the actor has none."""
+        slots = [t for ws in self.members for t in ws]
+        slots.append(self.log_std)
+        if self.norms is not None:
+            for n in self.norms:
+                slots += (None, None) if n is None else n[:2]
+        if self.gru is not None:
+            slots += self.gru[:4] + self.gru.norm[:2]
+        if self.in_bn is not None:
+            for bn in self._in_bns():
+                slots += bn[:4]
+        return slots
+
+    def tensors(self):
+        """Every tensor the launch reads in place (`_slots` without the Nones): what a bound launcher must keep alive."""
+        return tuple(t for t in self._slots() if t is not None)
+
+    def binding_key(self):
+        """What tells one binding of the record from another: the addresses of `_slots` (None kept in its place), the shape
+        facts, every eps - baked into the launch's structs - and the identity of the OUNoiseActor, whose scalars are read anew
+        per launch.  Equal for two resolutions of an unchanged module; a parameter re-allocated changes it."""
+        eps = None                                         # the plain body has none
+        if self.norms is not None or self.gru is not None or self.in_bn is not None:
+            eps = (None if self.norms is None else tuple([None if n is None else n[2] for n in self.norms]),
+                   None if self.gru is None else self.gru.norm[2], tuple([bn[4] for bn in self._in_bns()]))
+        return (self.hidden, self.out_tanh, self.per_agent, tuple([t if t is None else t.data_ptr() for t in self._slots()]),
+                eps, id(self.ou))
 
 
 def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,

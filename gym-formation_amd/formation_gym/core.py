@@ -422,6 +422,9 @@ class World(_Tracked):
             p.rng_offset_dev = counter.data_ptr()
         if hetero:
             p.agent_props = props.data_ptr()
+        # the struct holds these two by address only: whoever keeps p (every bound launch does) keeps the tensors, so that a
+        # binding re-selected after agent_props() has replaced its table never reads a freed block
+        p._pinned = (counter, props if hetero else None)
         for k, w in enumerate(self.walls):
             p.walls[k] = _native.FgWall(vertical=0 if w.orient == "H" else 1, axis_pos=float(w.axis_pos),
                                         end0=float(w.endpoints[0]), end1=float(w.endpoints[1]),

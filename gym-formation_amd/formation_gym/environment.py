@@ -200,87 +200,134 @@ class MultiAgentEnv(object):
         if roll is None or self.post_step_callback is not None:
             # no multi-step launch (a reference-style Scenario file: its callbacks run on the host), or a post_step_callback
             # (environment.py:140-141: a host function after every step): K `step` calls behind the same interface
-            return self._rollout_by_steps(action_seq, out, int(obs_every))
+            return self._rollout_by_steps(action_seq, out, obs_every)
         mode = self._action_mode()
         if mode:
             # the discrete action modes of _set_action (environment.py:194-215): the whole sequence is decoded to raw u in
             # ONE launch (`fg_decode_actions` over K B N entries), then the K steps run as for continuous actions
             act = self._decode_action_seq(action_seq, mode)
-            K = int(act.shape[0])
         else:
             if not torch.is_tensor(action_seq) or action_seq.dim() != 4 or tuple(action_seq.shape[1:]) != tuple(self._act.shape):
                 raise ValueError("action_seq must be a tensor of shape [K, %d, %d, 2]" % tuple(self._act.shape[:2]))
-            K = int(action_seq.shape[0])
             act = action_seq
             if act.dtype != torch.float32 or act.device != self._act.device or not act.is_contiguous():
                 act = act.to(device=self._act.device, dtype=torch.float32).contiguous()
-        obs_every = int(obs_every)
+        K, obs_every = self._check_steps(act.shape[0], obs_every)
+        want = self._rollout_shapes(K, obs_every)
+        out, own_buffers = self._rollout_out(want, out, K, obs_every, False, obs_dtype)
+        self._run_rollout(("roll", act.data_ptr(), K), want, out, own_buffers, K, obs_every, obs_dtype,
+                          getattr(self.scenario, "bind_rollout", None), roll, (act,))
+        return self._rollout_result(out)
+
+    # ---- the one path of the three K-step launches: rollout, rollout_policy, rollout_actor --------------------------------
+    @staticmethod
+    def _check_steps(K, obs_every):
+        """(K, obs_every) as ints: at least one step, and an observation every `obs_every` >= 1 steps."""
+        K, obs_every = int(K), int(obs_every)
         if K < 1 or obs_every < 1:
             raise ValueError("need K >= 1 steps and obs_every >= 1")
+        return K, obs_every
+
+    def _rollout_shapes(self, K, obs_every, act=False, log_prob=False, rnn_states=None):
+        """The shapes of a K-step launch's outputs by key of `out`: obs, reward, indiv and done always; `act` (the closed
+        loops' actions), `log_prob` (a Gaussian actor's) and `rnn_states` (that shape: the kept hidden states) on request."""
         B, N = self.num_envs, self.num_agents
-        D = self._out["obs"].shape[-1]
-        if out is None:
-            out = self._default_out(K, obs_every, False) if self.default_placed and not fmt else False
-        own_buffers = out is not False
-        if out is False:
-            f = dict(dtype=torch.float32, device=self._act.device)
-            out = dict(obs=torch.empty((K // obs_every, B, N, D), dtype=obs_dtype or torch.float32, device=self._act.device),
-                       reward=torch.empty((K, B, N), **f),
-                       indiv=torch.empty((K, B, N), **f),
-                       done=torch.zeros((K, B, N), dtype=torch.uint8, device=self._act.device))
-        # launches into CALLER-OWNED buffers are bound once per (actions, buffers, stream, constants): a training
-        # loop that re-uses its buffers pays one ctypes call per launch (cf. _bound_step).  A binding keeps its
-        # tensors alive (their addresses are baked in), so the cache is small and skips internally allocated outputs.
-        bind = getattr(self.scenario, "bind_rollout", None)
+        want = dict(obs=(K // obs_every, B, N, self._out["obs"].shape[-1]), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
+        if act:
+            want["act"] = (K, B, N, 2)
+        if log_prob:
+            want["log_prob"] = (K, B, N)
+        if rnn_states is not None:
+            want["rnn_states"] = tuple(rnn_states)
+        return want
+
+    def _rollout_out(self, want, out, K, obs_every, policy, obs_dtype=None):
+        """(`out` resolved, whether its launch may be cached).  None: the env's placed buffers of this shape (`_default_out`)
+        while `default_placed` is set and no 16-bit format is asked for, else as False; the optional tensors (log_prob,
+        rnn_states) are kept with them, under the same aliasing rule - another rnn_states shape replaces the kept one.  False:
+        fresh tensors per call, never cached.  A caller's dict: itself; one without an optional tensor gets a fresh one in a
+        copy, and that call is not cached."""
+        placed = out is None and self.default_placed and obs_dtype is None
+        if placed:
+            out = self._default_out(K, obs_every, policy)
+        elif out is None or out is False:
+            return {k: self._fresh_out(k, want[k], obs_dtype) for k in want}, False
+        own_buffers = True
+        for k in ("log_prob", "rnn_states"):
+            if k not in want:
+                continue
+            if placed and tuple(getattr(out.get(k), "shape", ())) != want[k]:
+                out[k] = self._fresh_out(k, want[k])
+            elif k not in out:
+                out, own_buffers = dict(out, **{k: self._fresh_out(k, want[k])}), False
+            elif k == "rnn_states":
+                self._state_tensor("out['rnn_states']", out[k], want[k], None)
+        return out, own_buffers
+
+    def _fresh_out(self, k, shape, obs_dtype=None):
+        """A new tensor for key `k` of `out`: done as zeroed bytes, obs in `obs_dtype` if given, everything else fp32."""
+        if k == "done":
+            return torch.zeros(shape, dtype=torch.uint8, device=self._act.device)
+        return torch.empty(shape, dtype=(obs_dtype or torch.float32) if k == "obs" else torch.float32, device=self._act.device)
+
+    def _run_rollout(self, lead_key, want, out, own_buffers, K, obs_every, obs_dtype, bind, unbound, args, extra=()):
+        """One K-step launch into `out`, and the env's bookkeeping after it.  Launches into CALLER-OWNED (or env-owned, placed)
+        buffers are bound once per (`lead_key`: what the launch reads besides - actions, weights, states -, buffers, stream,
+        constants): a training loop that re-uses its buffers pays one dict lookup and one ctypes call per launch (cf.
+        _bound_step).  A binding keeps its tensors alive (their addresses are baked in), so the cache is small - cleared when
+        it holds 8 - and skips internally allocated outputs.  `bind(world, *args, out, ...)` is the scenario's `bind_*`
+        (None: it has none), `unbound` its launch-at-once twin for what is not cached (None: bind anyway); `extra`: further
+        keywords of `bind`.  `out` is checked against `want` when a launch is bound or runs unbound, not on a cache hit."""
         key = None
-        if own_buffers and bind is not None and all(k in out for k in ("obs", "reward", "indiv", "done")):
-            key = ("roll", act.data_ptr(), K, out["obs"].data_ptr(), tuple(out["obs"].stride()), out["reward"].data_ptr(),
-                   out["indiv"].data_ptr(), out["done"].data_ptr(), obs_every, self.auto_reset,
-                   _native.current_stream_fast(self.world.device),
-                   self.world.params_signature(), getattr(self.scenario, "_seed", 0), obs_dtype)
+        if own_buffers and bind is not None and want.keys() <= out.keys():
+            key = lead_key + (tuple([out[k].data_ptr() for k in want]), tuple(out["obs"].stride()), obs_every,
+                              self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
+                              getattr(self.scenario, "_seed", 0), obs_dtype)
         launch = self._roll_launchers.get(key) if key is not None else None
-        fmt_kw = dict(obs_format=fmt) if fmt else {}
+        off = self._launch_rng_offset()
         if launch is None:
-            want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
             for k, shp in want.items():
                 if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
                     raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
             self._check_obs_dtype(out, obs_dtype)
+            kw = dict(extra, obs_every=obs_every, auto_reset=self.auto_reset)
+            if obs_dtype is not None:
+                kw["obs_format"] = _native.obs_format(obs_dtype)
+            if key is not None or unbound is None:
+                launch = bind(self.world, *args, out, **kw)
             if key is not None:
                 if len(self._roll_launchers) >= 8:
                     self._roll_launchers.clear()
-                launch = self._roll_launchers[key] = bind(self.world, act, out, obs_every=obs_every,
-                                                          auto_reset=self.auto_reset, **fmt_kw)
+                self._roll_launchers[key] = launch
         if launch is not None:
-            launch(self._launch_rng_offset())
+            launch(off)
             self.scenario._cache = None
         else:
-            roll(self.world, act, out, obs_every=obs_every, auto_reset=self.auto_reset, rng_offset=self._launch_rng_offset(),
-                 **fmt_kw)
+            unbound(self.world, *args, out, rng_offset=off, **kw)
         self._advance_rng(K)
         self.current_step += K
         self.world.world_step += K
-        rew = out["reward"] if self.shared_reward else out["indiv"]
-        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), {"individual_reward": out["indiv"]}
+
+    def _rollout_result(self, out, info=(), rew=None):
+        """(obs, reward [..., 1], done as bool, info) of a K-step call from its `out`; `info`: the keys besides
+        'individual_reward'; `rew`: the per-agent reward where it is not out's (shared: out["reward"], else out["indiv"])."""
+        if rew is None:
+            rew = out["reward"] if self.shared_reward else out["indiv"]
+        info = dict(info, individual_reward=out["indiv"])
+        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
 
     def _rollout_by_steps(self, action_seq, out, obs_every):
         """`rollout` as K calls of `step` (host-paced: one launch - and whatever the scenario / the post_step_callback does on
         the host - per step), results stacked like `rollout`'s."""
-        K = int(len(action_seq))
-        if K < 1 or obs_every < 1:
-            raise ValueError("need K >= 1 steps and obs_every >= 1")
-        B, N = self.num_envs, self.num_agents
-        D = self._out["obs"].shape[-1]
+        K, obs_every = self._check_steps(len(action_seq), obs_every)
         dev = self._act.device
+        want = self._rollout_shapes(K, obs_every)
         if out is None or out is False:
-            f = dict(dtype=torch.float32, device=dev)
-            out = dict(obs=torch.empty((K // obs_every, B, N, D), **f), reward=torch.empty((K, B, N), **f),
-                       indiv=torch.empty((K, B, N), **f), done=torch.zeros((K, B, N), dtype=torch.uint8, device=dev))
-        want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
+            out = self._rollout_out(want, False, K, obs_every, False)[0]
         for k, shp in want.items():
             if k not in out or tuple(out[k].shape) != shp:
                 raise ValueError("out[%r] must be a tensor of shape %s" % (k, shp))
-        first = None if self.shared_reward else torch.empty((K, B, N), dtype=torch.float32, device=dev)
+        first = None if self.shared_reward else torch.empty(want["reward"], dtype=torch.float32, device=dev)
         for k in range(K):
             act = action_seq[k]
             if torch.is_tensor(act) and (act.dtype != torch.float32 or act.device != dev) and not self._action_mode():
@@ -292,8 +339,25 @@ class MultiAgentEnv(object):
                 first[k].copy_(r[..., 0])
             if (k + 1) % obs_every == 0:
                 out["obs"][k // obs_every].copy_(o)
-        rew = out["reward"] if self.shared_reward else first
-        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), {"individual_reward": out["indiv"]}
+        return self._rollout_result(out, rew=first)      # not shared: what `step` returned (a Scenario file's first_reward)
+
+    def _step_loop(self, K, obs_every, act_fn, after_step=None):
+        """The host-paced closed loop, K x (act = act_fn(obs, k); obs, ... = step(act); after_step(done)), from the env's
+        current observation, stacked like a K-step launch's results (fresh tensors; obs every `obs_every`-th step, an empty
+        [0, B, N, D] when there is none), the actions taken under info['actions']."""
+        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act")}
+        obs = self._out["obs"]
+        for k in range(K):
+            act = act_fn(obs, k)
+            res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
+            obs, r, d, info = self.step(act)
+            if (k + 1) % obs_every == 0:
+                res["obs"].append(obs.clone())
+            res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
+            if after_step is not None:
+                after_step(d)
+        return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
+                torch.stack(res["done"]), {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])})
 
     def rollout_policy(self, K, num_agents_per_layer=3, out=None, obs_every=1, obs_dtype=None):
         """The reference's demo loop (test.py:17-27) for K steps in one call:
@@ -315,66 +379,14 @@ class MultiAgentEnv(object):
         if self.post_step_callback is not None:
             # a host function after every step (environment.py:140-141): the demo loop itself, launch by launch
             from .policy_bfs import ezpolicy, get_action_BFS
-            if K < 1 or obs_every < 1:
-                raise ValueError("need K >= 1 steps and obs_every >= 1")
-            acts = torch.empty((K,) + tuple(self._act.shape), dtype=torch.float32, device=self._act.device)
-            res = {k: [] for k in ("obs", "rew", "done", "indiv")}
-            obs = self._out["obs"]
-            for k in range(K):
-                acts[k].copy_(get_action_BFS(ezpolicy, obs, int(num_agents_per_layer)))
-                obs, r, d, info = self.step(acts[k])
-                if (k + 1) % obs_every == 0:
-                    res["obs"].append(obs.clone())
-                res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
-            return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
-                    torch.stack(res["done"]), {"individual_reward": torch.stack(res["indiv"]), "actions": acts})
-        if K < 1 or obs_every < 1:
-            raise ValueError("need K >= 1 steps and obs_every >= 1")
-        B, N = self.num_envs, self.num_agents
-        D = self._out["obs"].shape[-1]
-        f = dict(dtype=torch.float32, device=self._act.device)
-        want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
-        if out is None:
-            out = self._default_out(K, obs_every, True) if self.default_placed and not fmt else False
-        own_buffers = out is not False
-        if out is False:
-            out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
-                       else torch.empty(shp, **f)) for k, shp in want.items()}
-            if fmt:
-                out["obs"] = torch.empty(want["obs"], dtype=obs_dtype, device=self._act.device)
-        # launches into CALLER-OWNED buffers are bound once (cf. rollout): a loop that steps K = 1 at a time pays one
-        # ctypes call per launch
-        bind = getattr(self.scenario, "bind_rollout_policy", None)
-        key = None
-        if own_buffers and bind is not None and all(k in out for k in want):
-            key = ("pol", K, int(num_agents_per_layer), tuple(out[k].data_ptr() for k in sorted(want)),
-                   tuple(out["obs"].stride()), obs_every,
-                   self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
-                   getattr(self.scenario, "_seed", 0), obs_dtype)
-        launch = self._roll_launchers.get(key) if key is not None else None
-        fmt_kw = dict(obs_format=fmt) if fmt else {}
-        if launch is None:
-            for k, shp in want.items():
-                if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
-                    raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
-            self._check_obs_dtype(out, obs_dtype)
-            if key is not None:
-                if len(self._roll_launchers) >= 8:
-                    self._roll_launchers.clear()
-                launch = self._roll_launchers[key] = bind(self.world, K, num_agents_per_layer, out, obs_every=obs_every,
-                                                          auto_reset=self.auto_reset, **fmt_kw)
-        if launch is not None:
-            launch(self._launch_rng_offset())
-            self.scenario._cache = None
-        else:
-            roll(self.world, K, num_agents_per_layer, out, obs_every=obs_every, auto_reset=self.auto_reset,
-                 rng_offset=self._launch_rng_offset(), **fmt_kw)
-        self._advance_rng(K)
-        self.current_step += K
-        self.world.world_step += K
-        rew = out["reward"] if self.shared_reward else out["indiv"]
-        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), \
-            {"individual_reward": out["indiv"], "actions": out["act"]}
+            K, obs_every = self._check_steps(K, obs_every)
+            return self._step_loop(K, obs_every, lambda obs, k: get_action_BFS(ezpolicy, obs, int(num_agents_per_layer)).float())
+        K, obs_every = self._check_steps(K, obs_every)
+        want = self._rollout_shapes(K, obs_every, act=True)
+        out, own_buffers = self._rollout_out(want, out, K, obs_every, True, obs_dtype)
+        self._run_rollout(("pol", K, int(num_agents_per_layer)), want, out, own_buffers, K, obs_every, obs_dtype,
+                          getattr(self.scenario, "bind_rollout_policy", None), roll, (K, num_agents_per_layer))
+        return self._rollout_result(out, {"actions": out["act"]})
 
     def obs_path(self, obs_dtype, policy=False):
         """How `rollout(..., obs_dtype=obs_dtype)` (policy=True: `rollout_policy`, 3 agents per layer) produces its 16-bit
@@ -528,9 +540,8 @@ class MultiAgentEnv(object):
         the shape overwrites it - and out=False gives a fresh one per call.  With an actor that keeps no state: ValueError."""
         if self._action_mode():
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
-        K, obs_every = int(K), int(obs_every)
-        if K < 1 or obs_every < 1:
-            raise ValueError("need K >= 1 steps and obs_every >= 1")
+        K, obs_every = self._check_steps(K, obs_every)
+        B, N = self.num_envs, self.num_agents
         recurrent = actor_rollout.recurrent_mean(actor)
         if recurrent is None and rnn_state is not None:
             raise ValueError("rnn_state given, but the actor is not a RecurrentActor (nor a GaussianActor with one as its mean)")
@@ -540,133 +551,56 @@ class MultiAgentEnv(object):
         ou = actor if isinstance(actor, actor_rollout.OUNoiseActor) else None
         if ou is None and noise_state is not None:
             raise ValueError("noise_state given, but the actor is not an OUNoiseActor")
-        if ou is not None:
-            noise_state = self._noise_state(ou, noise_state)
+        if ou is not None:                                 # None: a fresh `initial_state`
+            noise_state = self._state_tensor("noise_state", noise_state, (B, N, 2),
+                                             lambda: ou.initial_state(B, N, device=self.world.device))
         S = None
         if rnn_states_every is not None:
             if isinstance(rnn_states_every, bool) or not isinstance(rnn_states_every, numbers.Integral) or rnn_states_every < 1:
                 raise ValueError("rnn_states_every must be an integer >= 1 (or None)")
             S = int(rnn_states_every)
-        if recurrent is not None:
-            rnn_state = self._rnn_state(recurrent, rnn_state)
+        if recurrent is not None:                          # None: fresh zeros
+            shape = (B, N, recurrent.state_size)
+            rnn_state = self._state_tensor("rnn_state", rnn_state, shape,
+                                           lambda: torch.zeros(shape, dtype=torch.float32, device=self.world.device))
         states_shape = None if S is None else ((K + S - 1) // S,) + tuple(rnn_state.shape)
         fused = self._resolve_actor(actor)
         if fused is None:
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
-                self._check_rnn_states(out["rnn_states"], states_shape)
+                self._state_tensor("out['rnn_states']", out["rnn_states"], states_shape, None)
             res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S, noise_state)
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 res[3]["rnn_states"] = out["rnn_states"].copy_(res[3]["rnn_states"])
             return res
-        log_std = fused.log_std
-        gaussian = log_std is not None
-        B, N = self.num_envs, self.num_agents
-        D = self._out["obs"].shape[-1]
-        f = dict(dtype=torch.float32, device=self._act.device)
-        want = dict(obs=(K // obs_every, B, N, D), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N), act=(K, B, N, 2))
-        if gaussian:
-            want["log_prob"] = (K, B, N)
-        if S is not None:
-            want["rnn_states"] = states_shape
-        if out is None:
-            out = self._default_out(K, obs_every, True) if self.default_placed else False
-            if gaussian and out is not False and "log_prob" not in out:
-                out["log_prob"] = torch.empty(want["log_prob"], **f)     # kept with this shape's buffers, same aliasing
-            if S is not None and out is not False and tuple(getattr(out.get("rnn_states"), "shape", ())) != states_shape:
-                out["rnn_states"] = torch.empty(states_shape, **f)       # likewise; another S or state width replaces it
-        own_buffers = out is not False
-        if out is False:
-            out = {k: (torch.zeros(shp, dtype=torch.uint8, device=self._act.device) if k == "done"
-                       else torch.empty(shp, **f)) for k, shp in want.items()}
-        elif gaussian and "log_prob" not in out:                        # the caller's buffers without one: a fresh one
-            out = dict(out, log_prob=torch.empty(want["log_prob"], **f))
-            own_buffers = False
-        if S is not None and "rnn_states" not in out:
-            out = dict(out, rnn_states=torch.empty(states_shape, **f))
-            own_buffers = False
-        elif S is not None:
-            self._check_rnn_states(out["rnn_states"], states_shape)
-        # bound once per (buffers, weights, stream, constants), like rollout_policy: the binding holds the parameter tensors'
-        # addresses, so it keys on them and keeps them alive - a parameter re-allocated (not updated in place) binds anew
-        key = None
-        if own_buffers and all(k in out for k in want):
-            key = ("actor", K, fused.hidden, fused.out_tanh, fused.per_agent,
-                   tuple(0 if t is None else t.data_ptr() for ws in fused.members for t in ws),
-                   0 if log_std is None else log_std.data_ptr(),
-                   None if fused.norms is None else tuple(
-                       None if n is None else (_native.ptr(n[0]), _native.ptr(n[1]), n[2]) for n in fused.norms),
-                   None if fused.gru is None else tuple(_native.ptr(t) for t in fused.gru[:4] + fused.gru.norm[:2])
-                   + (fused.gru.norm[2], rnn_state.data_ptr()), S,
-                   None if fused.in_bn is None else tuple(
-                       tuple(_native.ptr(t) for t in bn[:4]) + (bn[4],)
-                       for bn in (fused.in_bn if fused.per_agent else [fused.in_bn])),
-                   None if fused.ou is None else (id(fused.ou), noise_state.data_ptr()),
-                   tuple(out[k].data_ptr() for k in sorted(want)), tuple(out["obs"].stride()), obs_every,
-                   self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
-                   getattr(self.scenario, "_seed", 0))
-        launch = self._roll_launchers.get(key) if key is not None else None
-        if launch is None:
-            for k, shp in want.items():
-                if k not in out or tuple(out[k].shape) != shp or not (out[k].is_contiguous() or k == "obs"):
-                    raise ValueError("out[%r] must be a contiguous tensor of shape %s" % (k, shp))   # obs: or a padded env pitch
-            extra = {} if fused.gru is None else {"rnn_state": rnn_state}
-            if S is not None:
-                extra["rnn_states_every"] = S
-            if fused.ou is not None:
-                extra["noise_state"] = noise_state
-            launch = self.scenario.bind_rollout_actor(self.world, K, fused, out, obs_every=obs_every,
-                                                      auto_reset=self.auto_reset, **extra)
-            if key is not None:
-                if len(self._roll_launchers) >= 8:
-                    self._roll_launchers.clear()
-                self._roll_launchers[key] = launch
-        launch(self._launch_rng_offset())
-        self.scenario._cache = None
-        self._advance_rng(K)
-        self.current_step += K
-        self.world.world_step += K
-        rew = out["reward"] if self.shared_reward else out["indiv"]
-        info = {"individual_reward": out["indiv"], "actions": out["act"]}
-        if gaussian:
+        want = self._rollout_shapes(K, obs_every, act=True, log_prob=fused.log_std is not None, rnn_states=states_shape)
+        out, own_buffers = self._rollout_out(want, out, K, obs_every, True)
+        # what the launch reads in place besides `out`, by name for the binder and by address for the key: the binding holds
+        # the parameter tensors' addresses, so it keys on them (`binding_key`) and keeps them alive - a parameter re-allocated
+        # (not updated in place) binds anew
+        state = {} if fused.gru is None else {"rnn_state": rnn_state}
+        if fused.ou is not None:
+            state["noise_state"] = noise_state
+        self._run_rollout(("actor", K, fused.binding_key(), _native.ptr(rnn_state), S, _native.ptr(noise_state)), want, out,
+                          own_buffers, K, obs_every, None, self.scenario.bind_rollout_actor, None, (K, fused),
+                          state if S is None else dict(state, rnn_states_every=S))
+        info = dict(state, actions=out["act"])             # the states come back as updated in place
+        if "log_prob" in want:
             info["log_prob"] = out["log_prob"]
-        if fused.gru is not None:
-            info["rnn_state"] = rnn_state
         if S is not None:
             info["rnn_states"] = out["rnn_states"]
-        if fused.ou is not None:
-            info["noise_state"] = noise_state
-        return out["obs"], rew.unsqueeze(-1), out["done"].view(torch.bool), info
+        return self._rollout_result(out, info)
 
-    def _check_rnn_states(self, t, shape):
-        """out['rnn_states'] as `rollout_actor(rnn_states_every=S)` takes it: contiguous fp32 of `shape` on the env's device."""
-        dev = self.world.device
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() \
+    def _state_tensor(self, name, t, shape, fresh):
+        """A state tensor a launch reads and writes in place - `rnn_state`, `noise_state`, out['rnn_states'] - as the caller
+        passed it: `fresh()` for None (where there is a `fresh`), else `t` itself, checked to be contiguous fp32 of `shape` on
+        the env's device."""
+        if t is None and fresh is not None:
+            return fresh()
+        shape, dev = tuple(shape), self.world.device
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
                 or not actor_rollout._on_device(t, dev):
-            raise ValueError("out[%r] must be a contiguous float32 tensor of shape %s on %s" % ("rnn_states", tuple(shape), dev))
-
-    def _rnn_state(self, recurrent, rnn_state):
-        """The hidden state `rollout_actor` runs the RecurrentActor `recurrent` with: the caller's tensor, checked - contiguous
-        fp32 [B, N, H] on the env's device - or, for None, fresh zeros."""
-        shape = (self.num_envs, self.num_agents, recurrent.state_size)
-        dev = self.world.device
-        if rnn_state is None:
-            return torch.zeros(shape, dtype=torch.float32, device=dev)
-        if not torch.is_tensor(rnn_state) or rnn_state.dtype != torch.float32 or tuple(rnn_state.shape) != shape \
-                or not rnn_state.is_contiguous() or not actor_rollout._on_device(rnn_state, dev):
-            raise ValueError("rnn_state must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
-        return rnn_state
-
-    def _noise_state(self, ou, noise_state):
-        """The OU state `rollout_actor` runs the OUNoiseActor `ou` with: the caller's tensor, checked - contiguous fp32
-        [B, N, 2] on the env's device - or, for None, a fresh `initial_state`."""
-        shape = (self.num_envs, self.num_agents, 2)
-        dev = self.world.device
-        if noise_state is None:
-            return ou.initial_state(*shape[:2], device=dev)
-        if not torch.is_tensor(noise_state) or noise_state.dtype != torch.float32 or tuple(noise_state.shape) != shape \
-                or not noise_state.is_contiguous() or not actor_rollout._on_device(noise_state, dev):
-            raise ValueError("noise_state must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
-        return noise_state
+            raise ValueError("%s must be a contiguous float32 tensor of shape %s on %s" % (name, shape, dev))
+        return t
 
     def _ou_step(self, ou, eps, x):
         """x <- x + theta * (mu - x) + sigma * eps in place (`fg_actor_ou_step`: the fused kernels' device function)."""
@@ -708,55 +642,56 @@ class MultiAgentEnv(object):
         ou = actor if noise_state is not None else None
         x = noise_state.clone() if ou is not None else None
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
-        recurrent = rnn_state is not None
-        h = rnn_state.clone() if recurrent else None
+        body = actor.mean if gaussian else actor
+        h = rnn_state.clone() if rnn_state is not None else None
+        logp, states = [], []
         observe = getattr(self.scenario, "observe_batch", None)
         if observe is not None:                            # the observation of the current state (a multi-step launch
             observe(self.world, {"obs": self._out["obs"]})  # leaves the env's own step buffer behind)
-        obs = self._out["obs"]
-        res = {k: [] for k in ("obs", "rew", "done", "indiv", "act", "logp", "states")}
-        with torch.no_grad():
-            for k in range(K):
-                if rnn_states_every is not None and k % rnn_states_every == 0:
-                    res["states"].append(h.clone())
-                if gaussian:
-                    eps = self.actor_noise()
-                    ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
-                    if recurrent:
-                        mu, h = actor.mean(obs, h)
-                    else:
-                        mu = actor.mean(obs)
-                    act = mu + torch.exp(ls) * eps
-                    res["logp"].append(self._noise_log_prob(eps, ls))
-                elif recurrent:
-                    act, h = actor(obs, h)
-                elif ou is not None:
-                    self._ou_step(ou, self.actor_noise(), x)
-                    act = ou.explore(ou.actor(obs), x)
-                else:
-                    act = actor(obs)
-                res["act"].append(act.clone() if torch.is_tensor(act) else torch.as_tensor(act, device=self._act.device))
-                obs, r, d, info = self.step(act)
-                if (k + 1) % obs_every == 0:
-                    res["obs"].append(obs.clone())
-                res["rew"].append(r.clone()); res["done"].append(d.clone()); res["indiv"].append(info["individual_reward"].clone())
-                if ou is not None:
-                    ou.reset(x, torch.as_tensor(d, device=x.device).view(torch.bool).reshape(x.shape[:-1]))
-                if recurrent:
-                    h = h * (~torch.as_tensor(d, device=h.device).view(torch.bool).reshape(h.shape[:-1] + (1,))).to(h.dtype)
-        info = {"individual_reward": torch.stack(res["indiv"]), "actions": torch.stack(res["act"])}
+
+        def mean(obs, k):                                  # a recurrent body: h goes through, a copy kept every S-th step
+            nonlocal h
+            if rnn_states_every is not None and k % rnn_states_every == 0:
+                states.append(h.clone())
+            act, h = body(obs, h)
+            return act
+
+        def sample(obs, k):                                # a GaussianActor on either body
+            eps = self.actor_noise()
+            ls = actor.log_std.detach().to(device=eps.device, dtype=torch.float32)
+            logp.append(self._noise_log_prob(eps, ls))
+            return (body(obs) if h is None else mean(obs, k)) + torch.exp(ls) * eps
+
+        def explore(obs, k):                               # an OUNoiseActor
+            self._ou_step(ou, self.actor_noise(), x)
+            return ou.explore(ou.actor(obs), x)
+
+        def after_step(d):                                 # an episode's end resets the states, with or without auto_reset
+            nonlocal h
+            if ou is not None:
+                ou.reset(x, torch.as_tensor(d, device=x.device).view(torch.bool).reshape(x.shape[:-1]))
+            if h is not None:
+                h = h * (~torch.as_tensor(d, device=h.device).view(torch.bool).reshape(h.shape[:-1] + (1,))).to(h.dtype)
+
         if gaussian:
-            info["log_prob"] = torch.stack(res["logp"])
-        if recurrent:
+            act_fn = sample
+        elif h is not None:
+            act_fn = mean
+        else:
+            act_fn = explore if ou is not None else lambda obs, k: actor(obs)
+        with torch.no_grad():
+            obs, rew, done, info = self._step_loop(K, obs_every, act_fn, after_step)
+        if gaussian:
+            info["log_prob"] = torch.stack(logp)
+        if h is not None:
             rnn_state.copy_(h)
             info["rnn_state"] = rnn_state
         if rnn_states_every is not None:
-            info["rnn_states"] = torch.stack(res["states"])
+            info["rnn_states"] = torch.stack(states)
         if ou is not None:
             noise_state.copy_(x)
             info["noise_state"] = noise_state
-        return (torch.stack(res["obs"]) if res["obs"] else obs.new_empty((0,) + tuple(obs.shape)), torch.stack(res["rew"]),
-                torch.stack(res["done"]), info)
+        return obs, rew, done, info
 
     # ------------------------------------------------------------ buffers
     def _default_out(self, K, obs_every, policy):

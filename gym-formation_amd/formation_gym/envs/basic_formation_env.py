@@ -103,17 +103,8 @@ class Scenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
                 act.data_ptr(), world.landmark_pos.data_ptr(), world.step_count.data_ptr(),
                 out["obs"].data_ptr(), _native.ptr(out.get("reward")), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), _native.ptr(out.get("near_ag")), _native.current_stream(world.device))
-        fn = lib.fg_step_basic
-        keep = (act, out)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, *args)
-            if rc:
-                _native.check(rc)
-            return keep
         self._cache = None
-        return launch
+        return _native.bind_launch(lib.fg_step_basic, p, *args, keep=(act, out))
 
     def step_batch(self, world, act, out, auto_reset=False, rng_offset=0):
         """auto_reset: envs whose episode ends restart inside the launch (device counter RNG; the reset observation comes
@@ -136,8 +127,7 @@ class Scenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
 
     def rollout_batch(self, world, act_seq, out, obs_every=1, auto_reset=False, rng_offset=0):
         """K steps in one launch (`fg_rollout_scenario`); act_seq [K,B,N,2], out tensors carry a leading K."""
-        _native.check(_native.load().fg_rollout_scenario(self.params(world, rng_offset, auto_reset), self._descriptor(world),
-                                                         *self._rollout_args(world, act_seq, out, obs_every)))
+        self.bind_rollout(world, act_seq, out, obs_every, auto_reset)(rng_offset)
         self._cache = None
 
     def bind_rollout(self, world, act_seq, out, obs_every=1, auto_reset=False):

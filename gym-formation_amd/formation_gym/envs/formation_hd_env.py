@@ -131,7 +131,9 @@ class Scenario(BaseScenario):
             if world.dim_c != 2:
                 raise NotImplementedError("formation_hd_env's observation has a communication block of dim_c = 2 (:40, :48-51); "
                                           "World.step / update_agent_state take any dim_c")
-            p.comm_state = world.ensure_comm()[0].data_ptr()
+            comm = world.ensure_comm()[0]
+            p.comm_state = comm.data_ptr()
+            p._pinned += (comm,)                          # as native_params pins its own: whoever keeps p keeps the tensor
         if obs is not None and obs.numel() and placement.is_placed(obs.data_ptr()):
             p.obs_placed = 1                              # a buffer of chunks spread over the device memory: more writer waves pay
         return p
@@ -163,16 +165,26 @@ class Scenario(BaseScenario):
             return 0
         return int(pitch)
 
+    def _state_ptrs(self, world, act):
+        """The world state as every step / rollout entry takes it, the action (sequence) tensor `act` in its place."""
+        return (world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                act.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(), world.step_count.data_ptr())
+
+    @staticmethod
+    def _out_ptrs(out):
+        """The outputs every step / rollout entry writes, in the entries' order (the reward alone is required)."""
+        return (_native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
+                _native.ptr(out.get("done")))
+
+    def _step_args(self, world, act, out):
+        """The arguments of `fg_step_hd` / `fg_step_hd_plan` after the FgParams struct."""
+        return (world.num_envs, len(world.agents)) + self._state_ptrs(world, act) + self._out_ptrs(out) + (
+            _native.ptr(out.get("near_lm")), _native.ptr(out.get("near_ag")), _native.ptr(out.get("hd_idx")),
+            _native.current_stream(world.device))
+
     def step_batch(self, world, act, out, auto_reset=False, rng_offset=0):
-        lib = _native.load()
-        _native.check(lib.fg_step_hd(
-            self.params(world, auto_reset, rng_offset, out.get("obs")), world.num_envs, len(world.agents),
-            world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-            act.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-            world.step_count.data_ptr(),
-            out["obs"].data_ptr(), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-            _native.ptr(out.get("done")), _native.ptr(out.get("near_lm")), _native.ptr(out.get("near_ag")),
-            _native.ptr(out.get("hd_idx")), _native.current_stream(world.device)))
+        _native.check(_native.load().fg_step_hd(self.params(world, auto_reset, rng_offset, out.get("obs")),
+                                                *self._step_args(world, act, out)))
         self._cache = out
 
     def bind_step(self, world, act, out, auto_reset=False):
@@ -180,13 +192,7 @@ class Scenario(BaseScenario):
         host work is one ctypes call (rollout loops, bench.py)."""
         lib = _native.load()
         p = self.params(world, auto_reset, 0, out.get("obs"))
-        args = (world.num_envs, len(world.agents),
-                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                act.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                world.step_count.data_ptr(),
-                out["obs"].data_ptr(), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                _native.ptr(out.get("done")), _native.ptr(out.get("near_lm")), _native.ptr(out.get("near_ag")),
-                _native.ptr(out.get("hd_idx")), _native.current_stream(world.device))
+        args = self._step_args(world, act, out)
         # the checked launch description is kept by the library (fg_step_hd_plan): a step is a two-argument call
         handle = ctypes.c_void_p()
         _native.check(lib.fg_step_hd_plan(p, *args, ctypes.byref(handle)))
@@ -234,30 +240,13 @@ class Scenario(BaseScenario):
     def rollout_batch(self, world, act_seq, out, obs_every=1, auto_reset=False, rng_offset=0, obs_format=0):
         """K steps in one launch; act_seq [K,B,N,2], out tensors carry a leading K.  obs_format (_native.FG_OBS_F16 / _BF16):
         out["obs"] is a contiguous tensor of that 16-bit dtype, written by the launch itself (`fg_rollout_hd_obs16`)."""
-        lib = _native.load()
-        K = act_seq.shape[0]
-        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd", obs_format)
-        _native.check(fn(
-            self.params(world, auto_reset, rng_offset, out.get("obs")), *fmt, world.num_envs, len(world.agents), K,
-            world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-            act_seq.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-            world.step_count.data_ptr(),
-            _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-            _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device)))
+        self.bind_rollout(world, act_seq, out, obs_every, auto_reset, obs_format)(rng_offset)
         self._cache = None
 
     def rollout_policy_batch(self, world, K, per_layer, out, obs_every=1, auto_reset=False, rng_offset=0, obs_format=0):
         """K closed-loop steps with the built-in controller (`fg_rollout_hd_policy`): out["act"] [K,B,N,2]
         receives the actions taken, the other tensors (and obs_format) are those of `rollout_batch`."""
-        lib = _native.load()
-        fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_policy", obs_format)
-        _native.check(fn(
-            self.params(world, auto_reset, rng_offset, out.get("obs")), *fmt, world.num_envs, len(world.agents), int(K), int(per_layer),
-            world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-            out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-            world.step_count.data_ptr(),
-            _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-            _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device)))
+        self.bind_rollout_policy(world, K, per_layer, out, obs_every, auto_reset, obs_format)(rng_offset)
         self._cache = None
 
     def bind_rollout_policy(self, world, K, per_layer, out, obs_every=1, auto_reset=False, obs_format=0):
@@ -266,12 +255,8 @@ class Scenario(BaseScenario):
         lib = _native.load()
         p = self.params(world, auto_reset, 0, out.get("obs"))
         fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_policy", obs_format)
-        args = fmt + (world.num_envs, len(world.agents), int(K), int(per_layer),
-                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                world.step_count.data_ptr(),
-                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
+        args = fmt + (world.num_envs, len(world.agents), int(K), int(per_layer)) + self._state_ptrs(world, out["act"]) \
+            + self._out_ptrs(out) + (int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(fn, p, *args, keep=out)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None,
@@ -299,21 +284,13 @@ class Scenario(BaseScenario):
                                                 before every launch, so a scale annealed between calls needs no new binding"""
         lib = _native.load()
         log_std = actor.log_std
-        norm = None if actor.norms is None else _native.actor_norm(actor.norms)
-        gru = None if actor.gru is None else _native.actor_gru(actor.gru)
+        fas, norm, gru, bns = _native.actor_structs(actor)
         if gru is not None and rnn_state is None:
             raise ValueError("a recurrent actor's launch needs its rnn_state")
         if rnn_states_every is not None and gru is None:
             raise ValueError("rnn_states_every needs a recurrent actor")
-        fas = (_native.FgActor * len(actor.members))(*[
-            _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in ws]) for ws in actor.members])
-        in_bn = actor.in_bn
-        bns = None
-        if in_bn is not None:
-            if norm is not None or gru is not None:
-                raise NotImplementedError("an input BatchNorm fuses in front of the plain body only")
-            members = list(in_bn) if actor.per_agent else [in_bn]
-            bns = (_native.FgActorInBn * len(members))(*[_native.actor_in_bn(m) for m in members])
+        if bns is not None and (norm is not None or gru is not None):
+            raise NotImplementedError("an input BatchNorm fuses in front of the plain body only")
         ou = actor.ou
         if ou is not None and (norm is not None or gru is not None or log_std is not None):
             raise NotImplementedError("OU noise fuses on a deterministic actor without LayerNorms only")
@@ -321,12 +298,7 @@ class Scenario(BaseScenario):
             raise ValueError("an OUNoiseActor's launch needs its noise_state")
         fou = None if ou is None else _native.actor_ou(ou)
         p = self.params(world, auto_reset, 0, out.get("obs"))
-        state = (world.num_envs, len(world.agents), int(K),
-                 world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                 out["act"].data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                 world.step_count.data_ptr(),
-                 _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                 _native.ptr(out.get("done")))
+        state = (world.num_envs, len(world.agents), int(K)) + self._state_ptrs(world, out["act"]) + self._out_ptrs(out)
         tail = (int(obs_every), _native.current_stream(world.device))
         if (gru is not None and norm is None) or (norm is not None and actor.per_agent):
             raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
@@ -351,8 +323,7 @@ class Scenario(BaseScenario):
             hidden += (out["rnn_states"].data_ptr(), int(rnn_states_every))
         args = lead + state + logp + hidden + tail
         launch = _native.bind_launch(getattr(lib, entry), p, *args,
-                                     keep=(out, tuple(tuple(ws) for ws in actor.members), fas, log_std, actor.norms, norm,
-                                           actor.gru, gru, rnn_state, in_bn, bns, fou, noise_state))
+                                     keep=(out, actor.tensors(), fas, norm, gru, bns, fou, rnn_state, noise_state))
         if ou is None:
             return launch
 
@@ -380,12 +351,8 @@ class Scenario(BaseScenario):
         lib = _native.load()
         p = self.params(world, auto_reset, 0, out.get("obs"))
         fn, fmt = self._rollout_entry(lib, "fg_rollout_hd", obs_format)
-        args = fmt + (world.num_envs, len(world.agents), int(act_seq.shape[0]),
-                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
-                act_seq.data_ptr(), self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(),
-                world.step_count.data_ptr(),
-                _native.ptr(out.get("obs")), out["reward"].data_ptr(), _native.ptr(out.get("indiv")),
-                _native.ptr(out.get("done")), int(obs_every), _native.current_stream(world.device))
+        args = fmt + (world.num_envs, len(world.agents), int(act_seq.shape[0])) + self._state_ptrs(world, act_seq) \
+            + self._out_ptrs(out) + (int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(fn, p, *args, keep=(act_seq, out))
 
     def upload_mt_streams(self, world):

@@ -108,14 +108,13 @@ class ActorRolloutMixin(object):
             raise NotImplementedError("a BatchNorm actor has no fused launch in %s" % type(self).__name__)
         if actor.ou is not None:
             raise NotImplementedError("an OUNoiseActor has no fused launch in %s" % type(self).__name__)
-        weights, log_std = actor.members[0], actor.log_std
-        fa = _native.FgActor(int(actor.hidden), int(actor.out_tanh), *[_native.ptr(t) for t in weights])
+        log_std, fa = actor.log_std, _native.actor_structs(actor)[0]
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)
         # _rollout_args with the recorded actions in the place of the action sequence: (B, N, K, state ..., act, landmarks, ...)
         r = self._rollout_args(world, out["act"][:int(K)], out, obs_every)
         args = (_native.ptr(log_std),) + r[:7] + r[8:16] + \
                (r[7], None if log_std is None else out["log_prob"].data_ptr(), r[17], r[18])
-        return _native.bind_launch(fn, p, d, fa, *args, keep=(out, tuple(weights), fa, log_std))
+        return _native.bind_launch(fn, p, d, fa, *args, keep=(out, actor.tensors(), fa))
 
 
 class LandmarkScenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
@@ -252,17 +251,8 @@ class LandmarkScenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
                 world.step_count.data_ptr(),
                 out["obs"].data_ptr(), _native.ptr(out.get("reward")), _native.ptr(out.get("indiv")),
                 _native.ptr(out.get("done")), _native.current_stream(world.device))
-        fn = lib.fg_step_scenario
-        keep = (act, out)
-
-        def launch(rng_offset=0):
-            p.rng_offset = rng_offset
-            rc = fn(p, d, *args)
-            if rc:
-                _native.check(rc)
-            return keep
         self._cache = None
-        return launch
+        return _native.bind_launch(lib.fg_step_scenario, p, d, *args, keep=(act, out))
 
     def step_batch(self, world, act, out, auto_reset=False, rng_offset=0):
         """auto_reset: envs whose episode ends restart inside the launch (device counter RNG; the reset observation comes
@@ -283,8 +273,7 @@ class LandmarkScenario(MtResetMixin, ActorRolloutMixin, BaseScenario):
 
     def rollout_batch(self, world, act_seq, out, obs_every=1, auto_reset=False, rng_offset=0):
         """K steps in one launch (`fg_rollout_scenario`); act_seq [K,B,N,2], out tensors carry a leading K."""
-        _native.check(_native.load().fg_rollout_scenario(self.params(world, rng_offset, auto_reset), self.descriptor(),
-                                                         *self._rollout_args(world, act_seq, out, obs_every)))
+        self.bind_rollout(world, act_seq, out, obs_every, auto_reset)(rng_offset)
         self._cache = None
 
     def bind_rollout(self, world, act_seq, out, obs_every=1, auto_reset=False):

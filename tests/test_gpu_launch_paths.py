@@ -954,3 +954,111 @@ def test_probe_looks_at_more_memory_when_the_first_arena_gains_nothing(monkeypat
     assert len(rep["stages"]) == 1 and rep["arena_GB"] <= 2.2
     del flat
     arena.close()
+
+
+# ---- the one bound-launch path of rollout, rollout_policy and rollout_actor ----
+_RN, _RB, _RK, _REVERY = 3, 8, 3, 2        # one stored observation, K no multiple of obs_every, an episode end inside the launch
+
+
+def _small_env(**agent1):
+    import formation_gym
+    e = formation_gym.make_env("formation_hd_env", False, _RN, num_envs=_RB, device="cuda:0", episode_length=2)
+    for k, v in agent1.items():
+        setattr(e.world.agents[1], k, v)
+    e.seed(5)
+    e.reset()
+    e.auto_reset = True
+    return e
+
+
+def _small_actor(seed=0):
+    torch.manual_seed(seed)
+    nn = torch.nn
+    return nn.Sequential(nn.Linear(6 * _RN, 32), nn.ReLU(), nn.Linear(32, 32), nn.ReLU(), nn.Linear(32, 2), nn.Tanh()).to("cuda:0")
+
+
+def _flat(res):
+    """Everything a K-step call returns, by name, cloned."""
+    obs, rew, done, info = res
+    return dict({"obs": obs.clone(), "reward": rew.clone(), "done": done.clone()}, **{k: v.clone() for k, v in info.items()})
+
+
+@pytest.mark.parametrize("kind", ["rollout", "rollout_policy", "rollout_actor"])
+def test_the_three_rollouts_share_one_cache_rule(kind):
+    """A caller's `out` is bound once and re-used, every other `out` dict is one more binding, out=False and a dict that
+    lacks an optional tensor are never cached, the cache is cleared when it holds 8, and a cached launch returns the bits of an
+    uncached one from the same state."""
+    from formation_gym import GaussianActor
+    e = _small_env()
+    actor = _small_actor()
+    acts = torch.rand((_RK, _RB, _RN, 2), device="cuda:0") * 2 - 1
+
+    def call(out, actor=actor):
+        if kind == "rollout":
+            return e.rollout(acts, out=out, obs_every=_REVERY)
+        if kind == "rollout_policy":
+            return e.rollout_policy(_RK, 3, out=out, obs_every=_REVERY)
+        return e.rollout_actor(_RK, actor, out=out, obs_every=_REVERY)
+
+    def buffers():
+        return e.alloc_rollout_buffers(_RK, obs_every=_REVERY, policy=kind != "rollout")
+
+    outs = [buffers() for _ in range(9)]
+    e._roll_launchers.clear()
+    snap = e._snapshot()
+    call(outs[0])
+    assert len(e._roll_launchers) == 1
+    e._restore(snap)
+    cached = _flat(call(outs[0]))
+    assert len(e._roll_launchers) == 1
+    assert bool(cached["done"].any()) and not bool(cached["done"].all()), "no episode end inside the launch"
+    e._restore(snap)
+    fresh = _flat(call(False))
+    assert len(e._roll_launchers) == 1
+    assert sorted(fresh) == sorted(cached) and ("actions" in fresh) == (kind != "rollout")
+    assert fresh["obs"].shape[0] == _RK // _REVERY
+    for k in fresh:
+        assert torch.equal(fresh[k], cached[k]), k
+    call(outs[1])
+    assert len(e._roll_launchers) == 2
+    if kind == "rollout_actor":
+        assert "log_prob" not in outs[0]
+        info = call(outs[0], GaussianActor(actor).to("cuda:0"))[3]
+        assert info["log_prob"].shape == (_RK, _RB, _RN) and len(e._roll_launchers) == 2
+    for out in outs[2:8]:
+        call(out)
+    assert len(e._roll_launchers) == 8
+    call(outs[8])
+    assert len(e._roll_launchers) == 1
+    torch.cuda.synchronize()
+
+
+def test_a_mass_edit_and_back_reads_the_live_agent_table():
+    """Agent 1's mass A -> B -> A with bound steps and a bound rollout in every phase: the bindings of the first phase are
+    selected again in the last (the launcher caches key on the world's signature) and must read a per-agent table that is still
+    alive, not the block the second phase's table freed.  Against a fresh env of mass A in the same state."""
+    A, B_ = 2.0, 3.0
+    e = _small_env(initial_mass=A)
+    act = torch.rand((_RB, _RN, 2), device="cuda:0") * 2 - 1
+    acts = torch.rand((_RK, _RB, _RN, 2), device="cuda:0") * 2 - 1
+    out = e.alloc_rollout_buffers(_RK, obs_every=_REVERY)
+
+    def phase(env, out):
+        res = [_flat(env.step(act)), _flat(env.step(act)), _flat(env.rollout(acts, out=out, obs_every=_REVERY))]
+        return [{k: r[k] for k in ("obs", "reward", "individual_reward", "done")} for r in res]
+
+    phase(e, out)
+    assert len(e._launchers) == 1 and len(e._roll_launchers) == 1
+    e.world.agents[1].initial_mass = B_
+    phase(e, out)
+    junk = [torch.full((_RN, 8), 50.0, device="cuda:0") for _ in range(4)]      # what the allocator may put where table A was
+    e.world.agents[1].initial_mass = A
+    ref = _small_env(initial_mass=A)
+    ref._restore(e._snapshot())
+    got = phase(e, out)
+    assert len(e._launchers) == 2 and len(e._roll_launchers) == 2, "the last phase re-uses the first phase's bindings"
+    want = phase(ref, ref.alloc_rollout_buffers(_RK, obs_every=_REVERY))
+    for g, w in zip(got, want):
+        for k in w:
+            assert torch.equal(g[k], w[k]), k
+    del junk
