@@ -7,12 +7,14 @@
 //     FG_ACTOR_ABSENT              the FG_ACTOR_NO_* constants of the operands the family does not take
 //     FG_ACTOR_OUK (optional)      the name of the family's third member, the OU-noise actor: the deterministic kernel with
 //                                  `constexpr bool OU = true`, which takes `ow` (ActorOuW) after the family's operands
+//     FG_ACTOR_CATK (optional)     the name of the family's fourth member, the categorical actor: the deterministic kernel
+//                                  with `constexpr bool CAT = true`, which takes `cw` (ActorCatW) after the family's operands
 // and they are undefined again here.  Not a header: no guard.  The body stays a textual include in each kernel
 // (fg_actor_rollout_body.inc says why), so a kernel's token stream is what its hand-written wrapper was.
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, FG_ACTOR_OPERANDS) {
-    constexpr bool SAMPLE = false, OU = false, FG_ACTOR_FLAGS;
-    FG_ACTOR_ABSENT FG_ACTOR_NO_OW
+    constexpr bool SAMPLE = false, OU = false, CAT = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_OW FG_ACTOR_NO_CW
     const float* const log_std = nullptr;
     float* const logp = nullptr;
 #include "fg_actor_rollout_body.inc"
@@ -22,8 +24,8 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, F
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP(const Args a, FG_ACTOR_OPERANDS, const float* log_std,
                                                                  float* logp) {
-    constexpr bool SAMPLE = true, OU = false, FG_ACTOR_FLAGS;
-    FG_ACTOR_ABSENT FG_ACTOR_NO_OW
+    constexpr bool SAMPLE = true, OU = false, CAT = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_OW FG_ACTOR_NO_CW
 #include "fg_actor_rollout_body.inc"
 }
 
@@ -31,13 +33,26 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP(const Args a, F
 #ifdef FG_ACTOR_OUK
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_OUK(const Args a, FG_ACTOR_OPERANDS, const ActorOuW ow) {
-    constexpr bool SAMPLE = false, OU = true, FG_ACTOR_FLAGS;
-    FG_ACTOR_ABSENT
+    constexpr bool SAMPLE = false, OU = true, CAT = false, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_CW
     const float* const log_std = nullptr;
     float* const logp = nullptr;
 #include "fg_actor_rollout_body.inc"
 }
 #undef FG_ACTOR_OUK
+#endif
+
+// the categorical actor: no log_std; indices to cw.idx [K][B][N], log-probs to cw.logp [K][B][N] when it is not NULL
+#ifdef FG_ACTOR_CATK
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_CATK(const Args a, FG_ACTOR_OPERANDS, const ActorCatW cw) {
+    constexpr bool SAMPLE = false, OU = false, CAT = true, FG_ACTOR_FLAGS;
+    FG_ACTOR_ABSENT FG_ACTOR_NO_OW
+    const float* const log_std = nullptr;
+    float* const logp = nullptr;
+#include "fg_actor_rollout_body.inc"
+}
+#undef FG_ACTOR_CATK
 #endif
 
 #undef FG_ACTOR_DET

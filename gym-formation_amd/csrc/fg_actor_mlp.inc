@@ -12,15 +12,19 @@
 // env q / N, agent q % N), `y` (the lane's action component, noise added) and, SAMPLE only, the row's draw `n` with `ls0`,
 // `ls1` for gauss_logp(n, ls0, ls1).  The body stores them - each to its own place - and ends the pass with a WaveSync.
 // `constexpr bool LNORM` (with `nw`): a LayerNorm over each row of the tile after either ReLU hand-over (actor_row_norm on
-// gamma | beta at wsm + WS + 4, fg_actor_mlp_preload.inc), with a WaveSync of its own before the next layer reads the tile.
+// gamma | beta at wsm + WS + WB, fg_actor_mlp_preload.inc), with a WaveSync of its own before the next layer reads the tile.
 // `constexpr bool GRU` (with `gw`, `gsm`, `hst`; formation_hd_env's body only): the recurrent layer on the tile between the
 // second hidden norm and layer 3 (fg_actor_gru.inc), which leaves LayerNorm(h') in the tile for layer 3.
 // `constexpr bool OU` (with `ow`, `oust`, `El`; formation_hd_env's body only): the row's noise state at oust + 2 q steps with
 // the row's draw (ou_step) and `y` becomes clamp(y + scale x, -clip, clip) (ou_action).
+// `constexpr bool CAT` (with `cw`; formation_hd_env's body only): layer 3 has five outputs, W3 [5][H] at wsm + 2 H and b3 [5] at
+// wsm + WS.  Both lanes of a row evaluate the five ascending chains (the same bits), draw the row's uniform at `off` and run
+// cat_pick (cw.greedy: the mode instead of a sample, wave-uniform); `y` is component o of the decoded action (cat_decode by
+// cw.mode) and `pick` the row's index and log-prob, which the body stores.  No tanh.
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
             if constexpr (LNORM) {
-                actor_row_norm<H>(hb, HS, wsm + WS + 4, nw.eps1, lane);
+                actor_row_norm<H>(hb, HS, wsm + WS + WB, nw.eps1, lane);
                 WaveSync()();
             }
             // ---- layer 2 ----
@@ -47,7 +51,7 @@
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
             if constexpr (LNORM) {
-                actor_row_norm<H>(hb, HS, wsm + WS + 4 + 2 * H, nw.eps2, lane);
+                actor_row_norm<H>(hb, HS, wsm + WS + WB + 2 * H, nw.eps2, lane);
                 WaveSync()();
             }
             if constexpr (GRU) {
@@ -56,11 +60,31 @@
             // ---- layer 3 on the VALU: lane = (row of the pass, output), an ascending fmaf chain ----
             const int row = lane >> 1, o = lane & 1;
             const float* const hr = hb + row * HS;
-            const float* const w3 = wsm + 2 * H + o * H;
-            float y = wsm[4 * H + o];
+            const float* const w3 = wsm + 2 * H + (CAT ? 0 : o * H);
+            float y = CAT ? 0.f : wsm[4 * H + o];
+            CatPick pick = {};                     // CAT: the row's index and log-prob
+            if constexpr (CAT) {
+                float l[FG_CAT];
+#pragma unroll
+                for (int j = 0; j < FG_CAT; ++j) l[j] = wsm[WS + j];
+#pragma unroll 4
+                for (int k = 0; k < H; ++k) {
+                    const float hk = hr[k];
+#pragma unroll
+                    for (int j = 0; j < FG_CAT; ++j) l[j] = __builtin_fmaf(hk, w3[j * H + k], l[j]);
+                }
+                const int qc = q0 + row, ee = qc / N;
+                // both lanes of a row draw the row's uniform at counter offset `off` and pick the same index
+                const float ud = cw.greedy ? 0.f
+                                           : actor_uniform(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(qc - ee * N), off);
+                pick = cat_pick(l, ud, cw.greedy != 0);
+                const float2 ua = cat_decode(cw.mode, pick.idx);
+                y = o ? ua.y : ua.x;
+            } else {
 #pragma unroll 8
-            for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
-            if (w.out_tanh) y = tanhf(y);
+                for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);
+                if (w.out_tanh) y = tanhf(y);
+            }
             // the pass's row as an env-major row of the workgroup: env q / N, agent q % N
             const int q = q0 + row;
             float2 n = {};                         // SAMPLE: the row's draw and log_std, for gauss_logp(n, ls0, ls1)

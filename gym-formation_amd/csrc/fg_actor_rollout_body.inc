@@ -20,6 +20,9 @@
 // deterministic body with the noise state's block in LDS - loaded from ow.state before the first pass, stepped by layer 3's lanes
 // (fg_actor_mlp.inc; the per-agent branch here), its done envs' rows set to mu by the physics phase, stored back after the last
 // step.
+// `constexpr bool CAT` with `cw` (ActorCatW; CAT = false: an empty constant) selects cat_actor_kernel / ln_cat_actor_kernel /
+// gru_cat_actor_kernel: the shared body with the five-output head of fg_actor_mlp.inc, whose lanes leave the decoded action in
+// the actions' block and the row's index and log-prob in two blocks [E N] behind it; the physics phase stores the three.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -39,7 +42,9 @@
     // EP >= 16 - so that every 16-row MFMA tile holds one agent and takes that agent's weights as its B operand
     constexpr int EP = E >= 16 ? E : 16;
     constexpr int TILES = ((PER_AGENT ? EP * N : E * N) + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
-    constexpr int WS = PER_AGENT ? 0 : 4 * H;           // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
+    constexpr int WS = actor_w_floats(H, PER_AGENT, CAT);   // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
+    constexpr int WB = actor_b3_floats(CAT);            // ... and of the b3 | log_std slot behind them
+    static_assert(!CAT || (!SAMPLE && !OU && !PER_AGENT && !INBN), "the categorical actor: a shared body, no Gaussian or OU noise");
     static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
     constexpr int LNS = actor_norm_floats(N, H, LNORM), DP = actor_in_pad(N);   // LNORM: gamma / beta of the three norms in LDS
     static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
@@ -53,16 +58,17 @@
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
-    float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE only
-    float* const wsm = logp_lds + (SAMPLE ? E * N : 0);                     // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + 4 + LNS + BNS + GS;
-    float* const gsm = wsm + WS + 4 + LNS + BNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
+    float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE and CAT only
+    int* const idx_lds = reinterpret_cast<int*>(logp_lds + E * N);          // CAT only
+    float* const wsm = logp_lds + (actor_out_blocks(SAMPLE, CAT) - 2) * E * N;   // b1 | b2 | W3 | b3 | log_std
+    float* const hbuf = wsm + WS + WB + LNS + BNS + GS;
+    float* const gsm = wsm + WS + WB + LNS + BNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
     float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
-    static_assert(!GRU || (E * env_block_floats(N) + (SAMPLE ? 3 : 2) * E * N + WS + 4 + LNS + BNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
+    static_assert(!GRU || (E * env_block_floats(N) + actor_out_blocks(SAMPLE, CAT) * E * N + WS + WB + LNS + BNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
                   "the hidden state's block is 16-byte aligned (fg_actor_gru.inc stores its rows with 16-byte reads)");
     float* const oust = hbuf + NW * FG_ACTOR_ROWS * HS; // OU: the noise state, component o of env-major slot q at oust + 2 q + o
-    const float* const ln0 = wsm + WS + 4 + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
-    const float* const bn0 = wsm + WS + 4 + LNS;                            // INBN, shared: the four tables, zeros at k >= D
+    const float* const ln0 = wsm + WS + WB + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
+    const float* const bn0 = wsm + WS + WB + LNS;                            // INBN, shared: the four tables, zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,7 +91,7 @@
     }
     if constexpr (LNORM) {
         if (nw.in_norm) {
-            float* const lnp = wsm + WS + 4 + 4 * H;
+            float* const lnp = wsm + WS + WB + 4 * H;
             for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
                 lnp[q] = q < D ? (nw.g0 ? nw.g0[q] : 1.f) : 0.f;
                 lnp[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
@@ -93,7 +99,7 @@
         }
     }
     if constexpr (INBN && !PER_AGENT) {
-        float* const bnp = wsm + WS + 4 + LNS;
+        float* const bnp = wsm + WS + WB + LNS;
         for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
             const bool in = q < D;
             bnp[q] = in ? bw.mean[q] : 0.f;
@@ -389,6 +395,9 @@
                 if constexpr (SAMPLE) {
                     if (q < M && o == 0) logp_lds[q] = gauss_logp(n, ls0, ls1);
                 }
+                if constexpr (CAT) {
+                    if (q < M && o == 0) { idx_lds[q] = pick.idx; logp_lds[q] = pick.logp; }
+                }
                 if (q < M) reinterpret_cast<float*>(act_lds)[2 * q + o] = y;
             }
             WaveSync()();                              // the tile is free for the next pass
@@ -408,6 +417,10 @@
             reinterpret_cast<float2*>(a.act_out)[((size_t)k * a.B + b) * N + i] = u_act;
             if constexpr (SAMPLE) {
                 if (logp) logp[((size_t)k * a.B + b) * N + i] = logp_lds[e * N + i];
+            }
+            if constexpr (CAT) {
+                cw.idx[((size_t)k * a.B + b) * N + i] = idx_lds[e * N + i];
+                if (cw.logp) cw.logp[((size_t)k * a.B + b) * N + i] = logp_lds[e * N + i];
             }
             float2 f = contact_force_packed<NPS>(QX, QY, NP, i, p, a.p.contact_force, a.p.contact_margin,
                                                  a.p.dist_min, cutoff2);

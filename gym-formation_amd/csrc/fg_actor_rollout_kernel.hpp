@@ -101,6 +101,16 @@
 //              of an env whose step ended its episode (is_done, with or without auto-reset), a workgroup barrier away from
 //              either neighbour - the convention of the GRU state's masking.
 //
+// cat_actor_kernel<N,H>, ln_cat_actor_kernel<N,H> and gru_cat_actor_kernel<N,H> (fg_rollout_hd_actor_cat) are the fourth member
+// of the plain, LayerNorm and recurrent families: the body with a five-output head under a Categorical (the MAPPO trainers'
+// discrete-action policy), selected by `constexpr bool CAT` (false in every other kernel, whose instructions it leaves as they
+// were).  W3 [5][H] and b3 [5] sit in LDS where W3 [2][H] | b3 [2] do (fg_actor_mlp_preload.inc).  Both lanes of a row evaluate
+// the five logits (ascending fmaf chains from b3[j]: identical bits in both), draw the row's uniform (actor_uniform: word 2 of
+// the Gaussian members' Philox block) and run cat_pick; lane o writes component o of the decoded u (cat_decode, by the env's
+// action mode) to the actions' block, lane 0 the index and the log-prob to two blocks [E N] behind it, and the physics phase
+// stores all three.  ONE kernel per (family, N, H): `greedy` and the action mode are run-time, wave-uniform facts of the launch
+// (ActorCatW).  There is no tanh and no log_std.
+//
 // How a family is wired up: the twelve kernels (sixteen with the OU members) are six family blocks at the end of this file, each the two kernel names, the
 // four flags, the operands the family takes and the ones it does not, around fg_actor_kernel_pair.inc, which emits the
 // deterministic / Gaussian pair - and, where the block names one (FG_ACTOR_OUK), the OU member - with
@@ -195,13 +205,25 @@ FG_DEV float ou_action(float mean, float x, float scale, float clip) {
     return fminf(fmaxf(v, -clip), clip);
 }
 
+// the categorical head of *cat_actor_kernel (fg_rollout_hd_actor_cat): the env's action mode (FG_ACT_ONEHOT5 / FG_ACT_INDEX),
+// whether the launch takes the mode of the distribution instead of a sample, and the outputs idx [K][B][N] and logp [K][B][N]
+// (NULL: not written)
+struct ActorCatW {
+    int mode, greedy;
+    int* idx;
+    float* logp;
+};
+constexpr int FG_CAT = 5;                     // the five actions of the discrete action space: none, and two per axis
+
 constexpr int FG_ACTOR_THREADS = 256;
 constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-row MFMA tiles
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
 __host__ __device__ constexpr int actor_envs(int n) { return FG_ACTOR_THREADS / actor_lanes(n); }
 __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // row pitch of the activation tile: 16 rows x 4 k conflict-free
 // LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
+//               (CAT: log-probs [E N] indices [E N]) |
 //               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) |
+//               (CAT instead: b1 [H] b2 [H] W3 [5][H] | b3 [5] and padding to 8) |
 //               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
 //               (INBN, not PER_AGENT: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm) |
 //               (GRU: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]) |
@@ -218,18 +240,24 @@ __host__ __device__ constexpr int actor_bn_floats(int n, bool inbn, bool per_age
     return inbn && !per_agent ? 4 * actor_in_pad(n) : 0;
 }
 __host__ __device__ constexpr int actor_ou_floats(int n, bool ou) { return ou ? 2 * actor_envs(n) * n : 0; }
+// floats of b1 | b2 | W3 in LDS (a per-agent family reads them through L1), and of the b3 | log_std slot behind them
+__host__ __device__ constexpr int actor_w_floats(int h, bool per_agent, bool cat) { return per_agent ? 0 : (cat ? 2 + FG_CAT : 4) * h; }
+__host__ __device__ constexpr int actor_b3_floats(bool cat) { return cat ? 8 : 4; }
+// blocks [E N] between the env blocks and the weights: the actions' two, SAMPLE's log-probs, CAT's log-probs and indices
+__host__ __device__ constexpr int actor_out_blocks(bool sample, bool cat) { return sample ? 3 : cat ? 4 : 2; }
 template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
-          bool OU = false>
+          bool OU = false, bool CAT = false>
 constexpr int actor_lds_floats() {
-    return actor_envs(NC) * env_block_floats(NC) + (SAMPLE ? 3 : 2) * actor_envs(NC) * NC + (PER_AGENT ? 0 : 4 * H) + 4 +
+    return actor_envs(NC) * env_block_floats(NC) + actor_out_blocks(SAMPLE, CAT) * actor_envs(NC) * NC +
+           actor_w_floats(H, PER_AGENT, CAT) + actor_b3_floats(CAT) +
            actor_norm_floats(NC, H, LNORM) + actor_bn_floats(NC, INBN, PER_AGENT) + actor_gru_floats(H, GRU) +
            (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0) +
            actor_ou_floats(NC, OU);
 }
 template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
-          bool OU = false>
+          bool OU = false, bool CAT = false>
 constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN, OU>() * (int)sizeof(float);
+    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN, OU, CAT>() * (int)sizeof(float);
 }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
@@ -245,6 +273,49 @@ FG_DEV float2 actor_eps(uint64_t seed, uint32_t g, uint32_t i, uint64_t offset) 
 // -0.5 |n|^2 - (ls0 + ls1) - log(2 pi).  The one spelling for the shared, per-agent and landmark kernels.
 FG_DEV float gauss_logp(float2 n, float ls0, float ls1) {
     return -0.5f * (n.x * n.x + n.y * n.y) - (ls0 + ls1) - 1.8378770664093453f;
+}
+
+// The uniform draw u in [0, 1) of agent i of global env g for the step whose counter offset is `offset` (the categorical
+// members): word 2 of actor_eps's Philox block - key `seed`, counter {g, i ^ 0xA0000000, lo32(offset), hi32(offset)} - as
+// (c[2] >> 8) 2^-24.  Words 0 and 1 stay the Gaussian members' draw.
+FG_DEV float actor_uniform(uint64_t seed, uint32_t g, uint32_t i, uint64_t offset) {
+    uint32_t c[4] = {g, i ^ 0xA0000000u, (uint32_t)offset, (uint32_t)(offset >> 32)};
+    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (float)(c[2] >> 8) * (1.0f / 16777216.0f);
+}
+
+// The Categorical over five fp32 logits, the one spelling for the fused kernels and fg_actor_categorical, in fp32:
+//     m = max_j l_j,   e_j = exp(l_j - m),   c_j = e_0 + .. + e_j (ascending),   s = c_4
+//     sampled: t = u s, idx the first j in 0..3 with t < c_j, else 4;   greedy: idx the lowest index attaining m
+//     log_prob = (l_idx - m) - log(s)
+// exp and log are __expf and __logf (v_exp_f32 / v_log_f32 behind one multiply): about 2 ulp on e_j in (0, 1] and on log(s),
+// s in [1, 5]; a class further than ~87 below the maximum underflows to e_j = 0 and is never sampled.
+struct CatPick { int idx; float logp; };
+FG_DEV CatPick cat_pick(const float (&l)[FG_CAT], float u, bool greedy) {
+    float m = l[0];
+#pragma unroll
+    for (int j = 1; j < FG_CAT; ++j) m = fmaxf(m, l[j]);
+    float c[FG_CAT];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < FG_CAT; ++j) { s += __expf(l[j] - m); c[j] = s; }
+    const float t = u * s;
+    int idx = FG_CAT - 1;
+    float li = l[FG_CAT - 1];
+#pragma unroll
+    for (int j = FG_CAT - 2; j >= 0; --j) {            // descending, so that the lowest index that qualifies stays
+        const bool take = greedy ? l[j] == m : t < c[j];
+        idx = take ? j : idx;
+        li = take ? l[j] : li;
+    }
+    return {idx, (li - m) - __logf(s)};
+}
+// The index as the env's raw action u (MultiAgentEnv._set_action): FG_ACT_ONEHOT5 takes the one-hot e_idx through
+// u = (a1 - a2, a3 - a4) - 1: +x, 2: -x, 3: +y, 4: -y - and FG_ACT_INDEX is decode_actions_kernel's 1: -x, 2: +x, 3: -y, 4: +y;
+// index 0 is no move in both.
+FG_DEV float2 cat_decode(int mode, int idx) {
+    const float sgn = mode == FG_ACT_INDEX ? -1.0f : 1.0f;
+    return make_float2(idx == 1 ? sgn : idx == 2 ? -sgn : 0.0f, idx == 3 ? sgn : idx == 4 ? -sgn : 0.0f);
 }
 
 // The pieces of one wave pass of the actor MLP (fg_actor_mlp.inc) that layer 1 of each body shares with it.  acc: the pass's
@@ -314,6 +385,32 @@ __global__ __launch_bounds__(256) void actor_logp_kernel(long long count, const 
     logp[t] = gauss_logp(eps[t], log_std[0], log_std[1]);
 }
 
+// One step's uniform draw for every (env, agent) at rng_base(p) (fg_actor_uniform): the host-paced loop of a CategoricalActor
+// draws what the *cat_actor_kernel draw.
+__global__ __launch_bounds__(256) void actor_uniform_kernel(const KParams p, int B, int N, float* __restrict__ u) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)B * N) return;
+    const int b = (int)(t / N), i = (int)(t - (long long)b * N);
+    u[t] = actor_uniform(p.seed, (uint32_t)(b + p.env_index_base), (uint32_t)i, rng_base(p));
+}
+
+// cat_pick and cat_decode on each of `count` rows of caller-supplied logits [count][5] and draws u [count]
+// (fg_actor_categorical): the host-paced loop of a CategoricalActor takes the fused launch's arithmetic from its own logits.
+__global__ __launch_bounds__(256) void actor_categorical_kernel(int mode, int greedy, long long count,
+                                                                const float* __restrict__ logits, const float* __restrict__ u,
+                                                                int* __restrict__ idx, float2* __restrict__ act,
+                                                                float* __restrict__ logp) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    float l[FG_CAT];
+#pragma unroll
+    for (int j = 0; j < FG_CAT; ++j) l[j] = logits[t * FG_CAT + j];
+    const CatPick pk = cat_pick(l, greedy ? 0.f : u[t], greedy != 0);
+    idx[t] = pk.idx;
+    if (act) act[t] = cat_decode(mode, pk.idx);
+    if (logp) logp[t] = pk.logp;
+}
+
 // ou_step on each of `count` (env, agent) pairs in place (fg_actor_ou_step): the host-paced loop of an OUNoiseActor carries
 // the state the fused kernels carry, from the same eps.
 __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, float theta, float mu, float sigma,
@@ -327,7 +424,8 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 // ---- the twelve kernels: one block per family, each the deterministic / Gaussian pair of fg_actor_kernel_pair.inc around
 // fg_actor_rollout_body.inc.  A family is its two names, its four flags, the operands it takes as kernel arguments and the
 // ones it does not, and - the four families without LayerNorms - the name of its OU member, which takes `ow` (ActorOuW)
-// after them; the body names all of `w tab nw gw bw btab ow`, and an operand a family does not take is the empty constant
+// after them, and - the plain, LayerNorm and recurrent families - the name of its categorical member, which takes `cw`
+// (ActorCatW) after them; the body names all of `w tab nw gw bw btab ow cw`, and an operand a family does not take is the empty constant
 // below (`w` of a per-agent family: only tab's tanh flag), so that no kernel carries an argument it never reads.
 #define FG_ACTOR_NO_W    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
 #define FG_ACTOR_NO_TAB  constexpr ActorTab tab{};
@@ -336,10 +434,12 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 #define FG_ACTOR_NO_BW   constexpr ActorBnW bw{};
 #define FG_ACTOR_NO_BTAB constexpr ActorBnTab btab{};
 #define FG_ACTOR_NO_OW   constexpr ActorOuW ow{};
+#define FG_ACTOR_NO_CW   constexpr ActorCatW cw{};
 
 // the shared actor
 #define FG_ACTOR_DET      actor_rollout_kernel
 #define FG_ACTOR_OUK      ou_actor_kernel
+#define FG_ACTOR_CATK     cat_actor_kernel
 #define FG_ACTOR_SMP      actor_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w
@@ -357,6 +457,7 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 
 // LNORM: the shared actor with LayerNorms `nw`
 #define FG_ACTOR_DET      ln_actor_kernel
+#define FG_ACTOR_CATK     ln_cat_actor_kernel
 #define FG_ACTOR_SMP      ln_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw
@@ -365,6 +466,7 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 
 // GRU: the LayerNorm actor with the recurrent layer `gw` before its head
 #define FG_ACTOR_DET      gru_actor_kernel
+#define FG_ACTOR_CATK     gru_cat_actor_kernel
 #define FG_ACTOR_SMP      gru_sample_kernel
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = true, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw, const ActorGruW gw
@@ -398,6 +500,7 @@ static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(Acto
 #undef FG_ACTOR_NO_BW
 #undef FG_ACTOR_NO_BTAB
 #undef FG_ACTOR_NO_OW
+#undef FG_ACTOR_NO_CW
 
 }  // namespace fg
 

@@ -15,6 +15,8 @@
     constexpr bool OU = false;                          // nor one with OU noise
     constexpr ActorOuW ow{};
     float* const oust = nullptr;
+    constexpr bool CAT = false;                         // nor a categorical one
+    constexpr ActorCatW cw{};
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
     constexpr int NE = N + M;
@@ -26,6 +28,7 @@
     constexpr int BLOCK_UNITS = scn_lane_block_bytes(KIND, N, L, M, NBR, 1) / 8;
     constexpr int HS = actor_hstride(H), CB = H / 16, RT = FG_ACTOR_ROWS / 16;
     constexpr int WS = 4 * H;                           // floats of b1 | b2 | W3 in LDS
+    constexpr int WB = 4;                               // ... and of the b3 | log_std slot behind them
     constexpr int TILES = (ENVS * N + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
     static_assert(NE <= 8 && L <= 8, "one env per lane: a handful of entities");
     static_assert(H % 16 == 0 && D % 2 == 0 && RT == 2, "bad actor geometry");
@@ -33,7 +36,7 @@
     float2* const smem = smem_all;
     float* const act_lds = reinterpret_cast<float*>(smem_all + BLOCK_UNITS);            // [64 N][2]
     float* const wsm = act_lds + 2 * ENVS * N;                                           // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + 4;
+    float* const hbuf = wsm + WS + WB;
 
     const int tid = threadIdx.x, lane = tid & 63;
     // consecutive workgroup ids take consecutive 64-env spans within an XCD's eighth of the batch (scn_lane_kernel's map)

@@ -1000,14 +1000,17 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
 //     HD_ACTOR_NORM          ActorW, ActorNormW              HD_ACTOR_BN_PER_AGENT  ActorTab, ActorBnTab
 // The OU column is the family's third member (fg_rollout_hd_actor_ou*: a call with `noise` set), which takes an ActorOuW after
 // those operands; the LayerNorm families have none (hd_no_ou_kernel, never instantiated: no entry builds such a call).
+// The categorical column is the fourth member (fg_rollout_hd_actor_cat: a call with `cat` set), which takes an ActorCatW after
+// the operands; the per-agent and BatchNorm families have none (hd_no_cat_kernel, likewise).
 enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
                    HD_ACTOR_BN_PER_AGENT };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
                                              "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
                                              "fg_rollout_hd_actor_bn_per_agent"};
 template <int NC, int H> constexpr std::nullptr_t hd_no_ou_kernel = nullptr;
+template <int NC, int H> constexpr std::nullptr_t hd_no_cat_kernel = nullptr;
 template <HdActorKind> struct HdActorFamily;
-#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, WHAT)                                            \
+#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, CATK, WHAT)                                      \
     template <> struct HdActorFamily<KIND> {                                                                      \
         static constexpr bool per_agent = PA, lnorm = LN, gru = GR, in_bn = BN;                                   \
         static constexpr int max_h = MAXH;                                                                        \
@@ -1015,29 +1018,34 @@ template <HdActorKind> struct HdActorFamily;
         template <int NC, int H> static constexpr auto smp = &SMP<NC, H>;                                         \
         static constexpr bool has_ou = !LN;                                                                       \
         template <int NC, int H> static constexpr auto ou = OUK<NC, H>;                                           \
+        static constexpr bool has_cat = !PA && !BN;                                                               \
+        template <int NC, int H> static constexpr auto cat = CATK<NC, H>;                                         \
         static constexpr const char* det_name = #DET;                                                             \
         static constexpr const char* smp_name = #SMP;                                                             \
         static constexpr const char* ou_name = #OUK;                                                              \
+        static constexpr const char* cat_name = #CATK;                                                            \
         static constexpr const char* fail_fmt = WHAT "actor rollout launch failed: %s";                           \
         static_assert(!(PA && LN), "no per-agent actor kernel with LayerNorms");                                  \
         static_assert(!GR || LN, "the recurrent actor's base is the LayerNorm actor");                            \
         static_assert(!(BN && LN), "the input BatchNorm is in front of the plain body only");                     \
-        template <int NC, int H, bool SAMPLE, bool OU = false>                                                    \
-        static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN, OU>();                    \
+        template <int NC, int H, bool SAMPLE, bool OU = false, bool CAT = false>                                  \
+        static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN, OU, CAT>();               \
     };
-//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise
-FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       "")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    "per-agent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       "LayerNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       "recurrent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    "BatchNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, "per-agent BatchNorm ")
+//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise               categorical
+FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       cat_actor_kernel,     "")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    hd_no_cat_kernel,     "per-agent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       ln_cat_actor_kernel,  "LayerNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       gru_cat_actor_kernel, "recurrent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    hd_no_cat_kernel,     "BatchNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, hd_no_cat_kernel,     "per-agent BatchNorm ")
 #undef FG_HD_ACTOR_FAMILY
 template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
 
-// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member; `w`: the family's operands
+// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member, or with `cw` its categorical member; `w`:
+// the family's operands
 template <int NC, int H, class F, class... W>
-static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, hipStream_t st, const W&... w) {
+static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, const ActorCatW* cw, hipStream_t st,
+                           const W&... w) {
     static_assert(F::template lds_bytes<NC, H, true> <= 160 * 1024, "actor rollout LDS");
     constexpr int E = actor_envs(NC);
     char targs[16];
@@ -1049,6 +1057,15 @@ static int launch_hd_actor(const Args& a, const float* log_std, float* logp, con
             const int grid = (a.B + E - 1) / E;
             if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::ou_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
             return launch<F::template ou<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *ow);
+        }
+    }
+    if constexpr (F::has_cat) {
+        if (cw) {
+            constexpr int lds = F::template lds_bytes<NC, H, false, false, true>;
+            static_assert(lds <= 160 * 1024, "actor rollout LDS");
+            const int grid = (a.B + E - 1) / E;
+            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::cat_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
+            return launch<F::template cat<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *cw);
         }
     }
     return launch_actor_pair<F::template det<NC, H>, F::template smp<NC, H>>(
@@ -1106,6 +1123,12 @@ struct HdActorNoise {                                  // fg_rollout_hd_actor_ou
     const FgActorOu* ou = nullptr;
     float* state = nullptr;
 };
+struct HdActorHead {                                   // fg_rollout_hd_actor_cat: the categorical head's facts and its outputs [K][B][N]
+    bool on = false;
+    int mode = 0, greedy = 0;
+    int32_t* idx = nullptr;
+    float* logp = nullptr;
+};
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
@@ -1123,9 +1146,13 @@ struct HdActorCall {
     // fg_rollout_hd_actor_ou and fg_rollout_hd_actor_ou_per_agent only (`noise.on`, which also puts their names on the messages):
     // the kind is the inner actor's family - shared or per-agent, with `in_bn` the BatchNorm one - whose OU member runs
     HdActorNoise noise = {};
+    // fg_rollout_hd_actor_cat only (`cat.on`, which also puts its name on the messages): the kind is the body's family - shared,
+    // LayerNorm or recurrent - whose categorical member runs
+    HdActorHead cat = {};
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
 static const char* hd_actor_who(const HdActorCall& c) {
+    if (c.cat.on) return "fg_rollout_hd_actor_cat";
     if (c.noise.on) return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
     return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
 }
@@ -1194,10 +1221,21 @@ static int actor_ou_check(const char* who, const FgActorOu* ou, const float* sta
     if ((uintptr_t)state & 7u) return bad(FG_ERR_ALIGNMENT, "noise_state must be 8-byte aligned");
     return FG_OK;
 }
+// The categorical head's checks (no device touched), in the name of the entry `who`: FG_ERR_BAD_ARG for an actor with a tanh
+// after its head, an action mode other than FG_ACT_ONEHOT5 / FG_ACT_INDEX, a NULL idx_seq where there are envs; FG_ERR_ALIGNMENT
+// for an idx_seq or logp_seq that is not 4-byte aligned.
+static int actor_cat_check(const char* who, const FgActor* actor, const HdActorHead& h, int B) {
+    const ActorComplaint bad{who};
+    if (actor->out_tanh != 0) return bad(FG_ERR_BAD_ARG, "out_tanh must be 0: the head's outputs are logits");
+    if (h.mode != FG_ACT_ONEHOT5 && h.mode != FG_ACT_INDEX) return bad(FG_ERR_BAD_ARG, "act_mode must be FG_ACT_ONEHOT5 or FG_ACT_INDEX");
+    if (!h.idx && B > 0) return bad(FG_ERR_BAD_ARG, "idx_seq is NULL");
+    if (((uintptr_t)h.idx | (uintptr_t)h.logp) & 3u) return bad(FG_ERR_ALIGNMENT, "idx_seq and logp_seq must be 4-byte aligned");
+    return FG_OK;
+}
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
 // this order, which is ABI - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
-// and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), the OU noise with its state, log_std,
-// logp.  The shared actor's
+// and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), the OU noise with its state, the
+// categorical head with its outputs, log_std, logp.  The shared actor's
 // checks name fg_rollout_hd_actor through the sample and norm entries too, the log_std checks fg_rollout_hd_actor_sample.
 // Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
@@ -1233,6 +1271,7 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
         }
     }
     if (c.noise.on && (rc = actor_ou_check(who, c.noise.ou, c.noise.state, B)) != FG_OK) return rc;
+    if (c.cat.on && (rc = actor_cat_check(who, c.actor, c.cat, B)) != FG_OK) return rc;
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1301,9 +1340,10 @@ template <HdActorKind KIND, class... W>
 static int hd_actor_run(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
     const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
     const ActorOuW ow = c.noise.on ? actor_ou_w(c.noise) : ActorOuW{};
+    const ActorCatW cw = {c.cat.mode, c.cat.greedy ? 1 : 0, c.cat.idx, c.cat.logp};
     return actor_nh_dispatch<HdActorFamily<KIND>::max_h>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(a, c.log_std, c.logp,
-                                                                                           c.noise.on ? &ow : nullptr, st, w...);
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(
+            a, c.log_std, c.logp, c.noise.on ? &ow : nullptr, c.cat.on ? &cw : nullptr, st, w...);
     });
 }
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
@@ -2054,6 +2094,59 @@ int fg_rollout_hd_actor_ou_per_agent(const FgParams* params, const FgActor* acto
                                done_seq}, obs_every, stream);
 }
 
+// the categorical entries' call: the body's family - recurrent with `gru`, LayerNorm with `norm` alone, else shared - with `cat`
+// set (no log_std); `rnn_states` NULL: no record of the states.  A `gru` without `norm` fails the recurrent family's own check
+// of its norms (FG_ERR_BAD_ARG, "norm is NULL").
+static HdActorCall hd_actor_cat_call(const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru, int act_mode, int greedy,
+                                     int32_t* idx, float* logp, float* rnn_state, float* rnn_states, int states_every) {
+    HdActorCall c{gru ? HD_ACTOR_GRU : norm ? HD_ACTOR_NORM : HD_ACTOR_SHARED, actor};
+    c.norm = norm;
+    c.gru = gru;
+    c.rnn_state = rnn_state;
+    if (gru && rnn_states) { c.states_entry = true; c.rnn_states = rnn_states; c.states_every = states_every; }
+    c.cat = {true, act_mode, greedy, idx, logp};
+    return c;
+}
+
+int fg_rollout_hd_actor_cat(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                            int act_mode, int greedy, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                            float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                            float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                            float* logp_seq, float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream) {
+    return rollout_actor_impl(params, hd_actor_cat_call(actor, norm, gru, act_mode, greedy, idx_seq, logp_seq, rnn_state, rnn_states,
+                                                        states_every), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
+}
+
+int fg_actor_uniform(const FgParams* params, int B, int N, float* u, void* stream) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || N < 1 || N >= (1 << 29)) return fail(FG_ERR_BAD_ARG, "fg_actor_uniform: B >= 0 and 1 <= N < 2^29 required%s");
+    if (!u) return fail(FG_ERR_BAD_ARG, "fg_actor_uniform: u is NULL%s");
+    if ((uintptr_t)u & 3u) return fail(FG_ERR_ALIGNMENT, "fg_actor_uniform: u must be 4-byte aligned%s");
+    if (B == 0) return FG_OK;
+    const DeviceGuard device_guard(stream, u);
+    const long long count = (long long)B * N;
+    return launch<&actor_uniform_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream,
+                                         "actor uniform launch failed: %s", *params, B, N, u);
+}
+
+int fg_actor_categorical(int act_mode, int greedy, int64_t count, const float* logits, const float* u, int32_t* idx, float* act,
+                         float* logp, void* stream) {
+    if (act_mode != FG_ACT_ONEHOT5 && act_mode != FG_ACT_INDEX)
+        return fail(FG_ERR_BAD_ARG, "fg_actor_categorical: act_mode must be FG_ACT_ONEHOT5 or FG_ACT_INDEX%s");
+    if (count < 0 || count > ((int64_t)1 << 38)) return fail(FG_ERR_BAD_ARG, "fg_actor_categorical: count out of range%s");
+    if (count == 0) return FG_OK;
+    if (!logits || !idx || (!u && !greedy)) return fail(FG_ERR_BAD_ARG, "fg_actor_categorical: logits, idx and (sampling) u are required%s");
+    if ((((uintptr_t)logits | (uintptr_t)u | (uintptr_t)idx | (uintptr_t)logp) & 3u) || ((uintptr_t)act & 7u))
+        return fail(FG_ERR_ALIGNMENT, "fg_actor_categorical: act must be 8-byte, the other buffers 4-byte aligned%s");
+    const DeviceGuard device_guard(stream, idx);
+    return launch<&actor_categorical_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream,
+                                             "actor categorical launch failed: %s", act_mode, greedy ? 1 : 0, (long long)count, logits, u,
+                                             reinterpret_cast<int*>(idx), reinterpret_cast<float2*>(act), logp);
+}
+
 int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream) {
     if (count < 0) return fail(FG_ERR_BAD_ARG, "fg_actor_ou_step: count >= 0 required%s");
     const int rc = actor_ou_check("fg_actor_ou_step", ou, state, count > 0 ? 1 : 0);
@@ -2145,6 +2238,15 @@ int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor*
                                           const FgActorOu* ou, int B, int N, int K, int obs_every, char* out, int out_len) {
     float* const state = reinterpret_cast<float*>((uintptr_t)4096);
     return describe_actor_impl("fg_describe_actor_ou_per_agent_launch", params, hd_actor_ou_call(true, actors, in_bns, ou, state),
+                               B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_cat_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                 int act_mode, int greedy, int B, int N, int K, int obs_every, char* out, int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // stand-ins: the dry run has no state and no outputs
+    int32_t* const idx = reinterpret_cast<int32_t*>((uintptr_t)4096);
+    return describe_actor_impl("fg_describe_actor_cat_launch", params,
+                               hd_actor_cat_call(actor, norm, gru, act_mode, greedy, idx, nullptr, state, nullptr, 1),
                                B, N, K, obs_every, out, out_len);
 }
 

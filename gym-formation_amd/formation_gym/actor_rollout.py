@@ -50,6 +50,18 @@ scalars are plain Python numbers read at every call.  Host-paced (the same loop 
 device function): a LayerNorm inner actor, any inner actor that would run host-paced itself, the landmark scenarios
 (`fused_ou=False`) and World options.  A GaussianActor stays "no clipping".
 
+A `CategoricalActor(logits)` is the MAPPO / rMAPPO trainers' discrete-action policy (`make_env(..., discrete_action=True)`):
+`logits` maps observations to five logits, an index is sampled from Categorical(logits=...) - or, with `deterministic`, its mode
+is taken - and the env turns the index into the raw action.  It fuses (`fg_rollout_hd_actor_cat`: cat_actor_kernel,
+ln_cat_actor_kernel, gru_cat_actor_kernel) in formation_hd_env when the env is in one of the action modes FG_ACT_ONEHOT5
+(`discrete_action_space`) or FG_ACT_INDEX (`discrete_action_input`) and `logits` is the plain form, the LayerNorm form or a
+RecurrentActor as above with the head Linear(H, 5) and no Tanh, under the existing rules (silent agents, no World options, no
+callback); `deterministic` is read at every launch.  Host-paced (the same loop in Python, the pick and the decode by the kernels'
+own device functions, `fg_actor_uniform` + `fg_actor_categorical`): a head of any other width, a Tanh after it, PerAgentActor
+members, a leading BatchNorm, H = 128 with norms, the landmark scenarios (`fused_cat=False`) and World options.  No path at all:
+FG_ACT_ARGMAX (`force_discrete_action`), any other actor in a discrete action mode, a CategoricalActor on a continuous env.
+Gumbel-softmax (MADDPG's discrete exploration) is not built.
+
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
 
@@ -79,6 +91,8 @@ FUSED_BN_HIDDEN = (32, 64)             # hidden widths of the BatchNorm actor's 
 LANDMARK_FUSED_SHAPES = ((1, 3, 3, 0, 2), (2, 5, 5, 0, 3), (2, 3, 5, 0, 3), (3, 4, 4, 0, 3), (3, 3, 4, 0, 2),
                          (4, 4, 4, 3, 3), (4, 3, 4, 3, 2))
 LANDMARK_FUSED_HIDDEN = (32, 64)
+ACT_ONEHOT5, ACT_INDEX, ACT_ARGMAX = 1, 2, 3    # the env's discrete action modes (_native.FG_ACT_*); 0: continuous actions
+CAT_ACTIONS = 5                                 # a CategoricalActor's head width: no move, and two directions per axis
 
 
 def landmark_facts(kind, num_agents, num_landmarks, num_obstacles, num_obs, obs_dim, variant=0):
@@ -135,7 +149,7 @@ def _in_bn(m, width, device):
 
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
-               fused_ou=True):
+               fused_ou=True, fused_cat=True, head_width=2):
     """The FusedActor fields hidden, out_tanh, members = [[w1, b1, w2, b2, w3, b3]] and the form's own (below) when a fused kernel
     can evaluate the shared actor body `actor` for `num_agents` agents, else None.  The three forms, each with its own kernels
     and so its own hidden widths:
@@ -149,17 +163,22 @@ def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
     are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact and
-    `fused_ou` (whether the scenario's launch has OU members) `resolve_actor`'s, neither read here."""
+    `fused_ou` / `fused_cat` (whether the scenario's launch has OU / categorical members) `resolve_actor`'s, none read here.
+    `head_width`: the last Linear's outputs - 2, or CAT_ACTIONS for a CategoricalActor's logits, which take no Tanh and no
+    leading BatchNorm."""
     if type(actor) is not torch.nn.Sequential:
         return None
-    return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden)
+    return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden,
+                         head_width)
 
 
-def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden=()):
+def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden=(), head_width=2):
     """`_body_spec` of the body whose modules, in order, are `mods`."""
     nn = torch.nn
     if int(num_agents) not in fused_n:
         return None
+    if head_width != 2 and (not mods or type(mods[-1]) is nn.Tanh or type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm)):
+        return None                                        # logits: no Tanh after the head, no BatchNorm family member
     if in_features is None:
         in_features = 6 * int(num_agents)
     if mods and type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm):     # in front of the plain form only
@@ -177,10 +196,10 @@ def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, 
     if out_tanh:
         kinds.pop()
     if kinds == [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] and not lead:
-        return _linears_spec(rest[0], rest[2], rest[4], out_tanh, in_features, device, fused_hidden)
+        return _linears_spec(rest[0], rest[2], rest[4], out_tanh, in_features, device, fused_hidden, head_width)
     if kinds != [nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear, nn.ReLU, nn.LayerNorm, nn.Linear]:
         return None
-    fields = _linears_spec(rest[0], rest[3], rest[6], out_tanh, in_features, device, fused_ln_hidden)
+    fields = _linears_spec(rest[0], rest[3], rest[6], out_tanh, in_features, device, fused_ln_hidden, head_width)
     if fields is None:
         return None
     H = fields["hidden"]
@@ -220,13 +239,14 @@ def _shared_triple(fields):
     return fields["hidden"], fields["out_tanh"], fields["members"][0]
 
 
-def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden):
+def _linears_spec(l1, l2, l3, out_tanh, in_features, device, fused_hidden, head_width=2):
     """The FusedActor fields hidden, out_tanh and members = [[w1, b1, w2, b2, w3, b3]] of the three Linears of a body whose
     module kinds have been checked, else None.  `fused_hidden`: the hidden widths of that body's kernels (None or empty:
-    none)."""
+    none).  `head_width`: the outputs of the last Linear - 2 for every member but the categorical one, whose CAT_ACTIONS logits
+    take no Tanh."""
     H = l1.out_features
     if H not in tuple(fused_hidden or ()) or l1.in_features != int(in_features) or (l2.in_features, l2.out_features) != (H, H) \
-            or (l3.in_features, l3.out_features) != (H, 2):
+            or (l3.in_features, l3.out_features) != (H, int(head_width)) or (head_width != 2 and out_tanh):
         return None
     params = [l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias]
     if not all(t is None or _param_ok(t, None, device) for t in params):
@@ -324,13 +344,14 @@ class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
 
 def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                     fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
-               fused_ou=True):
+                    fused_ou=True, fused_cat=True, head_width=2):
     """The FusedActor fields of `_body_spec`'s LayerNorm form and `gru`, the ActorGru, when the fused recurrent kernel can evaluate
     the RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
     of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
     one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
     parameter fp32, contiguous and on `device`.  `fused_bn_hidden` is `_body_spec`'s fact, not read here: a base that starts
-    with a BatchNorm has no recurrent kernel; nor is `fused_ou`, `resolve_actor`'s fact."""
+    with a BatchNorm has no recurrent kernel; nor are `fused_ou` and `fused_cat`, `resolve_actor`'s facts.  `head_width`: the
+    head's outputs, from the member - 2, or CAT_ACTIONS for a CategoricalActor's logits (a bare Linear, no Tanh)."""
     nn = torch.nn
     if type(actor) is not RecurrentActor or type(actor.base) is not nn.Sequential:
         return None
@@ -341,7 +362,8 @@ def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FU
         head_mods = list(head)
     else:
         return None
-    fields = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden)
+    fields = _modules_spec(list(actor.base) + head_mods, num_agents, device, in_features, fused_n, (), fused_gru_hidden, (),
+                           head_width)
     if fields is None or "norms" not in fields:
         return None
     H = fields["hidden"]
@@ -439,6 +461,49 @@ class GaussianActor(torch.nn.Module):
         return self.log_std.sum() + LOG_2PI + 1.0
 
 
+class CategoricalActor(torch.nn.Module):
+    """The MAPPO / rMAPPO trainers' discrete-action policy (onpolicy's ACTLayer over a Discrete(5) space): `logits` maps
+    observations [..., D] to five logits [..., 5] - the plain or LayerNorm Sequential ending in Linear(H, 5), or a RecurrentActor
+    whose head is Linear(H, 5) - and the action is an index 0 .. 4 drawn from Categorical(logits=...): 0 no move, 1 .. 4 the two
+    directions of each axis, as the env's action mode reads them.  `deterministic` (read at every call): the mode of the
+    distribution - the lowest index of the largest logit - instead of a sample (onpolicy's `deterministic=True`).
+    `forward` samples with torch and is meant for use outside the env: inside `env.rollout_actor` the env's counter stream
+    supplies the uniform draw (`env.actor_uniform()`), the indices come back in info['actions'] and their log-probabilities in
+    info['log_prob'].  `distribution`, `log_prob` and `entropy` are differentiable in the parameters: what a PPO update calls."""
+
+    def __init__(self, logits, deterministic=False):
+        super().__init__()
+        self.logits = logits
+        self.deterministic = bool(deterministic)
+
+    def _logits(self, obs, rnn_state=None):
+        """logits(obs), or for a RecurrentActor with its state the logits part of logits(obs, rnn_state)."""
+        return self.logits(obs) if rnn_state is None else self.logits(obs, rnn_state)[0]
+
+    def forward(self, obs, rnn_state=None):
+        """The index [...] (int64); with `rnn_state` (a RecurrentActor's hidden state) the pair (index, new state)."""
+        if rnn_state is None:
+            lg, h = self.logits(obs), None
+        else:
+            lg, h = self.logits(obs, rnn_state)
+        idx = lg.argmax(-1) if self.deterministic else torch.distributions.Categorical(logits=lg).sample()
+        return idx if rnn_state is None else (idx, h)
+
+    def distribution(self, obs, rnn_state=None):
+        """torch.distributions.Categorical(logits=logits(obs)) (`rnn_state`: a recurrent body's hidden state)."""
+        return torch.distributions.Categorical(logits=self._logits(obs, rnn_state))
+
+    def log_prob(self, obs, idx, rnn_state=None):
+        """Log-probability of the indices `idx` [...] under the policy at `obs`: log_softmax(logits)[idx]."""
+        lsm = torch.log_softmax(self._logits(obs, rnn_state), dim=-1)
+        return lsm.gather(-1, idx.to(torch.int64).unsqueeze(-1)).squeeze(-1)
+
+    def entropy(self, obs, rnn_state=None):
+        """Entropy of the action distribution at `obs` [...]: -sum_j p_j log p_j."""
+        lsm = torch.log_softmax(self._logits(obs, rnn_state), dim=-1)
+        return -(lsm.exp() * lsm).sum(-1)
+
+
 def _on_device(t, device):
     if device is None:
         return True
@@ -521,8 +586,8 @@ class OUNoiseActor(torch.nn.Module):
         return act if noise_state is None else (act, x)
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn ou",
-                                        defaults=(None, None, None, None))):
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn ou cat",
+                                        defaults=(None, None, None, None, None))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
     N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
@@ -531,6 +596,8 @@ class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members p
     input BatchNorm in front of the plain body - the (running_mean, running_var, weight, bias, eps) tuple (ActorInBn) of a
     shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own.  `ou`: the
     OUNoiseActor whose exploration runs on top of the actor (None: none) - the module itself, whose scalars every launch reads.
+    `cat`: the CategoricalActor whose head the members' w3 [5][H], b3 [5] are (None: a two-output head) - the module itself,
+    whose `deterministic` flag every launch reads.
     `tensors()` and `binding_key()` are the one statement of what a launch reads by address: a binder keeps the first alive
     and a launcher cache keys on the second, so a new field is added to `_slots` and nowhere else."""
     __slots__ = ()
@@ -560,18 +627,18 @@ class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members p
 
     def binding_key(self):
         """What tells one binding of the record from another: the addresses of `_slots` (None kept in its place), the shape
-        facts, every eps - baked into the launch's structs - and the identity of the OUNoiseActor, whose scalars are read anew
-        per launch.  Equal for two resolutions of an unchanged module; a parameter re-allocated changes it."""
+        facts, every eps - baked into the launch's structs - and the identities of the OUNoiseActor and the CategoricalActor,
+        whose scalars / `deterministic` flag are read anew per launch.  Equal for two resolutions of an unchanged module; a parameter re-allocated changes it."""
         eps = None                                         # the plain body has none
         if self.norms is not None or self.gru is not None or self.in_bn is not None:
             eps = (None if self.norms is None else tuple([None if n is None else n[2] for n in self.norms]),
                    None if self.gru is None else self.gru.norm[2], tuple([bn[4] for bn in self._in_bns()]))
         return (self.hidden, self.out_tanh, self.per_agent, tuple([t if t is None else t.data_ptr() for t in self._slots()]),
-                eps, id(self.ou))
+                eps, id(self.ou)) + (() if self.cat is None else (id(self.cat),))
 
 
 def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
-                  callback=False, per_agent=True, **facts):
+                  callback=False, per_agent=True, action_mode=0, **facts):
     """The one decision `MultiAgentEnv.actor_path` / `rollout_actor` take, with what the launch needs: a FusedActor when
     `rollout_actor(K, actor)` runs fused, None when it runs host-paced.  The keyword facts describe the env: a scenario with
     the fused launch (formation_hd_env), continuous actions, silent agents, no World options (walls, accel, max_speed,
@@ -586,8 +653,25 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     `fused_bn_hidden=()`.  An OUNoiseActor is unwrapped likewise, into its inner actor and itself (`FusedActor.ou`): it fuses
     where the fact `fused_ou` holds (the scenario's launch has OU members: formation_hd_env's; the landmark scenarios state
     False) and the
-    inner actor resolves to a form without LayerNorms - plain or BatchNorm, shared or per-agent."""
-    if not (fused_scenario and continuous and silent) or world_options or callback:
+    inner actor resolves to a form without LayerNorms - plain or BatchNorm, shared or per-agent.
+    `action_mode`: the env's action mode as a fact - 0 continuous actions, else ACT_ONEHOT5 / ACT_INDEX / ACT_ARGMAX
+    (`continuous=False` without it: some discrete mode, nothing fuses).  A CategoricalActor is unwrapped likewise, into its
+    logits module and itself (`FusedActor.cat`): it fuses in the modes ACT_ONEHOT5 and ACT_INDEX where the fact `fused_cat` holds
+    (formation_hd_env; the landmark scenarios state False) and its logits resolve to the plain form, the LayerNorm form or a
+    RecurrentActor with a head of CAT_ACTIONS outputs and no Tanh.  Every other actor fuses with continuous actions only."""
+    if not (fused_scenario and silent) or world_options or callback:
+        return None
+    cat = actor if isinstance(actor, CategoricalActor) else None
+    if cat is not None:
+        if action_mode not in (ACT_ONEHOT5, ACT_INDEX) or not facts.get("fused_cat", True):
+            return None
+        logits = cat.logits
+        if isinstance(logits, RecurrentActor):
+            fields = _recurrent_spec(logits, num_agents, device, **dict(facts, head_width=CAT_ACTIONS))
+        else:
+            fields = _body_spec(logits, num_agents, device, **dict(facts, head_width=CAT_ACTIONS))
+        return None if fields is None else FusedActor(per_agent=False, log_std=None, cat=cat, **fields)
+    if not continuous or action_mode:
         return None
     ou = None
     if isinstance(actor, OUNoiseActor):
@@ -615,8 +699,9 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
 
 
 def recurrent_mean(actor):
-    """The RecurrentActor that `actor` is or, for a GaussianActor, has as its mean; else None: the actor keeps no state."""
-    mean = actor.mean if isinstance(actor, GaussianActor) else actor
+    """The RecurrentActor that `actor` is or, for a GaussianActor, has as its mean, or, for a CategoricalActor, as its logits;
+    else None: the actor keeps no state."""
+    mean = actor.mean if isinstance(actor, GaussianActor) else actor.logits if isinstance(actor, CategoricalActor) else actor
     return mean if isinstance(mean, RecurrentActor) else None
 
 

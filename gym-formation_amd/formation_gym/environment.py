@@ -228,9 +228,10 @@ class MultiAgentEnv(object):
             raise ValueError("need K >= 1 steps and obs_every >= 1")
         return K, obs_every
 
-    def _rollout_shapes(self, K, obs_every, act=False, log_prob=False, rnn_states=None):
+    def _rollout_shapes(self, K, obs_every, act=False, log_prob=False, rnn_states=None, idx=False):
         """The shapes of a K-step launch's outputs by key of `out`: obs, reward, indiv and done always; `act` (the closed
-        loops' actions), `log_prob` (a Gaussian actor's) and `rnn_states` (that shape: the kept hidden states) on request."""
+        loops' actions), `log_prob` (a Gaussian or categorical actor's), `rnn_states` (that shape: the kept hidden states) and
+        `idx` (a categorical actor's indices, int32) on request."""
         B, N = self.num_envs, self.num_agents
         want = dict(obs=(K // obs_every, B, N, self._out["obs"].shape[-1]), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
         if act:
@@ -239,6 +240,8 @@ class MultiAgentEnv(object):
             want["log_prob"] = (K, B, N)
         if rnn_states is not None:
             want["rnn_states"] = tuple(rnn_states)
+        if idx:
+            want["idx"] = (K, B, N)
         return want
 
     def _rollout_out(self, want, out, K, obs_every, policy, obs_dtype=None):
@@ -253,7 +256,7 @@ class MultiAgentEnv(object):
         elif out is None or out is False:
             return {k: self._fresh_out(k, want[k], obs_dtype) for k in want}, False
         own_buffers = True
-        for k in ("log_prob", "rnn_states"):
+        for k in ("log_prob", "rnn_states", "idx"):
             if k not in want:
                 continue
             if placed and tuple(getattr(out.get(k), "shape", ())) != want[k]:
@@ -262,12 +265,17 @@ class MultiAgentEnv(object):
                 out, own_buffers = dict(out, **{k: self._fresh_out(k, want[k])}), False
             elif k == "rnn_states":
                 self._state_tensor("out['rnn_states']", out[k], want[k], None)
+            elif k == "idx" and (not torch.is_tensor(out[k]) or out[k].dtype != torch.int32):
+                raise ValueError("out['idx'] must be an int32 tensor of shape %s" % (want[k],))
         return out, own_buffers
 
     def _fresh_out(self, k, shape, obs_dtype=None):
-        """A new tensor for key `k` of `out`: done as zeroed bytes, obs in `obs_dtype` if given, everything else fp32."""
+        """A new tensor for key `k` of `out`: done as zeroed bytes, idx as int32, obs in `obs_dtype` if given, everything else
+        fp32."""
         if k == "done":
             return torch.zeros(shape, dtype=torch.uint8, device=self._act.device)
+        if k == "idx":
+            return torch.empty(shape, dtype=torch.int32, device=self._act.device)
         return torch.empty(shape, dtype=(obs_dtype or torch.float32) if k == "obs" else torch.float32, device=self._act.device)
 
     def _run_rollout(self, lead_key, want, out, own_buffers, K, obs_every, obs_dtype, bind, unbound, args, extra=()):
@@ -458,7 +466,8 @@ class MultiAgentEnv(object):
         if facts is None:                                  # a landmark scenario at a shape without the fused launch
             fused, facts = False, {}
         return actor_rollout.resolve_actor(actor, self.num_agents, self.world.device, fused_scenario=fused,
-                                           continuous=not self._action_mode(), silent=not self.world.any_non_silent(),
+                                           continuous=not self._action_mode(), action_mode=self._action_mode(),
+                                           silent=not self.world.any_non_silent(),
                                            world_options=world_options, callback=self.post_step_callback is not None,
                                            **facts)
 
@@ -537,9 +546,28 @@ class MultiAgentEnv(object):
         as it goes; nothing else of its results changes, and the entries of a K-step call are those of any split of K.  `out`
         may carry 'rnn_states' of exactly that shape; with out=None the tensor is kept with this shape's env-owned buffers
         like 'log_prob' (replaced when S or the state width changes) under the same aliasing rule - the next out=None call of
-        the shape overwrites it - and out=False gives a fresh one per call.  With an actor that keeps no state: ValueError."""
-        if self._action_mode():
+        the shape overwrites it - and out=False gives a fresh one per call.  With an actor that keeps no state: ValueError.
+        A `CategoricalActor(logits, deterministic=False)` is the MAPPO / rMAPPO trainers' discrete-action policy, for an env
+        made with discrete actions (`discrete_action_space`: FG_ACT_ONEHOT5, or `discrete_action_input`: FG_ACT_INDEX): step k
+        takes the index drawn from Categorical(logits=logits(o)) by the softmax CDF at the uniform draw `actor_uniform()` of
+        step k's RNG offset (the same on either path and for a shard as for its slice of the full batch) - or, with
+        `deterministic`, the lowest index of the largest logit - and the env's action mode turns it into the raw action.
+        info['actions'] [K, B, N] holds the int32 indices - `env.rollout` takes them back in FG_ACT_INDEX mode and
+        `one_hot(actions.long(), 5).float()` in FG_ACT_ONEHOT5 mode, with the same bits - info['u'] [K, B, N, 2] the raw
+        actions and info['log_prob'] [K, B, N] the log-probabilities; `out` may carry 'idx' (int32), 'act' (the raw actions)
+        and 'log_prob'.  `rnn_state` / `rnn_states_every` as above when `logits` is a RecurrentActor.  It fuses
+        (`fg_rollout_hd_actor_cat`) in formation_hd_env on the plain, the LayerNorm and the recurrent form with the head
+        Linear(H, 5); per-agent members, a leading BatchNorm, the landmark scenarios and World options run host-paced, the
+        pick and the decode by the kernels' own device functions (`fg_actor_categorical`).  Any other actor in a discrete
+        action mode, and any actor with `force_discrete_action` (FG_ACT_ARGMAX), raises NotImplementedError; a
+        CategoricalActor on an env with continuous actions raises ValueError."""
+        mode = self._action_mode()
+        cat = actor if isinstance(actor, actor_rollout.CategoricalActor) else None
+        if mode and (cat is None or mode == _native.FG_ACT_ARGMAX):
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
+        if cat is not None and not mode:
+            raise ValueError("a CategoricalActor needs an env with discrete actions (discrete_action_space or "
+                             "discrete_action_input)")
         K, obs_every = self._check_steps(K, obs_every)
         B, N = self.num_envs, self.num_agents
         recurrent = actor_rollout.recurrent_mean(actor)
@@ -569,10 +597,15 @@ class MultiAgentEnv(object):
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 self._state_tensor("out['rnn_states']", out["rnn_states"], states_shape, None)
             res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S, noise_state)
+            if cat is not None and isinstance(out, dict):
+                for key, src in (("idx", "actions"), ("act", "u"), ("log_prob", "log_prob")):
+                    if key in out:
+                        res[3][src] = out[key].copy_(res[3][src])
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 res[3]["rnn_states"] = out["rnn_states"].copy_(res[3]["rnn_states"])
             return res
-        want = self._rollout_shapes(K, obs_every, act=True, log_prob=fused.log_std is not None, rnn_states=states_shape)
+        want = self._rollout_shapes(K, obs_every, act=True, log_prob=fused.log_std is not None or cat is not None,
+                                    rnn_states=states_shape, idx=cat is not None)
         out, own_buffers = self._rollout_out(want, out, K, obs_every, True)
         # what the launch reads in place besides `out`, by name for the binder and by address for the key: the binding holds
         # the parameter tensors' addresses, so it keys on them (`binding_key`) and keeps them alive - a parameter re-allocated
@@ -580,10 +613,15 @@ class MultiAgentEnv(object):
         state = {} if fused.gru is None else {"rnn_state": rnn_state}
         if fused.ou is not None:
             state["noise_state"] = noise_state
-        self._run_rollout(("actor", K, fused.binding_key(), _native.ptr(rnn_state), S, _native.ptr(noise_state)), want, out,
-                          own_buffers, K, obs_every, None, self.scenario.bind_rollout_actor, None, (K, fused),
-                          state if S is None else dict(state, rnn_states_every=S))
+        extra = state if S is None else dict(state, rnn_states_every=S)
+        if cat is not None:
+            extra = dict(extra, act_mode=mode)
+        lead = ("actor", K, fused.binding_key(), _native.ptr(rnn_state), S, _native.ptr(noise_state))
+        self._run_rollout(lead if cat is None else lead + (mode,), want, out,    # the categorical launch bakes the mode in
+                          own_buffers, K, obs_every, None, self.scenario.bind_rollout_actor, None, (K, fused), extra)
         info = dict(state, actions=out["act"])             # the states come back as updated in place
+        if cat is not None:
+            info.update(actions=out["idx"], u=out["act"])
         if "log_prob" in want:
             info["log_prob"] = out["log_prob"]
         if S is not None:
@@ -620,6 +658,32 @@ class MultiAgentEnv(object):
         _native.check(_native.load().fg_actor_noise(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
         return out
 
+    def actor_uniform(self, out=None):
+        """The uniform draws u [B, N] in [0, 1) that a CategoricalActor's next step samples with (`fg_actor_uniform` at the
+        offset of the next launch): word 2 of the Philox block whose words 0 and 1 give `actor_noise()`."""
+        B, N = self.num_envs, self.num_agents
+        if out is None:
+            out = torch.empty((B, N), dtype=torch.float32, device=self.world.device)
+        sc = self.scenario
+        p = self.world.native_params(seed=getattr(sc, "_seed", 0), rng_offset=self._launch_rng_offset(), scripted_ok=True)
+        p.env_index_base = int(getattr(sc, "env_base", 0))
+        _native.check(_native.load().fg_actor_uniform(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
+        return out
+
+    def _categorical(self, logits, u, greedy):
+        """(idx int32 [...], u [..., 2], log_prob [...]) of logits [..., 5] and draws u [...] in the env's action mode
+        (`fg_actor_categorical`: the fused kernels' pick and decode)."""
+        dev = self.world.device
+        logits = logits.detach().to(device=dev, dtype=torch.float32).contiguous()
+        lead = tuple(logits.shape[:-1])
+        idx = torch.empty(lead, dtype=torch.int32, device=dev)
+        act = torch.empty(lead + (2,), dtype=torch.float32, device=dev)
+        logp = torch.empty(lead, dtype=torch.float32, device=dev)
+        _native.check(_native.load().fg_actor_categorical(self._action_mode(), int(bool(greedy)), idx.numel(), logits.data_ptr(),
+                                                          _native.ptr(u), idx.data_ptr(), act.data_ptr(), logp.data_ptr(),
+                                                          _native.current_stream(dev)))
+        return idx, act, logp
+
     def _noise_log_prob(self, eps, log_std):
         """-(eps_0^2 + eps_1^2) / 2 - sum(log_std) - log(2 pi) of eps [B, N, 2] (`fg_actor_log_prob`): [B, N]."""
         eps, log_std = eps.contiguous(), log_std.contiguous()
@@ -638,11 +702,16 @@ class MultiAgentEnv(object):
         step k with k % S == 0, stacked as info['rnn_states'] [ceil(K / S), B, N, state_size].  An OUNoiseActor: `noise_state`
         [B, N, 2] steps with eps from `actor_noise` by the kernels' device function (`fg_actor_ou_step`: for the same eps the
         fused launch's state bits), the action is clamp(inner(obs) + scale * x, -clip, clip), x goes back to mu where the
-        step's done flag is set, is updated in place at the end and comes back as info['noise_state']."""
+        step's done flag is set, is updated in place at the end and comes back as info['noise_state'].  A CategoricalActor:
+        the logits from the module, the draw from `actor_uniform`, the pick and the decode by the kernels' own device functions
+        (`fg_actor_categorical`), then `step` with the index (FG_ACT_INDEX) or its one-hot (FG_ACT_ONEHOT5); info['actions']
+        holds the indices, info['u'] the raw actions, info['log_prob'] the log-probabilities."""
         ou = actor if noise_state is not None else None
         x = noise_state.clone() if ou is not None else None
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
-        body = actor.mean if gaussian else actor
+        cat = actor if isinstance(actor, actor_rollout.CategoricalActor) else None
+        body = actor.mean if gaussian else actor.logits if cat is not None else actor
+        picked, raw = [], []
         h = rnn_state.clone() if rnn_state is not None else None
         logp, states = [], []
         observe = getattr(self.scenario, "observe_batch", None)
@@ -662,6 +731,15 @@ class MultiAgentEnv(object):
             logp.append(self._noise_log_prob(eps, ls))
             return (body(obs) if h is None else mean(obs, k)) + torch.exp(ls) * eps
 
+        def pick(obs, k):                                  # a CategoricalActor on either body
+            greedy = cat.deterministic
+            idx, u_act, lp = self._categorical(body(obs) if h is None else mean(obs, k), None if greedy else self.actor_uniform(),
+                                               greedy)
+            picked.append(idx); raw.append(u_act); logp.append(lp)
+            if self._action_mode() == _native.FG_ACT_INDEX:
+                return idx
+            return torch.nn.functional.one_hot(idx.long(), 5).to(torch.float32)
+
         def explore(obs, k):                               # an OUNoiseActor
             self._ou_step(ou, self.actor_noise(), x)
             return ou.explore(ou.actor(obs), x)
@@ -675,14 +753,18 @@ class MultiAgentEnv(object):
 
         if gaussian:
             act_fn = sample
+        elif cat is not None:
+            act_fn = pick
         elif h is not None:
             act_fn = mean
         else:
             act_fn = explore if ou is not None else lambda obs, k: actor(obs)
         with torch.no_grad():
             obs, rew, done, info = self._step_loop(K, obs_every, act_fn, after_step)
-        if gaussian:
+        if gaussian or cat is not None:
             info["log_prob"] = torch.stack(logp)
+        if cat is not None:
+            info["actions"], info["u"] = torch.stack(picked), torch.stack(raw)
         if h is not None:
             rnn_state.copy_(h)
             info["rnn_state"] = rnn_state
@@ -744,7 +826,8 @@ class MultiAgentEnv(object):
         `mem_fraction` of the free memory; `max_arena_bytes` overrides), this env's own K-step launch is timed on
         `candidates` or more of them and the fastest is kept, every other chunk released (formation_gym/placement.py: the
         rate of a launch depends on which physical memory its buffer is composed of, by 10-20 %; ~0.2 s); where the arena
-        cannot be made, on up to `candidates` whole allocations.  candidates < 2 switches the probe off.  The env's state
+        cannot be made, on up to `candidates` whole allocations.  candidates < 2 switches the probe off.  An env in a discrete
+        action mode (a CategoricalActor's buffers) is timed on the same launches with the mode set aside and put back.  The env's state
         is restored afterwards, also when the probe fails.  escalate=False: one arena only (an arena whose winner gains
         nothing is otherwise followed by up to two four times larger ones).  `obs_env_pitch` (floats, 0 = contiguous) asks for padded env blocks.  The probe's report
         is left in `self.placement`.  Returns the `out` dict to pass to `rollout(..., out=out)`.  The arena lives exactly
@@ -792,6 +875,10 @@ class MultiAgentEnv(object):
 
         arena = None
         self._placing = True
+        # the probe's own launches take raw continuous actions (the built-in controller's, or zeros): an env in a discrete
+        # action mode - whose rollout_actor buffers these are - is timed with the mode set aside, on the same store stream
+        modes = (self.discrete_action_input, self.discrete_action_space, self.force_discrete_action)
+        self.discrete_action_input = self.discrete_action_space = self.force_discrete_action = False
         try:
             placed = placement.probe_arena(slots * B * pitch, lambda flat: time_fn(shaped(flat)), dev, trials=candidates,
                                            mem_fraction=mem_fraction, max_arena_bytes=max_arena_bytes, escalate=escalate)
@@ -803,6 +890,7 @@ class MultiAgentEnv(object):
         finally:
             # whatever happened inside the probe (out of memory, a failed launch): the env is usable and unchanged afterwards
             self._placing = False
+            self.discrete_action_input, self.discrete_action_space, self.force_discrete_action = modes
             self._roll_launchers.clear()               # bindings made on the candidates keep them alive: drop them,
             torch.cuda.empty_cache()                   # then hand the losers back to the driver
             self._restore(snap)

@@ -260,7 +260,7 @@ class Scenario(BaseScenario):
         return _native.bind_launch(fn, p, *args, keep=out)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None,
-                           noise_state=None):
+                           noise_state=None, act_mode=0):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
@@ -281,7 +281,12 @@ class Scenario(BaseScenario):
           an OUNoiseActor (`actor.ou`)          `fg_rollout_hd_actor_ou` / `fg_rollout_hd_actor_ou_per_agent` on the plain or the
                                                 BatchNorm actor (in_bn or NULL), `noise_state` [B,N,2] read and updated in place
                                                 like `rnn_state`; the FgActorOu struct is filled from the module's scalars
-                                                before every launch, so a scale annealed between calls needs no new binding"""
+                                                before every launch, so a scale annealed between calls needs no new binding
+          a CategoricalActor (`actor.cat`)      `fg_rollout_hd_actor_cat` on the plain, the LayerNorm or the recurrent body
+                                                (norm / gru or NULL) in the env's action mode `act_mode`: the indices in
+                                                out["idx"] [K,B,N] int32, the log-probs in out["log_prob"], the decoded actions
+                                                in out["act"]; `rnn_state` and out["rnn_states"] as above; the module's
+                                                `deterministic` flag is read before every launch"""
         lib = _native.load()
         log_std = actor.log_std
         fas, norm, gru, bns = _native.actor_structs(actor)
@@ -300,6 +305,20 @@ class Scenario(BaseScenario):
         p = self.params(world, auto_reset, 0, out.get("obs"))
         state = (world.num_envs, len(world.agents), int(K)) + self._state_ptrs(world, out["act"]) + self._out_ptrs(out)
         tail = (int(obs_every), _native.current_stream(world.device))
+        cat = actor.cat
+        if cat is not None:
+            if ou is not None or bns is not None or actor.per_agent or log_std is not None:
+                raise NotImplementedError("a CategoricalActor fuses on the plain, the LayerNorm and the recurrent body only")
+            keep_states = rnn_states_every is not None
+            args = state + (out["idx"].data_ptr(), out["log_prob"].data_ptr(), _native.ptr(rnn_state) if gru is not None else None,
+                            out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1) + tail
+            keep = (out, actor.tensors(), fas, norm, gru, rnn_state)
+            by_flag = [_native.bind_launch(lib.fg_rollout_hd_actor_cat, p, fas, norm, gru, int(act_mode), greedy, *args, keep=keep)
+                       for greedy in (0, 1)]
+
+            def launch_cat(rng_offset=0):              # the module's flag as it is now: sampled or the distribution's mode
+                return by_flag[1 if cat.deterministic else 0](rng_offset)
+            return launch_cat
         if (gru is not None and norm is None) or (norm is not None and actor.per_agent):
             raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
         # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, and

@@ -84,12 +84,13 @@ class ActorRolloutMixin(object):
         `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here;
         `fused_gru_hidden=()`: nor a recurrent one, so a RecurrentActor does too; `fused_bn_hidden=()`: nor one with an input
         BatchNorm, so the MADDPG trainers' BatchNorm actor does too; `fused_ou=False`: no OU kernel, so an OUNoiseActor does
-        too."""
+        too; `fused_cat=False`: nor a categorical one, so a CategoricalActor does too."""
         from formation_gym import actor_rollout
         d = self._actor_descriptor(world)
         facts = actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
                                              self.obs_dim(world), d.variant)
-        return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=(), fused_bn_hidden=(), fused_ou=False)
+        return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=(), fused_bn_hidden=(), fused_ou=False,
+                                                 fused_cat=False)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs
@@ -108,6 +109,8 @@ class ActorRolloutMixin(object):
             raise NotImplementedError("a BatchNorm actor has no fused launch in %s" % type(self).__name__)
         if actor.ou is not None:
             raise NotImplementedError("an OUNoiseActor has no fused launch in %s" % type(self).__name__)
+        if actor.cat is not None:
+            raise NotImplementedError("a CategoricalActor has no fused launch in %s" % type(self).__name__)
         log_std, fa = actor.log_std, _native.actor_structs(actor)[0]
         p, d = self.params(world, auto_reset=auto_reset), self._actor_descriptor(world)
         # _rollout_args with the recorded actions in the place of the action sequence: (B, N, K, state ..., act, landmarks, ...)

@@ -744,6 +744,46 @@ int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor*
  * no-op. */
 int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream);
 
+/* The MAPPO trainers' discrete-action policy (make_env(..., discrete_action=True): a head Linear(hidden, 5) under a
+ * Categorical) as the fourth member of the plain, LayerNorm and recurrent families: cat_actor_kernel (norm == NULL),
+ * ln_cat_actor_kernel (norm) and gru_cat_actor_kernel (norm and gru), at those families' N and hidden widths.  The actor is
+ * fg_rollout_hd_actor's / _norm's / _gru's with w3 [5][hidden], b3 [5] (or NULL) and out_tanh == 0.  Per (env b, agent i,
+ * step k) the five fp32 logits l_j are ascending fmaf chains from b3[j], and, in fp32,
+ *     m = max_j l_j,  e_j = exp(l_j - m),  c_j = e_0 + .. + e_j,  s = c_4          (exp: __expf, log below: __logf)
+ *     sampled (greedy == 0): t = u s, idx the first j in 0..3 with t < c_j, else 4
+ *     greedy  (greedy != 0): idx the lowest index attaining m (the distribution's mode)
+ *     log_prob = (l_idx - m) - log(s)
+ * with u = (c[2] >> 8) 2^-24 in [0, 1), c the Philox4x32-10 block fg_actor_noise draws for (b, i, k) - key seed, counter
+ * {b + env_index_base, i ^ 0xA0000000, lo32(off), hi32(off)}, off = rng_base + k; its words 0 and 1 stay the Gaussian members'
+ * draw.  The index becomes the raw action u by act_mode, the env's own: FG_ACT_ONEHOT5 takes the one-hot e_idx through
+ * (a1 - a2, a3 - a4) - 1: +x, 2: -x, 3: +y, 4: -y - and FG_ACT_INDEX is fg_decode_actions' 1: -x, 2: +x, 3: -y, 4: +y; index 0
+ * is no move.  `greedy` and `act_mode` are run-time facts of the launch: one kernel per (family, N, hidden).
+ * act_seq [K][B][N][2] (required) receives the decoded u, so fg_rollout_hd driven by it returns the same results bit for bit;
+ * idx_seq [K][B][N] int32 (required) the indices, logp_seq [K][B][N] (NULL: not written) the log-probs.  rnn_state [B][N][hidden]
+ * (gru only; else ignored) as in fg_rollout_hd_actor_gru; rnn_states (NULL: none kept) / states_every as in
+ * fg_rollout_hd_actor_gru_states.  Checks and status codes are fg_rollout_hd_actor_norm's / _gru's in their order; in addition
+ * FG_ERR_BAD_ARG for out_tanh != 0, an act_mode other than the two above (FG_ACT_ARGMAX included), gru without norm, a NULL
+ * idx_seq with B > 0, and FG_ERR_ALIGNMENT for an idx_seq or logp_seq that is not 4-byte aligned.  B == 0 returns FG_OK. */
+int fg_rollout_hd_actor_cat(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                            int act_mode, int greedy, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                            float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                            float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                            float* logp_seq, float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream);
+/* Dry run: same checks and status codes (the buffers' apart), names the cat_actor_kernel<N,H> / ln_cat_actor_kernel<N,H> /
+ * gru_cat_actor_kernel<N,H> instantiation and its launch geometry.  Touches no device. */
+int fg_describe_actor_cat_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
+                                 int act_mode, int greedy, int B, int N, int K, int obs_every, char* out, int out_len);
+/* One step's uniform draws u [B][N] (fp32 in DEVICE memory, 4-byte aligned) at rng_base(params), by the device function of
+ * the categorical kernels: fg_actor_noise's sibling for the host-paced loop of a categorical policy. */
+int fg_actor_uniform(const FgParams* params, int B, int N, float* u, void* stream);
+/* The pick above and the decode on `count` rows of caller-supplied logits [count][5] and draws u [count] (NULL allowed when
+ * greedy), by the fused kernels' device functions: idx [count] int32 (required), act [count][2] (8-byte aligned; NULL: not
+ * written), logp [count] (NULL: not written), all fp32 / int32 in DEVICE memory.  The host-paced loop calls it once per step
+ * on the module's logits and fg_actor_uniform's draw.  FG_ERR_BAD_ARG for another act_mode, a negative count, a NULL logits,
+ * idx or (sampling) u; count == 0 is a no-op. */
+int fg_actor_categorical(int act_mode, int greedy, int64_t count, const float* logits, const float* u, int32_t* idx, float* act,
+                         float* logp, void* stream);
+
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
  * (scn_lane_actor, or scn_lane_actor_gauss when log_std is not NULL), with the actor

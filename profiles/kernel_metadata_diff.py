@@ -3,7 +3,8 @@ libformation_hip.so, for the kernels whose demangled name contains one of the gi
 
     python profiles/kernel_metadata_diff.py OLD.so NEW.so [substring ...]
 
-Default substrings: the twelve formation_hd_env actor kernels (six families, each deterministic and Gaussian).  Prints one
+Default substrings: the formation_hd_env actor kernels (six families, each deterministic and Gaussian, their OU members and the
+three categorical members).  Prints one
 line per substring - kernels compared, kernels that differ - then every differing kernel with both records, and exits 1 if any
 differ or a kernel is missing on either side."""
 import os
@@ -15,7 +16,7 @@ from tests.isa_scan import kernel_resources  # noqa: E402
 FAMILIES = ("actor_rollout_kernel<", "actor_sample_kernel<", "pa_actor_kernel<", "pa_sample_kernel<", "ln_actor_kernel<",
             "ln_sample_kernel<", "gru_actor_kernel<", "gru_sample_kernel<", "::bn_actor_kernel<", "::bn_sample_kernel<",
             "pa_bn_actor_kernel<", "pa_bn_sample_kernel<", "::ou_actor_kernel<", "::pa_ou_actor_kernel<", "::bn_ou_actor_kernel<",
-            "pa_bn_ou_actor_kernel<")
+            "pa_bn_ou_actor_kernel<", "::cat_actor_kernel<", "ln_cat_actor_kernel<", "gru_cat_actor_kernel<")
 
 
 def main(argv):
