@@ -23,6 +23,10 @@
 // `constexpr bool CAT` with `cw` (ActorCatW; CAT = false: an empty constant) selects cat_actor_kernel / ln_cat_actor_kernel /
 // gru_cat_actor_kernel: the shared body with the five-output head of fg_actor_mlp.inc, whose lanes leave the decoded action in
 // the actions' block and the row's index and log-prob in two blocks [E N] behind it; the physics phase stores the three.
+// `constexpr bool OBS16` with `obs_fmt` (the last kernel argument; OBS16 = false: the constant 0) selects the 16-bit members
+// actor_sample_obs16 / ln_sample_obs16 / gru_sample_obs16 / cat_actor_obs16 / ln_cat_actor_obs16 / gru_cat_actor_obs16: the
+// Gaussian or categorical body whose stream phase stores fp16 / bf16 units through write_obs16 (fg_obs_writers.hpp) instead of
+// write_obs_rows, the format a run-time, wave-uniform fact of the launch; its tile is the wave's own activation tile.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -500,8 +504,23 @@
         if (a.obs_every > 1) { want_obs = want_obs && ((k + 1) % a.obs_every == 0); slot = k / a.obs_every; }
         if (want_obs) {
             const size_t unit0 = ((size_t)slot * a.B + b0) * (size_t)a.obs_pitch;
+            if constexpr (OBS16) {
+                // the wave's 16-bit tile in its own activation tile: only this wave touches either, the stream phase precedes
+                // its actor pass in program order and LDS operations of a wave complete in order - no barrier.  ONE tile per
+                // wave: at 3 and 9 agents a wave has one tile per step anyway, at 27 its up to six are composed and streamed in
+                // turn (a second tile fits at H = 64 only, and with it gru_cat_actor_obs16<27,64> keeps a scratch slot).
+                constexpr int OW = obs16_tile_words<NC, NW, E>(), OT = 1;
+                static_assert(OT * OW <= FG_ACTOR_ROWS * HS, "the 16-bit tile fits the wave's activation tile");
+                static_assert((E * env_block_floats(N) + actor_out_blocks(SAMPLE, CAT) * E * N + WS + WB + LNS + BNS + GS) % 4 == 0 &&
+                              (FG_ACTOR_ROWS * HS) % 4 == 0, "the 16-bit tiles start on a 16-byte boundary");
+                write_obs16<NC, NW, E, FG_WR_OBS_RT, OT, FG_ACTOR_ROWS * HS>(
+                    reinterpret_cast<const float2*>(smemf), env_block_floats(N) / 2, wave, reinterpret_cast<uint32_t*>(hbuf),
+                    reinterpret_cast<uint32_t*>(a.obs) + unit0, unit0, El, obs_fmt);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the tiles' reads before the pass's stores (other types)
+            } else {
             write_obs_rows<NC, NW, E>(reinterpret_cast<const float2*>(smemf), env_block_floats(N) / 2, wave,
                                       reinterpret_cast<float2*>(a.obs) + unit0, (size_t)a.obs_pitch, El, 3);
+            }
         }
         if (k + 1 < a.K) actor(rbase + k + 1);         // step k + 1 draws at its own offset
         __syncthreads();

@@ -111,6 +111,17 @@
 // stores all three.  ONE kernel per (family, N, H): `greedy` and the action mode are run-time, wave-uniform facts of the launch
 // (ActorCatW).  There is no tanh and no log_std.
 //
+// actor_sample_obs16<N,H>, ln_sample_obs16<N,H>, gru_sample_obs16<N,H>, cat_actor_obs16<N,H>, ln_cat_actor_obs16<N,H> and
+// gru_cat_actor_obs16<N,H> (fg_rollout_hd_actor_obs16, fg_rollout_hd_actor_cat_obs16; N in {3, 9, 27}, H in {32, 64}) are the
+// Gaussian and the categorical member of the plain, LayerNorm and recurrent families with 16-bit observations, selected by
+// `constexpr bool OBS16` (false in every other kernel, whose instructions it leaves as they were): the stream phase stores each
+// (x, y) unit as one 32-bit word of two fp16 or bf16 halves through write_obs16 (fg_obs_writers.hpp) - the subtractions of
+// write_obs_rows on the same table entries, packed round to nearest even: `.to(dtype)` of the fp32 kernel's observations bit for
+// bit - and nothing else differs.  ONE kernel per (member, N, H): the format is the last kernel argument, a run-time,
+// wave-uniform fact of the launch.  The writer's tile (one per wave, obs16_tile_words words) is the wave's own activation tile:
+// only that wave touches either, its stream phase precedes its actor pass in program order, so no barrier and no LDS is added.
+// a.obs then holds 32-bit units and a.obs_pitch counts them (3 N^2 per env: a contiguous tensor only).
+//
 // How a family is wired up: the twelve kernels (sixteen with the OU members) are six family blocks at the end of this file, each the two kernel names, the
 // four flags, the operands the family takes and the ones it does not, around fg_actor_kernel_pair.inc, which emits the
 // deterministic / Gaussian pair - and, where the block names one (FG_ACTOR_OUK), the OU member - with
@@ -441,6 +452,8 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 #define FG_ACTOR_OUK      ou_actor_kernel
 #define FG_ACTOR_CATK     cat_actor_kernel
 #define FG_ACTOR_SMP      actor_sample_kernel
+#define FG_ACTOR_SMP16    actor_sample_obs16
+#define FG_ACTOR_CAT16    cat_actor_obs16
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
@@ -459,6 +472,8 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 #define FG_ACTOR_DET      ln_actor_kernel
 #define FG_ACTOR_CATK     ln_cat_actor_kernel
 #define FG_ACTOR_SMP      ln_sample_kernel
+#define FG_ACTOR_SMP16    ln_sample_obs16
+#define FG_ACTOR_CAT16    ln_cat_actor_obs16
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = false, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
@@ -468,6 +483,8 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 #define FG_ACTOR_DET      gru_actor_kernel
 #define FG_ACTOR_CATK     gru_cat_actor_kernel
 #define FG_ACTOR_SMP      gru_sample_kernel
+#define FG_ACTOR_SMP16    gru_sample_obs16
+#define FG_ACTOR_CAT16    gru_cat_actor_obs16
 #define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = true, INBN = false
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw, const ActorGruW gw
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_TAB

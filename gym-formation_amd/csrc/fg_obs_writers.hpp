@@ -514,6 +514,10 @@ template <int NC, int NW, int E, int CHMAX = 4> struct SpanGather {
 // ---------------------------------------------------------------------------
 constexpr int FG_WR_OBS_F16 = 65, FG_WR_OBS_BF16 = 66;                  // rollout_kernel's WR values for this writer, one per format
 constexpr bool roll_writer_obs16(int wr) { return wr == FG_WR_OBS_F16 || wr == FG_WR_OBS_BF16; }
+// FMT of write_obs16 for a format that is a run-time, wave-uniform fact of the launch (the actor kernels' 16-bit members,
+// fg_actor_rollout_body.inc): the argument `fmt` then holds one of the two values above, and the call is one scalar branch
+// between the two formats' code (a select per unit between both conversions costs the recurrent kernels a scratch slot)
+constexpr int FG_WR_OBS_RT = 67;
 template <int NC> constexpr int obs16_rows() { return NC > 9 ? 9 : NC; }                                  // rows of an env per tile
 template <int NC, int NW, int E> constexpr int obs16_envs() { return NC <= 9 ? E / NW : 1; }                // envs per tile
 // 32-bit words of one tile: its units, the 16-byte phase in front, rounded up to whole 16-byte pieces
@@ -535,16 +539,24 @@ template <int FMT> FG_DEV uint32_t obs16_pack(float x, float y) {
 
 // tables0 / env_stride: as write_obs_rows; tiles: 2 * NW tiles of obs16_tile_words (16-byte aligned); span: the workgroup's
 // first unit in the observation tensor, unit0 its index there (the tensor's base is 16-byte aligned); El envs, 3 N^2 units apart
-template <int NC, int NW, int E, int FMT>
+// NT: tiles per wave - 2, or 1: every tile composed and streamed in turn in the one tile (LDS operations of a wave complete in
+// order).  WSTRIDE: words between the tiles of consecutive waves (0: NT tiles), a multiple of 4.  fmt: FMT == FG_WR_OBS_RT only.
+template <int NC, int NW, int E, int FMT, int NT = 2, int WSTRIDE = 0>
 FG_DEV void write_obs16(const float2* __restrict__ tables0, int env_stride, int w, uint32_t* __restrict__ tiles,
-                        uint32_t* __restrict__ span, size_t unit0, int El) {
+                        uint32_t* __restrict__ span, size_t unit0, int El, int fmt = 0) {
     constexpr int N = NC, RT = obs16_rows<NC>(), ET = obs16_envs<NC, NW, E>(), WORDS = obs16_tile_words<NC, NW, E>();
     static_assert(N <= 32 && N % RT == 0 && E >= NW && E % NW == 0, "16-bit writer: N <= 32, whole rows per tile, whole envs per wave");
     static_assert(ET == 1 || RT == N, "a tile of several envs holds them whole");
+    if constexpr (FMT == FG_WR_OBS_RT) {
+        if (fmt == FG_WR_OBS_F16) write_obs16<NC, NW, E, FG_WR_OBS_F16, NT, WSTRIDE>(tables0, env_stride, w, tiles, span, unit0, El);
+        else write_obs16<NC, NW, E, FG_WR_OBS_BF16, NT, WSTRIDE>(tables0, env_stride, w, tiles, span, unit0, El);
+        return;
+    }
+    static_assert((NT == 1 || NT == 2) && WSTRIDE % 4 == 0 && (WSTRIDE == 0 || WSTRIDE >= NT * WORDS), "16-bit writer: tiles per wave");
     constexpr unsigned ROWU = 3u * N, ENVU = ROWU * N, TU = ROWU * RT;    // units per row, per env, per env's share of a tile
     constexpr int TILES_ENV = N / RT;
     const int lane = threadIdx.x & 63;
-    uint32_t* const tile0 = tiles + w * 2 * WORDS;
+    uint32_t* const tile0 = tiles + w * (WSTRIDE ? WSTRIDE : NT * WORDS);
     constexpr int RW = 64 / N;
     const int rsub = lane / N, u = lane - rsub * N;
     const bool act = rsub < RW;
@@ -565,7 +577,7 @@ FG_DEV void write_obs16(const float2* __restrict__ tables0, int env_stride, int 
     auto compose = [&](int t) {
         int ee, r0, ne; locate(t, ee, r0, ne);
         const unsigned par = (unsigned)((unit0 + (size_t)ee * ENVU + (size_t)r0 * ROWU) & 3);
-        uint32_t* img = tile0 + (t & 1) * WORDS + par;                    // no restrict: the two tiles alternate
+        uint32_t* img = tile0 + (NT == 2 ? (t & 1) : 0) * WORDS + par;    // no restrict: the two tiles alternate
         for (int j = 0; j < ne; ++j, img += TU) {
             const float2* __restrict__ AA = tables0 + (size_t)(ee + j) * env_stride;
             const float2 Pm = lds_if(act && u >= 1, AA, u - 1);           // per-env register cache, as write_obs_rows
@@ -593,7 +605,7 @@ FG_DEV void write_obs16(const float2* __restrict__ tables0, int env_stride, int 
         int ee, r0, ne; locate(t, ee, r0, ne);
         const size_t first = (size_t)ee * ENVU + (size_t)r0 * ROWU;
         const unsigned par = (unsigned)((unit0 + first) & 3);
-        const uint32_t* img = tile0 + (t & 1) * WORDS + par;
+        const uint32_t* img = tile0 + (NT == 2 ? (t & 1) : 0) * WORDS + par;
         uint32_t* __restrict__ out = span + first;
         const unsigned n = (unsigned)ne * TU;                             // units of this tile (>= 27: more than a head)
         const unsigned head = (4u - par) & 3u;                            // single words up to the first 16-byte boundary
@@ -610,6 +622,10 @@ FG_DEV void write_obs16(const float2* __restrict__ tables0, int env_stride, int 
         const unsigned tail = (n - head) & 3u, t0 = head + 4u * nq;       // ... and behind the last one
         if ((unsigned)lane < tail) out[t0 + lane] = img[t0 + lane];
     };
+    if constexpr (NT == 1) {
+        for (int t = 0; t < total; ++t) { compose(t); stream(t); }
+        return;
+    }
     if (total > 0) compose(0);
     for (int t = 0; t < total; ++t) {
         if (t + 1 < total) compose(t + 1);

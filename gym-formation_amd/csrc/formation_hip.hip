@@ -1002,6 +1002,10 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
 // those operands; the LayerNorm families have none (hd_no_ou_kernel, never instantiated: no entry builds such a call).
 // The categorical column is the fourth member (fg_rollout_hd_actor_cat: a call with `cat` set), which takes an ActorCatW after
 // the operands; the per-agent and BatchNorm families have none (hd_no_cat_kernel, likewise).
+// The two 16-bit columns are the Gaussian and the categorical member with the 16-bit observation writer
+// (fg_rollout_hd_actor_obs16 / fg_rollout_hd_actor_cat_obs16: a call with `obs_format` set), which take the writer's format
+// after the member's arguments; the families with a categorical member have them, at N in {3, 9, 27} and H in {32, 64}
+// (hd_no_obs16_kernel elsewhere, likewise).
 enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
                    HD_ACTOR_BN_PER_AGENT };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
@@ -1009,8 +1013,10 @@ static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_
                                              "fg_rollout_hd_actor_bn_per_agent"};
 template <int NC, int H> constexpr std::nullptr_t hd_no_ou_kernel = nullptr;
 template <int NC, int H> constexpr std::nullptr_t hd_no_cat_kernel = nullptr;
+template <int NC, int H> constexpr std::nullptr_t hd_no_obs16_kernel = nullptr;
+constexpr bool actor_obs16_shape(int n, int h) { return (n == 3 || n == 9 || n == 27) && (h == 32 || h == 64); }
 template <HdActorKind> struct HdActorFamily;
-#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, CATK, WHAT)                                      \
+#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, CATK, SMP16, CAT16, WHAT)                        \
     template <> struct HdActorFamily<KIND> {                                                                      \
         static constexpr bool per_agent = PA, lnorm = LN, gru = GR, in_bn = BN;                                   \
         static constexpr int max_h = MAXH;                                                                        \
@@ -1020,10 +1026,15 @@ template <HdActorKind> struct HdActorFamily;
         template <int NC, int H> static constexpr auto ou = OUK<NC, H>;                                           \
         static constexpr bool has_cat = !PA && !BN;                                                               \
         template <int NC, int H> static constexpr auto cat = CATK<NC, H>;                                         \
+        static constexpr bool has_obs16 = !PA && !BN;                                                             \
+        template <int NC, int H> static constexpr auto smp16 = SMP16<NC, H>;                                      \
+        template <int NC, int H> static constexpr auto cat16 = CAT16<NC, H>;                                      \
         static constexpr const char* det_name = #DET;                                                             \
         static constexpr const char* smp_name = #SMP;                                                             \
         static constexpr const char* ou_name = #OUK;                                                              \
         static constexpr const char* cat_name = #CATK;                                                            \
+        static constexpr const char* smp16_name = #SMP16;                                                         \
+        static constexpr const char* cat16_name = #CAT16;                                                         \
         static constexpr const char* fail_fmt = WHAT "actor rollout launch failed: %s";                           \
         static_assert(!(PA && LN), "no per-agent actor kernel with LayerNorms");                                  \
         static_assert(!GR || LN, "the recurrent actor's base is the LayerNorm actor");                            \
@@ -1031,25 +1042,41 @@ template <HdActorKind> struct HdActorFamily;
         template <int NC, int H, bool SAMPLE, bool OU = false, bool CAT = false>                                  \
         static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN, OU, CAT>();               \
     };
-//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise               categorical
-FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       cat_actor_kernel,     "")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    hd_no_cat_kernel,     "per-agent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       ln_cat_actor_kernel,  "LayerNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       gru_cat_actor_kernel, "recurrent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    hd_no_cat_kernel,     "BatchNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, hd_no_cat_kernel,     "per-agent BatchNorm ")
+//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise               categorical           Gaussian, 16-bit    categorical, 16-bit
+FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       cat_actor_kernel,     actor_sample_obs16, cat_actor_obs16,     "")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "per-agent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       ln_cat_actor_kernel,  ln_sample_obs16,    ln_cat_actor_obs16,  "LayerNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       gru_cat_actor_kernel, gru_sample_obs16,   gru_cat_actor_obs16, "recurrent ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "BatchNorm ")
+FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "per-agent BatchNorm ")
 #undef FG_HD_ACTOR_FAMILY
 template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
 
-// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member, or with `cw` its categorical member; `w`:
-// the family's operands
+// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member, or with `cw` its categorical member, or with
+// `obs_format` (FG_OBS_F16 / FG_OBS_BF16; 0: fp32) the 16-bit twin of its Gaussian or - `cw` - categorical member; `w`: the
+// family's operands
 template <int NC, int H, class F, class... W>
-static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, const ActorCatW* cw, hipStream_t st,
-                           const W&... w) {
+static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, const ActorCatW* cw, int obs_format,
+                           hipStream_t st, const W&... w) {
     static_assert(F::template lds_bytes<NC, H, true> <= 160 * 1024, "actor rollout LDS");
     constexpr int E = actor_envs(NC);
     char targs[16];
     snprintf(targs, sizeof(targs), "%d,%d", NC, H);
+    if (obs_format) {                                  // (the 16-bit tiles share the wave's activation tile: the fp32 twin's LDS)
+        if constexpr (F::has_obs16 && actor_obs16_shape(NC, H)) {
+            const int fmt = obs_format == FG_OBS_F16 ? FG_WR_OBS_F16 : FG_WR_OBS_BF16;
+            const int grid = (a.B + E - 1) / E;
+            if (cw) {
+                constexpr int lds = F::template lds_bytes<NC, H, false, false, true>;
+                if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::cat16_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
+                return launch<F::template cat16<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *cw, fmt);
+            }
+            constexpr int lds = F::template lds_bytes<NC, H, true>;
+            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::smp16_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
+            return launch<F::template smp16<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., log_std, logp, fmt);
+        }
+        return fail(FG_ERR_UNSUPPORTED_N, "16-bit observations: no fused actor launch for this family, agent count or width%s");   // (unreachable after hd_actor_check)
+    }
     if constexpr (F::has_ou) {
         if (ow) {
             constexpr int lds = F::template lds_bytes<NC, H, false, true>;
@@ -1149,9 +1176,14 @@ struct HdActorCall {
     // fg_rollout_hd_actor_cat only (`cat.on`, which also puts its name on the messages): the kind is the body's family - shared,
     // LayerNorm or recurrent - whose categorical member runs
     HdActorHead cat = {};
+    // fg_rollout_hd_actor_obs16 and fg_rollout_hd_actor_cat_obs16 only (not 0, which also puts their names on the messages):
+    // FG_OBS_F16 / FG_OBS_BF16, or -1 for a value that is neither; the kind is the body's family, whose 16-bit Gaussian or
+    // - `cat.on` - categorical member runs, and the observations' buffer holds 16-bit elements
+    int obs_format = 0;
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
 static const char* hd_actor_who(const HdActorCall& c) {
+    if (c.obs_format) return c.cat.on ? "fg_rollout_hd_actor_cat_obs16" : "fg_rollout_hd_actor_obs16";
     if (c.cat.on) return "fg_rollout_hd_actor_cat";
     if (c.noise.on) return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
     return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
@@ -1233,7 +1265,7 @@ static int actor_cat_check(const char* who, const FgActor* actor, const HdActorH
     return FG_OK;
 }
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
-// this order, which is ABI - params, B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
+// this order, which is ABI - params, (a 16-bit member: obs_format, the env pitch, log_std, N in {3, 9, 27}, hidden = 128,) B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
 // and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), the OU noise with its state, the
 // categorical head with its outputs, log_std, logp.  The shared actor's
 // checks name fg_rollout_hd_actor through the sample and norm entries too, the log_std checks fg_rollout_hd_actor_sample.
@@ -1243,6 +1275,13 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
     const char* const shared = hd_actor_entry[hd_actor_members(c) ? HD_ACTOR_PER_AGENT : HD_ACTOR_SHARED];
     int rc = check_params(params);
     if (rc) return rc;
+    if (c.obs_format) {                                // the 16-bit members: what the writer and their instantiations ask for
+        if (c.obs_format < 0) return fail(FG_ERR_BAD_ARG, "%s: obs_format must be FG_OBS_F16 or FG_OBS_BF16", who);
+        if (params->obs_env_pitch != 0) return fail(FG_ERR_BAD_ARG, "%s: a padded env pitch (obs_env_pitch) is not supported", who);
+        if (!c.cat.on && !c.log_std) return fail(FG_ERR_BAD_ARG, "%s: log_std is NULL", who);
+        if (N != 3 && N != 9 && N != 27) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 9 or 27", who);
+        if (c.actor && c.actor->hidden == 128) return fail(FG_ERR_BAD_ARG, "%s: hidden must be 32 or 64", who);
+    }
     if (B < 0 || K < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0 and K >= 1 required", shared);
     if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", shared);
     if (hd_actor_members(c)) {
@@ -1343,7 +1382,7 @@ static int hd_actor_run(const Args& a, const HdActorCall& c, hipStream_t st, con
     const ActorCatW cw = {c.cat.mode, c.cat.greedy ? 1 : 0, c.cat.idx, c.cat.logp};
     return actor_nh_dispatch<HdActorFamily<KIND>::max_h>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
         return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(
-            a, c.log_std, c.logp, c.noise.on ? &ow : nullptr, c.cat.on ? &cw : nullptr, st, w...);
+            a, c.log_std, c.logp, c.noise.on ? &ow : nullptr, c.cat.on ? &cw : nullptr, c.obs_format, st, w...);
     });
 }
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream
@@ -2119,6 +2158,44 @@ int fg_rollout_hd_actor_cat(const FgParams* params, const FgActor* actor, const 
                                done_seq}, obs_every, stream);
 }
 
+// the 16-bit entries' call: the Gaussian (`log_std`, required) or categorical call of the body's family with `obs_format` set
+static HdActorCall hd_actor_obs16_call(HdActorCall c, int obs_format) {
+    c.obs_format = (obs_format == FG_OBS_F16 || obs_format == FG_OBS_BF16) ? obs_format : -1;
+    return c;
+}
+static HdActorCall hd_actor_gauss_call(const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru, const float* log_std,
+                                       float* logp, float* rnn_state, float* rnn_states, int states_every) {
+    HdActorCall c{gru ? HD_ACTOR_GRU : norm ? HD_ACTOR_NORM : HD_ACTOR_SAMPLE, actor, log_std, logp};
+    c.norm = norm;
+    c.gru = gru;
+    c.rnn_state = rnn_state;
+    if (gru && rnn_states) { c.states_entry = true; c.rnn_states = rnn_states; c.states_every = states_every; }
+    return c;
+}
+
+int fg_rollout_hd_actor_obs16(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                              const FgActorGru* gru, const float* log_std, int B, int N, int K, float* pos_x, float* pos_y,
+                              float* vel_x, float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                              void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                              float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream) {
+    return rollout_actor_impl(params, hd_actor_obs16_call(hd_actor_gauss_call(actor, norm, gru, log_std, logp_seq, rnn_state, rnn_states,
+                                                                              states_every), obs_format), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, static_cast<float*>(obs_seq), reward_seq,
+                               indiv_seq, done_seq}, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_cat_obs16(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                  const FgActorGru* gru, int act_mode, int greedy, int B, int N, int K, float* pos_x, float* pos_y,
+                                  float* vel_x, float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                  void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                                  float* logp_seq, float* rnn_state, float* rnn_states, int states_every, int obs_every,
+                                  void* stream) {
+    return rollout_actor_impl(params, hd_actor_obs16_call(hd_actor_cat_call(actor, norm, gru, act_mode, greedy, idx_seq, logp_seq,
+                                                                            rnn_state, rnn_states, states_every), obs_format), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, static_cast<float*>(obs_seq), reward_seq,
+                               indiv_seq, done_seq}, obs_every, stream);
+}
+
 int fg_actor_uniform(const FgParams* params, int B, int N, float* u, void* stream) {
     int rc = check_params(params);
     if (rc) return rc;
@@ -2247,6 +2324,26 @@ int fg_describe_actor_cat_launch(const FgParams* params, const FgActor* actor, c
     int32_t* const idx = reinterpret_cast<int32_t*>((uintptr_t)4096);
     return describe_actor_impl("fg_describe_actor_cat_launch", params,
                                hd_actor_cat_call(actor, norm, gru, act_mode, greedy, idx, nullptr, state, nullptr, 1),
+                               B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_obs16_launch(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                   const FgActorGru* gru, const float* log_std, int B, int N, int K, int obs_every, char* out,
+                                   int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // a stand-in: the dry run has no hidden state
+    return describe_actor_impl("fg_describe_actor_obs16_launch", params,
+                               hd_actor_obs16_call(hd_actor_gauss_call(actor, norm, gru, log_std, nullptr, state, nullptr, 1), obs_format),
+                               B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_cat_obs16_launch(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                       const FgActorGru* gru, int act_mode, int greedy, int B, int N, int K, int obs_every,
+                                       char* out, int out_len) {
+    float* const state = reinterpret_cast<float*>((uintptr_t)4096);      // stand-ins: the dry run has no state and no outputs
+    int32_t* const idx = reinterpret_cast<int32_t*>((uintptr_t)4096);
+    return describe_actor_impl("fg_describe_actor_cat_obs16_launch", params,
+                               hd_actor_obs16_call(hd_actor_cat_call(actor, norm, gru, act_mode, greedy, idx, nullptr, state, nullptr, 1),
+                                                   obs_format),
                                B, N, K, obs_every, out, out_len);
 }
 

@@ -281,6 +281,14 @@ SIGNATURES = {
                                      _I, _I, _I, _I, _I] + [_P] * 16 + [_I, _I, _P]),
     "fg_describe_actor_cat_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru),
                                           _I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_obs16": (_I, [_PP, _I, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm), ctypes.POINTER(FgActorGru),
+                                       _P, _I, _I, _I] + [_P] * 15 + [_I, _I, _P]),
+    "fg_describe_actor_obs16_launch": (_I, [_PP, _I, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm),
+                                            ctypes.POINTER(FgActorGru), _P, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_actor_cat_obs16": (_I, [_PP, _I, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm),
+                                           ctypes.POINTER(FgActorGru), _I, _I, _I, _I, _I] + [_P] * 16 + [_I, _I, _P]),
+    "fg_describe_actor_cat_obs16_launch": (_I, [_PP, _I, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorNorm),
+                                                ctypes.POINTER(FgActorGru), _I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_actor_uniform": (_I, [_PP, _I, _I, _P, _P]),
     "fg_actor_categorical": (_I, [_I, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14

@@ -396,8 +396,10 @@ class MultiAgentEnv(object):
                           getattr(self.scenario, "bind_rollout_policy", None), roll, (K, num_agents_per_layer))
         return self._rollout_result(out, {"actions": out["act"]})
 
-    def obs_path(self, obs_dtype, policy=False):
-        """How `rollout(..., obs_dtype=obs_dtype)` (policy=True: `rollout_policy`, 3 agents per layer) produces its 16-bit
+    def obs_path(self, obs_dtype, policy=False, actor=None):
+        """How `rollout(..., obs_dtype=obs_dtype)` (policy=True: `rollout_policy`, 3 agents per layer; actor=...:
+        `rollout_actor` with that actor, 'fused' when the actor resolves to a fused launch - `_resolve_actor` - and the
+        library's dry run `fg_describe_actor_obs16_launch` / `fg_describe_actor_cat_obs16_launch` accepts it) produces its 16-bit
         observations: 'fused' - the launch itself stores fp16 / bf16 units (`fg_rollout_hd_obs16`; formation_hd_env at 3, 9
         or 27 agents without World options) - or 'cast' - the fp32 launch runs into the env's usual buffers and the result
         is cast, which is the same bits by definition and works for every scenario, agent count and option.  Decided without
@@ -406,6 +408,10 @@ class MultiAgentEnv(object):
         if not _native.obs_format(obs_dtype):
             raise ValueError("obs_dtype must be torch.float16 or torch.bfloat16")
         sc = self.scenario
+        if actor is not None:
+            supported = getattr(sc, "actor_obs16_supported", None)
+            fused = None if supported is None or self.post_step_callback is not None else self._resolve_actor(actor)
+            return "fused" if fused is not None and supported(self.world, 1, fused, self._action_mode()) else "cast"
         supported = getattr(sc, "obs16_supported", None)
         launch = getattr(sc, "rollout_policy_batch" if policy else "rollout_batch", None)
         if supported is None or launch is None or self.post_step_callback is not None:
@@ -478,7 +484,8 @@ class MultiAgentEnv(object):
         rule = getattr(self.scenario, "actor_fused_rule", None)
         return {} if rule is None else rule(self.world)
 
-    def rollout_actor(self, K, actor, out=None, obs_every=1, noise_state=None, rnn_state=None, rnn_states_every=None):
+    def rollout_actor(self, K, actor, out=None, obs_every=1, obs_dtype=None, noise_state=None, rnn_state=None,
+                      rnn_states_every=None):
         """The loop of a learned actor for K steps in one call:
             act_n = actor(obs_n); obs_n, rew_n, done_n, info = env.step(act_n)
         from the current state (step 0 acts on the observation of the current state, step k on the one step k-1 returned -
@@ -560,7 +567,18 @@ class MultiAgentEnv(object):
         Linear(H, 5); per-agent members, a leading BatchNorm, the landmark scenarios and World options run host-paced, the
         pick and the decode by the kernels' own device functions (`fg_actor_categorical`).  Any other actor in a discrete
         action mode, and any actor with `force_discrete_action` (FG_ACT_ARGMAX), raises NotImplementedError; a
-        CategoricalActor on an env with continuous actions raises ValueError."""
+        CategoricalActor on an env with continuous actions raises ValueError.
+        `obs_dtype` = torch.float16 or torch.bfloat16: as `rollout`'s - the returned obs has that dtype and holds, bit for bit,
+        `.to(obs_dtype)` of what the same call without it returns; everything else (actions, log-probs, rewards, done flags,
+        the states, the state left behind, the RNG counter) is that call's.  `obs_path(obs_dtype, actor=actor)` tells how:
+        'fused' - the actor launch itself stores 16-bit units (`fg_rollout_hd_actor_obs16`, `fg_rollout_hd_actor_cat_obs16`:
+        a GaussianActor or CategoricalActor on the plain, the LayerNorm or the recurrent form in formation_hd_env at 3, 9 or
+        27 agents, H in {32, 64}, no World options, any K >= 1 and obs_every) - or 'cast' - everything else: the deterministic,
+        OU, BatchNorm and per-agent actors, H = 128, the other agent counts, host-paced actors, the landmark scenarios; the
+        fp32 call runs, fused or host-paced as without `obs_dtype`, and its observations are cast.  `out` follows `rollout`'s
+        rules with `obs_dtype`: a caller's dict with a CONTIGUOUS out["obs"] of that dtype, else fresh tensors per call.
+        `FormationVecEnv.rollout_actor` and placed 16-bit buffers are not part of it."""
+        fmt = _native.obs_format(obs_dtype)
         mode = self._action_mode()
         cat = actor if isinstance(actor, actor_rollout.CategoricalActor) else None
         if mode and (cat is None or mode == _native.FG_ACT_ARGMAX):
@@ -592,6 +610,14 @@ class MultiAgentEnv(object):
             rnn_state = self._state_tensor("rnn_state", rnn_state, shape,
                                            lambda: torch.zeros(shape, dtype=torch.float32, device=self.world.device))
         states_shape = None if S is None else ((K + S - 1) // S,) + tuple(rnn_state.shape)
+        if fmt and self.obs_path(obs_dtype, actor=actor) == "cast":
+            res = self._rollout_cast(obs_dtype, out, K, obs_every, True,
+                                     lambda o: self.rollout_actor(K, actor, o, obs_every, noise_state=noise_state, rnn_state=rnn_state,
+                                                                  rnn_states_every=rnn_states_every))
+            for key, t in (("rnn_state", rnn_state), ("noise_state", noise_state)):
+                if key in res[3]:
+                    res[3][key] = t                        # the states come back as updated in place, not as copies
+            return res
         fused = self._resolve_actor(actor)
         if fused is None:
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
@@ -606,7 +632,7 @@ class MultiAgentEnv(object):
             return res
         want = self._rollout_shapes(K, obs_every, act=True, log_prob=fused.log_std is not None or cat is not None,
                                     rnn_states=states_shape, idx=cat is not None)
-        out, own_buffers = self._rollout_out(want, out, K, obs_every, True)
+        out, own_buffers = self._rollout_out(want, out, K, obs_every, True, obs_dtype)
         # what the launch reads in place besides `out`, by name for the binder and by address for the key: the binding holds
         # the parameter tensors' addresses, so it keys on them (`binding_key`) and keeps them alive - a parameter re-allocated
         # (not updated in place) binds anew
@@ -618,7 +644,7 @@ class MultiAgentEnv(object):
             extra = dict(extra, act_mode=mode)
         lead = ("actor", K, fused.binding_key(), _native.ptr(rnn_state), S, _native.ptr(noise_state))
         self._run_rollout(lead if cat is None else lead + (mode,), want, out,    # the categorical launch bakes the mode in
-                          own_buffers, K, obs_every, None, self.scenario.bind_rollout_actor, None, (K, fused), extra)
+                          own_buffers, K, obs_every, obs_dtype, self.scenario.bind_rollout_actor, None, (K, fused), extra)
         info = dict(state, actions=out["act"])             # the states come back as updated in place
         if cat is not None:
             info.update(actions=out["idx"], u=out["act"])

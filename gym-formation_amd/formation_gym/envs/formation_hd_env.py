@@ -259,8 +259,30 @@ class Scenario(BaseScenario):
             + self._out_ptrs(out) + (int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(fn, p, *args, keep=out)
 
+    def actor_obs16_supported(self, world, K, actor, act_mode=0):
+        """Whether a K-step `bind_rollout_actor` launch of this world with `actor` (a FusedActor record) can store its
+        observations in fp16 / bf16 itself (`obs_format`): the Gaussian and the categorical member of the plain, the LayerNorm
+        and the recurrent family, by the library's own answer (`fg_describe_actor_obs16_launch` /
+        `fg_describe_actor_cat_obs16_launch`, which touch no device).  False: the caller runs the fp32 launch and casts."""
+        if actor.ou is not None or actor.per_agent or (actor.cat is None and actor.log_std is None):
+            return False
+        try:
+            p = self.params(world)
+        except NotImplementedError:                        # scripted agents: only the World API drives them
+            return False
+        fas, norm, gru, bns = _native.actor_structs(actor)
+        if bns is not None:
+            return False
+        lib, buf = _native.load(), ctypes.create_string_buffer(256)
+        shape = (world.num_envs, len(world.agents), int(K), 1, buf, len(buf))
+        if actor.cat is not None:
+            rc = lib.fg_describe_actor_cat_obs16_launch(p, _native.FG_OBS_F16, fas, norm, gru, int(act_mode), 0, *shape)
+        else:
+            rc = lib.fg_describe_actor_obs16_launch(p, _native.FG_OBS_F16, fas, norm, gru, _native.ptr(actor.log_std), *shape)
+        return rc == _native.FG_OK
+
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False, rnn_state=None, rnn_states_every=None,
-                           noise_state=None, act_mode=0):
+                           noise_state=None, act_mode=0, obs_format=0):
         """K closed-loop steps with the caller's MLP actor, every pointer and the FgParams struct resolved once: returns
         `launch(rng_offset)`.  `actor`: the FusedActor record of `actor_rollout.resolve_actor`; the kernel reads its tensors
         in place at every launch, and the launcher keeps them alive.  out["act"] [K,B,N,2] receives the actions taken, the
@@ -286,7 +308,12 @@ class Scenario(BaseScenario):
                                                 (norm / gru or NULL) in the env's action mode `act_mode`: the indices in
                                                 out["idx"] [K,B,N] int32, the log-probs in out["log_prob"], the decoded actions
                                                 in out["act"]; `rnn_state` and out["rnn_states"] as above; the module's
-                                                `deterministic` flag is read before every launch"""
+                                                `deterministic` flag is read before every launch
+          16-bit observations (`obs_format`)    `fg_rollout_hd_actor_obs16` (a GaussianActor on the plain, the LayerNorm or the
+                                                recurrent body: norm / gru or NULL, log_std required, rnn_states or NULL) and
+                                                `fg_rollout_hd_actor_cat_obs16` (a CategoricalActor likewise): out["obs"] is a
+                                                contiguous tensor of that 16-bit dtype, written by the launch itself; where
+                                                `actor_obs16_supported` says no, the library refuses and the caller casts"""
         lib = _native.load()
         log_std = actor.log_std
         fas, norm, gru, bns = _native.actor_structs(actor)
@@ -313,7 +340,8 @@ class Scenario(BaseScenario):
             args = state + (out["idx"].data_ptr(), out["log_prob"].data_ptr(), _native.ptr(rnn_state) if gru is not None else None,
                             out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1) + tail
             keep = (out, actor.tensors(), fas, norm, gru, rnn_state)
-            by_flag = [_native.bind_launch(lib.fg_rollout_hd_actor_cat, p, fas, norm, gru, int(act_mode), greedy, *args, keep=keep)
+            fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_actor_cat", obs_format)
+            by_flag = [_native.bind_launch(fn, p, *fmt, fas, norm, gru, int(act_mode), greedy, *args, keep=keep)
                        for greedy in (0, 1)]
 
             def launch_cat(rng_offset=0):              # the module's flag as it is now: sampled or the distribution's mode
@@ -324,7 +352,11 @@ class Scenario(BaseScenario):
         # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, and
         # what follows the state: logp_seq, rnn_state, (rnn_states, states_every))
         ls, nst = _native.ptr(log_std), _native.ptr(noise_state)
+        if obs_format and (ou is not None or bns is not None or actor.per_agent or log_std is None):
+            raise NotImplementedError("16-bit observations fuse with a Gaussian or categorical actor on the plain, the LayerNorm "
+                                      "and the recurrent body only")
         families = (
+            (bool(obs_format), "fg_rollout_hd_actor_obs16", (int(obs_format), fas, norm, gru, ls), True, True, True),
             (ou is not None and actor.per_agent, "fg_rollout_hd_actor_ou_per_agent", (fas, bns, fou, nst), False, False, False),
             (ou is not None, "fg_rollout_hd_actor_ou", (fas, bns, fou, nst), False, False, False),
             (bns is not None and actor.per_agent, "fg_rollout_hd_actor_bn_per_agent", (fas, bns, ls), True, False, False),
@@ -337,9 +369,10 @@ class Scenario(BaseScenario):
             (True, "fg_rollout_hd_actor", (fas,), False, False, False))
         entry, lead, with_logp, with_state, with_states = next(row[1:] for row in families if row[0])
         logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
-        hidden = (rnn_state.data_ptr(),) if with_state else ()
-        if with_states:
-            hidden += (out["rnn_states"].data_ptr(), int(rnn_states_every))
+        hidden = (_native.ptr(rnn_state) if gru is not None else None,) if with_state else ()
+        if with_states:                                    # (the 16-bit entry takes both: NULL and 1 where none are kept)
+            keep_states = rnn_states_every is not None
+            hidden += (out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1)
         args = lead + state + logp + hidden + tail
         launch = _native.bind_launch(getattr(lib, entry), p, *args,
                                      keep=(out, actor.tensors(), fas, norm, gru, bns, fou, rnn_state, noise_state))

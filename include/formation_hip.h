@@ -773,6 +773,44 @@ int fg_rollout_hd_actor_cat(const FgParams* params, const FgActor* actor, const 
  * gru_cat_actor_kernel<N,H> instantiation and its launch geometry.  Touches no device. */
 int fg_describe_actor_cat_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,
                                  int act_mode, int greedy, int B, int N, int K, int obs_every, char* out, int out_len);
+
+/* 16-bit observations out of the fused actor launch: the Gaussian member of the plain (norm == NULL), LayerNorm (norm) and
+ * recurrent (norm and gru) family - fg_rollout_hd_actor_sample / _norm / _gru_states with a log_std, which is required - with
+ * obs_seq [K / obs_every][B][N][6N] in `obs_format` (FG_OBS_F16 / FG_OBS_BF16; 2 bytes per element, 16-byte aligned, contiguous;
+ * NULL: not written).  Every element is the round-to-nearest-even conversion of the fp32 value the fp32 entry stores there -
+ * what `obs.to(dtype)` gives, bit for bit (fp16: overflow to inf, subnormals kept; signed zeros kept) - stored by the kernel's
+ * stream phase through the 16-bit tile writer of fg_rollout_hd_obs16 (wave-private LDS tiles in the wave's activation tile, 16
+ * bytes per lane and store).  Everything else - act_seq, logp_seq, reward_seq, indiv_seq, done_seq, rnn_state, rnn_states, the
+ * state and the RNG counter - is the fp32 entry's, bit for bit.  The format is a run-time fact of the launch: one kernel
+ * (actor_sample_obs16 / ln_sample_obs16 / gru_sample_obs16 <N,H>) serves both.  rnn_state (gru only; else ignored), rnn_states
+ * (NULL: none kept) and states_every as in fg_rollout_hd_actor_gru_states; K >= 1, any obs_every.
+ * Fused support: N in {3, 9, 27}, hidden in {32, 64}, no World options.  Status, checked in this order and in this entry's
+ * name: FG_ERR_BAD_ARG for an unknown obs_format, a padded env pitch (params->obs_env_pitch != 0) or a NULL log_std;
+ * FG_ERR_UNSUPPORTED_N for any other N; FG_ERR_BAD_ARG for hidden = 128; then every check of the fp32 entries in their order
+ * (FG_ERR_ALIGNMENT for an obs_seq that is not 16-byte aligned among the buffers').  There is no fall-back inside the library:
+ * a caller that gets one of these runs the fp32 entry and casts.  B == 0 returns FG_OK without a launch. */
+int fg_rollout_hd_actor_obs16(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                              const FgActorGru* gru, const float* log_std, int B, int N, int K, float* pos_x, float* pos_y,
+                              float* vel_x, float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                              void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, float* logp_seq,
+                              float* rnn_state, float* rnn_states, int states_every, int obs_every, void* stream);
+/* ... and the categorical member likewise: fg_rollout_hd_actor_cat's arguments and checks behind the same first ones (there is
+ * no log_std), kernels cat_actor_obs16 / ln_cat_actor_obs16 / gru_cat_actor_obs16 <N,H>. */
+int fg_rollout_hd_actor_cat_obs16(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                  const FgActorGru* gru, int act_mode, int greedy, int B, int N, int K, float* pos_x, float* pos_y,
+                                  float* vel_x, float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                  void* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                                  float* logp_seq, float* rnn_state, float* rnn_states, int states_every, int obs_every,
+                                  void* stream);
+/* Dry runs: the same checks and status codes (the buffers' apart; B > 0 required), then the instantiation, grid and LDS as
+ * fg_describe_actor_launch writes them; the name does not depend on the format.  Touch no device: this is how a caller
+ * decides between the fused 16-bit launch and the fp32 entry + cast. */
+int fg_describe_actor_obs16_launch(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                   const FgActorGru* gru, const float* log_std, int B, int N, int K, int obs_every, char* out,
+                                   int out_len);
+int fg_describe_actor_cat_obs16_launch(const FgParams* params, int obs_format, const FgActor* actor, const FgActorNorm* norm,
+                                       const FgActorGru* gru, int act_mode, int greedy, int B, int N, int K, int obs_every,
+                                       char* out, int out_len);
 /* One step's uniform draws u [B][N] (fp32 in DEVICE memory, 4-byte aligned) at rng_base(params), by the device function of
  * the categorical kernels: fg_actor_noise's sibling for the host-paced loop of a categorical policy. */
 int fg_actor_uniform(const FgParams* params, int B, int N, float* u, void* stream);

@@ -16,7 +16,9 @@ from tests.isa_scan import kernel_resources  # noqa: E402
 FAMILIES = ("actor_rollout_kernel<", "actor_sample_kernel<", "pa_actor_kernel<", "pa_sample_kernel<", "ln_actor_kernel<",
             "ln_sample_kernel<", "gru_actor_kernel<", "gru_sample_kernel<", "::bn_actor_kernel<", "::bn_sample_kernel<",
             "pa_bn_actor_kernel<", "pa_bn_sample_kernel<", "::ou_actor_kernel<", "::pa_ou_actor_kernel<", "::bn_ou_actor_kernel<",
-            "pa_bn_ou_actor_kernel<", "::cat_actor_kernel<", "ln_cat_actor_kernel<", "gru_cat_actor_kernel<")
+            "pa_bn_ou_actor_kernel<", "::cat_actor_kernel<", "ln_cat_actor_kernel<", "gru_cat_actor_kernel<",
+            "::actor_sample_obs16<", "::ln_sample_obs16<", "::gru_sample_obs16<", "::cat_actor_obs16<", "::ln_cat_actor_obs16<",
+            "::gru_cat_actor_obs16<")
 
 
 def main(argv):
