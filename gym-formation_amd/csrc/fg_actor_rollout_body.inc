@@ -1,32 +1,26 @@
-// fg_actor_rollout_body.inc - the one body of the twelve formation_hd_env actor kernels: actor_rollout_kernel,
-// actor_sample_kernel, pa_actor_kernel, pa_sample_kernel, ln_actor_kernel, ln_sample_kernel, gru_actor_kernel,
-// gru_sample_kernel, bn_actor_kernel, bn_sample_kernel, pa_bn_actor_kernel and pa_bn_sample_kernel, and of the four OU members
-// ou_actor_kernel, pa_ou_actor_kernel, bn_ou_actor_kernel and pa_bn_ou_actor_kernel (the family blocks of
-// fg_actor_rollout_kernel.hpp).  Included inside each kernel (fg_actor_kernel_pair.inc), whose scope provides the kernel
-// arguments `a` (Args), `w` (ActorW: the shared actor) and `tab` (ActorTab: one per agent), the template parameters NC and H,
-// `constexpr bool SAMPLE`, `constexpr bool PER_AGENT` and `log_std` / `logp` (SAMPLE = false: nullptr).  A kernel reads `w`
-// (PER_AGENT = false) or `tab` and `w.out_tanh` (PER_AGENT = true), never both.  `constexpr bool LNORM` with `nw` (ActorNormW;
-// LNORM = false: an empty constant) selects ln_actor_kernel / ln_sample_kernel: the hidden LayerNorms are fg_actor_mlp.inc's,
-// the input LayerNorm (nw.in_norm, wave-uniform) is here - row statistics from the tables, then layer 1 over the whole k range
-// on the normalised operand.  `constexpr bool GRU` with `gw` (ActorGruW; GRU = false: an empty constant) selects
-// gru_actor_kernel / gru_sample_kernel, an LNORM body whose pass runs fg_actor_gru.inc between the second hidden norm and layer 3
-// (fg_actor_mlp.inc); here are the hidden state's block in LDS - loaded from gw.state before the first pass, its done envs' rows
-// zeroed by the physics phase, stored back after the last step (the per-step record gw.states is fg_actor_gru.inc's) - and the
-// preload of the layer's biases and norm.  `constexpr bool INBN` with `bw` (ActorBnW, the shared actor) or `btab` (ActorBnTab,
-// PER_AGENT; the other an empty constant, both when INBN = false) selects bn_*_kernel / pa_bn_*_kernel: the plain body behind an
-// eval-mode input BatchNorm - layer 1's A operand through bn_apply, over the whole k range; the shared actor's tables mean |
-// istd | gamma | beta are filled here once per workgroup, the per-agent ones are read through L1 per element.
-// `constexpr bool OU` with `ow` (ActorOuW; OU = false: an empty constant) selects the families' *ou_actor_kernel: the
-// deterministic body with the noise state's block in LDS - loaded from ow.state before the first pass, stepped by layer 3's lanes
-// (fg_actor_mlp.inc; the per-agent branch here), its done envs' rows set to mu by the physics phase, stored back after the last
-// step.
-// `constexpr bool CAT` with `cw` (ActorCatW; CAT = false: an empty constant) selects cat_actor_kernel / ln_cat_actor_kernel /
-// gru_cat_actor_kernel: the shared body with the five-output head of fg_actor_mlp.inc, whose lanes leave the decoded action in
-// the actions' block and the row's index and log-prob in two blocks [E N] behind it; the physics phase stores the three.
-// `constexpr bool OBS16` with `obs_fmt` (the last kernel argument; OBS16 = false: the constant 0) selects the 16-bit members
-// actor_sample_obs16 / ln_sample_obs16 / gru_sample_obs16 / cat_actor_obs16 / ln_cat_actor_obs16 / gru_cat_actor_obs16: the
-// Gaussian or categorical body whose stream phase stores fp16 / bf16 units through write_obs16 (fg_obs_writers.hpp) instead of
-// write_obs_rows, the format a run-time, wave-uniform fact of the launch; its tile is the wave's own activation tile.
+// fg_actor_rollout_body.inc - the one body of every formation_hd_env actor kernel: each member of each family block of
+// fg_actor_rollout_kernel.hpp.  Included inside each kernel (fg_actor_family.inc), whose scope provides NC and H, the member and
+// the family's flags (FG_ACTOR_IS: MEMBER and FLAGS, and from them the eight `constexpr bool`s the branches below test), the
+// kernel arguments `a` (Args) and `w tab nw gw bw btab ow cw`, `log_std` / `logp` and `obs_fmt` - each a kernel parameter where
+// the family or the member takes it, and an empty constant, nullptr or 0 where it does not.  The LDS blocks are
+// actor_lds_layout's, the function the host sizes the launch with.
+//   PER_AGENT  `tab` (ActorTab) instead of `w` (ActorW), of which only `w.out_tanh` is read; its layers 1 to 3 are here.
+//   LNORM      `nw` (ActorNormW): the hidden LayerNorms are fg_actor_mlp.inc's, the input LayerNorm (nw.in_norm, wave-uniform)
+//              is here - row statistics from the tables, then layer 1 over the whole k range on the normalised operand.
+//   GRU        `gw` (ActorGruW), an LNORM body whose pass runs fg_actor_gru.inc between the second hidden norm and layer 3; here
+//              are the hidden state's block - loaded from gw.state before the first pass, its done envs' rows zeroed by the
+//              physics phase, stored back after the last step (the record gw.states is fg_actor_gru.inc's) - and the preload
+//              of the layer's biases and norm.
+//   INBN       `bw` (ActorBnW) or `btab` (ActorBnTab, PER_AGENT): layer 1's A operand through bn_apply, over the whole k range;
+//              the shared actor's tables are filled here once per workgroup, the per-agent ones read through L1 per element.
+//   SAMPLE     `log_std` / `logp`: the Gaussian step of layer 3's lanes (fg_actor_mlp.inc; the per-agent branch here) and the
+//              log-probs' block, which the physics phase stores.
+//   OU         `ow` (ActorOuW): the noise state's block - loaded from ow.state before the first pass, stepped by layer 3's lanes,
+//              its done envs' rows set to mu by the physics phase, stored back after the last step.
+//   CAT        `cw` (ActorCatW): the five-output head of fg_actor_mlp.inc leaves the decoded action in the actions' block and
+//              the row's index and log-prob in two blocks [E N] behind it; the physics phase stores the three.
+//   OBS16      `obs_fmt`: the stream phase stores fp16 / bf16 units through write_obs16 (fg_obs_writers.hpp) instead of
+//              write_obs_rows, the format a run-time, wave-uniform fact of the launch; its tile is the wave's activation tile.
 // Not a header: no guard.
 // This body holds the physics, the observation stream and layer 1 on the observation tables (two K ranges); what follows
 // layer 1 for the shared actor - layers 2 and 3, the tanh, the Gaussian step - is fg_actor_mlp.inc, shared with the landmark
@@ -50,29 +44,30 @@
     constexpr int WB = actor_b3_floats(CAT);            // ... and of the b3 | log_std slot behind them
     static_assert(!CAT || (!SAMPLE && !OU && !PER_AGENT && !INBN), "the categorical actor: a shared body, no Gaussian or OU noise");
     static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
-    constexpr int LNS = actor_norm_floats(N, H, LNORM), DP = actor_in_pad(N);   // LNORM: gamma / beta of the three norms in LDS
+    constexpr int DP = actor_in_pad(N);                 // the input width rounded up to 4: the input norms' tables
     static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
     static_assert(!GRU || LNORM, "the recurrent actor's base is the LayerNorm body");
-    constexpr int GS = actor_gru_floats(H, GRU);        // GRU: the gates' biases and the post-GRU norm in LDS
     static_assert(!(INBN && LNORM), "the input BatchNorm is in front of the plain body only");
     static_assert(!INBN || H <= 64, "the BatchNorm actor's kernels: H 32 or 64");
-    constexpr int BNS = actor_bn_floats(N, INBN, PER_AGENT);   // INBN, shared: mean | istd | gamma | beta [DP] each in LDS
     static_assert(!OU || (!SAMPLE && !LNORM && !GRU), "the OU-noise actor: a deterministic body without LayerNorms");
     static_assert(G <= 64 && NP <= G && E % NW == 0 && H % 16 == 0, "bad actor rollout geometry");
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     float* const smemf = reinterpret_cast<float*>(smem);
-    float2* const act_lds = reinterpret_cast<float2*>(smemf + E * env_block_floats(N));
-    float* const logp_lds = smemf + E * env_block_floats(N) + 2 * E * N;  // SAMPLE and CAT only
-    int* const idx_lds = reinterpret_cast<int*>(logp_lds + E * N);          // CAT only
-    float* const wsm = logp_lds + (actor_out_blocks(SAMPLE, CAT) - 2) * E * N;   // b1 | b2 | W3 | b3 | log_std
-    float* const hbuf = wsm + WS + WB + LNS + BNS + GS;
-    float* const gsm = wsm + WS + WB + LNS + BNS;              // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
-    float* const hst = hbuf + NW * FG_ACTOR_ROWS * HS;  // GRU: the hidden state, row q of the workgroup at hst + q HS
-    static_assert(!GRU || (E * env_block_floats(N) + actor_out_blocks(SAMPLE, CAT) * E * N + WS + WB + LNS + BNS + GS + NW * FG_ACTOR_ROWS * HS) % 4 == 0,
+    // The blocks by actor_lds_layout's offsets.  Each pointer is chained from logp_lds, wsm or hbuf, not taken from `smemf`
+    // directly: the compiler allocates registers differently in some kernels when it is.
+    constexpr ActorLds L = actor_lds_layout(N, H, FLAGS, MEMBER);
+    float2* const act_lds = reinterpret_cast<float2*>(smemf + L.act);
+    float* const logp_lds = smemf + L.logp;             // SAMPLE and CAT only
+    int* const idx_lds = reinterpret_cast<int*>(logp_lds + (L.idx - L.logp));   // CAT only
+    float* const wsm = logp_lds + (L.wsm - L.logp);     // b1 | b2 | W3 | b3 | log_std
+    float* const ln0 = wsm + (L.ln - L.wsm) + 4 * H;    // LNORM: behind the hidden norms' four [H], gamma0 [DP] | beta0 [DP], zeros at k >= D
+    float* const bn0 = wsm + (L.bn - L.wsm);            // INBN, shared: mean | istd | gamma | beta [DP] each, zeros at k >= D
+    float* const gsm = wsm + (L.gru - L.wsm);           // GRU: b_ir + b_hr | b_iz + b_hz | b_in | b_hn | gamma3 | beta3
+    float* const hbuf = wsm + (L.tiles - L.wsm);
+    float* const hst = hbuf + (L.state - L.tiles);      // GRU: the hidden state, row q of the workgroup at hst + q HS
+    float* const oust = hbuf + (L.state - L.tiles);     // OU: the noise state, component o of env-major slot q at oust + 2 q + o
+    static_assert(!GRU || L.state % 4 == 0,
                   "the hidden state's block is 16-byte aligned (fg_actor_gru.inc stores its rows with 16-byte reads)");
-    float* const oust = hbuf + NW * FG_ACTOR_ROWS * HS; // OU: the noise state, component o of env-major slot q at oust + 2 q + o
-    const float* const ln0 = wsm + WS + WB + 4 * H;                          // LNORM: gamma0 [DP] | beta0 [DP], zeros at k >= D
-    const float* const bn0 = wsm + WS + WB + LNS;                            // INBN, shared: the four tables, zeros at k >= D
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -95,21 +90,19 @@
     }
     if constexpr (LNORM) {
         if (nw.in_norm) {
-            float* const lnp = wsm + WS + WB + 4 * H;
             for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
-                lnp[q] = q < D ? (nw.g0 ? nw.g0[q] : 1.f) : 0.f;
-                lnp[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
+                ln0[q] = q < D ? (nw.g0 ? nw.g0[q] : 1.f) : 0.f;
+                ln0[DP + q] = (q < D && nw.be0) ? nw.be0[q] : 0.f;
             }
         }
     }
     if constexpr (INBN && !PER_AGENT) {
-        float* const bnp = wsm + WS + WB + LNS;
         for (int q = tid; q < DP; q += FG_ACTOR_THREADS) {
             const bool in = q < D;
-            bnp[q] = in ? bw.mean[q] : 0.f;
-            bnp[DP + q] = in ? bn_istd(bw.var[q], bw.eps) : 0.f;
-            bnp[2 * DP + q] = in ? (bw.gamma ? bw.gamma[q] : 1.f) : 0.f;
-            bnp[3 * DP + q] = (in && bw.beta) ? bw.beta[q] : 0.f;
+            bn0[q] = in ? bw.mean[q] : 0.f;
+            bn0[DP + q] = in ? bn_istd(bw.var[q], bw.eps) : 0.f;
+            bn0[2 * DP + q] = in ? (bw.gamma ? bw.gamma[q] : 1.f) : 0.f;
+            bn0[3 * DP + q] = (in && bw.beta) ? bw.beta[q] : 0.f;
         }
     }
 
@@ -511,8 +504,7 @@
                 // turn (a second tile fits at H = 64 only, and with it gru_cat_actor_obs16<27,64> keeps a scratch slot).
                 constexpr int OW = obs16_tile_words<NC, NW, E>(), OT = 1;
                 static_assert(OT * OW <= FG_ACTOR_ROWS * HS, "the 16-bit tile fits the wave's activation tile");
-                static_assert((E * env_block_floats(N) + actor_out_blocks(SAMPLE, CAT) * E * N + WS + WB + LNS + BNS + GS) % 4 == 0 &&
-                              (FG_ACTOR_ROWS * HS) % 4 == 0, "the 16-bit tiles start on a 16-byte boundary");
+                static_assert(L.tiles % 4 == 0 && (FG_ACTOR_ROWS * HS) % 4 == 0, "the 16-bit tiles start on a 16-byte boundary");
                 write_obs16<NC, NW, E, FG_WR_OBS_RT, OT, FG_ACTOR_ROWS * HS>(
                     reinterpret_cast<const float2*>(smemf), env_block_floats(N) / 2, wave, reinterpret_cast<uint32_t*>(hbuf),
                     reinterpret_cast<uint32_t*>(a.obs) + unit0, unit0, El, obs_fmt);

@@ -88,7 +88,7 @@
 //              istd is recomputed per element (the same two lines of arithmetic).
 //
 // ou_actor_kernel<N,H>, pa_ou_actor_kernel<N,H>, bn_ou_actor_kernel<N,H> and pa_bn_ou_actor_kernel<N,H> (fg_rollout_hd_actor_ou,
-// fg_rollout_hd_actor_ou_per_agent) are the third member of the four families without LayerNorms: the deterministic body with
+// fg_rollout_hd_actor_ou_per_agent) are the OU member (ACTOR_OU) of the four families without LayerNorms: the deterministic body with
 // the MADDPG trainers' exploration on top, selected by `constexpr bool OU` (false in every other kernel, whose instructions it
 // leaves as they were).  Per (env, agent) a noise state x [2] is carried from step to step; the step that takes an action does
 //     x <- ou_step(x, eps)  =  x + theta (mu - x) + sigma eps,         a = clamp(actor(o) + scale x, -clip, clip)
@@ -101,8 +101,8 @@
 //              of an env whose step ended its episode (is_done, with or without auto-reset), a workgroup barrier away from
 //              either neighbour - the convention of the GRU state's masking.
 //
-// cat_actor_kernel<N,H>, ln_cat_actor_kernel<N,H> and gru_cat_actor_kernel<N,H> (fg_rollout_hd_actor_cat) are the fourth member
-// of the plain, LayerNorm and recurrent families: the body with a five-output head under a Categorical (the MAPPO trainers'
+// cat_actor_kernel<N,H>, ln_cat_actor_kernel<N,H> and gru_cat_actor_kernel<N,H> (fg_rollout_hd_actor_cat) are the categorical member
+// (ACTOR_CAT) of the plain, LayerNorm and recurrent families: the body with a five-output head under a Categorical (the MAPPO trainers'
 // discrete-action policy), selected by `constexpr bool CAT` (false in every other kernel, whose instructions it leaves as they
 // were).  W3 [5][H] and b3 [5] sit in LDS where W3 [2][H] | b3 [2] do (fg_actor_mlp_preload.inc).  Both lanes of a row evaluate
 // the five logits (ascending fmaf chains from b3[j]: identical bits in both), draw the row's uniform (actor_uniform: word 2 of
@@ -113,7 +113,8 @@
 //
 // actor_sample_obs16<N,H>, ln_sample_obs16<N,H>, gru_sample_obs16<N,H>, cat_actor_obs16<N,H>, ln_cat_actor_obs16<N,H> and
 // gru_cat_actor_obs16<N,H> (fg_rollout_hd_actor_obs16, fg_rollout_hd_actor_cat_obs16; N in {3, 9, 27}, H in {32, 64}) are the
-// Gaussian and the categorical member of the plain, LayerNorm and recurrent families with 16-bit observations, selected by
+// Gaussian and the categorical member of the plain, LayerNorm and recurrent families with 16-bit observations (ACTOR_GAUSS16,
+// ACTOR_CAT16), selected by
 // `constexpr bool OBS16` (false in every other kernel, whose instructions it leaves as they were): the stream phase stores each
 // (x, y) unit as one 32-bit word of two fp16 or bf16 halves through write_obs16 (fg_obs_writers.hpp) - the subtractions of
 // write_obs_rows on the same table entries, packed round to nearest even: `.to(dtype)` of the fp32 kernel's observations bit for
@@ -122,12 +123,12 @@
 // only that wave touches either, its stream phase precedes its actor pass in program order, so no barrier and no LDS is added.
 // a.obs then holds 32-bit units and a.obs_pitch counts them (3 N^2 per env: a contiguous tensor only).
 //
-// How a family is wired up: the twelve kernels (sixteen with the OU members) are six family blocks at the end of this file, each the two kernel names, the
-// four flags, the operands the family takes and the ones it does not, around fg_actor_kernel_pair.inc, which emits the
-// deterministic / Gaussian pair - and, where the block names one (FG_ACTOR_OUK), the OU member - with
-// fg_actor_rollout_body.inc as a textual include.  The host's side of the same table is
-// HdActorFamily in formation_hip.hip.  Adding a family: its operand struct here, an FG_ACTOR_NO_* constant for the blocks that
-// do not take it, its block, its `if constexpr` branches in the body; then the host's row (DESIGN.md lists the places).
+// How the kernels are wired up: a kernel is (family, member).  A member (ActorMember) is stated once, by its predicates below:
+// the body's SAMPLE / OU / CAT / OBS16 and the host's LDS bytes both come from them, and actor_lds_layout is the one statement
+// of the LDS blocks.  A family is one block at the end of this file - its kind, its flags, the operands it takes and the ones it
+// does not, the names of the members it has - around fg_actor_family.inc, which emits a kernel per named member with
+// fg_actor_rollout_body.inc as a textual include, and then HdActorFamily<kind>, the record the host launches from
+// (formation_hip.hip: launch_hd_member).  DESIGN.md lists what adding a member or a family takes.
 #ifndef FG_ACTOR_ROLLOUT_KERNEL_HPP_
 #define FG_ACTOR_ROLLOUT_KERNEL_HPP_
 
@@ -231,45 +232,60 @@ constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-r
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
 __host__ __device__ constexpr int actor_envs(int n) { return FG_ACTOR_THREADS / actor_lanes(n); }
 __host__ __device__ constexpr int actor_hstride(int h) { return h + 4; }   // row pitch of the activation tile: 16 rows x 4 k conflict-free
-// LDS (floats): env blocks [E][env_block_floats] | actions [E N][2] | (SAMPLE: log-probs [E N]) |
-//               (CAT: log-probs [E N] indices [E N]) |
-//               b1 [H] b2 [H] W3 [2][H] (not PER_AGENT) | b3 [2] (SAMPLE: log_std [2], else padding) |
-//               (CAT instead: b1 [H] b2 [H] W3 [5][H] | b3 [5] and padding to 8) |
-//               (LNORM: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4) |
-//               (INBN, not PER_AGENT: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm) |
-//               (GRU: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]) |
-//               activations [4][32][H + 4] | (GRU: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32)) |
-//               (OU: noise state [E N][2])
-// (E N is a multiple of 8, so the log-prob block keeps every later block 32-byte aligned)
 __host__ __device__ constexpr int actor_in_pad(int n) { return (6 * n + 3) / 4 * 4; }
-__host__ __device__ constexpr int actor_norm_floats(int n, int h, bool lnorm) { return lnorm ? 4 * h + 2 * actor_in_pad(n) : 0; }
 __host__ __device__ constexpr int actor_state_rows(int n) {
     return (actor_envs(n) * n + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS * FG_ACTOR_ROWS;
 }
-__host__ __device__ constexpr int actor_gru_floats(int h, bool gru) { return gru ? 6 * h : 0; }
-__host__ __device__ constexpr int actor_bn_floats(int n, bool inbn, bool per_agent) {
-    return inbn && !per_agent ? 4 * actor_in_pad(n) : 0;
-}
-__host__ __device__ constexpr int actor_ou_floats(int n, bool ou) { return ou ? 2 * actor_envs(n) * n : 0; }
+
+// A kernel is (family, member).  The family is the network around the MLP - four flags, one value per family block below -
+// and the member is what happens to the head's output and to the observations; its four facts are the predicates' answers.
+struct ActorFlags { bool per_agent, lnorm, gru, in_bn; };
+// Members: the deterministic actor; under a diagonal Gaussian (log_std, log-probs); with OU noise and the clamp (ActorOuW); the
+// five-output head under a Categorical (ActorCatW); and the last two storing 16-bit observations (obs_fmt).
+enum ActorMember { ACTOR_DET, ACTOR_GAUSS, ACTOR_OU, ACTOR_CAT, ACTOR_GAUSS16, ACTOR_CAT16 };
+__host__ __device__ constexpr bool actor_member_sample(ActorMember m) { return m == ACTOR_GAUSS || m == ACTOR_GAUSS16; }
+__host__ __device__ constexpr bool actor_member_ou(ActorMember m) { return m == ACTOR_OU; }
+__host__ __device__ constexpr bool actor_member_cat(ActorMember m) { return m == ACTOR_CAT || m == ACTOR_CAT16; }
+__host__ __device__ constexpr bool actor_member_obs16(ActorMember m) { return m == ACTOR_GAUSS16 || m == ACTOR_CAT16; }
+__host__ __device__ constexpr bool actor_obs16_shape(int n, int h) { return (n == 3 || n == 9 || n == 27) && (h == 32 || h == 64); }  // built for
+
 // floats of b1 | b2 | W3 in LDS (a per-agent family reads them through L1), and of the b3 | log_std slot behind them
 __host__ __device__ constexpr int actor_w_floats(int h, bool per_agent, bool cat) { return per_agent ? 0 : (cat ? 2 + FG_CAT : 4) * h; }
 __host__ __device__ constexpr int actor_b3_floats(bool cat) { return cat ? 8 : 4; }
-// blocks [E N] between the env blocks and the weights: the actions' two, SAMPLE's log-probs, CAT's log-probs and indices
-__host__ __device__ constexpr int actor_out_blocks(bool sample, bool cat) { return sample ? 3 : cat ? 4 : 2; }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
-          bool OU = false, bool CAT = false>
-constexpr int actor_lds_floats() {
-    return actor_envs(NC) * env_block_floats(NC) + actor_out_blocks(SAMPLE, CAT) * actor_envs(NC) * NC +
-           actor_w_floats(H, PER_AGENT, CAT) + actor_b3_floats(CAT) +
-           actor_norm_floats(NC, H, LNORM) + actor_bn_floats(NC, INBN, PER_AGENT) + actor_gru_floats(H, GRU) +
-           (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * actor_hstride(H) + (GRU ? actor_state_rows(NC) * actor_hstride(H) : 0) +
-           actor_ou_floats(NC, OU);
+// The LDS of one workgroup: the float offset of every block behind the env blocks [E][env_block_floats], and the total.  A
+// block a kernel does not have is empty; the body takes its pointers, and the host the launch's bytes, from this one function.
+// (E N is a multiple of 8, so the [E N] blocks keep every later block 32-byte aligned.)
+struct ActorLds {
+    int act;      // actions [E N][2]
+    int logp;     // Gaussian and categorical members: log-probs [E N]
+    int idx;      // categorical members: indices [E N]
+    int wsm;      // b1 [H] b2 [H] W3 [2][H] (not per_agent) | b3 [2], then log_std [2] (Gaussian members) or padding;
+                  // categorical members: b1 [H] b2 [H] W3 [5][H] | b3 [5] and padding to 8
+    int ln;       // lnorm: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4
+    int bn;       // in_bn, not per_agent: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm
+    int gru;      // gru: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]
+    int tiles;    // activations [4][32][H + 4]
+    int state;    // gru: hidden state [TILES 32][H + 4], TILES = ceil(E N / 32); the OU member: noise state [E N][2]
+    int total;
+};
+__host__ __device__ constexpr ActorLds actor_lds_layout(int n, int h, ActorFlags f, ActorMember m) {
+    const bool cat = actor_member_cat(m);
+    const int rows = actor_envs(n) * n, dp = actor_in_pad(n), hs = actor_hstride(h);
+    ActorLds l{};
+    l.act = actor_envs(n) * env_block_floats(n);
+    l.logp = l.act + 2 * rows;
+    l.idx = l.logp + (actor_member_sample(m) || cat ? rows : 0);
+    l.wsm = l.idx + (cat ? rows : 0);
+    l.ln = l.wsm + actor_w_floats(h, f.per_agent, cat) + actor_b3_floats(cat);
+    l.bn = l.ln + (f.lnorm ? 4 * h + 2 * dp : 0);
+    l.gru = l.bn + (f.in_bn && !f.per_agent ? 4 * dp : 0);
+    l.tiles = l.gru + (f.gru ? 6 * h : 0);
+    l.state = l.tiles + (FG_ACTOR_THREADS / 64) * FG_ACTOR_ROWS * hs;
+    l.total = l.state + (f.gru ? actor_state_rows(n) * hs : 0) + (actor_member_ou(m) ? 2 * rows : 0);
+    return l;
 }
-template <int NC, int H, bool SAMPLE = false, bool PER_AGENT = false, bool LNORM = false, bool GRU = false, bool INBN = false,
-          bool OU = false, bool CAT = false>
-constexpr int actor_lds_bytes() {
-    return actor_lds_floats<NC, H, SAMPLE, PER_AGENT, LNORM, GRU, INBN, OU, CAT>() * (int)sizeof(float);
-}
+__host__ __device__ constexpr int actor_lds_floats(int n, int h, ActorFlags f, ActorMember m) { return actor_lds_layout(n, h, f, m).total; }
+__host__ __device__ constexpr int actor_lds_bytes(int n, int h, ActorFlags f, ActorMember m) { return 4 * actor_lds_floats(n, h, f, m); }
 
 // The exploration noise eps [2] of agent i of global env g for the step whose counter offset is `offset`: its own Philox
 // stream, word 1 = i ^ 0xA0000000 (motor_noise flips bit 31 of i | 0x20000000).  The other streams keyed by (g, i, offset):
@@ -432,83 +448,115 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
     state[t] = make_float2(ou_step(x.x, n.x, theta, mu, sigma), ou_step(x.y, n.y, theta, mu, sigma));
 }
 
-// ---- the twelve kernels: one block per family, each the deterministic / Gaussian pair of fg_actor_kernel_pair.inc around
-// fg_actor_rollout_body.inc.  A family is its two names, its four flags, the operands it takes as kernel arguments and the
-// ones it does not, and - the four families without LayerNorms - the name of its OU member, which takes `ow` (ActorOuW)
-// after them, and - the plain, LayerNorm and recurrent families - the name of its categorical member, which takes `cw`
-// (ActorCatW) after them; the body names all of `w tab nw gw bw btab ow cw`, and an operand a family does not take is the empty constant
-// below (`w` of a per-agent family: only tab's tanh flag), so that no kernel carries an argument it never reads.
-#define FG_ACTOR_NO_W    const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
-#define FG_ACTOR_NO_TAB  constexpr ActorTab tab{};
-#define FG_ACTOR_NO_NW   constexpr ActorNormW nw{};
-#define FG_ACTOR_NO_GW   constexpr ActorGruW gw{};
-#define FG_ACTOR_NO_BW   constexpr ActorBnW bw{};
-#define FG_ACTOR_NO_BTAB constexpr ActorBnTab btab{};
-#define FG_ACTOR_NO_OW   constexpr ActorOuW ow{};
-#define FG_ACTOR_NO_CW   constexpr ActorCatW cw{};
+// ---- the kernels: one block per family around fg_actor_family.inc.  The body names all of `w tab nw gw bw btab ow cw`, and an
+// operand a kernel does not take is the empty constant below (`w` of a per-agent family: only tab's tanh flag), so that no
+// kernel carries an argument it never reads.
+#define FG_ACTOR_NO_W     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
+#define FG_ACTOR_NO_TAB   constexpr ActorTab tab{};
+#define FG_ACTOR_NO_NW    constexpr ActorNormW nw{};
+#define FG_ACTOR_NO_GW    constexpr ActorGruW gw{};
+#define FG_ACTOR_NO_BW    constexpr ActorBnW bw{};
+#define FG_ACTOR_NO_BTAB  constexpr ActorBnTab btab{};
+#define FG_ACTOR_NO_OW    constexpr ActorOuW ow{};
+#define FG_ACTOR_NO_CW    constexpr ActorCatW cw{};
+#define FG_ACTOR_NO_GAUSS const float* const log_std = nullptr; float* const logp = nullptr;
+#define FG_ACTOR_NO_OBS16 constexpr int obs_fmt = 0;
+// what the body reads of its kernel: the member and the family's flags, each fact from the one predicate or field
+#define FG_ACTOR_IS(M)                                                                                                         \
+    constexpr ActorMember MEMBER = M;                                                                                          \
+    constexpr ActorFlags FLAGS = FG_ACTOR_FLAGS;                                                                               \
+    constexpr bool SAMPLE = actor_member_sample(M), OU = actor_member_ou(M), CAT = actor_member_cat(M), OBS16 = actor_member_obs16(M), \
+                   PER_AGENT = FLAGS.per_agent, LNORM = FLAGS.lnorm, GRU = FLAGS.gru, INBN = FLAGS.in_bn;                      \
+    FG_ACTOR_ABSENT
+#define FG_ACTOR_STR_(x) #x
+#define FG_ACTOR_STR(x) FG_ACTOR_STR_(x)
+
+// One kind per entry point fg_rollout_hd_actor* (formation_hip.hip: hd_actor_entry); HD_ACTOR_SAMPLE shares the shared family's kernels.
+enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
+                   HD_ACTOR_BN_PER_AGENT };
+template <HdActorKind> struct HdActorFamily;
 
 // the shared actor
-#define FG_ACTOR_DET      actor_rollout_kernel
-#define FG_ACTOR_OUK      ou_actor_kernel
-#define FG_ACTOR_CATK     cat_actor_kernel
-#define FG_ACTOR_SMP      actor_sample_kernel
-#define FG_ACTOR_SMP16    actor_sample_obs16
-#define FG_ACTOR_CAT16    cat_actor_obs16
-#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = false
+#define FG_ACTOR_KIND     HD_ACTOR_SHARED
+#define FG_ACTOR_MAXH     128
+#define FG_ACTOR_WHAT     ""
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ false, /* lnorm */ false, /* gru */ false, /* in_bn */ false}
 #define FG_ACTOR_OPERANDS const ActorW w
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      actor_rollout_kernel
+#define FG_ACTOR_SMP      actor_sample_kernel
+#define FG_ACTOR_OUK      ou_actor_kernel
+#define FG_ACTOR_CATK     cat_actor_kernel
+#define FG_ACTOR_SMP16    actor_sample_obs16
+#define FG_ACTOR_CAT16    cat_actor_obs16
+#include "fg_actor_family.inc"
+template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
 
-// PER_AGENT: agent i evaluates tab's actor i; the Gaussian twin has one log_std [2] for all agents
-#define FG_ACTOR_DET      pa_actor_kernel
-#define FG_ACTOR_OUK      pa_ou_actor_kernel
-#define FG_ACTOR_SMP      pa_sample_kernel
-#define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = false
+// per_agent: agent i evaluates tab's actor i; the Gaussian member has one log_std [2] for all agents
+#define FG_ACTOR_KIND     HD_ACTOR_PER_AGENT
+#define FG_ACTOR_MAXH     128
+#define FG_ACTOR_WHAT     "per-agent "
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ true, /* lnorm */ false, /* gru */ false, /* in_bn */ false}
 #define FG_ACTOR_OPERANDS const ActorTab tab
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_W
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      pa_actor_kernel
+#define FG_ACTOR_SMP      pa_sample_kernel
+#define FG_ACTOR_OUK      pa_ou_actor_kernel
+#include "fg_actor_family.inc"
 
-// LNORM: the shared actor with LayerNorms `nw`
-#define FG_ACTOR_DET      ln_actor_kernel
-#define FG_ACTOR_CATK     ln_cat_actor_kernel
-#define FG_ACTOR_SMP      ln_sample_kernel
-#define FG_ACTOR_SMP16    ln_sample_obs16
-#define FG_ACTOR_CAT16    ln_cat_actor_obs16
-#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = false, INBN = false
+// lnorm: the shared actor with LayerNorms `nw`
+#define FG_ACTOR_KIND     HD_ACTOR_NORM
+#define FG_ACTOR_MAXH     64
+#define FG_ACTOR_WHAT     "LayerNorm "
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ false, /* lnorm */ true, /* gru */ false, /* in_bn */ false}
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_GW FG_ACTOR_NO_TAB
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      ln_actor_kernel
+#define FG_ACTOR_SMP      ln_sample_kernel
+#define FG_ACTOR_CATK     ln_cat_actor_kernel
+#define FG_ACTOR_SMP16    ln_sample_obs16
+#define FG_ACTOR_CAT16    ln_cat_actor_obs16
+#include "fg_actor_family.inc"
 
-// GRU: the LayerNorm actor with the recurrent layer `gw` before its head
-#define FG_ACTOR_DET      gru_actor_kernel
-#define FG_ACTOR_CATK     gru_cat_actor_kernel
-#define FG_ACTOR_SMP      gru_sample_kernel
-#define FG_ACTOR_SMP16    gru_sample_obs16
-#define FG_ACTOR_CAT16    gru_cat_actor_obs16
-#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = true, GRU = true, INBN = false
+// gru: the LayerNorm actor with the recurrent layer `gw` before its head
+#define FG_ACTOR_KIND     HD_ACTOR_GRU
+#define FG_ACTOR_MAXH     64
+#define FG_ACTOR_WHAT     "recurrent "
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ false, /* lnorm */ true, /* gru */ true, /* in_bn */ false}
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorNormW nw, const ActorGruW gw
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_BW FG_ACTOR_NO_BTAB FG_ACTOR_NO_TAB
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      gru_actor_kernel
+#define FG_ACTOR_SMP      gru_sample_kernel
+#define FG_ACTOR_CATK     gru_cat_actor_kernel
+#define FG_ACTOR_SMP16    gru_sample_obs16
+#define FG_ACTOR_CAT16    gru_cat_actor_obs16
+#include "fg_actor_family.inc"
 
-// INBN: the shared actor behind the eval-mode input BatchNorm `bw`
-#define FG_ACTOR_DET      bn_actor_kernel
-#define FG_ACTOR_OUK      bn_ou_actor_kernel
-#define FG_ACTOR_SMP      bn_sample_kernel
-#define FG_ACTOR_FLAGS    PER_AGENT = false, LNORM = false, GRU = false, INBN = true
+// in_bn: the shared actor behind the eval-mode input BatchNorm `bw`
+#define FG_ACTOR_KIND     HD_ACTOR_BN
+#define FG_ACTOR_MAXH     64
+#define FG_ACTOR_WHAT     "BatchNorm "
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ false, /* lnorm */ false, /* gru */ false, /* in_bn */ true}
 #define FG_ACTOR_OPERANDS const ActorW w, const ActorBnW bw
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_TAB FG_ACTOR_NO_BTAB
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      bn_actor_kernel
+#define FG_ACTOR_SMP      bn_sample_kernel
+#define FG_ACTOR_OUK      bn_ou_actor_kernel
+#include "fg_actor_family.inc"
 
-// INBN, PER_AGENT: agent i evaluates tab's actor i behind btab's BatchNorm i
+// in_bn, per_agent: agent i evaluates tab's actor i behind btab's BatchNorm i
 static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + 2 * sizeof(void*) <= 4096, "kernel arguments: 4 KiB");
 static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(ActorOuW) <= 4096, "kernel arguments: 4 KiB");
-#define FG_ACTOR_DET      pa_bn_actor_kernel
-#define FG_ACTOR_OUK      pa_bn_ou_actor_kernel
-#define FG_ACTOR_SMP      pa_bn_sample_kernel
-#define FG_ACTOR_FLAGS    PER_AGENT = true, LNORM = false, GRU = false, INBN = true
+#define FG_ACTOR_KIND     HD_ACTOR_BN_PER_AGENT
+#define FG_ACTOR_MAXH     64
+#define FG_ACTOR_WHAT     "per-agent BatchNorm "
+#define FG_ACTOR_FLAGS    ActorFlags{/* per_agent */ true, /* lnorm */ false, /* gru */ false, /* in_bn */ true}
 #define FG_ACTOR_OPERANDS const ActorTab tab, const ActorBnTab btab
 #define FG_ACTOR_ABSENT   FG_ACTOR_NO_NW FG_ACTOR_NO_GW FG_ACTOR_NO_BW FG_ACTOR_NO_W
-#include "fg_actor_kernel_pair.inc"
+#define FG_ACTOR_DET      pa_bn_actor_kernel
+#define FG_ACTOR_SMP      pa_bn_sample_kernel
+#define FG_ACTOR_OUK      pa_bn_ou_actor_kernel
+#include "fg_actor_family.inc"
 
 #undef FG_ACTOR_NO_W
 #undef FG_ACTOR_NO_TAB
@@ -518,6 +566,11 @@ static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(Acto
 #undef FG_ACTOR_NO_BTAB
 #undef FG_ACTOR_NO_OW
 #undef FG_ACTOR_NO_CW
+#undef FG_ACTOR_NO_GAUSS
+#undef FG_ACTOR_NO_OBS16
+#undef FG_ACTOR_IS
+#undef FG_ACTOR_STR_
+#undef FG_ACTOR_STR
 
 }  // namespace fg
 

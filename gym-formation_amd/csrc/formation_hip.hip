@@ -991,113 +991,29 @@ static int launch_actor_pair(const char* det_name, const char* smp_name, const c
     return launch<Det>(grid, threads, lds, st, fail_fmt, args...);
 }
 
-// The formation_hd_env actor families, one kind per entry point fg_rollout_hd_actor* (in hd_actor_entry's order) and one
-// record per kind: the flags of its kernel pair (fg_actor_rollout_kernel.hpp), the widest H the pair is built for, the pair
-// itself, its names in the describe strings and what a failed launch is called.  HD_ACTOR_SAMPLE is a kind of its own for the
-// messages only: its kernels are the shared family's.  The kernels' operands after `a`, as hd_actor_dispatch builds them:
+// The formation_hd_env actor families: HdActorFamily<kind> (fg_actor_rollout_kernel.hpp) holds each family's flags, widest H,
+// members and failure text; here are the entry point that names each kind and the kernels' operands after `a` (hd_actor_dispatch):
 //     HD_ACTOR_SHARED        ActorW                          HD_ACTOR_GRU           ActorW, ActorNormW, ActorGruW
 //     HD_ACTOR_PER_AGENT     ActorTab                        HD_ACTOR_BN            ActorW, ActorBnW
 //     HD_ACTOR_NORM          ActorW, ActorNormW              HD_ACTOR_BN_PER_AGENT  ActorTab, ActorBnTab
-// The OU column is the family's third member (fg_rollout_hd_actor_ou*: a call with `noise` set), which takes an ActorOuW after
-// those operands; the LayerNorm families have none (hd_no_ou_kernel, never instantiated: no entry builds such a call).
-// The categorical column is the fourth member (fg_rollout_hd_actor_cat: a call with `cat` set), which takes an ActorCatW after
-// the operands; the per-agent and BatchNorm families have none (hd_no_cat_kernel, likewise).
-// The two 16-bit columns are the Gaussian and the categorical member with the 16-bit observation writer
-// (fg_rollout_hd_actor_obs16 / fg_rollout_hd_actor_cat_obs16: a call with `obs_format` set), which take the writer's format
-// after the member's arguments; the families with a categorical member have them, at N in {3, 9, 27} and H in {32, 64}
-// (hd_no_obs16_kernel elsewhere, likewise).
-enum HdActorKind { HD_ACTOR_SHARED, HD_ACTOR_SAMPLE, HD_ACTOR_PER_AGENT, HD_ACTOR_NORM, HD_ACTOR_GRU, HD_ACTOR_BN,
-                   HD_ACTOR_BN_PER_AGENT };
 static const char* const hd_actor_entry[] = {"fg_rollout_hd_actor", "fg_rollout_hd_actor_sample", "fg_rollout_hd_actor_per_agent",
                                              "fg_rollout_hd_actor_norm", "fg_rollout_hd_actor_gru", "fg_rollout_hd_actor_bn",
                                              "fg_rollout_hd_actor_bn_per_agent"};
-template <int NC, int H> constexpr std::nullptr_t hd_no_ou_kernel = nullptr;
-template <int NC, int H> constexpr std::nullptr_t hd_no_cat_kernel = nullptr;
-template <int NC, int H> constexpr std::nullptr_t hd_no_obs16_kernel = nullptr;
-constexpr bool actor_obs16_shape(int n, int h) { return (n == 3 || n == 9 || n == 27) && (h == 32 || h == 64); }
-template <HdActorKind> struct HdActorFamily;
-#define FG_HD_ACTOR_FAMILY(KIND, PA, LN, GR, BN, MAXH, DET, SMP, OUK, CATK, SMP16, CAT16, WHAT)                        \
-    template <> struct HdActorFamily<KIND> {                                                                      \
-        static constexpr bool per_agent = PA, lnorm = LN, gru = GR, in_bn = BN;                                   \
-        static constexpr int max_h = MAXH;                                                                        \
-        template <int NC, int H> static constexpr auto det = &DET<NC, H>;                                         \
-        template <int NC, int H> static constexpr auto smp = &SMP<NC, H>;                                         \
-        static constexpr bool has_ou = !LN;                                                                       \
-        template <int NC, int H> static constexpr auto ou = OUK<NC, H>;                                           \
-        static constexpr bool has_cat = !PA && !BN;                                                               \
-        template <int NC, int H> static constexpr auto cat = CATK<NC, H>;                                         \
-        static constexpr bool has_obs16 = !PA && !BN;                                                             \
-        template <int NC, int H> static constexpr auto smp16 = SMP16<NC, H>;                                      \
-        template <int NC, int H> static constexpr auto cat16 = CAT16<NC, H>;                                      \
-        static constexpr const char* det_name = #DET;                                                             \
-        static constexpr const char* smp_name = #SMP;                                                             \
-        static constexpr const char* ou_name = #OUK;                                                              \
-        static constexpr const char* cat_name = #CATK;                                                            \
-        static constexpr const char* smp16_name = #SMP16;                                                         \
-        static constexpr const char* cat16_name = #CAT16;                                                         \
-        static constexpr const char* fail_fmt = WHAT "actor rollout launch failed: %s";                           \
-        static_assert(!(PA && LN), "no per-agent actor kernel with LayerNorms");                                  \
-        static_assert(!GR || LN, "the recurrent actor's base is the LayerNorm actor");                            \
-        static_assert(!(BN && LN), "the input BatchNorm is in front of the plain body only");                     \
-        template <int NC, int H, bool SAMPLE, bool OU = false, bool CAT = false>                                  \
-        static constexpr int lds_bytes = actor_lds_bytes<NC, H, SAMPLE, PA, LN, GR, BN, OU, CAT>();               \
-    };
-//                 kind                   PER_AGENT LNORM  GRU    INBN   max H  deterministic         Gaussian             OU noise               categorical           Gaussian, 16-bit    categorical, 16-bit
-FG_HD_ACTOR_FAMILY(HD_ACTOR_SHARED,       false,    false, false, false, 128,   actor_rollout_kernel, actor_sample_kernel, ou_actor_kernel,       cat_actor_kernel,     actor_sample_obs16, cat_actor_obs16,     "")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_PER_AGENT,    true,     false, false, false, 128,   pa_actor_kernel,      pa_sample_kernel,    pa_ou_actor_kernel,    hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "per-agent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_NORM,         false,    true,  false, false, 64,    ln_actor_kernel,      ln_sample_kernel,    hd_no_ou_kernel,       ln_cat_actor_kernel,  ln_sample_obs16,    ln_cat_actor_obs16,  "LayerNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_GRU,          false,    true,  true,  false, 64,    gru_actor_kernel,     gru_sample_kernel,   hd_no_ou_kernel,       gru_cat_actor_kernel, gru_sample_obs16,   gru_cat_actor_obs16, "recurrent ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN,           false,    false, false, true,  64,    bn_actor_kernel,      bn_sample_kernel,    bn_ou_actor_kernel,    hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "BatchNorm ")
-FG_HD_ACTOR_FAMILY(HD_ACTOR_BN_PER_AGENT, true,     false, false, true,  64,    pa_bn_actor_kernel,   pa_bn_sample_kernel, pa_bn_ou_actor_kernel, hd_no_cat_kernel,     hd_no_obs16_kernel, hd_no_obs16_kernel,  "per-agent BatchNorm ")
-#undef FG_HD_ACTOR_FAMILY
-template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARED> {};
 
-// one kernel pair of the family F at <NC, H>, or with `ow` the family's OU member, or with `cw` its categorical member, or with
-// `obs_format` (FG_OBS_F16 / FG_OBS_BF16; 0: fp32) the 16-bit twin of its Gaussian or - `cw` - categorical member; `w`: the
-// family's operands
-template <int NC, int H, class F, class... W>
-static int launch_hd_actor(const Args& a, const float* log_std, float* logp, const ActorOuW* ow, const ActorCatW* cw, int obs_format,
-                           hipStream_t st, const W&... w) {
-    static_assert(F::template lds_bytes<NC, H, true> <= 160 * 1024, "actor rollout LDS");
-    constexpr int E = actor_envs(NC);
-    char targs[16];
-    snprintf(targs, sizeof(targs), "%d,%d", NC, H);
-    if (obs_format) {                                  // (the 16-bit tiles share the wave's activation tile: the fp32 twin's LDS)
-        if constexpr (F::has_obs16 && actor_obs16_shape(NC, H)) {
-            const int fmt = obs_format == FG_OBS_F16 ? FG_WR_OBS_F16 : FG_WR_OBS_BF16;
-            const int grid = (a.B + E - 1) / E;
-            if (cw) {
-                constexpr int lds = F::template lds_bytes<NC, H, false, false, true>;
-                if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::cat16_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
-                return launch<F::template cat16<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *cw, fmt);
-            }
-            constexpr int lds = F::template lds_bytes<NC, H, true>;
-            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::smp16_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
-            return launch<F::template smp16<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., log_std, logp, fmt);
-        }
-        return fail(FG_ERR_UNSUPPORTED_N, "16-bit observations: no fused actor launch for this family, agent count or width%s");   // (unreachable after hd_actor_check)
+// Describe-or-launch of the member M of the family F at <NC, H>: `args` are the kernel's arguments after `a` - the family's
+// operands, then the member's.  The LDS bytes come from the value the kernel's own flags come from.
+template <ActorMember M, int NC, int H, class F, class... A>
+static int launch_hd_member(const Args& a, hipStream_t st, const A&... args) {
+    if constexpr (F::has(M, NC, H)) {
+        constexpr int E = actor_envs(NC), lds = actor_lds_bytes(NC, H, F::flags, M);
+        static_assert(lds <= 160 * 1024, "actor rollout LDS");
+        const int grid = (a.B + E - 1) / E;
+        if (describe("%s<%d,%d> grid %d block %d envs/wg %d lds %d; ", F::name(M), NC, H, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
+        return launch<F::template kernel<M, NC, H>()>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, args...);
+    } else {                                           // (no entry builds such a call: hd_actor_check)
+        return actor_member_obs16(M) ? fail(FG_ERR_UNSUPPORTED_N, "16-bit observations: no fused actor launch for this family, agent count or width%s")
+                                     : fail(FG_ERR_BAD_ARG, "this actor family has no such member%s");
     }
-    if constexpr (F::has_ou) {
-        if (ow) {
-            constexpr int lds = F::template lds_bytes<NC, H, false, true>;
-            static_assert(lds <= 160 * 1024, "actor rollout LDS");
-            const int grid = (a.B + E - 1) / E;
-            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::ou_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
-            return launch<F::template ou<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *ow);
-        }
-    }
-    if constexpr (F::has_cat) {
-        if (cw) {
-            constexpr int lds = F::template lds_bytes<NC, H, false, false, true>;
-            static_assert(lds <= 160 * 1024, "actor rollout LDS");
-            const int grid = (a.B + E - 1) / E;
-            if (describe("%s<%s> grid %d block %d envs/wg %d lds %d; ", F::cat_name, targs, grid, FG_ACTOR_THREADS, E, lds)) return FG_OK;
-            return launch<F::template cat<NC, H>>(grid, FG_ACTOR_THREADS, lds, st, F::fail_fmt, a, w..., *cw);
-        }
-    }
-    return launch_actor_pair<F::template det<NC, H>, F::template smp<NC, H>>(
-        F::det_name, F::smp_name, targs, "block", (a.B + E - 1) / E, FG_ACTOR_THREADS, E,
-        log_std ? F::template lds_bytes<NC, H, true> : F::template lds_bytes<NC, H, false>, F::fail_fmt, st, log_std, logp, a, w...);
 }
 
 // A failed check of an actor description, in the name of the entry `who` [and of the per-agent entry's member `member`]:
@@ -1182,11 +1098,21 @@ struct HdActorCall {
     int obs_format = 0;
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
+// the member of the call's family that runs: the one place that reads these four fields for it
+static ActorMember hd_actor_member(const HdActorCall& c) {
+    if (c.obs_format) return c.cat.on ? ACTOR_CAT16 : ACTOR_GAUSS16;
+    if (c.cat.on) return ACTOR_CAT;
+    if (c.noise.on) return ACTOR_OU;
+    return c.log_std ? ACTOR_GAUSS : ACTOR_DET;
+}
 static const char* hd_actor_who(const HdActorCall& c) {
-    if (c.obs_format) return c.cat.on ? "fg_rollout_hd_actor_cat_obs16" : "fg_rollout_hd_actor_obs16";
-    if (c.cat.on) return "fg_rollout_hd_actor_cat";
-    if (c.noise.on) return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
-    return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
+    switch (hd_actor_member(c)) {
+    case ACTOR_CAT16: return "fg_rollout_hd_actor_cat_obs16";
+    case ACTOR_GAUSS16: return "fg_rollout_hd_actor_obs16";
+    case ACTOR_CAT: return "fg_rollout_hd_actor_cat";
+    case ACTOR_OU: return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
+    default: return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
+    }
 }
 // FgActorNorm's checks (no device touched), in the name of the entry `who`: hidden 32 or 64, every eps that is read positive and
 // finite, gamma / beta 4-byte aligned
@@ -1374,15 +1300,27 @@ static int actor_nh_dispatch(int N, int hidden, const char* who, F&& launch) {
 #undef FG_ACTOR
     return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
 }
+// the call's member of the family F at <NC, H>: `w` are the family's operands, and each case adds its member's arguments
+template <int NC, int H, class F, class... W>
+static int launch_hd_actor(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
+    const ActorOuW ow = c.noise.on ? actor_ou_w(c.noise) : ActorOuW{};
+    const ActorCatW cw = {c.cat.mode, c.cat.greedy ? 1 : 0, c.cat.idx, c.cat.logp};
+    const int fmt = c.obs_format == FG_OBS_F16 ? FG_WR_OBS_F16 : FG_WR_OBS_BF16;      // (the writer's, read by the 16-bit members)
+    switch (hd_actor_member(c)) {
+    case ACTOR_GAUSS: return launch_hd_member<ACTOR_GAUSS, NC, H, F>(a, st, w..., c.log_std, c.logp);
+    case ACTOR_OU: return launch_hd_member<ACTOR_OU, NC, H, F>(a, st, w..., ow);
+    case ACTOR_CAT: return launch_hd_member<ACTOR_CAT, NC, H, F>(a, st, w..., cw);
+    case ACTOR_GAUSS16: return launch_hd_member<ACTOR_GAUSS16, NC, H, F>(a, st, w..., c.log_std, c.logp, fmt);
+    case ACTOR_CAT16: return launch_hd_member<ACTOR_CAT16, NC, H, F>(a, st, w..., cw, fmt);
+    default: return launch_hd_member<ACTOR_DET, NC, H, F>(a, st, w...);
+    }
+}
 // the family KIND's kernel for the call's (N, hidden), with the family's operands `w`
 template <HdActorKind KIND, class... W>
 static int hd_actor_run(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
     const char* const who = c.kind == HD_ACTOR_SAMPLE ? hd_actor_entry[HD_ACTOR_SHARED] : hd_actor_who(c);
-    const ActorOuW ow = c.noise.on ? actor_ou_w(c.noise) : ActorOuW{};
-    const ActorCatW cw = {c.cat.mode, c.cat.greedy ? 1 : 0, c.cat.idx, c.cat.logp};
     return actor_nh_dispatch<HdActorFamily<KIND>::max_h>(a.N, c.actor[0].hidden, who, [&](auto n, auto h) {
-        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(
-            a, c.log_std, c.logp, c.noise.on ? &ow : nullptr, c.cat.on ? &cw : nullptr, c.obs_format, st, w...);
+        return launch_hd_actor<decltype(n)::value, decltype(h)::value, HdActorFamily<KIND>>(a, c, st, w...);
     });
 }
 // a checked call (hd_actor_check) to its kernel; a describe twin passes a NULL stream

@@ -336,46 +336,45 @@ class Scenario(BaseScenario):
         if cat is not None:
             if ou is not None or bns is not None or actor.per_agent or log_std is not None:
                 raise NotImplementedError("a CategoricalActor fuses on the plain, the LayerNorm and the recurrent body only")
-            keep_states = rnn_states_every is not None
-            args = state + (out["idx"].data_ptr(), out["log_prob"].data_ptr(), _native.ptr(rnn_state) if gru is not None else None,
-                            out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1) + tail
-            keep = (out, actor.tensors(), fas, norm, gru, rnn_state)
-            fn, fmt = self._rollout_entry(lib, "fg_rollout_hd_actor_cat", obs_format)
-            by_flag = [_native.bind_launch(fn, p, *fmt, fas, norm, gru, int(act_mode), greedy, *args, keep=keep)
-                       for greedy in (0, 1)]
+        elif (gru is not None and norm is None) or (norm is not None and actor.per_agent):
+            raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
+        elif obs_format and (ou is not None or bns is not None or actor.per_agent or log_std is None):
+            raise NotImplementedError("16-bit observations fuse with a Gaussian or categorical actor on the plain, the LayerNorm "
+                                      "and the recurrent body only")
+        # What may follow the state block: the indices, the log-probs, the hidden state, the kept states with their stride
+        # (NULL and 1 where none are kept)
+        keep_states = rnn_states_every is not None
+        idx = (out["idx"].data_ptr(),) if cat is not None else ()
+        logp = (None if cat is None and log_std is None else out["log_prob"].data_ptr(),)
+        rnn = (_native.ptr(rnn_state) if gru is not None else None,)
+        states = (out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1)
+        # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, what follows
+        # the state).  A categorical entry takes `greedy` as its last leading argument, one bound launch per value.
+        ls, nst = _native.ptr(log_std), _native.ptr(noise_state)
+        fmt, x16 = ((int(obs_format),), "_obs16") if obs_format else ((), "")
+        families = (
+            (cat is not None, "fg_rollout_hd_actor_cat" + x16, fmt + (fas, norm, gru, int(act_mode)), idx + logp + rnn + states),
+            (bool(obs_format), "fg_rollout_hd_actor_obs16", fmt + (fas, norm, gru, ls), logp + rnn + states),
+            (ou is not None and actor.per_agent, "fg_rollout_hd_actor_ou_per_agent", (fas, bns, fou, nst), ()),
+            (ou is not None, "fg_rollout_hd_actor_ou", (fas, bns, fou, nst), ()),
+            (bns is not None and actor.per_agent, "fg_rollout_hd_actor_bn_per_agent", (fas, bns, ls), logp),
+            (bns is not None, "fg_rollout_hd_actor_bn", (fas, bns, ls), logp),
+            (keep_states, "fg_rollout_hd_actor_gru_states", (fas, norm, gru, ls), logp + rnn + states),
+            (gru is not None, "fg_rollout_hd_actor_gru", (fas, norm, gru, ls), logp + rnn),
+            (norm is not None, "fg_rollout_hd_actor_norm", (fas, norm, ls), logp),
+            (actor.per_agent, "fg_rollout_hd_actor_per_agent", (fas, ls), logp),
+            (log_std is not None, "fg_rollout_hd_actor_sample", (fas, ls), logp),
+            (True, "fg_rollout_hd_actor", (fas,), ()))
+        entry, lead, after = next(row[1:] for row in families if row[0])
+        args = state + after + tail
+        keep = (out, actor.tensors(), fas, norm, gru, bns, fou, rnn_state, noise_state)
+        if cat is not None:
+            by_flag = [_native.bind_launch(getattr(lib, entry), p, *lead, greedy, *args, keep=keep) for greedy in (0, 1)]
 
             def launch_cat(rng_offset=0):              # the module's flag as it is now: sampled or the distribution's mode
                 return by_flag[1 if cat.deterministic else 0](rng_offset)
             return launch_cat
-        if (gru is not None and norm is None) or (norm is not None and actor.per_agent):
-            raise NotImplementedError("PerAgentActor members with LayerNorms or a recurrent layer have no fused launch")
-        # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, and
-        # what follows the state: logp_seq, rnn_state, (rnn_states, states_every))
-        ls, nst = _native.ptr(log_std), _native.ptr(noise_state)
-        if obs_format and (ou is not None or bns is not None or actor.per_agent or log_std is None):
-            raise NotImplementedError("16-bit observations fuse with a Gaussian or categorical actor on the plain, the LayerNorm "
-                                      "and the recurrent body only")
-        families = (
-            (bool(obs_format), "fg_rollout_hd_actor_obs16", (int(obs_format), fas, norm, gru, ls), True, True, True),
-            (ou is not None and actor.per_agent, "fg_rollout_hd_actor_ou_per_agent", (fas, bns, fou, nst), False, False, False),
-            (ou is not None, "fg_rollout_hd_actor_ou", (fas, bns, fou, nst), False, False, False),
-            (bns is not None and actor.per_agent, "fg_rollout_hd_actor_bn_per_agent", (fas, bns, ls), True, False, False),
-            (bns is not None, "fg_rollout_hd_actor_bn", (fas, bns, ls), True, False, False),
-            (rnn_states_every is not None, "fg_rollout_hd_actor_gru_states", (fas, norm, gru, ls), True, True, True),
-            (gru is not None, "fg_rollout_hd_actor_gru", (fas, norm, gru, ls), True, True, False),
-            (norm is not None, "fg_rollout_hd_actor_norm", (fas, norm, ls), True, False, False),
-            (actor.per_agent, "fg_rollout_hd_actor_per_agent", (fas, ls), True, False, False),
-            (log_std is not None, "fg_rollout_hd_actor_sample", (fas, ls), True, False, False),
-            (True, "fg_rollout_hd_actor", (fas,), False, False, False))
-        entry, lead, with_logp, with_state, with_states = next(row[1:] for row in families if row[0])
-        logp = (None if log_std is None else out["log_prob"].data_ptr(),) if with_logp else ()
-        hidden = (_native.ptr(rnn_state) if gru is not None else None,) if with_state else ()
-        if with_states:                                    # (the 16-bit entry takes both: NULL and 1 where none are kept)
-            keep_states = rnn_states_every is not None
-            hidden += (out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1)
-        args = lead + state + logp + hidden + tail
-        launch = _native.bind_launch(getattr(lib, entry), p, *args,
-                                     keep=(out, actor.tensors(), fas, norm, gru, bns, fou, rnn_state, noise_state))
+        launch = _native.bind_launch(getattr(lib, entry), p, *lead, *args, keep=keep)
         if ou is None:
             return launch
 

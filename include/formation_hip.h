@@ -745,7 +745,7 @@ int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor*
 int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream);
 
 /* The MAPPO trainers' discrete-action policy (make_env(..., discrete_action=True): a head Linear(hidden, 5) under a
- * Categorical) as the fourth member of the plain, LayerNorm and recurrent families: cat_actor_kernel (norm == NULL),
+ * Categorical) as the categorical member of the plain, LayerNorm and recurrent families: cat_actor_kernel (norm == NULL),
  * ln_cat_actor_kernel (norm) and gru_cat_actor_kernel (norm and gru), at those families' N and hidden widths.  The actor is
  * fg_rollout_hd_actor's / _norm's / _gru's with w3 [5][hidden], b3 [5] (or NULL) and out_tanh == 0.  Per (env b, agent i,
  * step k) the five fp32 logits l_j are ascending fmaf chains from b3[j], and, in fp32,
