@@ -3,27 +3,27 @@
 // FG_ACTOR_WHAT (its HdActorKind, the widest H it is built for, its word in a failed launch's text), FG_ACTOR_FLAGS (its
 // ActorFlags), FG_ACTOR_OPERANDS (the kernel parameters after `a`), FG_ACTOR_ABSENT (the FG_ACTOR_NO_* constants of the operands
 // it does not take), FG_ACTOR_DET and FG_ACTOR_SMP (the names of the deterministic and the Gaussian member) and, where it has
-// them, FG_ACTOR_OUK, FG_ACTOR_CATK and - together - FG_ACTOR_SMP16 and FG_ACTOR_CAT16 (the OU, categorical and 16-bit
-// members); they are undefined again here.  A wrapper is its member (FG_ACTOR_IS: the body's flags, from the predicates the
+// them, FG_ACTOR_OUK, FG_ACTOR_CATK, FG_ACTOR_GUMK and - together - FG_ACTOR_SMP16 and FG_ACTOR_CAT16 (the OU, categorical, Gumbel
+// and 16-bit members); they are undefined again here.  A wrapper is its member (FG_ACTOR_IS: the body's flags, from the predicates the
 // host sizes the LDS with), the member's kernel parameters after the family's operands, and the stand-ins for the ones it lacks.
 // Not a header: no guard.  The body stays a textual include in each kernel (fg_actor_rollout_body.inc says why).
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_DET(const Args a, FG_ACTOR_OPERANDS) {
-    FG_ACTOR_IS(ACTOR_DET) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16
+    FG_ACTOR_IS(ACTOR_DET) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16 FG_ACTOR_NO_GUM
 #include "fg_actor_rollout_body.inc"
 }
 // log_std [2] read in place, log-probs to logp [K][B][N] when it is not NULL
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP(const Args a, FG_ACTOR_OPERANDS, const float* log_std,
                                                                  float* logp) {
-    FG_ACTOR_IS(ACTOR_GAUSS) FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16
+    FG_ACTOR_IS(ACTOR_GAUSS) FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16 FG_ACTOR_NO_GUM
 #include "fg_actor_rollout_body.inc"
 }
 // no log_std, no log-probs; the noise state ow.state [B][N][2] read at launch start, written at the end
 #ifdef FG_ACTOR_OUK
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_OUK(const Args a, FG_ACTOR_OPERANDS, const ActorOuW ow) {
-    FG_ACTOR_IS(ACTOR_OU) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16
+    FG_ACTOR_IS(ACTOR_OU) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16 FG_ACTOR_NO_GUM
 #include "fg_actor_rollout_body.inc"
 }
 #endif
@@ -31,7 +31,15 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_OUK(const Args a, F
 #ifdef FG_ACTOR_CATK
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_CATK(const Args a, FG_ACTOR_OPERANDS, const ActorCatW cw) {
-    FG_ACTOR_IS(ACTOR_CAT) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_OBS16
+    FG_ACTOR_IS(ACTOR_CAT) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_OBS16 FG_ACTOR_NO_GUM
+#include "fg_actor_rollout_body.inc"
+}
+#endif
+// no log_std, no log-probs; indices to gum.idx [K][B][N]
+#ifdef FG_ACTOR_GUMK
+template <int NC, int H>
+__global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_GUMK(const Args a, FG_ACTOR_OPERANDS, const ActorGumW gum) {
+    FG_ACTOR_IS(ACTOR_GUMBEL) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_OBS16
 #include "fg_actor_rollout_body.inc"
 }
 #endif
@@ -40,13 +48,13 @@ __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_CATK(const Args a, 
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_SMP16(const Args a, FG_ACTOR_OPERANDS, const float* log_std,
                                                                    float* logp, const int obs_fmt) {
-    FG_ACTOR_IS(ACTOR_GAUSS16) FG_ACTOR_NO_OW FG_ACTOR_NO_CW
+    FG_ACTOR_IS(ACTOR_GAUSS16) FG_ACTOR_NO_OW FG_ACTOR_NO_CW FG_ACTOR_NO_GUM
 #include "fg_actor_rollout_body.inc"
 }
 template <int NC, int H>
 __global__ __launch_bounds__(FG_ACTOR_THREADS) void FG_ACTOR_CAT16(const Args a, FG_ACTOR_OPERANDS, const ActorCatW cw,
                                                                    const int obs_fmt) {
-    FG_ACTOR_IS(ACTOR_CAT16) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW
+    FG_ACTOR_IS(ACTOR_CAT16) FG_ACTOR_NO_GAUSS FG_ACTOR_NO_OW FG_ACTOR_NO_GUM
 #include "fg_actor_rollout_body.inc"
 }
 #endif
@@ -71,6 +79,9 @@ template <> struct HdActorFamily<FG_ACTOR_KIND> {
         case ACTOR_GAUSS16: return FG_ACTOR_STR(FG_ACTOR_SMP16);
         case ACTOR_CAT16: return FG_ACTOR_STR(FG_ACTOR_CAT16);
 #endif
+#ifdef FG_ACTOR_GUMK
+        case ACTOR_GUMBEL: return FG_ACTOR_STR(FG_ACTOR_GUMK);
+#endif
         default: return nullptr;
         }
     }
@@ -87,6 +98,9 @@ template <> struct HdActorFamily<FG_ACTOR_KIND> {
         else if constexpr (M == ACTOR_GAUSS16) return &FG_ACTOR_SMP16<NC, H>;
         else if constexpr (M == ACTOR_CAT16) return &FG_ACTOR_CAT16<NC, H>;
 #endif
+#ifdef FG_ACTOR_GUMK
+        else if constexpr (M == ACTOR_GUMBEL) return &FG_ACTOR_GUMK<NC, H>;
+#endif
     }
 };
 
@@ -100,5 +114,6 @@ template <> struct HdActorFamily<FG_ACTOR_KIND> {
 #undef FG_ACTOR_SMP
 #undef FG_ACTOR_OUK
 #undef FG_ACTOR_CATK
+#undef FG_ACTOR_GUMK
 #undef FG_ACTOR_SMP16
 #undef FG_ACTOR_CAT16

@@ -21,6 +21,9 @@
 // wsm + WS.  Both lanes of a row evaluate the five ascending chains (the same bits), draw the row's uniform at `off` and run
 // cat_pick (cw.greedy: the mode instead of a sample, wave-uniform); `y` is component o of the decoded action (cat_decode by
 // cw.mode) and `pick` the row's index and log-prob, which the body stores.  No tanh.
+// `constexpr bool GUM` (with `gum`, ActorGumW; formation_hd_env's body only): the same five-logit block, then the row's five
+// Gumbel draws at `off` (actor_gumbel; none when gum.explore is 0, wave-uniform) and gumbel_pick; `y` is component o of the decoded
+// action (cat_decode by gum.mode) and `pick.idx` the row's index, which the body stores.  No log-prob, no tanh.
             actor_store_tile(hb, HS, acc, col, kq);
             WaveSync()();
             if constexpr (LNORM) {
@@ -60,10 +63,10 @@
             // ---- layer 3 on the VALU: lane = (row of the pass, output), an ascending fmaf chain ----
             const int row = lane >> 1, o = lane & 1;
             const float* const hr = hb + row * HS;
-            const float* const w3 = wsm + 2 * H + (CAT ? 0 : o * H);
-            float y = CAT ? 0.f : wsm[4 * H + o];
-            CatPick pick = {};                     // CAT: the row's index and log-prob
-            if constexpr (CAT) {
+            const float* const w3 = wsm + 2 * H + ((CAT || GUM) ? 0 : o * H);
+            float y = (CAT || GUM) ? 0.f : wsm[4 * H + o];
+            CatPick pick = {};                     // CAT: the row's index and log-prob; GUM: the row's index
+            if constexpr (CAT || GUM) {
                 float l[FG_CAT];
 #pragma unroll
                 for (int j = 0; j < FG_CAT; ++j) l[j] = wsm[WS + j];
@@ -74,12 +77,21 @@
                     for (int j = 0; j < FG_CAT; ++j) l[j] = __builtin_fmaf(hk, w3[j * H + k], l[j]);
                 }
                 const int qc = q0 + row, ee = qc / N;
+                if constexpr (GUM) {
+                    // both lanes of a row draw the row's five Gumbel values at counter offset `off` and pick the same index
+                    float gd[FG_CAT] = {};
+                    if (gum.explore) actor_gumbel(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(qc - ee * N), off, gd);
+                    pick.idx = gumbel_pick(l, gd, gum.explore != 0);
+                    const float2 ua = cat_decode(gum.mode, pick.idx);
+                    y = o ? ua.y : ua.x;
+                } else {
                 // both lanes of a row draw the row's uniform at counter offset `off` and pick the same index
                 const float ud = cw.greedy ? 0.f
                                            : actor_uniform(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)(qc - ee * N), off);
                 pick = cat_pick(l, ud, cw.greedy != 0);
                 const float2 ua = cat_decode(cw.mode, pick.idx);
                 y = o ? ua.y : ua.x;
+                }
             } else {
 #pragma unroll 8
                 for (int k = 0; k < H; ++k) y = __builtin_fmaf(hr[k], w3[k], y);

@@ -5,18 +5,18 @@
 // fg_actor_mlp.inc and the bodies' layer 1 (actor_bias_init) read it back.  Not a header: no guard.
 // `constexpr bool LNORM` (with `nw`, ActorNormW): the two hidden LayerNorms' gamma1 [H] | beta1 [H] | gamma2 [H] | beta2 [H]
 // follow at wsm + WS + WB (WB: the floats of the b3 | log_std slot, 4), a NULL gamma as ones and a NULL beta as zeros.
-// `constexpr bool CAT` (WS = 7 H, WB = 8): W3 [5][H] at wsm + 2 H and b3 [5] at wsm + WS; no log_std.
+// `constexpr bool CAT` or `GUM` - a head of five - (WS = 7 H, WB = 8): W3 [5][H] at wsm + 2 H and b3 [5] at wsm + WS; no log_std.
     for (int q = tid; q < H; q += FG_ACTOR_THREADS) {
         wsm[q] = w.b1 ? w.b1[q] : 0.f;
         wsm[H + q] = w.b2 ? w.b2[q] : 0.f;
         wsm[2 * H + q] = w.w3[q];
         wsm[3 * H + q] = w.w3[H + q];
-        if constexpr (CAT) {
+        if constexpr (CAT || GUM) {
 #pragma unroll
             for (int j = 2; j < FG_CAT; ++j) wsm[(2 + j) * H + q] = w.w3[j * H + q];
         }
     }
-    if constexpr (CAT) {
+    if constexpr (CAT || GUM) {
         if (tid < FG_CAT) wsm[WS + tid] = w.b3 ? w.b3[tid] : 0.f;
     } else {
         if (tid < 2) wsm[4 * H + tid] = w.b3 ? w.b3[tid] : 0.f;

@@ -1,7 +1,7 @@
 // fg_actor_rollout_body.inc - the one body of every formation_hd_env actor kernel: each member of each family block of
 // fg_actor_rollout_kernel.hpp.  Included inside each kernel (fg_actor_family.inc), whose scope provides NC and H, the member and
-// the family's flags (FG_ACTOR_IS: MEMBER and FLAGS, and from them the eight `constexpr bool`s the branches below test), the
-// kernel arguments `a` (Args) and `w tab nw gw bw btab ow cw`, `log_std` / `logp` and `obs_fmt` - each a kernel parameter where
+// the family's flags (FG_ACTOR_IS: MEMBER and FLAGS, and from them the nine `constexpr bool`s the branches below test), the
+// kernel arguments `a` (Args) and `w tab nw gw bw btab ow cw gum`, `log_std` / `logp` and `obs_fmt` - each a kernel parameter where
 // the family or the member takes it, and an empty constant, nullptr or 0 where it does not.  The LDS blocks are
 // actor_lds_layout's, the function the host sizes the launch with.
 //   PER_AGENT  `tab` (ActorTab) instead of `w` (ActorW), of which only `w.out_tanh` is read; its layers 1 to 3 are here.
@@ -19,6 +19,9 @@
 //              its done envs' rows set to mu by the physics phase, stored back after the last step.
 //   CAT        `cw` (ActorCatW): the five-output head of fg_actor_mlp.inc leaves the decoded action in the actions' block and
 //              the row's index and log-prob in two blocks [E N] behind it; the physics phase stores the three.
+//   GUM        `gum` (ActorGumW): the five-output head under Gumbel noise - fg_actor_mlp.inc's for the shared families, the
+//              per-agent branch here - leaves the decoded action in the actions' block and the row's index in the block [E N]
+//              behind it; the physics phase stores the two.  There is no log-prob block.
 //   OBS16      `obs_fmt`: the stream phase stores fp16 / bf16 units through write_obs16 (fg_obs_writers.hpp) instead of
 //              write_obs_rows, the format a run-time, wave-uniform fact of the launch; its tile is the wave's activation tile.
 // Not a header: no guard.
@@ -40,9 +43,10 @@
     // EP >= 16 - so that every 16-row MFMA tile holds one agent and takes that agent's weights as its B operand
     constexpr int EP = E >= 16 ? E : 16;
     constexpr int TILES = ((PER_AGENT ? EP * N : E * N) + FG_ACTOR_ROWS - 1) / FG_ACTOR_ROWS;
-    constexpr int WS = actor_w_floats(H, PER_AGENT, CAT);   // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
-    constexpr int WB = actor_b3_floats(CAT);            // ... and of the b3 | log_std slot behind them
+    constexpr int WS = actor_w_floats(H, PER_AGENT, CAT || GUM);   // floats of b1 | b2 | W3 in LDS (PER_AGENT: read through L1)
+    constexpr int WB = actor_b3_floats(CAT || GUM);     // ... and of the b3 | log_std slot behind them
     static_assert(!CAT || (!SAMPLE && !OU && !PER_AGENT && !INBN), "the categorical actor: a shared body, no Gaussian or OU noise");
+    static_assert(!GUM || (!SAMPLE && !OU && !CAT && !OBS16 && !LNORM && !GRU), "the Gumbel actor: a body without LayerNorms, no other noise");
     static_assert(!PER_AGENT || (RT == 2 && (EP & (EP - 1)) == 0), "per-agent rows: two tiles per pass, EP a power of two");
     constexpr int DP = actor_in_pad(N);                 // the input width rounded up to 4: the input norms' tables
     static_assert(!LNORM || !PER_AGENT, "the LayerNorm actor is a shared actor");
@@ -58,7 +62,7 @@
     constexpr ActorLds L = actor_lds_layout(N, H, FLAGS, MEMBER);
     float2* const act_lds = reinterpret_cast<float2*>(smemf + L.act);
     float* const logp_lds = smemf + L.logp;             // SAMPLE and CAT only
-    int* const idx_lds = reinterpret_cast<int*>(logp_lds + (L.idx - L.logp));   // CAT only
+    int* const idx_lds = reinterpret_cast<int*>(logp_lds + (L.idx - L.logp));   // CAT and GUM only
     float* const wsm = logp_lds + (L.wsm - L.logp);     // b1 | b2 | W3 | b3 | log_std
     float* const ln0 = wsm + (L.ln - L.wsm) + 4 * H;    // LNORM: behind the hidden norms' four [H], gamma0 [DP] | beta0 [DP], zeros at k >= D
     float* const bn0 = wsm + (L.bn - L.wsm);            // INBN, shared: mean | istd | gamma | beta [DP] each, zeros at k >= D
@@ -363,6 +367,31 @@
                 const int row = lane >> 1, o = lane & 1;
                 const float* const hr = hb + row * HS;
                 gfloat* const b3 = (gfloat*)(row < 16 ? tab.b3[ra[0]] : tab.b3[ra[1]]);
+                if constexpr (GUM) {
+                    // a head of five: both lanes of a row evaluate the five ascending chains from b3[j] (the shared kernel's
+                    // bits), draw for (env ee, agent r) of the agent-major row and pick; lane o writes component o
+                    gfloat* const w3 = (gfloat*)(row < 16 ? tab.w3[ra[0]] : tab.w3[ra[1]]);
+                    float l[FG_CAT];
+#pragma unroll
+                    for (int j = 0; j < FG_CAT; ++j) l[j] = b3 ? b3[j] : 0.f;
+#pragma unroll 4
+                    for (int k = 0; k < H; ++k) {
+                        const float hk = hr[k];
+#pragma unroll
+                        for (int j = 0; j < FG_CAT; ++j) l[j] = __builtin_fmaf(hk, w3[j * H + k], l[j]);
+                    }
+                    const int q = q0 + row;
+                    const int ee = q % EP, r = q / EP, slot = ee * N + r;
+                    const bool ok = ee < El && r < N;
+                    float gd[FG_CAT] = {};
+                    if (gum.explore) actor_gumbel(a.p.seed, (uint32_t)(b0 + ee + a.p.env_index_base), (uint32_t)r, off, gd);
+                    const int pk = gumbel_pick(l, gd, gum.explore != 0);
+                    const float2 ua = cat_decode(gum.mode, pk);
+                    if (ok) {
+                        reinterpret_cast<float*>(act_lds)[2 * slot + o] = o ? ua.y : ua.x;
+                        if (o == 0) idx_lds[slot] = pk;
+                    }
+                } else {
                 gfloat* const w3 = (gfloat*)(row < 16 ? tab.w3[ra[0]] : tab.w3[ra[1]]) + o * H;
                 float y = b3 ? b3[o] : 0.f;
 #pragma unroll 8
@@ -387,6 +416,7 @@
                     }
                 }
                 if (ok) reinterpret_cast<float*>(act_lds)[2 * slot + o] = y;
+                }
             } else {
 #include "fg_actor_mlp.inc"
                 if constexpr (SAMPLE) {
@@ -394,6 +424,9 @@
                 }
                 if constexpr (CAT) {
                     if (q < M && o == 0) { idx_lds[q] = pick.idx; logp_lds[q] = pick.logp; }
+                }
+                if constexpr (GUM) {
+                    if (q < M && o == 0) idx_lds[q] = pick.idx;
                 }
                 if (q < M) reinterpret_cast<float*>(act_lds)[2 * q + o] = y;
             }
@@ -418,6 +451,9 @@
             if constexpr (CAT) {
                 cw.idx[((size_t)k * a.B + b) * N + i] = idx_lds[e * N + i];
                 if (cw.logp) cw.logp[((size_t)k * a.B + b) * N + i] = logp_lds[e * N + i];
+            }
+            if constexpr (GUM) {
+                gum.idx[((size_t)k * a.B + b) * N + i] = idx_lds[e * N + i];
             }
             float2 f = contact_force_packed<NPS>(QX, QY, NP, i, p, a.p.contact_force, a.p.contact_margin,
                                                  a.p.dist_min, cutoff2);

@@ -111,6 +111,19 @@
 // stores all three.  ONE kernel per (family, N, H): `greedy` and the action mode are run-time, wave-uniform facts of the launch
 // (ActorCatW).  There is no tanh and no log_std.
 //
+// gumbel_actor_kernel<N,H>, pa_gumbel_actor_kernel<N,H>, bn_gumbel_actor_kernel<N,H> and pa_bn_gumbel_actor_kernel<N,H>
+// (fg_rollout_hd_actor_gumbel, fg_rollout_hd_actor_gumbel_per_agent) are the Gumbel member (ACTOR_GUMBEL) of the four families
+// without LayerNorms - the OU member's discrete twin: the body with a five-output head whose action is MADDPG's
+// gumbel_softmax(logits, hard=True) while exploring and onehot_from_logits(logits) otherwise, selected by `constexpr bool GUM`
+// (false in every other kernel, whose instructions it leaves as they were).  The shared families keep W3 [5][H] | b3 [5] in LDS
+// as the categorical member does; the per-agent families read the tile's agent's through L1 (ActorTab).  Both lanes of a row
+// evaluate the five logits (ascending fmaf chains from b3[j]: identical bits in both), draw the row's five Gumbel values
+// (actor_gumbel: a Philox stream of its own, so the Gaussian, OU and categorical draws keep their bits) and run gumbel_pick -
+// the lowest index of the largest l_j + g_j, or of the largest l_j when not exploring; lane o writes component o of the decoded
+// u (cat_decode, by the env's action mode) to the actions' block and lane 0 the index to the block [E N] behind it, and the
+// physics phase stores both.  ONE kernel per (family, N, H): `explore` and the action mode are run-time, wave-uniform facts of
+// the launch (ActorGumW).  No temperature (argmax softmax(y / T) = argmax y), no tanh, no log_std, no log-prob.
+//
 // actor_sample_obs16<N,H>, ln_sample_obs16<N,H>, gru_sample_obs16<N,H>, cat_actor_obs16<N,H>, ln_cat_actor_obs16<N,H> and
 // gru_cat_actor_obs16<N,H> (fg_rollout_hd_actor_obs16, fg_rollout_hd_actor_cat_obs16; N in {3, 9, 27}, H in {32, 64}) are the
 // Gaussian and the categorical member of the plain, LayerNorm and recurrent families with 16-bit observations (ACTOR_GAUSS16,
@@ -124,7 +137,7 @@
 // a.obs then holds 32-bit units and a.obs_pitch counts them (3 N^2 per env: a contiguous tensor only).
 //
 // How the kernels are wired up: a kernel is (family, member).  A member (ActorMember) is stated once, by its predicates below:
-// the body's SAMPLE / OU / CAT / OBS16 and the host's LDS bytes both come from them, and actor_lds_layout is the one statement
+// the body's SAMPLE / OU / CAT / OBS16 / GUM and the host's LDS bytes both come from them, and actor_lds_layout is the one statement
 // of the LDS blocks.  A family is one block at the end of this file - its kind, its flags, the operands it takes and the ones it
 // does not, the names of the members it has - around fg_actor_family.inc, which emits a kernel per named member with
 // fg_actor_rollout_body.inc as a textual include, and then HdActorFamily<kind>, the record the host launches from
@@ -227,6 +240,13 @@ struct ActorCatW {
 };
 constexpr int FG_CAT = 5;                     // the five actions of the discrete action space: none, and two per axis
 
+// the Gumbel head of *gumbel_actor_kernel (fg_rollout_hd_actor_gumbel*): the env's action mode (FG_ACT_ONEHOT5 / FG_ACT_INDEX),
+// whether the launch explores (argmax of logits + Gumbel noise) or takes the largest logit, and the output idx [K][B][N]
+struct ActorGumW {
+    int mode, explore;
+    int* idx;
+};
+
 constexpr int FG_ACTOR_THREADS = 256;
 constexpr int FG_ACTOR_ROWS = 32;             // rows of one wave pass: two 16-row MFMA tiles
 __host__ __device__ constexpr int actor_lanes(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32; }
@@ -241,26 +261,30 @@ __host__ __device__ constexpr int actor_state_rows(int n) {
 // and the member is what happens to the head's output and to the observations; its four facts are the predicates' answers.
 struct ActorFlags { bool per_agent, lnorm, gru, in_bn; };
 // Members: the deterministic actor; under a diagonal Gaussian (log_std, log-probs); with OU noise and the clamp (ActorOuW); the
-// five-output head under a Categorical (ActorCatW); and the last two storing 16-bit observations (obs_fmt).
-enum ActorMember { ACTOR_DET, ACTOR_GAUSS, ACTOR_OU, ACTOR_CAT, ACTOR_GAUSS16, ACTOR_CAT16 };
+// five-output head under a Categorical (ActorCatW); the last two storing 16-bit observations (obs_fmt); and the five-output head
+// under Gumbel noise (ActorGumW).
+enum ActorMember { ACTOR_DET, ACTOR_GAUSS, ACTOR_OU, ACTOR_CAT, ACTOR_GAUSS16, ACTOR_CAT16, ACTOR_GUMBEL };
 __host__ __device__ constexpr bool actor_member_sample(ActorMember m) { return m == ACTOR_GAUSS || m == ACTOR_GAUSS16; }
 __host__ __device__ constexpr bool actor_member_ou(ActorMember m) { return m == ACTOR_OU; }
 __host__ __device__ constexpr bool actor_member_cat(ActorMember m) { return m == ACTOR_CAT || m == ACTOR_CAT16; }
 __host__ __device__ constexpr bool actor_member_obs16(ActorMember m) { return m == ACTOR_GAUSS16 || m == ACTOR_CAT16; }
+__host__ __device__ constexpr bool actor_member_gumbel(ActorMember m) { return m == ACTOR_GUMBEL; }
+__host__ __device__ constexpr bool actor_member_head5(ActorMember m) { return actor_member_cat(m) || actor_member_gumbel(m); }   // a head of five
 __host__ __device__ constexpr bool actor_obs16_shape(int n, int h) { return (n == 3 || n == 9 || n == 27) && (h == 32 || h == 64); }  // built for
 
 // floats of b1 | b2 | W3 in LDS (a per-agent family reads them through L1), and of the b3 | log_std slot behind them
-__host__ __device__ constexpr int actor_w_floats(int h, bool per_agent, bool cat) { return per_agent ? 0 : (cat ? 2 + FG_CAT : 4) * h; }
-__host__ __device__ constexpr int actor_b3_floats(bool cat) { return cat ? 8 : 4; }
+// (head5: a head of five, actor_member_head5)
+__host__ __device__ constexpr int actor_w_floats(int h, bool per_agent, bool head5) { return per_agent ? 0 : (head5 ? 2 + FG_CAT : 4) * h; }
+__host__ __device__ constexpr int actor_b3_floats(bool head5) { return head5 ? 8 : 4; }
 // The LDS of one workgroup: the float offset of every block behind the env blocks [E][env_block_floats], and the total.  A
 // block a kernel does not have is empty; the body takes its pointers, and the host the launch's bytes, from this one function.
 // (E N is a multiple of 8, so the [E N] blocks keep every later block 32-byte aligned.)
 struct ActorLds {
     int act;      // actions [E N][2]
     int logp;     // Gaussian and categorical members: log-probs [E N]
-    int idx;      // categorical members: indices [E N]
+    int idx;      // a head of five (categorical and Gumbel members): indices [E N]
     int wsm;      // b1 [H] b2 [H] W3 [2][H] (not per_agent) | b3 [2], then log_std [2] (Gaussian members) or padding;
-                  // categorical members: b1 [H] b2 [H] W3 [5][H] | b3 [5] and padding to 8
+                  // a head of five: b1 [H] b2 [H] W3 [5][H] | b3 [5] and padding to 8
     int ln;       // lnorm: gamma1 [H] beta1 [H] gamma2 [H] beta2 [H] gamma0 [DP] beta0 [DP], DP = 6N rounded up to 4
     int bn;       // in_bn, not per_agent: mean [DP] istd [DP] gamma [DP] beta [DP] of the input BatchNorm
     int gru;      // gru: b_ir + b_hr [H] b_iz + b_hz [H] b_in [H] b_hn [H] gamma3 [H] beta3 [H]
@@ -269,14 +293,14 @@ struct ActorLds {
     int total;
 };
 __host__ __device__ constexpr ActorLds actor_lds_layout(int n, int h, ActorFlags f, ActorMember m) {
-    const bool cat = actor_member_cat(m);
+    const bool cat = actor_member_cat(m), head5 = actor_member_head5(m);
     const int rows = actor_envs(n) * n, dp = actor_in_pad(n), hs = actor_hstride(h);
     ActorLds l{};
     l.act = actor_envs(n) * env_block_floats(n);
     l.logp = l.act + 2 * rows;
     l.idx = l.logp + (actor_member_sample(m) || cat ? rows : 0);
-    l.wsm = l.idx + (cat ? rows : 0);
-    l.ln = l.wsm + actor_w_floats(h, f.per_agent, cat) + actor_b3_floats(cat);
+    l.wsm = l.idx + (head5 ? rows : 0);
+    l.ln = l.wsm + actor_w_floats(h, f.per_agent, head5) + actor_b3_floats(head5);
     l.bn = l.ln + (f.lnorm ? 4 * h + 2 * dp : 0);
     l.gru = l.bn + (f.in_bn && !f.per_agent ? 4 * dp : 0);
     l.tiles = l.gru + (f.gru ? 6 * h : 0);
@@ -343,6 +367,49 @@ FG_DEV CatPick cat_pick(const float (&l)[FG_CAT], float u, bool greedy) {
 FG_DEV float2 cat_decode(int mode, int idx) {
     const float sgn = mode == FG_ACT_INDEX ? -1.0f : 1.0f;
     return make_float2(idx == 1 ? sgn : idx == 2 ? -sgn : 0.0f, idx == 3 ? sgn : idx == 4 ? -sgn : 0.0f);
+}
+
+// The five Gumbel draws g [5] of agent i of global env g for the step whose counter offset is `offset` (the Gumbel members): a
+// Philox stream of its own - key `seed`, counter {g, i | 0x60000000 | q << 12, lo32(offset), hi32(offset)}, draw j from word j & 3
+// of block q = j >> 2 - whose word 1 has the top three bits 011 for every i < 2^12, against 000 / 001 / 100 / 101 / 110 / 111 of
+// the other streams (actor_eps above), so that no other draw moves.  u_j = (2 (c >> 9) + 1) 2^-24 is an odd 24-bit integer
+// scaled: exact in fp32 and strictly inside (0, 1), so neither logarithm sees 0 or 1; g_j = -log(-log(u_j)) in [-2.82, 16.64].
+// Both logarithms are the math library's full-precision one (about 1 ulp) and NOT logf / __logf, which this build's
+// -fapprox-func lowers to v_log_f32 and one multiply: the inner result is the outer logarithm's argument, and next to u = 1
+// the hardware instruction's absolute error is not small against -ln u.
+extern "C" __device__ float __ocml_log_f32(float);
+FG_DEV float gumbel_log(float x) { return __ocml_log_f32(x); }
+FG_DEV void actor_gumbel(uint64_t seed, uint32_t g, uint32_t i, uint64_t offset, float (&out)[FG_CAT]) {
+#pragma unroll
+    for (uint32_t q = 0; q < (FG_CAT + 3) / 4; ++q) {
+        uint32_t c[4] = {g, i | 0x60000000u | (q << 12), (uint32_t)offset, (uint32_t)(offset >> 32)};
+        philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+#pragma unroll
+        for (int wd = 0; wd < 4; ++wd) {
+            const int j = (int)q * 4 + wd;
+            if (j < FG_CAT) {
+                const float u = (float)(2u * (c[wd] >> 9) + 1u) * (1.0f / 16777216.0f);
+                out[j] = -gumbel_log(-gumbel_log(u));
+            }
+        }
+    }
+}
+// MADDPG's discrete action from five fp32 logits, the one spelling for the fused kernels and fg_actor_gumbel_pick: exploring
+// (gumbel_softmax(logits, hard=True)), y_j = l_j + g_j - one fp32 addition of the finished logit, never contracted into its
+// chain - else (onehot_from_logits) y_j = l_j and g is not read; the index is the lowest j attaining max_j y_j.  The
+// temperature does not enter: argmax softmax(y / T) = argmax y for every T > 0.
+FG_DEV int gumbel_pick(const float (&l)[FG_CAT], const float (&g)[FG_CAT], bool explore) {
+#pragma clang fp contract(off)
+    float y[FG_CAT];
+#pragma unroll
+    for (int j = 0; j < FG_CAT; ++j) y[j] = explore ? l[j] + g[j] : l[j];
+    float m = y[0];
+#pragma unroll
+    for (int j = 1; j < FG_CAT; ++j) m = fmaxf(m, y[j]);
+    int idx = FG_CAT - 1;
+#pragma unroll
+    for (int j = FG_CAT - 2; j >= 0; --j) idx = y[j] == m ? j : idx;   // descending, so that the lowest index that qualifies stays
+    return idx;
 }
 
 // The pieces of one wave pass of the actor MLP (fg_actor_mlp.inc) that layer 1 of each body shares with it.  acc: the pass's
@@ -438,6 +505,37 @@ __global__ __launch_bounds__(256) void actor_categorical_kernel(int mode, int gr
     if (logp) logp[t] = pk.logp;
 }
 
+// One step's five Gumbel draws for every (env, agent) at rng_base(p) (fg_actor_gumbel): the host-paced loop of a
+// GumbelSoftmaxActor draws what the *gumbel_actor_kernel draw.
+__global__ __launch_bounds__(256) void actor_gumbel_kernel(const KParams p, int B, int N, float* __restrict__ g) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)B * N) return;
+    const int b = (int)(t / N), i = (int)(t - (long long)b * N);
+    float d[FG_CAT];
+    actor_gumbel(p.seed, (uint32_t)(b + p.env_index_base), (uint32_t)i, rng_base(p), d);
+#pragma unroll
+    for (int j = 0; j < FG_CAT; ++j) g[t * FG_CAT + j] = d[j];
+}
+
+// gumbel_pick and cat_decode on each of `count` rows of caller-supplied logits [count][5] and draws g [count][5] (NULL when not
+// exploring) (fg_actor_gumbel_pick): the host-paced loop of a GumbelSoftmaxActor takes the fused launch's arithmetic from its
+// own logits.
+__global__ __launch_bounds__(256) void actor_gumbel_pick_kernel(int mode, int explore, long long count,
+                                                                const float* __restrict__ logits, const float* __restrict__ g,
+                                                                int* __restrict__ idx, float2* __restrict__ act) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    float l[FG_CAT], d[FG_CAT];
+#pragma unroll
+    for (int j = 0; j < FG_CAT; ++j) {
+        l[j] = logits[t * FG_CAT + j];
+        d[j] = explore ? g[t * FG_CAT + j] : 0.f;
+    }
+    const int pk = gumbel_pick(l, d, explore != 0);
+    idx[t] = pk;
+    if (act) act[t] = cat_decode(mode, pk);
+}
+
 // ou_step on each of `count` (env, agent) pairs in place (fg_actor_ou_step): the host-paced loop of an OUNoiseActor carries
 // the state the fused kernels carry, from the same eps.
 __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, float theta, float mu, float sigma,
@@ -448,7 +546,7 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
     state[t] = make_float2(ou_step(x.x, n.x, theta, mu, sigma), ou_step(x.y, n.y, theta, mu, sigma));
 }
 
-// ---- the kernels: one block per family around fg_actor_family.inc.  The body names all of `w tab nw gw bw btab ow cw`, and an
+// ---- the kernels: one block per family around fg_actor_family.inc.  The body names all of `w tab nw gw bw btab ow cw gum`, and an
 // operand a kernel does not take is the empty constant below (`w` of a per-agent family: only tab's tanh flag), so that no
 // kernel carries an argument it never reads.
 #define FG_ACTOR_NO_W     const ActorW w = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tab.out_tanh};
@@ -459,6 +557,7 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
 #define FG_ACTOR_NO_BTAB  constexpr ActorBnTab btab{};
 #define FG_ACTOR_NO_OW    constexpr ActorOuW ow{};
 #define FG_ACTOR_NO_CW    constexpr ActorCatW cw{};
+#define FG_ACTOR_NO_GUM   constexpr ActorGumW gum{};
 #define FG_ACTOR_NO_GAUSS const float* const log_std = nullptr; float* const logp = nullptr;
 #define FG_ACTOR_NO_OBS16 constexpr int obs_fmt = 0;
 // what the body reads of its kernel: the member and the family's flags, each fact from the one predicate or field
@@ -466,6 +565,7 @@ __global__ __launch_bounds__(256) void actor_ou_step_kernel(long long count, flo
     constexpr ActorMember MEMBER = M;                                                                                          \
     constexpr ActorFlags FLAGS = FG_ACTOR_FLAGS;                                                                               \
     constexpr bool SAMPLE = actor_member_sample(M), OU = actor_member_ou(M), CAT = actor_member_cat(M), OBS16 = actor_member_obs16(M), \
+                   GUM = actor_member_gumbel(M),                                                                               \
                    PER_AGENT = FLAGS.per_agent, LNORM = FLAGS.lnorm, GRU = FLAGS.gru, INBN = FLAGS.in_bn;                      \
     FG_ACTOR_ABSENT
 #define FG_ACTOR_STR_(x) #x
@@ -486,6 +586,7 @@ template <HdActorKind> struct HdActorFamily;
 #define FG_ACTOR_DET      actor_rollout_kernel
 #define FG_ACTOR_SMP      actor_sample_kernel
 #define FG_ACTOR_OUK      ou_actor_kernel
+#define FG_ACTOR_GUMK     gumbel_actor_kernel
 #define FG_ACTOR_CATK     cat_actor_kernel
 #define FG_ACTOR_SMP16    actor_sample_obs16
 #define FG_ACTOR_CAT16    cat_actor_obs16
@@ -502,6 +603,7 @@ template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARE
 #define FG_ACTOR_DET      pa_actor_kernel
 #define FG_ACTOR_SMP      pa_sample_kernel
 #define FG_ACTOR_OUK      pa_ou_actor_kernel
+#define FG_ACTOR_GUMK     pa_gumbel_actor_kernel
 #include "fg_actor_family.inc"
 
 // lnorm: the shared actor with LayerNorms `nw`
@@ -542,6 +644,7 @@ template <> struct HdActorFamily<HD_ACTOR_SAMPLE> : HdActorFamily<HD_ACTOR_SHARE
 #define FG_ACTOR_DET      bn_actor_kernel
 #define FG_ACTOR_SMP      bn_sample_kernel
 #define FG_ACTOR_OUK      bn_ou_actor_kernel
+#define FG_ACTOR_GUMK     bn_gumbel_actor_kernel
 #include "fg_actor_family.inc"
 
 // in_bn, per_agent: agent i evaluates tab's actor i behind btab's BatchNorm i
@@ -556,6 +659,7 @@ static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(Acto
 #define FG_ACTOR_DET      pa_bn_actor_kernel
 #define FG_ACTOR_SMP      pa_bn_sample_kernel
 #define FG_ACTOR_OUK      pa_bn_ou_actor_kernel
+#define FG_ACTOR_GUMK     pa_bn_gumbel_actor_kernel
 #include "fg_actor_family.inc"
 
 #undef FG_ACTOR_NO_W
@@ -566,6 +670,7 @@ static_assert(sizeof(Args) + sizeof(ActorTab) + sizeof(ActorBnTab) + sizeof(Acto
 #undef FG_ACTOR_NO_BTAB
 #undef FG_ACTOR_NO_OW
 #undef FG_ACTOR_NO_CW
+#undef FG_ACTOR_NO_GUM
 #undef FG_ACTOR_NO_GAUSS
 #undef FG_ACTOR_NO_OBS16
 #undef FG_ACTOR_IS

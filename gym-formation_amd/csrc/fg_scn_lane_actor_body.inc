@@ -17,6 +17,8 @@
     float* const oust = nullptr;
     constexpr bool CAT = false;                         // nor a categorical one
     constexpr ActorCatW cw{};
+    constexpr bool GUM = false;                         // nor one with Gumbel noise
+    constexpr ActorGumW gum{};
     constexpr bool DB = false;                          // one hand-over block, two barriers per step
     constexpr int PW = 1, ENVS = FG_SCN_ACTOR_ENVS, NWW = FG_SCN_ACTOR_THREADS / 64;   // every wave streams
     constexpr int NE = N + M;

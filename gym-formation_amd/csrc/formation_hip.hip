@@ -1072,6 +1072,11 @@ struct HdActorHead {                                   // fg_rollout_hd_actor_ca
     int32_t* idx = nullptr;
     float* logp = nullptr;
 };
+struct HdActorGumbel {                                 // fg_rollout_hd_actor_gumbel*: the Gumbel head's facts and its output [K][B][N]
+    bool on = false;
+    int mode = 0, explore = 0;
+    int32_t* idx = nullptr;
+};
 struct HdActorCall {
     HdActorKind kind;
     const FgActor* actor;
@@ -1096,10 +1101,14 @@ struct HdActorCall {
     // FG_OBS_F16 / FG_OBS_BF16, or -1 for a value that is neither; the kind is the body's family, whose 16-bit Gaussian or
     // - `cat.on` - categorical member runs, and the observations' buffer holds 16-bit elements
     int obs_format = 0;
+    // fg_rollout_hd_actor_gumbel and fg_rollout_hd_actor_gumbel_per_agent only (`gumbel.on`, which also puts their names on the
+    // messages): the kind is the logits' family - shared or per-agent, with `in_bn` the BatchNorm one - whose Gumbel member runs
+    HdActorGumbel gumbel = {};
 };
 static bool hd_actor_members(const HdActorCall& c) { return c.kind == HD_ACTOR_PER_AGENT || c.kind == HD_ACTOR_BN_PER_AGENT; }
-// the member of the call's family that runs: the one place that reads these four fields for it
+// the member of the call's family that runs: the one place that reads these five fields for it
 static ActorMember hd_actor_member(const HdActorCall& c) {
+    if (c.gumbel.on) return ACTOR_GUMBEL;
     if (c.obs_format) return c.cat.on ? ACTOR_CAT16 : ACTOR_GAUSS16;
     if (c.cat.on) return ACTOR_CAT;
     if (c.noise.on) return ACTOR_OU;
@@ -1111,6 +1120,7 @@ static const char* hd_actor_who(const HdActorCall& c) {
     case ACTOR_GAUSS16: return "fg_rollout_hd_actor_obs16";
     case ACTOR_CAT: return "fg_rollout_hd_actor_cat";
     case ACTOR_OU: return hd_actor_members(c) ? "fg_rollout_hd_actor_ou_per_agent" : "fg_rollout_hd_actor_ou";
+    case ACTOR_GUMBEL: return hd_actor_members(c) ? "fg_rollout_hd_actor_gumbel_per_agent" : "fg_rollout_hd_actor_gumbel";
     default: return c.states_entry ? "fg_rollout_hd_actor_gru_states" : hd_actor_entry[c.kind];
     }
 }
@@ -1190,10 +1200,22 @@ static int actor_cat_check(const char* who, const FgActor* actor, const HdActorH
     if (((uintptr_t)h.idx | (uintptr_t)h.logp) & 3u) return bad(FG_ERR_ALIGNMENT, "idx_seq and logp_seq must be 4-byte aligned");
     return FG_OK;
 }
+// The Gumbel head's checks (no device touched), in the name of the entry `who`; `actors` are the call's `n` members (1: the shared
+// actor), each with a head of logits: FG_ERR_BAD_ARG for a tanh after a head, an action mode other than FG_ACT_ONEHOT5 /
+// FG_ACT_INDEX, a NULL idx_seq where there are envs; FG_ERR_ALIGNMENT for an idx_seq that is not 4-byte aligned.
+static int actor_gumbel_check(const char* who, const FgActor* actors, int n, const HdActorGumbel& h, int B) {
+    const ActorComplaint bad{who};
+    for (int i = 0; i < n; ++i)
+        if (actors[i].out_tanh != 0) return bad(FG_ERR_BAD_ARG, "out_tanh must be 0: the head's outputs are logits");
+    if (h.mode != FG_ACT_ONEHOT5 && h.mode != FG_ACT_INDEX) return bad(FG_ERR_BAD_ARG, "act_mode must be FG_ACT_ONEHOT5 or FG_ACT_INDEX");
+    if (!h.idx && B > 0) return bad(FG_ERR_BAD_ARG, "idx_seq is NULL");
+    if ((uintptr_t)h.idx & 3u) return bad(FG_ERR_ALIGNMENT, "idx_seq must be 4-byte aligned");
+    return FG_OK;
+}
 // The checks of an hd-actor call before its buffers (no device touched): FG_OK, or the status of the first one that fails, in
 // this order, which is ABI - params, (a 16-bit member: obs_format, the env pitch, log_std, N in {3, 9, 27}, hidden = 128,) B and K, N, the actor (per-agent: every member, then that it has member 0's hidden width
 // and tanh flag), the norms, the recurrent layer with its state, the input BatchNorm(s), the OU noise with its state, the
-// categorical head with its outputs, log_std, logp.  The shared actor's
+// categorical head with its outputs, the Gumbel head with its output, log_std, logp.  The shared actor's
 // checks name fg_rollout_hd_actor through the sample and norm entries too, the log_std checks fg_rollout_hd_actor_sample.
 // Without log_std (the deterministic actor) `logp` is set to NULL.
 static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, int K) {
@@ -1237,6 +1259,7 @@ static int hd_actor_check(const FgParams* params, HdActorCall& c, int B, int N, 
     }
     if (c.noise.on && (rc = actor_ou_check(who, c.noise.ou, c.noise.state, B)) != FG_OK) return rc;
     if (c.cat.on && (rc = actor_cat_check(who, c.actor, c.cat, B)) != FG_OK) return rc;
+    if (c.gumbel.on && (rc = actor_gumbel_check(who, c.actor, hd_actor_members(c) ? N : 1, c.gumbel, B)) != FG_OK) return rc;
     if (!c.log_std) {
         if (c.kind == HD_ACTOR_SAMPLE) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_actor_sample: log_std is NULL%s");
         c.logp = nullptr;
@@ -1305,6 +1328,7 @@ template <int NC, int H, class F, class... W>
 static int launch_hd_actor(const Args& a, const HdActorCall& c, hipStream_t st, const W&... w) {
     const ActorOuW ow = c.noise.on ? actor_ou_w(c.noise) : ActorOuW{};
     const ActorCatW cw = {c.cat.mode, c.cat.greedy ? 1 : 0, c.cat.idx, c.cat.logp};
+    const ActorGumW gum = {c.gumbel.mode, c.gumbel.explore ? 1 : 0, c.gumbel.idx};
     const int fmt = c.obs_format == FG_OBS_F16 ? FG_WR_OBS_F16 : FG_WR_OBS_BF16;      // (the writer's, read by the 16-bit members)
     switch (hd_actor_member(c)) {
     case ACTOR_GAUSS: return launch_hd_member<ACTOR_GAUSS, NC, H, F>(a, st, w..., c.log_std, c.logp);
@@ -1312,6 +1336,7 @@ static int launch_hd_actor(const Args& a, const HdActorCall& c, hipStream_t st, 
     case ACTOR_CAT: return launch_hd_member<ACTOR_CAT, NC, H, F>(a, st, w..., cw);
     case ACTOR_GAUSS16: return launch_hd_member<ACTOR_GAUSS16, NC, H, F>(a, st, w..., c.log_std, c.logp, fmt);
     case ACTOR_CAT16: return launch_hd_member<ACTOR_CAT16, NC, H, F>(a, st, w..., cw, fmt);
+    case ACTOR_GUMBEL: return launch_hd_member<ACTOR_GUMBEL, NC, H, F>(a, st, w..., gum);
     default: return launch_hd_member<ACTOR_DET, NC, H, F>(a, st, w...);
     }
 }
@@ -2071,6 +2096,35 @@ int fg_rollout_hd_actor_ou_per_agent(const FgParams* params, const FgActor* acto
                                done_seq}, obs_every, stream);
 }
 
+// the Gumbel entries' call: the logits' family with `gumbel` set (no log_std, no logp)
+static HdActorCall hd_actor_gumbel_call(bool members, const FgActor* actor, const FgActorInBn* in_bn, int act_mode, int explore,
+                                        int32_t* idx) {
+    HdActorCall c{members ? (in_bn ? HD_ACTOR_BN_PER_AGENT : HD_ACTOR_PER_AGENT) : (in_bn ? HD_ACTOR_BN : HD_ACTOR_SHARED), actor};
+    c.in_bn = in_bn;
+    c.gumbel = {true, act_mode, explore, idx};
+    return c;
+}
+
+int fg_rollout_hd_actor_gumbel(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, int act_mode, int explore,
+                               int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                               int obs_every, void* stream) {
+    return rollout_actor_impl(params, hd_actor_gumbel_call(false, actor, in_bn, act_mode, explore, idx_seq), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
+}
+
+int fg_rollout_hd_actor_gumbel_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns, int act_mode,
+                                         int explore, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                         float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                                         int obs_every, void* stream) {
+    return rollout_actor_impl(params, hd_actor_gumbel_call(true, actors, in_bns, act_mode, explore, idx_seq), B, N, K,
+                              {pos_x, pos_y, vel_x, vel_y, act_seq, ideal_shape, ideal_vel, step, obs_seq, reward_seq, indiv_seq,
+                               done_seq}, obs_every, stream);
+}
+
 // the categorical entries' call: the body's family - recurrent with `gru`, LayerNorm with `norm` alone, else shared - with `cat`
 // set (no log_std); `rnn_states` NULL: no record of the states.  A `gru` without `norm` fails the recurrent family's own check
 // of its norms (FG_ERR_BAD_ARG, "norm is NULL").
@@ -2160,6 +2214,34 @@ int fg_actor_categorical(int act_mode, int greedy, int64_t count, const float* l
     return launch<&actor_categorical_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream,
                                              "actor categorical launch failed: %s", act_mode, greedy ? 1 : 0, (long long)count, logits, u,
                                              reinterpret_cast<int*>(idx), reinterpret_cast<float2*>(act), logp);
+}
+
+int fg_actor_gumbel(const FgParams* params, int B, int N, float* g, void* stream) {
+    int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || N < 1 || N > (1 << 12)) return fail(FG_ERR_BAD_ARG, "fg_actor_gumbel: B >= 0 and 1 <= N <= 2^12 required%s");
+    if (!g) return fail(FG_ERR_BAD_ARG, "fg_actor_gumbel: g is NULL%s");
+    if ((uintptr_t)g & 3u) return fail(FG_ERR_ALIGNMENT, "fg_actor_gumbel: g must be 4-byte aligned%s");
+    if (B == 0) return FG_OK;
+    const DeviceGuard device_guard(stream, g);
+    const long long count = (long long)B * N;
+    return launch<&actor_gumbel_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream,
+                                        "actor gumbel launch failed: %s", *params, B, N, g);
+}
+
+int fg_actor_gumbel_pick(int act_mode, int explore, int64_t count, const float* logits, const float* g, int32_t* idx, float* act,
+                         void* stream) {
+    if (act_mode != FG_ACT_ONEHOT5 && act_mode != FG_ACT_INDEX)
+        return fail(FG_ERR_BAD_ARG, "fg_actor_gumbel_pick: act_mode must be FG_ACT_ONEHOT5 or FG_ACT_INDEX%s");
+    if (count < 0 || count > ((int64_t)1 << 38)) return fail(FG_ERR_BAD_ARG, "fg_actor_gumbel_pick: count out of range%s");
+    if (count == 0) return FG_OK;
+    if (!logits || !idx || (!g && explore)) return fail(FG_ERR_BAD_ARG, "fg_actor_gumbel_pick: logits, idx and (exploring) g are required%s");
+    if ((((uintptr_t)logits | (uintptr_t)g | (uintptr_t)idx) & 3u) || ((uintptr_t)act & 7u))
+        return fail(FG_ERR_ALIGNMENT, "fg_actor_gumbel_pick: act must be 8-byte, the other buffers 4-byte aligned%s");
+    const DeviceGuard device_guard(stream, idx);
+    return launch<&actor_gumbel_pick_kernel>((unsigned)((count + 255) / 256), 256, 0, (hipStream_t)stream,
+                                             "actor gumbel pick launch failed: %s", act_mode, explore ? 1 : 0, (long long)count, logits, g,
+                                             reinterpret_cast<int*>(idx), reinterpret_cast<float2*>(act));
 }
 
 int fg_actor_ou_step(const FgActorOu* ou, int64_t count, const float* eps, float* state, void* stream) {
@@ -2254,6 +2336,21 @@ int fg_describe_actor_ou_per_agent_launch(const FgParams* params, const FgActor*
     float* const state = reinterpret_cast<float*>((uintptr_t)4096);
     return describe_actor_impl("fg_describe_actor_ou_per_agent_launch", params, hd_actor_ou_call(true, actors, in_bns, ou, state),
                                B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_gumbel_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, int act_mode,
+                                    int explore, int B, int N, int K, int obs_every, char* out, int out_len) {
+    int32_t* const idx = reinterpret_cast<int32_t*>((uintptr_t)4096);   // a stand-in: the dry run has no outputs
+    return describe_actor_impl("fg_describe_actor_gumbel_launch", params,
+                               hd_actor_gumbel_call(false, actor, in_bn, act_mode, explore, idx), B, N, K, obs_every, out, out_len);
+}
+
+int fg_describe_actor_gumbel_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                              int act_mode, int explore, int B, int N, int K, int obs_every, char* out,
+                                              int out_len) {
+    int32_t* const idx = reinterpret_cast<int32_t*>((uintptr_t)4096);
+    return describe_actor_impl("fg_describe_actor_gumbel_per_agent_launch", params,
+                               hd_actor_gumbel_call(true, actors, in_bns, act_mode, explore, idx), B, N, K, obs_every, out, out_len);
 }
 
 int fg_describe_actor_cat_launch(const FgParams* params, const FgActor* actor, const FgActorNorm* norm, const FgActorGru* gru,

@@ -18,11 +18,11 @@ import os.path as osp
 from .environment import MultiAgentEnv
 from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
-from .actor_rollout import (CategoricalActor, GaussianActor, InputBatchNorm, OUNoiseActor, PerAgentActor,  # noqa: F401
-                            RecurrentActor)
+from .actor_rollout import (CategoricalActor, GaussianActor, GumbelSoftmaxActor, InputBatchNorm, OUNoiseActor,  # noqa: F401
+                            PerAgentActor, RecurrentActor)
 
 __all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm",
-           "OUNoiseActor", "CategoricalActor"]
+           "OUNoiseActor", "CategoricalActor", "GumbelSoftmaxActor"]
 
 _counter = [0]
 

@@ -291,6 +291,16 @@ SIGNATURES = {
                                                 ctypes.POINTER(FgActorGru), _I, _I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "fg_actor_uniform": (_I, [_PP, _I, _I, _P, _P]),
     "fg_actor_categorical": (_I, [_I, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
+    "fg_rollout_hd_actor_gumbel": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _I, _I, _I, _I, _I] + [_P] * 13
+                                   + [_I, _P]),
+    "fg_rollout_hd_actor_gumbel_per_agent": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _I, _I, _I, _I, _I]
+                                             + [_P] * 13 + [_I, _P]),
+    "fg_describe_actor_gumbel_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _I, _I, _I, _I, _I, _I,
+                                             ctypes.c_char_p, _I]),
+    "fg_describe_actor_gumbel_per_agent_launch": (_I, [_PP, ctypes.POINTER(FgActor), ctypes.POINTER(FgActorInBn), _I, _I, _I, _I, _I,
+                                                       _I, ctypes.c_char_p, _I]),
+    "fg_actor_gumbel": (_I, [_PP, _I, _I, _P, _P]),
+    "fg_actor_gumbel_pick": (_I, [_I, _I, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "fg_rollout_scenario_actor": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I] + [_P] * 14
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,

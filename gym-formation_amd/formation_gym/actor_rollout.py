@@ -60,7 +60,19 @@ callback); `deterministic` is read at every launch.  Host-paced (the same loop i
 own device functions, `fg_actor_uniform` + `fg_actor_categorical`): a head of any other width, a Tanh after it, PerAgentActor
 members, a leading BatchNorm, H = 128 with norms, the landmark scenarios (`fused_cat=False`) and World options.  No path at all:
 FG_ACT_ARGMAX (`force_discrete_action`), any other actor in a discrete action mode, a CategoricalActor on a continuous env.
-Gumbel-softmax (MADDPG's discrete exploration) is not built.
+
+A `GumbelSoftmaxActor(logits, explore=True)` is the MADDPG trainers' discrete action (maddpg-pytorch's agents on
+`make_env(..., discrete_action=True)`): exploring, `gumbel_softmax(logits, hard=True)` - the one-hot of argmax(logits + g), g five
+Gumbel draws per row from a counter stream of their own (`env.actor_gumbel()`) - and otherwise `onehot_from_logits(logits)`, the
+lowest index of the largest logit.  The temperature does not enter (argmax softmax(y / T) = argmax y).  It is the OUNoiseActor's
+discrete twin and fuses where that one does (`fg_rollout_hd_actor_gumbel`, `fg_rollout_hd_actor_gumbel_per_agent`:
+gumbel_actor_kernel, bn_gumbel_actor_kernel, pa_gumbel_actor_kernel, pa_bn_gumbel_actor_kernel): in formation_hd_env in the modes
+FG_ACT_ONEHOT5 and FG_ACT_INDEX when `logits` is the plain or the eval-mode BatchNorm form above, shared or every member of a
+PerAgentActor, with the head Linear(H, 5) and no Tanh; `explore` is read at every launch.  Host-paced (the same loop in Python,
+the draws, the pick and the decode by the kernels' own device functions, `fg_actor_gumbel` + `fg_actor_gumbel_pick`): a LayerNorm
+or recurrent body, H = 128 behind a BatchNorm, a head of any other width, a Tanh after it, mixed members, the landmark scenarios
+(`fused_gumbel=False`) and World options.  No path under FG_ACT_ARGMAX; ValueError on a continuous env.  Not built: the soft
+(temperature) sample, epsilon-greedy onehot_from_logits, 16-bit observations out of this member's launch (they are cast).
 
 A `GaussianActor(mean, log_std)` explores: it fuses (`fg_rollout_hd_actor_sample`) when its mean fuses as above and its
 log_std is a contiguous fp32 [2] tensor on the env's device.
@@ -149,7 +161,7 @@ def _in_bn(m, width, device):
 
 def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
-               fused_ou=True, fused_cat=True, head_width=2):
+               fused_ou=True, fused_cat=True, fused_gumbel=True, head_width=2, head_bn=False):
     """The FusedActor fields hidden, out_tanh, members = [[w1, b1, w2, b2, w3, b3]] and the form's own (below) when a fused kernel
     can evaluate the shared actor body `actor` for `num_agents` agents, else None.  The three forms, each with its own kernels
     and so its own hidden widths:
@@ -163,22 +175,26 @@ def _body_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N
     actor's own parameters (b* may be None).  The scenario's facts: `in_features` the input width D (None:
     formation_hd_env's 6N), `fused_n` the agent counts and `fused_hidden` / `fused_ln_hidden` the hidden widths its kernels
     are built for (None or empty: it has no kernel for that form); `fused_gru_hidden` is `_recurrent_spec`'s fact and
-    `fused_ou` / `fused_cat` (whether the scenario's launch has OU / categorical members) `resolve_actor`'s, none read here.
-    `head_width`: the last Linear's outputs - 2, or CAT_ACTIONS for a CategoricalActor's logits, which take no Tanh and no
-    leading BatchNorm."""
+    `fused_ou` / `fused_cat` / `fused_gumbel` (whether the scenario's launch has OU / categorical / Gumbel members)
+    `resolve_actor`'s, none read here.
+    `head_width`: the last Linear's outputs - 2, or CAT_ACTIONS for a CategoricalActor's or a GumbelSoftmaxActor's logits, which
+    take no Tanh and - unless `head_bn`, the Gumbel member's fact: its families include the BatchNorm ones - no leading
+    BatchNorm."""
     if type(actor) is not torch.nn.Sequential:
         return None
     return _modules_spec(list(actor), num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden,
-                         head_width)
+                         head_width, head_bn)
 
 
-def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden=(), head_width=2):
+def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, fused_ln_hidden, fused_bn_hidden=(), head_width=2,
+                  head_bn=False):
     """`_body_spec` of the body whose modules, in order, are `mods`."""
     nn = torch.nn
     if int(num_agents) not in fused_n:
         return None
-    if head_width != 2 and (not mods or type(mods[-1]) is nn.Tanh or type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm)):
-        return None                                        # logits: no Tanh after the head, no BatchNorm family member
+    if head_width != 2 and (not mods or type(mods[-1]) is nn.Tanh
+                            or (not head_bn and type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm))):
+        return None                                        # logits: no Tanh after the head; a BatchNorm family member: `head_bn`
     if in_features is None:
         in_features = 6 * int(num_agents)
     if mods and type(mods[0]) in (nn.BatchNorm1d, InputBatchNorm):     # in front of the plain form only
@@ -186,7 +202,7 @@ def _modules_spec(mods, num_agents, device, in_features, fused_n, fused_hidden, 
         out_tanh = kinds[-1:] == [nn.Tanh]
         if kinds[:5] != [nn.Linear, nn.ReLU, nn.Linear, nn.ReLU, nn.Linear] or len(kinds) != 5 + out_tanh:
             return None
-        fields = _linears_spec(mods[1], mods[3], mods[5], out_tanh, in_features, device, fused_bn_hidden)
+        fields = _linears_spec(mods[1], mods[3], mods[5], out_tanh, in_features, device, fused_bn_hidden, head_width)
         bn = None if fields is None else _in_bn(mods[0], in_features, device)
         return None if bn is None else dict(fields, in_bn=bn)
     lead = bool(mods) and type(mods[0]) is nn.LayerNorm
@@ -344,13 +360,13 @@ class ActorGru(collections.namedtuple("ActorGru", "w_ih w_hh b_ih b_hh norm")):
 
 def _recurrent_spec(actor, num_agents, device=None, in_features=None, fused_n=FUSED_N, fused_hidden=FUSED_HIDDEN,
                     fused_ln_hidden=FUSED_LN_HIDDEN, fused_gru_hidden=FUSED_GRU_HIDDEN, fused_bn_hidden=FUSED_BN_HIDDEN,
-                    fused_ou=True, fused_cat=True, head_width=2):
+                    fused_ou=True, fused_cat=True, fused_gumbel=True, head_width=2):
     """The FusedActor fields of `_body_spec`'s LayerNorm form and `gru`, the ActorGru, when the fused recurrent kernel can evaluate
     the RecurrentActor `actor` for `num_agents` agents, else None.  Its base with its head - w3, b3 - must be the LayerNorm form
     of `_body_spec` (same arguments) with H in `fused_gru_hidden` (None or empty: the scenario has no such kernel); its GRU
     one layer, one direction, input_size == hidden_size == H, with biases; the norm after it `_norm_triple`'s; every
     parameter fp32, contiguous and on `device`.  `fused_bn_hidden` is `_body_spec`'s fact, not read here: a base that starts
-    with a BatchNorm has no recurrent kernel; nor are `fused_ou` and `fused_cat`, `resolve_actor`'s facts.  `head_width`: the
+    with a BatchNorm has no recurrent kernel; nor are `fused_ou`, `fused_cat` and `fused_gumbel`, `resolve_actor`'s facts.  `head_width`: the
     head's outputs, from the member - 2, or CAT_ACTIONS for a CategoricalActor's logits (a bare Linear, no Tanh)."""
     nn = torch.nn
     if type(actor) is not RecurrentActor or type(actor.base) is not nn.Sequential:
@@ -394,25 +410,27 @@ class PerAgentActor(torch.nn.Module):
         return torch.stack([a(obs[..., i, :]) for i, a in enumerate(self.actors)], dim=-2)
 
 
-def per_agent_spec(actor, num_agents, device=None):
+def per_agent_spec(actor, num_agents, device=None, head_width=2):
     """(hidden, out_tanh, [[w1, b1, w2, b2, w3, b3] per agent]) when the fused kernel can evaluate the PerAgentActor `actor`
-    for `num_agents` agents, else None: N members, each passing actor_spec, all with the same H and tanh flag."""
+    for `num_agents` agents, else None: N members, each passing actor_spec, all with the same H and tanh flag.  `head_width`:
+    every member's last Linear's outputs, as `_linears_spec` takes it (CAT_ACTIONS for a GumbelSoftmaxActor's logits)."""
     if not isinstance(actor, PerAgentActor) or len(actor.actors) != int(num_agents):
         return None
-    specs = [actor_spec(a, num_agents, device) for a in actor.actors]
+    specs = [actor_spec(a, num_agents, device, head_width=head_width) for a in actor.actors]
     if any(s is None for s in specs) or len({(s[0], s[1]) for s in specs}) != 1:
         return None
     return specs[0][0], specs[0][1], [s[2] for s in specs]
 
 
-def per_agent_bn_spec(actor, num_agents, device=None):
+def per_agent_bn_spec(actor, num_agents, device=None, head_width=2):
     """(hidden, out_tanh, [[w1, b1, w2, b2, w3, b3] per agent], [ActorInBn per agent]) when the fused kernel can evaluate the
     PerAgentActor `actor` for `num_agents` agents with every member behind its own eval-mode input BatchNorm, else None: N
     members, each passing batchnorm_spec (nn.BatchNorm1d is fine here: members see 2-D rows), all with the same H and tanh
-    flag; statistics, eps and affine-ness are each member's own.  Members of which only some have the BatchNorm: None."""
+    flag; statistics, eps and affine-ness are each member's own.  Members of which only some have the BatchNorm: None.
+    `head_width` as in `per_agent_spec`."""
     if not isinstance(actor, PerAgentActor) or len(actor.actors) != int(num_agents):
         return None
-    specs = [batchnorm_spec(a, num_agents, device) for a in actor.actors]
+    specs = [batchnorm_spec(a, num_agents, device, head_width=head_width, head_bn=head_width != 2) for a in actor.actors]
     if any(s is None for s in specs) or len({(s[0], s[1]) for s in specs}) != 1:
         return None
     return specs[0][0], specs[0][1], [s[2] for s in specs], [s[3] for s in specs]
@@ -504,6 +522,36 @@ class CategoricalActor(torch.nn.Module):
         return -(lsm.exp() * lsm).sum(-1)
 
 
+class GumbelSoftmaxActor(torch.nn.Module):
+    """The MADDPG trainers' discrete action (maddpg-pytorch's DDPGAgent.step on a discrete action space): `logits` maps
+    observations [..., D] to five logits [..., 5] - one MLPNetwork per agent (a PerAgentActor) or a shared one, plain or behind
+    the BatchNorm `in_fn`, ending in Linear(H, 5) - and the action is a one-hot [..., 5]:
+        exploring (`explore`, read at every call):  gumbel_softmax(logits, hard=True) = one_hot(argmax(logits + g)),
+                                                    g = -log(-log(U)), U uniform in (0, 1), five draws per row
+        otherwise:                                  onehot_from_logits(logits) = one_hot(argmax(logits))
+    with ties going to the lowest index.  There is NO temperature: the hard sample is one_hot(argmax softmax((logits + g) / T)),
+    and argmax softmax(y / T) = argmax y for every T > 0, so T never changes the action; the soft sample (hard=False), which does
+    depend on it, is a training-time quantity and is not built here, nor is onehot_from_logits' epsilon-greedy.
+    `forward(obs, gumbel=None)` draws g with torch when none is given and is meant for use outside the env: inside
+    `env.rollout_actor` the env's counter stream supplies the draws (`env.actor_gumbel()`), the indices come back in
+    info['actions'] and the raw actions in info['u']; there is no log-probability (MADDPG has no use for one)."""
+
+    def __init__(self, logits, explore=True):
+        super().__init__()
+        self.logits = logits
+        self.explore = bool(explore)
+
+    def forward(self, obs, gumbel=None):
+        """The one-hot action [..., 5] (fp32); `gumbel` [..., 5]: the draws to explore with (None: drawn with torch)."""
+        lg = self.logits(obs)
+        if self.explore:
+            if gumbel is None:
+                u = torch.rand_like(lg).clamp_(min=torch.finfo(lg.dtype).tiny, max=1.0 - torch.finfo(lg.dtype).eps)
+                gumbel = -torch.log(-torch.log(u))
+            lg = lg + gumbel
+        return torch.nn.functional.one_hot(lg.argmax(-1), CAT_ACTIONS).to(lg.dtype)
+
+
 def _on_device(t, device):
     if device is None:
         return True
@@ -586,8 +634,8 @@ class OUNoiseActor(torch.nn.Module):
         return act if noise_state is None else (act, x)
 
 
-class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn ou cat",
-                                        defaults=(None, None, None, None, None))):
+class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members per_agent log_std norms gru in_bn ou cat gumbel",
+                                        defaults=(None, None, None, None, None, None))):
     """An actor as the fused launch takes it (`resolve_actor`): `hidden` the width H, `out_tanh`, `members` a list of
     [w1, b1, w2, b2, w3, b3] lists - the actor's own parameter tensors, b* may be None; one entry for a shared actor,
     N for a PerAgentActor (`per_agent`) - `log_std`, a GaussianActor's [2] parameter (None: deterministic), and `norms`, the
@@ -597,7 +645,8 @@ class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members p
     shared actor, a list of N of them for a PerAgentActor, None without one; the tensors are the module's own.  `ou`: the
     OUNoiseActor whose exploration runs on top of the actor (None: none) - the module itself, whose scalars every launch reads.
     `cat`: the CategoricalActor whose head the members' w3 [5][H], b3 [5] are (None: a two-output head) - the module itself,
-    whose `deterministic` flag every launch reads.
+    whose `deterministic` flag every launch reads.  `gumbel`: the GumbelSoftmaxActor whose logits the members' w3 [5][H], b3 [5]
+    give (None: none) - the module itself, whose `explore` flag every launch reads.
     `tensors()` and `binding_key()` are the one statement of what a launch reads by address: a binder keeps the first alive
     and a launcher cache keys on the second, so a new field is added to `_slots` and nowhere else."""
     __slots__ = ()
@@ -627,14 +676,16 @@ class FusedActor(collections.namedtuple("FusedActor", "hidden out_tanh members p
 
     def binding_key(self):
         """What tells one binding of the record from another: the addresses of `_slots` (None kept in its place), the shape
-        facts, every eps - baked into the launch's structs - and the identities of the OUNoiseActor and the CategoricalActor,
-        whose scalars / `deterministic` flag are read anew per launch.  Equal for two resolutions of an unchanged module; a parameter re-allocated changes it."""
+        facts, every eps - baked into the launch's structs - and the identities of the OUNoiseActor, the CategoricalActor and the
+        GumbelSoftmaxActor (the last two appended only when set), whose scalars / `deterministic` / `explore` flag are read anew
+        per launch.  Equal for two resolutions of an unchanged module; a parameter re-allocated changes it."""
         eps = None                                         # the plain body has none
         if self.norms is not None or self.gru is not None or self.in_bn is not None:
             eps = (None if self.norms is None else tuple([None if n is None else n[2] for n in self.norms]),
                    None if self.gru is None else self.gru.norm[2], tuple([bn[4] for bn in self._in_bns()]))
         return (self.hidden, self.out_tanh, self.per_agent, tuple([t if t is None else t.data_ptr() for t in self._slots()]),
-                eps, id(self.ou)) + (() if self.cat is None else (id(self.cat),))
+                eps, id(self.ou)) + (() if self.cat is None else (id(self.cat),)) \
+            + (() if self.gumbel is None else (id(self.gumbel),))
 
 
 def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuous=True, silent=True, world_options=False,
@@ -658,7 +709,11 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
     (`continuous=False` without it: some discrete mode, nothing fuses).  A CategoricalActor is unwrapped likewise, into its
     logits module and itself (`FusedActor.cat`): it fuses in the modes ACT_ONEHOT5 and ACT_INDEX where the fact `fused_cat` holds
     (formation_hd_env; the landmark scenarios state False) and its logits resolve to the plain form, the LayerNorm form or a
-    RecurrentActor with a head of CAT_ACTIONS outputs and no Tanh.  Every other actor fuses with continuous actions only."""
+    RecurrentActor with a head of CAT_ACTIONS outputs and no Tanh.  A GumbelSoftmaxActor is unwrapped likewise
+    (`FusedActor.gumbel`): it fuses in the same two modes where the fact `fused_gumbel` holds (formation_hd_env; the landmark
+    scenarios state False) and its logits resolve to the plain or the eval-mode BatchNorm form, shared or every member of a
+    PerAgentActor (where `per_agent` holds), with a head of CAT_ACTIONS outputs and no Tanh.  Every other actor fuses with
+    continuous actions only."""
     if not (fused_scenario and silent) or world_options or callback:
         return None
     cat = actor if isinstance(actor, CategoricalActor) else None
@@ -671,6 +726,20 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
         else:
             fields = _body_spec(logits, num_agents, device, **dict(facts, head_width=CAT_ACTIONS))
         return None if fields is None else FusedActor(per_agent=False, log_std=None, cat=cat, **fields)
+    if isinstance(actor, GumbelSoftmaxActor):
+        if action_mode not in (ACT_ONEHOT5, ACT_INDEX) or not facts.get("fused_gumbel", True):
+            return None
+        logits = actor.logits
+        if isinstance(logits, PerAgentActor):
+            spec, names = per_agent_spec(logits, num_agents, device, CAT_ACTIONS) if per_agent else None, ("hidden", "out_tanh", "members")
+            if spec is None and per_agent and tuple(facts.get("fused_bn_hidden", FUSED_BN_HIDDEN) or ()):
+                spec, names = per_agent_bn_spec(logits, num_agents, device, CAT_ACTIONS), names + ("in_bn",)
+            fields = None if spec is None else dict(zip(names, spec))
+        else:
+            fields = _body_spec(logits, num_agents, device, **dict(facts, head_width=CAT_ACTIONS, head_bn=True))
+        if fields is None or "norms" in fields:            # a LayerNorm body has no Gumbel member
+            return None
+        return FusedActor(per_agent=isinstance(logits, PerAgentActor), log_std=None, gumbel=actor, **fields)
     if not continuous or action_mode:
         return None
     ou = None
@@ -699,9 +768,10 @@ def resolve_actor(actor, num_agents, device=None, fused_scenario=True, continuou
 
 
 def recurrent_mean(actor):
-    """The RecurrentActor that `actor` is or, for a GaussianActor, has as its mean, or, for a CategoricalActor, as its logits;
-    else None: the actor keeps no state."""
-    mean = actor.mean if isinstance(actor, GaussianActor) else actor.logits if isinstance(actor, CategoricalActor) else actor
+    """The RecurrentActor that `actor` is or, for a GaussianActor, has as its mean, or, for a CategoricalActor or a GumbelSoftmaxActor,
+    as its logits; else None: the actor keeps no state."""
+    mean = actor.mean if isinstance(actor, GaussianActor) \
+        else actor.logits if isinstance(actor, (CategoricalActor, GumbelSoftmaxActor)) else actor
     return mean if isinstance(mean, RecurrentActor) else None
 
 

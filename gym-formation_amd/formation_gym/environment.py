@@ -231,7 +231,7 @@ class MultiAgentEnv(object):
     def _rollout_shapes(self, K, obs_every, act=False, log_prob=False, rnn_states=None, idx=False):
         """The shapes of a K-step launch's outputs by key of `out`: obs, reward, indiv and done always; `act` (the closed
         loops' actions), `log_prob` (a Gaussian or categorical actor's), `rnn_states` (that shape: the kept hidden states) and
-        `idx` (a categorical actor's indices, int32) on request."""
+        `idx` (a categorical or Gumbel-softmax actor's indices, int32) on request."""
         B, N = self.num_envs, self.num_agents
         want = dict(obs=(K // obs_every, B, N, self._out["obs"].shape[-1]), reward=(K, B, N), indiv=(K, B, N), done=(K, B, N))
         if act:
@@ -568,6 +568,20 @@ class MultiAgentEnv(object):
         pick and the decode by the kernels' own device functions (`fg_actor_categorical`).  Any other actor in a discrete
         action mode, and any actor with `force_discrete_action` (FG_ACT_ARGMAX), raises NotImplementedError; a
         CategoricalActor on an env with continuous actions raises ValueError.
+        A `GumbelSoftmaxActor(logits, explore=True)` is the MADDPG trainers' discrete action (maddpg-pytorch's agents), for an
+        env made with discrete actions (FG_ACT_ONEHOT5, MADDPG's, or FG_ACT_INDEX): while `explore` is set, step k takes
+        argmax_j(logits(o)_j + g_j) - `gumbel_softmax(logits, hard=True)`, whose temperature never changes the index - with g
+        [B, N, 5] the draws `actor_gumbel()` of step k's RNG offset, a counter stream of their own (the same on either path and
+        for a shard as for its slice of the full batch; the Gaussian, OU and categorical draws keep their bits); otherwise
+        `onehot_from_logits`, the lowest index of the largest logit.  `explore` is read at every call.  info['actions']
+        [K, B, N] holds the int32 indices (replayable through `rollout` as a CategoricalActor's are), info['u'] [K, B, N, 2] the
+        raw actions; there is no info['log_prob'].  `out` may carry 'idx' and 'act'.  It fuses (`fg_rollout_hd_actor_gumbel`,
+        `fg_rollout_hd_actor_gumbel_per_agent`) in formation_hd_env when `logits` is the plain or the eval-mode BatchNorm body,
+        shared or every member of a PerAgentActor, with the head Linear(H, 5) and no Tanh; a LayerNorm or recurrent body, H =
+        128 behind a BatchNorm, mixed members, the landmark scenarios and World options run host-paced, the draws, the pick and
+        the decode by the kernels' own device functions (`fg_actor_gumbel`, `fg_actor_gumbel_pick`).  FG_ACT_ARGMAX raises
+        NotImplementedError, an env with continuous actions ValueError.  The soft (temperature) sample and epsilon-greedy
+        are not built; with `obs_dtype` the observations are cast.
         `obs_dtype` = torch.float16 or torch.bfloat16: as `rollout`'s - the returned obs has that dtype and holds, bit for bit,
         `.to(obs_dtype)` of what the same call without it returns; everything else (actions, log-probs, rewards, done flags,
         the states, the state left behind, the RNG counter) is that call's.  `obs_path(obs_dtype, actor=actor)` tells how:
@@ -581,11 +595,13 @@ class MultiAgentEnv(object):
         fmt = _native.obs_format(obs_dtype)
         mode = self._action_mode()
         cat = actor if isinstance(actor, actor_rollout.CategoricalActor) else None
-        if mode and (cat is None or mode == _native.FG_ACT_ARGMAX):
+        gumbel = actor if isinstance(actor, actor_rollout.GumbelSoftmaxActor) else None
+        if mode and ((cat is None and gumbel is None) or mode == _native.FG_ACT_ARGMAX):
             raise NotImplementedError("rollout_actor applies the actor's outputs as raw continuous actions")
-        if cat is not None and not mode:
-            raise ValueError("a CategoricalActor needs an env with discrete actions (discrete_action_space or "
-                             "discrete_action_input)")
+        if (cat is not None or gumbel is not None) and not mode:
+            raise ValueError("a %s needs an env with discrete actions (discrete_action_space or discrete_action_input)"
+                             % type(actor).__name__)
+        picks = cat is not None or gumbel is not None      # the actor gives an index, which the env's mode decodes
         K, obs_every = self._check_steps(K, obs_every)
         B, N = self.num_envs, self.num_agents
         recurrent = actor_rollout.recurrent_mean(actor)
@@ -623,15 +639,15 @@ class MultiAgentEnv(object):
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 self._state_tensor("out['rnn_states']", out["rnn_states"], states_shape, None)
             res = self._rollout_actor_by_steps(K, actor, obs_every, rnn_state, S, noise_state)
-            if cat is not None and isinstance(out, dict):
-                for key, src in (("idx", "actions"), ("act", "u"), ("log_prob", "log_prob")):
+            if picks and isinstance(out, dict):
+                for key, src in (("idx", "actions"), ("act", "u")) + ((("log_prob", "log_prob"),) if cat is not None else ()):
                     if key in out:
                         res[3][src] = out[key].copy_(res[3][src])
             if S is not None and isinstance(out, dict) and "rnn_states" in out:
                 res[3]["rnn_states"] = out["rnn_states"].copy_(res[3]["rnn_states"])
             return res
         want = self._rollout_shapes(K, obs_every, act=True, log_prob=fused.log_std is not None or cat is not None,
-                                    rnn_states=states_shape, idx=cat is not None)
+                                    rnn_states=states_shape, idx=picks)
         out, own_buffers = self._rollout_out(want, out, K, obs_every, True, obs_dtype)
         # what the launch reads in place besides `out`, by name for the binder and by address for the key: the binding holds
         # the parameter tensors' addresses, so it keys on them (`binding_key`) and keeps them alive - a parameter re-allocated
@@ -640,13 +656,13 @@ class MultiAgentEnv(object):
         if fused.ou is not None:
             state["noise_state"] = noise_state
         extra = state if S is None else dict(state, rnn_states_every=S)
-        if cat is not None:
+        if picks:
             extra = dict(extra, act_mode=mode)
         lead = ("actor", K, fused.binding_key(), _native.ptr(rnn_state), S, _native.ptr(noise_state))
-        self._run_rollout(lead if cat is None else lead + (mode,), want, out,    # the categorical launch bakes the mode in
+        self._run_rollout(lead if not picks else lead + (mode,), want, out,    # the categorical / Gumbel launch bakes the mode in
                           own_buffers, K, obs_every, obs_dtype, self.scenario.bind_rollout_actor, None, (K, fused), extra)
         info = dict(state, actions=out["act"])             # the states come back as updated in place
-        if cat is not None:
+        if picks:
             info.update(actions=out["idx"], u=out["act"])
         if "log_prob" in want:
             info["log_prob"] = out["log_prob"]
@@ -696,6 +712,32 @@ class MultiAgentEnv(object):
         _native.check(_native.load().fg_actor_uniform(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
         return out
 
+    def actor_gumbel(self, out=None):
+        """The Gumbel draws g [B, N, 5] that a GumbelSoftmaxActor's next step explores with (`fg_actor_gumbel` at the offset of
+        the next launch): -log(-log(u)) of five uniforms in (0, 1) per (env, agent) from a Philox stream of their own, so
+        `actor_noise()` and `actor_uniform()` keep their bits."""
+        B, N = self.num_envs, self.num_agents
+        if out is None:
+            out = torch.empty((B, N, actor_rollout.CAT_ACTIONS), dtype=torch.float32, device=self.world.device)
+        sc = self.scenario
+        p = self.world.native_params(seed=getattr(sc, "_seed", 0), rng_offset=self._launch_rng_offset(), scripted_ok=True)
+        p.env_index_base = int(getattr(sc, "env_base", 0))
+        _native.check(_native.load().fg_actor_gumbel(p, B, N, out.data_ptr(), _native.current_stream(self.world.device)))
+        return out
+
+    def _gumbel_pick(self, logits, g, explore):
+        """(idx int32 [...], u [..., 2]) of logits [..., 5] and Gumbel draws g [..., 5] (None when not exploring) in the env's
+        action mode (`fg_actor_gumbel_pick`: the fused kernels' pick and decode)."""
+        dev = self.world.device
+        logits = logits.detach().to(device=dev, dtype=torch.float32).contiguous()
+        lead = tuple(logits.shape[:-1])
+        idx = torch.empty(lead, dtype=torch.int32, device=dev)
+        act = torch.empty(lead + (2,), dtype=torch.float32, device=dev)
+        _native.check(_native.load().fg_actor_gumbel_pick(self._action_mode(), int(bool(explore)), idx.numel(), logits.data_ptr(),
+                                                          _native.ptr(g), idx.data_ptr(), act.data_ptr(),
+                                                          _native.current_stream(dev)))
+        return idx, act
+
     def _categorical(self, logits, u, greedy):
         """(idx int32 [...], u [..., 2], log_prob [...]) of logits [..., 5] and draws u [...] in the env's action mode
         (`fg_actor_categorical`: the fused kernels' pick and decode)."""
@@ -731,12 +773,15 @@ class MultiAgentEnv(object):
         step's done flag is set, is updated in place at the end and comes back as info['noise_state'].  A CategoricalActor:
         the logits from the module, the draw from `actor_uniform`, the pick and the decode by the kernels' own device functions
         (`fg_actor_categorical`), then `step` with the index (FG_ACT_INDEX) or its one-hot (FG_ACT_ONEHOT5); info['actions']
-        holds the indices, info['u'] the raw actions, info['log_prob'] the log-probabilities."""
+        holds the indices, info['u'] the raw actions, info['log_prob'] the log-probabilities.  A GumbelSoftmaxActor: the
+        logits from the module, the draws from `actor_gumbel` while it explores, the pick and the decode by the kernels' own
+        device functions (`fg_actor_gumbel_pick`), then `step` likewise; info['actions'] and info['u'], no log-probabilities."""
         ou = actor if noise_state is not None else None
         x = noise_state.clone() if ou is not None else None
         gaussian = isinstance(actor, actor_rollout.GaussianActor)
         cat = actor if isinstance(actor, actor_rollout.CategoricalActor) else None
-        body = actor.mean if gaussian else actor.logits if cat is not None else actor
+        gumbel = actor if isinstance(actor, actor_rollout.GumbelSoftmaxActor) else None
+        body = actor.mean if gaussian else actor.logits if cat is not None or gumbel is not None else actor
         picked, raw = [], []
         h = rnn_state.clone() if rnn_state is not None else None
         logp, states = [], []
@@ -766,6 +811,14 @@ class MultiAgentEnv(object):
                 return idx
             return torch.nn.functional.one_hot(idx.long(), 5).to(torch.float32)
 
+        def pick_gumbel(obs, k):                           # a GumbelSoftmaxActor
+            exploring = gumbel.explore
+            idx, u_act = self._gumbel_pick(body(obs) if h is None else mean(obs, k), self.actor_gumbel() if exploring else None, exploring)
+            picked.append(idx); raw.append(u_act)
+            if self._action_mode() == _native.FG_ACT_INDEX:
+                return idx
+            return torch.nn.functional.one_hot(idx.long(), 5).to(torch.float32)
+
         def explore(obs, k):                               # an OUNoiseActor
             self._ou_step(ou, self.actor_noise(), x)
             return ou.explore(ou.actor(obs), x)
@@ -781,6 +834,8 @@ class MultiAgentEnv(object):
             act_fn = sample
         elif cat is not None:
             act_fn = pick
+        elif gumbel is not None:
+            act_fn = pick_gumbel
         elif h is not None:
             act_fn = mean
         else:
@@ -789,7 +844,7 @@ class MultiAgentEnv(object):
             obs, rew, done, info = self._step_loop(K, obs_every, act_fn, after_step)
         if gaussian or cat is not None:
             info["log_prob"] = torch.stack(logp)
-        if cat is not None:
+        if cat is not None or gumbel is not None:
             info["actions"], info["u"] = torch.stack(picked), torch.stack(raw)
         if h is not None:
             rnn_state.copy_(h)

@@ -309,6 +309,10 @@ class Scenario(BaseScenario):
                                                 out["idx"] [K,B,N] int32, the log-probs in out["log_prob"], the decoded actions
                                                 in out["act"]; `rnn_state` and out["rnn_states"] as above; the module's
                                                 `deterministic` flag is read before every launch
+          a GumbelSoftmaxActor (`actor.gumbel`) `fg_rollout_hd_actor_gumbel` / `fg_rollout_hd_actor_gumbel_per_agent` on the plain or
+                                                the BatchNorm body (in_bn or NULL) in the env's action mode `act_mode`: the
+                                                indices in out["idx"] [K,B,N] int32, the decoded actions in out["act"]; the
+                                                module's `explore` flag is read before every launch
           16-bit observations (`obs_format`)    `fg_rollout_hd_actor_obs16` (a GaussianActor on the plain, the LayerNorm or the
                                                 recurrent body: norm / gru or NULL, log_std required, rnn_states or NULL) and
                                                 `fg_rollout_hd_actor_cat_obs16` (a CategoricalActor likewise): out["obs"] is a
@@ -332,8 +336,12 @@ class Scenario(BaseScenario):
         p = self.params(world, auto_reset, 0, out.get("obs"))
         state = (world.num_envs, len(world.agents), int(K)) + self._state_ptrs(world, out["act"]) + self._out_ptrs(out)
         tail = (int(obs_every), _native.current_stream(world.device))
-        cat = actor.cat
-        if cat is not None:
+        cat, gumbel = actor.cat, actor.gumbel
+        if gumbel is not None:
+            if cat is not None or ou is not None or norm is not None or gru is not None or log_std is not None or obs_format:
+                raise NotImplementedError("a GumbelSoftmaxActor fuses on the plain and the BatchNorm body, shared or per agent, with "
+                                          "fp32 observations only")
+        elif cat is not None:
             if ou is not None or bns is not None or actor.per_agent or log_std is not None:
                 raise NotImplementedError("a CategoricalActor fuses on the plain, the LayerNorm and the recurrent body only")
         elif (gru is not None and norm is None) or (norm is not None and actor.per_agent):
@@ -344,15 +352,18 @@ class Scenario(BaseScenario):
         # What may follow the state block: the indices, the log-probs, the hidden state, the kept states with their stride
         # (NULL and 1 where none are kept)
         keep_states = rnn_states_every is not None
-        idx = (out["idx"].data_ptr(),) if cat is not None else ()
+        idx = (out["idx"].data_ptr(),) if cat is not None or gumbel is not None else ()
         logp = (None if cat is None and log_std is None else out["log_prob"].data_ptr(),)
         rnn = (_native.ptr(rnn_state) if gru is not None else None,)
         states = (out["rnn_states"].data_ptr() if keep_states else None, int(rnn_states_every) if keep_states else 1)
         # The families, the first that applies giving the launch: (applies, C entry, its arguments before the state, what follows
-        # the state).  A categorical entry takes `greedy` as its last leading argument, one bound launch per value.
+        # the state).  A categorical entry takes `greedy` as its last leading argument and a Gumbel entry `explore`, one bound
+        # launch per value.
         ls, nst = _native.ptr(log_std), _native.ptr(noise_state)
         fmt, x16 = ((int(obs_format),), "_obs16") if obs_format else ((), "")
         families = (
+            (gumbel is not None and actor.per_agent, "fg_rollout_hd_actor_gumbel_per_agent", (fas, bns, int(act_mode)), idx),
+            (gumbel is not None, "fg_rollout_hd_actor_gumbel", (fas, bns, int(act_mode)), idx),
             (cat is not None, "fg_rollout_hd_actor_cat" + x16, fmt + (fas, norm, gru, int(act_mode)), idx + logp + rnn + states),
             (bool(obs_format), "fg_rollout_hd_actor_obs16", fmt + (fas, norm, gru, ls), logp + rnn + states),
             (ou is not None and actor.per_agent, "fg_rollout_hd_actor_ou_per_agent", (fas, bns, fou, nst), ()),
@@ -374,6 +385,12 @@ class Scenario(BaseScenario):
             def launch_cat(rng_offset=0):              # the module's flag as it is now: sampled or the distribution's mode
                 return by_flag[1 if cat.deterministic else 0](rng_offset)
             return launch_cat
+        if gumbel is not None:
+            by_flag = [_native.bind_launch(getattr(lib, entry), p, *lead, explore, *args, keep=keep) for explore in (0, 1)]
+
+            def launch_gumbel(rng_offset=0):           # the module's flag as it is now: exploring or the largest logit
+                return by_flag[1 if gumbel.explore else 0](rng_offset)
+            return launch_gumbel
         launch = _native.bind_launch(getattr(lib, entry), p, *lead, *args, keep=keep)
         if ou is None:
             return launch

@@ -84,13 +84,14 @@ class ActorRolloutMixin(object):
         `fused_ln_hidden=()`: this launch has no LayerNorm kernel, so a LayerNorm actor runs host-paced here;
         `fused_gru_hidden=()`: nor a recurrent one, so a RecurrentActor does too; `fused_bn_hidden=()`: nor one with an input
         BatchNorm, so the MADDPG trainers' BatchNorm actor does too; `fused_ou=False`: no OU kernel, so an OUNoiseActor does
-        too; `fused_cat=False`: nor a categorical one, so a CategoricalActor does too."""
+        too; `fused_cat=False`: nor a categorical one, so a CategoricalActor does too; `fused_gumbel=False`: nor a Gumbel one, so a
+        GumbelSoftmaxActor does too."""
         from formation_gym import actor_rollout
         d = self._actor_descriptor(world)
         facts = actor_rollout.landmark_facts(d.kind, len(world.agents), d.num_landmarks, d.num_obstacles, d.num_obs,
                                              self.obs_dim(world), d.variant)
         return None if facts is None else dict(facts, fused_ln_hidden=(), fused_gru_hidden=(), fused_bn_hidden=(), fused_ou=False,
-                                                 fused_cat=False)
+                                                 fused_cat=False, fused_gumbel=False)
 
     def bind_rollout_actor(self, world, K, actor, out, obs_every=1, auto_reset=False):
         """K closed-loop steps with the caller's MLP actor (`fg_rollout_scenario_actor`), every pointer and the structs

@@ -822,6 +822,63 @@ int fg_actor_uniform(const FgParams* params, int B, int N, float* u, void* strea
 int fg_actor_categorical(int act_mode, int greedy, int64_t count, const float* logits, const float* u, int32_t* idx, float* act,
                          float* logp, void* stream);
 
+/* The MADDPG trainers' discrete actions (maddpg-pytorch's agents on make_env(..., discrete_action=True): exploring,
+ * gumbel_softmax(logits, hard=True); otherwise onehot_from_logits(logits)) as the Gumbel member of the four families without
+ * LayerNorms - the discrete twin of fg_rollout_hd_actor_ou: gumbel_actor_kernel (in_bn == NULL) or bn_gumbel_actor_kernel
+ * (in_bn: the input BatchNorm), at those families' N and hidden widths (128 without, 64 with the BatchNorm).  The actor is
+ * fg_rollout_hd_actor's / _bn's with w3 [5][hidden], b3 [5] (or NULL) and out_tanh == 0.  Per (env b, agent i, step k) the five
+ * fp32 logits l_j are ascending fmaf chains from b3[j], as in fg_rollout_hd_actor_cat, and
+ *     Gumbel draws: five per row from a Philox4x32-10 stream of their own - key seed, counter
+ *         {b + env_index_base, i | 0x60000000 | (q << 12), lo32(off), hi32(off)}, off = rng_base + k;
+ *         draw j is word j & 3 of block q = j >> 2 (block 0: j = 0..3, word 0 of block 1: j = 4).  The top three bits of word 1
+ *         are 011 against 000 / 001 / 100 / 101 / 110 / 111 of every other stream, and the actor-noise block is not touched:
+ *         Gaussian, OU and categorical draws keep their bits.
+ *         u_j = (2 (c >> 9) + 1) 2^-24 - an odd 24-bit integer scaled: exact in fp32, strictly inside (0, 1) -
+ *         g_j = -log(-log(u_j)) in [-2.82, 16.64], both logarithms the full-precision fp32 log (not the hardware approximation:
+ *         the inner result is the outer logarithm's argument).
+ *     exploring (explore != 0): y_j = l_j + g_j, one fp32 addition of the finished logit, never contracted into its chain
+ *     otherwise (explore == 0): y_j = l_j, no draws
+ *     idx = the lowest j attaining max_j y_j
+ * gumbel_softmax's temperature does not enter - argmax softmax(y / T) = argmax y for every T > 0 - and its soft sample
+ * (hard=False), a training-time quantity, is not built; nor is onehot_from_logits' epsilon-greedy.  The index becomes the raw
+ * action by act_mode, the env's own, exactly as in fg_rollout_hd_actor_cat (FG_ACT_ONEHOT5, MADDPG's, or FG_ACT_INDEX).  There
+ * is no log-prob.  `explore` and `act_mode` are run-time facts of the launch: one kernel per (family, N, hidden).
+ * act_seq [K][B][N][2] (required) receives the decoded raw action, so fg_rollout_hd driven by it returns the same results bit
+ * for bit; idx_seq [K][B][N] int32 (required) the indices.  Checks and status codes are the inner entry's (fg_rollout_hd_actor's
+ * / _bn's) in their order, in this entry's name; then FG_ERR_BAD_ARG for out_tanh != 0, an act_mode other than the two
+ * (FG_ACT_ARGMAX included), a NULL idx_seq with B > 0, and FG_ERR_ALIGNMENT for an idx_seq that is not 4-byte aligned.  B == 0
+ * returns FG_OK.  Two launches from one state give the same bits. */
+int fg_rollout_hd_actor_gumbel(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, int act_mode,
+                               int explore, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x, float* vel_y,
+                               float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                               float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                               int obs_every, void* stream);
+/* ... with one actor per agent (MADDPG's one MLPNetwork per agent): fg_rollout_hd_actor_per_agent (in_bns == NULL) or
+ * fg_rollout_hd_actor_bn_per_agent (in_bns: a HOST array of N), kernels pa_gumbel_actor_kernel / pa_bn_gumbel_actor_kernel.  N
+ * identical members give the shared kernel's indices and actions bit for bit. */
+int fg_rollout_hd_actor_gumbel_per_agent(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns, int act_mode,
+                                         int explore, int B, int N, int K, float* pos_x, float* pos_y, float* vel_x,
+                                         float* vel_y, float* act_seq, float* ideal_shape, float* ideal_vel, int32_t* step,
+                                         float* obs_seq, float* reward_seq, float* indiv_seq, uint8_t* done_seq, int32_t* idx_seq,
+                                         int obs_every, void* stream);
+/* Dry runs of the two: same checks and status codes (the buffers' apart), name the gumbel_actor_kernel<N,H> /
+ * bn_gumbel_actor_kernel<N,H> or pa_gumbel_actor_kernel<N,H> / pa_bn_gumbel_actor_kernel<N,H> instantiation and its launch
+ * geometry.  Touch no device. */
+int fg_describe_actor_gumbel_launch(const FgParams* params, const FgActor* actor, const FgActorInBn* in_bn, int act_mode,
+                                    int explore, int B, int N, int K, int obs_every, char* out, int out_len);
+int fg_describe_actor_gumbel_per_agent_launch(const FgParams* params, const FgActor* actors, const FgActorInBn* in_bns,
+                                              int act_mode, int explore, int B, int N, int K, int obs_every, char* out,
+                                              int out_len);
+/* One step's Gumbel draws g [B][N][5] (fp32 in DEVICE memory, 4-byte aligned) at rng_base(params), by the device function of
+ * the Gumbel kernels: fg_actor_uniform's sibling for the host-paced loop of a Gumbel-softmax policy.  1 <= N <= 2^12. */
+int fg_actor_gumbel(const FgParams* params, int B, int N, float* g, void* stream);
+/* The pick above and the decode on `count` rows of caller-supplied logits [count][5] and draws g [count][5] (NULL allowed when
+ * not exploring), by the fused kernels' device functions: idx [count] int32 (required), act [count][2] (8-byte aligned; NULL:
+ * not written), all fp32 / int32 in DEVICE memory.  FG_ERR_BAD_ARG for another act_mode, a negative count, a NULL logits, idx or
+ * (exploring) g; FG_ERR_ALIGNMENT for a misaligned buffer; count == 0 is a no-op. */
+int fg_actor_gumbel_pick(int act_mode, int explore, int64_t count, const float* logits, const float* g,
+                         int32_t* idx, float* act, void* stream);
+
 /* fg_rollout_hd_actor / fg_rollout_hd_actor_sample for the landmark scenarios (basic_formation_env, formation_hd_partial_env,
  * formation_hd_partial_range_env, formation_hd_obs_env): K >= 1 closed-loop steps of all B envs in ONE launch
  * (scn_lane_actor, or scn_lane_actor_gauss when log_std is not NULL), with the actor
