@@ -70,7 +70,7 @@ def test_policy_kernel_matches_reference_actions(golden, name):
     out = {"obs": env._out["obs"], "reward": env._out["reward"]}
     env.scenario.observe_batch(env.world, out)
     act2 = bfs_actions(out["obs"], 3)
-    _check_actions(_np(act2), g["act"], margins, name + " (env observations)")
+    assert _check_actions(_np(act2), g["act"], margins, name + " (env observations)") <= max(1, T * N // 50)
     # (3) a strided view (padded env pitch) and a caller-owned output give the same bits
     pad = torch.zeros((T, N * 6 * N + 10), device="cuda")
     pad[:, :N * 6 * N] = obs.reshape(T, -1)
@@ -97,7 +97,9 @@ def test_policy_kernel_other_hierarchies_against_oracle(N, per, B):
     nb = B if N <= 64 else 2                                   # the Python queue walk is slow at large N
     want = np.stack([np.array(O.get_action_bfs(O.ezpolicy, list(_np(obs[b])), per, strict=False)) for b in range(nb)])
     margins = np.stack([O.bfs_margins(list(_np(obs[b])), per) for b in range(nb)])
-    _check_actions(act[:nb], want, margins, "N=%d per=%d" % (N, per), scale_with_magnitude=True)
+    # near-ties are rare: at these seeds the fp64 reference has NO row within 1e-6 of another decision in any of the ten cases
+    # (profiles/policy_branches.md), so the cap is generous; a case that exceeds it on the reference alone gets another seed
+    assert _check_actions(act[:nb], want, margins, "N=%d per=%d" % (N, per), scale_with_magnitude=True) <= max(1, nb * N // 50)
     assert np.isfinite(act).all()
 
 
