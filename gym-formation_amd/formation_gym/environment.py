@@ -1040,11 +1040,18 @@ class MultiAgentEnv(object):
         return report
 
     def use_device_rng_counter(self, on=True):
-        """Keep the per-step offset of the device counter RNG (auto-reset draws, motor noise) in DEVICE memory
-        (`FgParams.rng_offset_dev`) and advance it with a device-side add after every launch, instead of passing it
-        by value.  Needed when the step loop is captured in a hipGraph (torch.cuda.CUDAGraph) with auto-reset on: by-value
-        launch arguments are frozen at capture, so every replay would repeat the same reset draws.  The draws are the
-        same in both modes (a captured loop, replayed, equals the loop run launch by launch)."""
+        """Keep the per-step offset of the device counter RNG (auto-reset draws, motor noise, and a learned actor's
+        exploration draws in `rollout_actor`: a GaussianActor's and an OUNoiseActor's eps, a CategoricalActor's uniforms, a
+        GumbelSoftmaxActor's Gumbel draws - the fused launches and the host-paced loop's `actor_noise()`, `actor_uniform()`,
+        `actor_gumbel()` alike) in DEVICE memory (`FgParams.rng_offset_dev`) and advance it with a device-side add after
+        every launch, instead of passing it by value.  Needed when the step loop - `step`, `rollout`, `rollout_policy` or a
+        fused `rollout_actor` - is captured in a hipGraph (torch.cuda.CUDAGraph) with auto-reset on or an exploring actor:
+        by-value launch arguments are frozen at capture, so every replay would repeat the same reset draws and the same
+        exploration noise.  The draws are the same in both modes (a captured loop, replayed, equals the loop run launch by
+        launch): step k of a launch draws at FgParams.rng_offset + the counter + k, a 64-bit sum, so a carry into the high
+        word arrives through the counter as it does by value.  A captured `rollout_actor` reads the actor's weights
+        and the states (`rnn_state`, `noise_state`) in place at every replay; what the call reads on the HOST - an
+        OUNoiseActor's scalars, `deterministic`, `explore` - is frozen at capture (tests/test_gpu_actor_graph.py)."""
         if on and self.world.rng_counter is None:
             self.world.rng_counter = torch.full((1,), int(self._rng_offset), dtype=torch.int64, device=self.world.device)
         elif not on and self.world.rng_counter is not None:
