@@ -110,6 +110,11 @@ int main(int argc, char** argv) {
             float* obs_placed = static_cast<float*>(placed);
             FgParams Q = P;
             Q.obs_placed = 1;
+            // The rows' communication block (units [N, 2N-1): zeros, the agents are silent) never changes: fill the buffer
+            // with zeros ONCE and promise it - the rollout then leaves out the whole 128-byte lines inside that block.
+            // Only rollout launches without comm_state write this buffer afterwards, so the promise holds for every launch.
+            HIP_OK(hipMemsetAsync(placed, 0, need, st));
+            Q.obs_zero_primed = 1;
             auto run_placed = [&](int n_steps) -> int {
                 for (int t = 0; t < n_steps; t += K) {
                     Q.rng_offset = (uint64_t)t + 1;

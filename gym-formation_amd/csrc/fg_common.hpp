@@ -79,7 +79,7 @@ struct KParams {
     const uint64_t* rng_offset_dev;
     const double* agent_props;
     const double* comm_state;
-    int32_t obs_placed, reserved0;
+    int32_t obs_placed, obs_zero_primed;
 };
 #else
 typedef FgParams KParams;

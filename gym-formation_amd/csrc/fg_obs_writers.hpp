@@ -200,9 +200,48 @@ template <int NC, int RT> constexpr int tile_units() { return (3 * NC * RT + 16 
 // `tiles` holds TWO tiles per writing wave: tile t+1 is composed while tile t drains.
 // STREAM: the HBM-streaming form (line ownership + paced stores, see above and stream() below); false: the plain form
 // (every wave stores exactly its env's bytes, all LDS reads of a tile in flight before its stores).
+//
+// Zero skip (`primed`, FgParams.obs_zero_primed: the destination's zero blocks - units [N, 2N-1) of every row, the
+// communication block of silent agents - already hold zeros): a lane's 16-byte store is masked off iff the
+// FG_ZERO_SKIP_BYTES-aligned group (by device address) around its destination lies wholly inside that block of ONE row of
+// ONE env.  Whole aligned groups only: every request that still leaves the CU is a full one.  The decision depends on the
+// group's address and the env block's alone, so every lane, store instruction and wave that touches a group decides alike.
+// A group that starts in front of the env block, or reaches into the pad or the next env's head units, is never skipped
+// (its offset in the row is then outside the block); the 8-byte heads and tails sit at row boundaries, never in the block.
+// The offset of a group in its row is all that decides (a tile starts at a row's first unit, rows are 3N units apart): in
+// front of the env block it is one of the last 15 units of a "row", behind the env's last row one of the first 15 - outside
+// [N, 2N-1) for 16 <= N.  Store instruction c of a tile is 1 KiB = 128 units on from instruction 0, so a lane takes ONE
+// remainder per tile (zero_skip_m0) and per store an add, a wrap and a range test (zero_skip_at): the writer waves of the
+// 4-wave forms are bound by their own instruction chain, and a division per store cost them a quarter of their rate.
+// ---------------------------------------------------------------------------
+// G of the skip: whole 128-byte lines.  Measured with the headline's geometry, profiles/r06_zero_skip/holes.txt: lines left
+// out 242.6-245.0 us per 20 slabs against 254.2-256.3 written in full; 64-byte groups left out (half lines) 324-327.
+constexpr unsigned FG_ZERO_SKIP_BYTES = 128;
+template <bool B> struct ZeroPrimed { static constexpr bool value = B; };
+template <int NC> constexpr bool zero_skip_fits() { return NC >= 16 && NC - 1 >= (int)(FG_ZERO_SKIP_BYTES / 8); }
+// row0: the tile's first row in the destination; u0: the unit (from row0) of the lane's 16 bytes in store instruction 0.
+// Returns the offset in its row of the aligned group around them.
+template <int NC> FG_DEV unsigned zero_skip_m0(bool primed, const void* row0, unsigned u0) {
+    constexpr unsigned GU = FG_ZERO_SKIP_BYTES / 8, ROWU = 3u * NC;
+    static_assert(ROWU > GU && 128u % GU == 0, "a group in front of row 0 lies in the row before; 1 KiB is whole groups");
+    if constexpr (!zero_skip_fits<NC>()) return 0u;
+    if (!primed) return 0u;
+    const unsigned ph = ((unsigned)(uintptr_t)row0 >> 3) & (GU - 1u);   // the row's first unit inside its group, by device address
+    const unsigned g0 = ((u0 + ph) & ~(GU - 1u)) - ph + ROWU;           // the group's first unit from row0 (>= -15), one row up
+    return g0 % ROWU;
+}
+// ... of the lane's 16 bytes in store instruction c: masked off?
+template <int NC> FG_DEV bool zero_skip_at(bool primed, unsigned m0, unsigned c) {
+    constexpr unsigned GU = FG_ZERO_SKIP_BYTES / 8, ROWU = 3u * NC;
+    if constexpr (!zero_skip_fits<NC>()) return false;                  // no aligned group fits into N - 1 units
+    unsigned m = m0 + (c * 128u) % ROWU;                                // (c is a constant of the unrolled loops)
+    m = min(m, m - ROWU);                                               // wrap: m < 2 ROWU
+    return primed && m - (unsigned)NC <= (unsigned)(NC - 1) - GU;       // N <= m && m + GU <= 2N - 1
+}
+
 template <int NC, int NW, int E, int RT, bool STREAM>
 FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, int w, float2* __restrict__ tiles,
-                            float2* __restrict__ out_env0, size_t unit0, size_t env_units, int El) {
+                            float2* __restrict__ out_env0, size_t unit0, size_t env_units, int El, bool primed = false) {
     constexpr int N = NC;
     constexpr int WPE = (E >= NW) ? 1 : NW / E;
     static_assert((E >= NW) ? (E % NW == 0) : (NW % E == 0), "waves and envs must tile");
@@ -293,7 +332,9 @@ FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, 
             }
         }
     };
-    auto stream = [&](int t) {
+    // PR: the launch is zero-primed, as a type - an unflagged launch runs the very code it ran before the skip existed
+    auto stream = [&](int t, auto PR) {
+        constexpr bool primed = decltype(PR)::value;
         int ee, r0; locate(t, ee, r0);
         if (r0 >= N) return;
         const unsigned par = (unsigned)((unit0 + (size_t)ee * env_units + (size_t)r0 * ROWU) & 1);
@@ -305,10 +346,11 @@ FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, 
             const unsigned npair = (TU - par) >> 1;
             const f32x4* src4 = reinterpret_cast<const f32x4*>(img + par);
             f32x4* __restrict__ dst4 = reinterpret_cast<f32x4*>(out + par);
+            const unsigned m0 = zero_skip_m0<NC>(primed, out, par + 2u * lane);
 #pragma unroll
             for (unsigned q0 = 0; q0 < NPMAX; q0 += 64) {
                 const unsigned q = q0 + lane;
-                if (q < npair) dst4[q] = src4[q];
+                if (q < npair && !zero_skip_at<NC>(primed, m0, q0 / 64)) dst4[q] = src4[q];
             }
             if (((TU - par) & 1u) && lane == 63) out[TU - 1] = img[TU - 1];
         } else {
@@ -320,6 +362,7 @@ FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, 
             const unsigned npair = (end - s - p2) >> 1;
             const f32x4* src4 = reinterpret_cast<const f32x4*>(img + s + p2);
             f32x4* __restrict__ dst4 = reinterpret_cast<f32x4*>(out + s + p2);
+            const unsigned m0 = zero_skip_m0<NC>(primed, out, s + p2 + 2u * lane);
             // The first NFULL store instructions are full whatever s / end are (at most 15 units are skipped): ONE 1 KiB
             // store per LDS round trip and wave, then 64 idle cycles - no bursts.  Interleaved rounds on several boxes,
             // 27 x 4096 x 20 steps: 12.8-13.4 us/step against 13.6-14.7 for bursts of five stores (13.3-13.8 without the
@@ -329,15 +372,16 @@ FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, 
 #pragma unroll
             for (unsigned c = 0; c < NFULL; ++c) {
                 const f32x4 v = src4[c * 64 + lane];
+                const bool skip = zero_skip_at<NC>(primed, m0, c);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                dst4[c * 64 + lane] = v;                                // (non-temporal stores: no gain, profiles/r03_wide/ab_27_nt_placed.txt)
+                if (!skip) dst4[c * 64 + lane] = v;                     // (non-temporal stores: no gain, profiles/r03_wide/ab_27_nt_placed.txt)
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_s_sleep(1);
             }
 #pragma unroll
             for (unsigned q0 = NFULL * 64; q0 < NPMAX; q0 += 64) {
                 const unsigned q = q0 + lane;
-                if (q < npair) dst4[q] = src4[q];
+                if (q < npair && !zero_skip_at<NC>(primed, m0, q0 / 64)) dst4[q] = src4[q];
             }
             if (((end - s - p2) & 1u) && lane == 63) out[end - 1] = img[end - 1];
         }
@@ -345,7 +389,8 @@ FG_DEV void write_obs_tiled(const float2* __restrict__ tables0, int env_stride, 
     if (total > 0) compose(0);
     for (int t = 0; t < total; ++t) {
         if (t + 1 < total) compose(t + 1);
-        stream(t);
+        if (primed) stream(t, ZeroPrimed<true>{});                      // wave-uniform
+        else stream(t, ZeroPrimed<false>{});
     }
 }
 

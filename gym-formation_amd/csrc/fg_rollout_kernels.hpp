@@ -331,7 +331,8 @@ void rollout_kernel(const Args a) {
                 else
                     write_obs_tiled<NC, NWW, E, WR - 1, STREAM>(tables0, roll_block_floats(N) / 2, (tid - TP) >> 6,
                                                                 reinterpret_cast<real2*>(smemf + E * roll_block_floats(N)),
-                                                                reinterpret_cast<real2*>(a.obs) + unit0, unit0, env_units, El);
+                                                                reinterpret_cast<real2*>(a.obs) + unit0, unit0, env_units, El,
+                                                                a.p.obs_zero_primed != 0);
             }
         }
         __syncthreads();

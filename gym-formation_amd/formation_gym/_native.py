@@ -58,7 +58,7 @@ class FgParams(ctypes.Structure):
         ("agent_props", ctypes.c_void_p),       # device float [N][AGENT_PROPS] or NULL (uniform agents)
         ("comm_state", ctypes.c_void_p),        # device float [B][N][2] or NULL (silent agents)
         ("obs_placed", ctypes.c_int32),         # 1: the observation buffer was composed with fg_arena_* (placement.py)
-        ("reserved0", ctypes.c_int32),
+        ("obs_zero_primed", ctypes.c_int32),    # 1: the zero blocks of the fp32 observation buffer already hold zeros (placement.py)
     ]
 
 

@@ -24,7 +24,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _native, actor_rollout, spaces
+from . import _native, actor_rollout, placement, spaces
 
 cam_range = 2
 
@@ -290,7 +290,7 @@ class MultiAgentEnv(object):
         if own_buffers and bind is not None and want.keys() <= out.keys():
             key = lead_key + (tuple([out[k].data_ptr() for k in want]), tuple(out["obs"].stride()), obs_every,
                               self.auto_reset, _native.current_stream_fast(self.world.device), self.world.params_signature(),
-                              getattr(self.scenario, "_seed", 0), obs_dtype)
+                              getattr(self.scenario, "_seed", 0), obs_dtype, placement._primed_gen[0])
         launch = self._roll_launchers.get(key) if key is not None else None
         off = self._launch_rng_offset()
         if launch is None:
@@ -336,6 +336,10 @@ class MultiAgentEnv(object):
             if k not in out or tuple(out[k].shape) != shp:
                 raise ValueError("out[%r] must be a tensor of shape %s" % (k, shp))
         first = None if self.shared_reward else torch.empty(want["reward"], dtype=torch.float32, device=dev)
+        if torch.is_tensor(out["obs"]) and out["obs"].numel():
+            # the observations are COPIED in below, not written by a launch that Scenario.params has seen: whatever the steps
+            # put into the communication block lands in this buffer, so it is no longer known to hold zeros there
+            placement.drop_primed(out["obs"].data_ptr(), out["obs"].numel() * out["obs"].element_size())
         for k in range(K):
             act = action_seq[k]
             if torch.is_tensor(act) and (act.dtype != torch.float32 or act.device != dev) and not self._action_mode():
@@ -900,7 +904,7 @@ class MultiAgentEnv(object):
         sc._cache = None
 
     def alloc_rollout_buffers(self, K, obs_every=1, obs_env_pitch=0, policy=False, candidates=8, mem_fraction=0.5,
-                              max_arena_bytes=None, escalate=True):
+                              max_arena_bytes=None, escalate=True, primed=True):
         """Output buffers for `rollout` / `rollout_policy` launches of K steps, with the observation buffer - 99 % of
         the bytes - PLACED: when it is larger than the Infinity Cache, candidate buffers are composed of the chunks of a
         small arena of device memory (6 x the buffer up to 48 GiB, at least 1.5 x the buffer, never more than
@@ -912,8 +916,16 @@ class MultiAgentEnv(object):
         is restored afterwards, also when the probe fails.  escalate=False: one arena only (an arena whose winner gains
         nothing is otherwise followed by up to two four times larger ones).  `obs_env_pitch` (floats, 0 = contiguous) asks for padded env blocks.  The probe's report
         is left in `self.placement`.  Returns the `out` dict to pass to `rollout(..., out=out)`.  The arena lives exactly
-        as long as the observation tensor (or any view of it): dropping the tensors gives the memory back."""
-        from . import placement
+        as long as the observation tensor (or any view of it): dropping the tensors gives the memory back.
+        ZERO-PRIMED (formation_hd_env, `primed`): the observation buffer is filled with zeros once and registered
+        (placement.register_primed), on every path - the arena's winner after it is mapped for good, the winner of whole
+        allocations, the unprobed allocation - and each candidate of a probe before it is timed, so that the probe times the
+        launch the env will really run.  Launches of silent agents into it then leave out the stores of the rows'
+        communication block (whole 128-byte lines of it, `FgParams.obs_zero_primed`).  THE CONTRACT: the buffer is the env's -
+        launches write it, a consumer only reads it.  Who writes into it otherwise calls `prime_rollout_buffers(out)` before
+        the next launch; primed=False opts out (nothing is registered, every launch writes every byte).  A buffer, probed or
+        not, keeps its registration only if the flagged launch measured at least 2 % faster on it than the unflagged one
+        (self.placement["zero_primed"]: kept, flagged_ms, unflagged_ms; 12 launches)."""
         K, obs_every = int(K), int(obs_every)
         B, N = self.num_envs, self.num_agents
         D = self._out["obs"].shape[-1]
@@ -935,7 +947,17 @@ class MultiAgentEnv(object):
             return shaped(torch.empty(slots * B * pitch, **f))
 
         nbytes = slots * B * pitch * 4
-        if slots == 0 or nbytes < placement.MIN_PROBE_BYTES or candidates < 2:
+        primed = bool(primed) and slots > 0 and D == 6 * N and getattr(self.scenario, "obs_zero_block", False)
+
+        def prime(obs, keeper=None):
+            # zeros once, then the registration (the pad of a padded pitch is not part of `obs`: the writers fill it)
+            if primed:
+                obs.zero_()
+                placement.register_primed(obs if keeper is None else keeper, obs.data_ptr(), nbytes, N, B, pitch)
+            return obs
+
+        probe = not (slots == 0 or nbytes < placement.MIN_PROBE_BYTES or candidates < 2)
+        if not probe and not primed:
             self.placement = {"tried": 1, "probed": False}
             return dict(small, obs=alloc())
         snap = self._snapshot()
@@ -946,7 +968,11 @@ class MultiAgentEnv(object):
 
         per_layer = self._policy_per_layer() if closed else 0
 
-        def time_fn(obs):
+        def time_fn(obs, keeper=None, auto=True):
+            # a candidate seen for the first time (the probe's untimed first-touch launch) is primed and registered for as long
+            # as the probe holds it (`keeper`: the probe's own tensor; a loser's entry goes with it)
+            if auto and primed and not placement.is_primed(obs.data_ptr(), nbytes, N, B, pitch):
+                prime(obs, keeper)
             out = dict(small, obs=obs)
             if closed:
                 self.rollout_policy(K, per_layer, out=out, obs_every=obs_every)
@@ -961,13 +987,32 @@ class MultiAgentEnv(object):
         modes = (self.discrete_action_input, self.discrete_action_space, self.force_discrete_action)
         self.discrete_action_input = self.discrete_action_space = self.force_discrete_action = False
         try:
-            placed = placement.probe_arena(slots * B * pitch, lambda flat: time_fn(shaped(flat)), dev, trials=candidates,
-                                           mem_fraction=mem_fraction, max_arena_bytes=max_arena_bytes, escalate=escalate)
-            if placed is not None:
+            placed = None if not probe else \
+                placement.probe_arena(slots * B * pitch, lambda flat: time_fn(shaped(flat), flat), dev, trials=candidates,
+                                      mem_fraction=mem_fraction, max_arena_bytes=max_arena_bytes, escalate=escalate)
+            if not probe:
+                obs, report = alloc(), {"tried": 1, "probed": False}
+            elif placed is not None:
                 flat, report, arena = placed
                 obs = shaped(flat)
             else:
                 obs, report = placement.probe_allocation(alloc, time_fn, nbytes, dev, candidates=candidates, mem_fraction=mem_fraction)
+            # The buffer that is kept, probed or not (a probe's winner is mapped for good by now: candidates of one arena
+            # mapping overlap, and their launches wrote other rows here, so zeros once more).  Then the flagged launch
+            # against the unflagged one on this very buffer: the skip pays where the store stream is the bound (27 x 4096 x 20
+            # placed: 10.9 against 11.9 us/step), not where the writer waves' own instruction chain is (four writer waves: a
+            # buffer the Infinity Cache holds 14.1 against 11.8, an ordinary allocation 14.6 against 13.0).  The registration
+            # is kept only where the flagged launch is at least 2 % faster - a tie is decided the same way every time
+            # (profiles/r06_zero_skip.md).
+            placement.drop_primed(obs.data_ptr(), nbytes)
+            if primed:
+                stream = torch.cuda.current_stream(dev)
+                prime(obs)
+                t_on = placement._time_launch(lambda o: time_fn(o, auto=False), obs, stream, 5)
+                placement.drop_primed(obs.data_ptr(), nbytes)
+                t_off = placement._time_launch(lambda o: time_fn(o, auto=False), obs, stream, 5)
+                primed = t_on <= 0.98 * t_off
+                report["zero_primed"] = {"kept": primed, "flagged_ms": round(t_on, 4), "unflagged_ms": round(t_off, 4)}
         finally:
             # whatever happened inside the probe (out of memory, a failed launch): the env is usable and unchanged afterwards
             self._placing = False
@@ -975,13 +1020,28 @@ class MultiAgentEnv(object):
             self._roll_launchers.clear()               # bindings made on the candidates keep them alive: drop them,
             torch.cuda.empty_cache()                   # then hand the losers back to the driver
             self._restore(snap)
-        report["buffer_MB"] = round(nbytes / 1e6, 1)
+        if probe:
+            report["buffer_MB"] = round(nbytes / 1e6, 1)
         if report.get("probed") and D == 6 * N:
             alg = _native.step_hd_bytes(N) * B * K
             report["kept_GBps"] = round(alg / (report["kept_ms"] * 1e-3) / 1e9, 1)
             report["worst_GBps"] = round(alg / (report["worst_ms"] * 1e-3) / 1e9, 1)
         self.placement = report
-        return dict(small, obs=obs)
+        return dict(small, obs=prime(obs))
+
+    def prime_rollout_buffers(self, out):
+        """Fills out["obs"] (fp32, [slots, B, N, 6N], contiguous or with a padded env pitch) with zeros and registers it as
+        zero-primed again (`alloc_rollout_buffers`): for a caller that has written into the buffer, or launched a world with a
+        non-silent agent into it (which drops the registration).  Returns `out`."""
+        obs = out["obs"]
+        B, N = self.num_envs, self.num_agents
+        if not getattr(self.scenario, "obs_zero_block", False) or obs.dtype != torch.float32 or obs.dim() != 4 \
+                or tuple(obs.shape[1:]) != (B, N, 6 * N):
+            raise ValueError("prime_rollout_buffers: out['obs'] must be a float32 [slots, %d, %d, %d] tensor of formation_hd_env" % (B, N, 6 * N))
+        pitch = self.scenario.obs_env_pitch(obs, N) or 6 * N * N
+        obs.zero_()
+        placement.register_primed(obs, obs.data_ptr(), ((obs.shape[0] * B - 1) * pitch + 6 * N * N) * 4, N, B, pitch)
+        return out
 
     def _policy_per_layer(self):
         """Agents per layer of the built-in controller's hierarchy for this agent count (N = per^L): 3 where it fits (the

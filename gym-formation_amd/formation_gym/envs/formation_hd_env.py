@@ -34,6 +34,10 @@ class _Plan(object):
 
 
 class Scenario(BaseScenario):
+    # observation rows carry a communication block that is zero for silent agents: the env's rollout buffers are filled
+    # with zeros once and registered (placement.register_primed), see `params`
+    obs_zero_block = True
+
     def make_world(self, num_agents=3, episode_length=100, num_envs=1, device=None):
         world = World(num_envs=num_envs, device=device)
         world.world_length = episode_length
@@ -122,6 +126,11 @@ class Scenario(BaseScenario):
         return 6 * len(world.agents)
 
     def params(self, world, auto_reset=False, rng_offset=0, obs=None, scripted_ok=False):
+        """The FgParams of a launch of this world into `obs`.  NOT free of side effects where `obs` touches a zero-primed
+        buffer (placement.register_primed): params are built for a launch that is about to write `obs`, so a non-silent world,
+        a 16-bit `obs` or a view that does not start on a step slot of the registered buffer DROPS that buffer's registration -
+        also when the caller only describes the launch (`fg_describe_launch`) or never runs it.  That errs on the safe side:
+        `env.prime_rollout_buffers(out)` registers the buffer again."""
         a0 = world.agents[0]
         p = world.native_params(collide_thresh=(a0.size + a0.size) / 2,   # :121
                                 auto_reset=auto_reset, seed=self._seed, rng_offset=rng_offset, scripted_ok=scripted_ok)
@@ -136,7 +145,27 @@ class Scenario(BaseScenario):
             p._pinned += (comm,)                          # as native_params pins its own: whoever keeps p keeps the tensor
         if obs is not None and obs.numel() and placement.is_placed(obs.data_ptr()):
             p.obs_placed = 1                              # a buffer of chunks spread over the device memory: more writer waves pay
+        # (host cost: params are built per launch on the unbound paths - nothing below runs unless a registered buffer is near)
+        if obs is None or not placement.near_primed(obs):
+            pass
+        elif p.comm_state or obs.dtype != torch.float32:
+            # this launch writes the communication block, or 16-bit rows (another layout): no longer zeros where they were
+            placement.drop_primed(obs.data_ptr(), obs.numel() * obs.element_size())
+        else:
+            # a buffer alloc_rollout_buffers made, filled with zeros once and registered: the communication blocks of
+            # silent agents still hold those zeros, and the tile writers leave their whole 128-byte lines out
+            N = len(world.agents)
+            pitch = p.obs_env_pitch or 6 * N * N
+            if placement.is_primed(obs.data_ptr(), self._obs_extent(obs, p.obs_env_pitch, N), N, world.num_envs, pitch, launch=True):
+                p.obs_zero_primed = 1
         return p
+
+    @staticmethod
+    def _obs_extent(obs, env_pitch, N):
+        """Bytes from the first to behind the last env block of an observation tensor [.., B, N, 6N] (env_pitch floats
+        apart, 0 = contiguous)."""
+        blocks = obs.numel() // (6 * N * N)
+        return ((blocks - 1) * (env_pitch or 6 * N * N) + 6 * N * N) * obs.element_size()
 
     @staticmethod
     def obs_env_pitch(obs, N):

@@ -107,6 +107,89 @@ def is_placed(address):
     return hit
 
 
+# ---- zero-primed observation buffers -----------------------------------------------------------------------------------
+# A formation_hd observation row is [v_i | p_j - p_i | communication block | ideal shape | ideal velocity]; the
+# communication block - units [N, 2N-1) of the row's 3N 8-byte units - is zero while every agent is silent, in every step of
+# every launch.  A rollout buffer the env made itself (`alloc_rollout_buffers`) is filled with zeros ONCE and registered
+# here; `Scenario.params` then tells the library (`FgParams.obs_zero_primed`), whose 16-32-agent tile writers leave out the
+# whole 128-byte lines inside that block (profiles/r06_zero_skip.md).  The lifetime rule is `is_placed`'s: an
+# entry lives exactly as long as the object that keeps the memory (a weak reference), so a recycled address is never taken
+# for a primed one.  `primed_generation()` changes with every registration and drop: launches bound with the flag are keyed
+# by it (environment._run_rollout).  A keeper that dies is noticed only at the next look at the registry (`_primed_alive`),
+# so the generation lags behind it; that is safe only because a bound launcher keeps the tensors it was bound to - and with
+# them the memory, still holding its zeros - alive: a binding that stops pinning its buffers must advance the generation.
+_primed = []               # [weakref to the tensor that keeps the buffer, base address, bytes, N, B, env pitch in floats]
+_primed_gen = [0]
+
+
+def primed_generation():
+    return _primed_gen[0]
+
+
+def _primed_alive():
+    alive = [e for e in _primed if e[0]() is not None]
+    if len(alive) != len(_primed):
+        _primed[:] = alive
+        _primed_gen[0] += 1
+    return _primed
+
+
+def register_primed(keeper, address, nbytes, N, B, pitch):
+    """Registers [address, address + nbytes) as a zero-primed fp32 observation buffer of [slots][B] env blocks of N agents,
+    `pitch` floats apart, for as long as `keeper` (a tensor over that memory) lives.  The CALLER has filled it with zeros.
+    Entries that overlap the range are dropped first."""
+    import weakref
+    drop_primed(address, nbytes)
+    _primed.append([weakref.ref(keeper), int(address), int(nbytes), int(N), int(B), int(pitch)])
+    _primed_gen[0] += 1
+
+
+def drop_primed(address, nbytes=1):
+    """Forgets every registered buffer that overlaps [address, address + nbytes): something other than zeros may have been
+    written into its communication blocks.  Returns whether there was one."""
+    lo, hi = int(address), int(address) + max(1, int(nbytes))
+    keep = [e for e in _primed_alive() if e[1] + e[2] <= lo or hi <= e[1]]
+    hit = len(keep) != len(_primed)
+    if hit:
+        _primed[:] = keep
+        _primed_gen[0] += 1
+    return hit
+
+
+def near_primed(obs):
+    """Cheap pre-check for `Scenario.params`: can this tensor touch a registered buffer at all?  No registry, no cost; else one
+    address comparison per entry, with twice the tensor's dense size as its extent (a padded env pitch is never that much
+    larger).  A dead entry may answer yes: the full check prunes it."""
+    if not _primed:
+        return False
+    n = obs.numel()
+    if not n:
+        return False
+    lo = obs.data_ptr()
+    hi = lo + 2 * n * obs.element_size()
+    for e in _primed:
+        if e[1] < hi and lo < e[1] + e[2]:
+            return True
+    return False
+
+
+def is_primed(address, nbytes, N, B, pitch, launch=False):
+    """Do the `nbytes` at this device address lie inside a registered zero-primed buffer of the same N, B and env pitch
+    (floats), a whole number of step slots (B env pitches) from its base?  launch=True: the caller is about to write
+    observation rows there - a range that touches a registered buffer in any OTHER way (another N, B or pitch, mid-slot,
+    partly outside) puts rows where that buffer's launches expect zeros, so its registration is dropped."""
+    address, end = int(address), int(address) + int(nbytes)
+    for ref, base, size, n, b, p in list(_primed_alive()):
+        if end <= base or base + size <= address:
+            continue
+        if base <= address and end <= base + size and (n, b, p) == (int(N), int(B), int(pitch)) \
+                and (address - base) % (4 * b * p) == 0:
+            return True
+        if launch:
+            drop_primed(base, size)
+    return False
+
+
 class _Raw(object):
     """A device address range as something torch.as_tensor understands.  torch keeps this object alive for as long as
     the tensor's storage lives (any view of it included), and the object keeps the arena: a placed buffer's memory is

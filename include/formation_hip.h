@@ -166,7 +166,15 @@ typedef struct FgParams {
                                 over the device's memory.  Such a buffer takes the store stream of MORE writer
                                 waves: the 27-agent rollout then runs 8 paced writer waves per workgroup (11.7 us/step at
                                 27 x 4096) where 4 are best on an ordinary allocation (12.9 there, 13.2-14.4 with 8).  0 = unknown */
-    int32_t reserved0;
+    int32_t obs_zero_primed;   /* promise: 1 = in the fp32 observation buffer of this launch, units [N, 2N-1) of every row of every
+                                env block it writes - the communication block, zeros while comm_state is NULL - ALREADY hold
+                                zeros (the caller filled the buffer with zeros once, and since then only launches without
+                                comm_state have written it).  The 16-32-agent tile writers of fg_rollout_hd /
+                                fg_rollout_hd_policy then leave out the stores of whole 128-byte lines (by device address)
+                                that lie wholly inside one row's block: 13.6 % of the observation bytes at 27 agents.  Every
+                                other kernel, and any launch with comm_state, ignores it and writes everything.  The buffer's
+                                contents after the launch are the same either way.  0 = no promise (was reserved0: a caller that
+                                zero-fills FgParams keeps today's behaviour). */
 } FgParams;
 #define FG_AGENT_PROPS 8
 #define FG_AGENT_IMMOVABLE 1
