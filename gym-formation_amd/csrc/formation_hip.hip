@@ -25,7 +25,7 @@
 // Source layout: fg_common.hpp (arguments, LDS layout, reductions, RNG, World options),
 // fg_pair_loops.hpp, fg_obs_writers.hpp, fg_step_kernel.hpp, fg_rollout_kernels.hpp,
 // fg_policy_kernels.hpp (the reference's demo controller), fg_aux_kernels.hpp (resets) with fg_scn_kernel.hpp (landmark
-// scenarios); this file holds the host side: variant tables, dispatch and the extern "C" entry
+// scenarios), fg_returns_kernel.hpp (returns of candidate action sequences from the current state); this file holds the host side: variant tables, dispatch and the extern "C" entry
 // points.  formation_hip_f64.hip builds the step, rollout and scenario kernels' source in double (tests only).
 
 #include <atomic>
@@ -45,6 +45,7 @@
 #include "fg_policy_kernels.hpp"
 #include "fg_actor_rollout_kernel.hpp"
 #include "fg_scn_lane_actor_kernel.hpp"
+#include "fg_returns_kernel.hpp"
 
 namespace fg {
 
@@ -1440,6 +1441,36 @@ static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act
     return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_scenario_actor: (scenario, N, landmarks, obstacles, num_obs) is not one of the reference shapes%s");
 }
 
+// ---- discounted returns of C candidate action sequences from the current state (fg_returns_kernel.hpp) ----
+// the checks fg_rollout_hd_returns and its dry run share (no pointer, no device): FG_OK, or the status of the first that fails
+static int returns_check(const FgParams* params, int B, int N, int K, int C, float gamma) {
+    const int rc = check_params(params);
+    if (rc) return rc;
+    if (B < 0 || K < 1 || C < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: B >= 0, K >= 1 and C >= 1 required%s");
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: gamma must be a finite number in [0, 1]%s");
+    if (world_options_set(*params))
+        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: World options, per-agent properties and communication are not supported%s");
+    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_returns: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
+    if ((long long)B * C > 0x7fffffffLL) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: B * C must be below 2^31%s");
+    return FG_OK;
+}
+// One geometry per agent count (fg_returns_kernel.hpp): the lane group of step_kernel and the rollout producers, 256 threads
+template <int NC, int G>
+static int launch_returns_v(const ReturnsArgs& a, hipStream_t st) {
+    constexpr int T = 256, PW = T / G;
+    constexpr int lds = returns_lds_bytes<NC, G, T>();
+    const unsigned grid = (unsigned)(((long long)a.B * a.C + PW - 1) / PW);
+    if (describe("returns_kernel<%d,%d,%d> grid %u block %d lds %d; ", NC, G, T, grid, T, lds)) return FG_OK;
+    return launch<&returns_kernel<NC, G, T>>(grid, T, lds, st, "returns launch failed: %s", a);
+}
+static int returns_dispatch(const ReturnsArgs& a, int N, hipStream_t st) {
+#define FG_RETURNS(NN, G) if (N == NN) return launch_returns_v<NN, G>(a, st);
+    FG_RETURNS(3, 4) FG_RETURNS(4, 4) FG_RETURNS(8, 8) FG_RETURNS(9, 16) FG_RETURNS(16, 16)
+    FG_RETURNS(25, 32) FG_RETURNS(27, 32) FG_RETURNS(32, 32)
+#undef FG_RETURNS
+    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_returns: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");   // (unreachable after returns_check)
+}
+
 extern "C" {
 
 int fg_abi_version(void) { return FG_ABI_VERSION; }
@@ -2488,6 +2519,40 @@ int fg_describe_obs16_launch(const FgParams* params, int obs_format, int B, int 
     if ((rc = hd_args(&a, params, B, N, K, obs_every, 1, 1))) return rc;
     const DescribeScope describing(out, out_len);
     return obs16_dispatch(a, obs_format, per_layer, nullptr);
+}
+
+int fg_rollout_hd_returns(const FgParams* params, int B, int N, int K, int C, float gamma,
+                          const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                          const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                          const float* act, float* ret, float* indiv_ret, int32_t* steps, void* stream) {
+    const int rc = returns_check(params, B, N, K, C, gamma);
+    if (rc) return rc;
+    if (B == 0) return FG_OK;                         // an empty batch: nothing to do
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel || !step || !act || !ret)
+        return null_pointer("fg_rollout_hd_returns");
+    if ((((uintptr_t)act | (uintptr_t)ideal_shape | (uintptr_t)ideal_vel) & 7u) ||
+        (((uintptr_t)pos_x | (uintptr_t)pos_y | (uintptr_t)vel_x | (uintptr_t)vel_y | (uintptr_t)step | (uintptr_t)ret |
+          (uintptr_t)indiv_ret | (uintptr_t)steps) & 3u))
+        return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_returns: act/ideal_shape/ideal_vel must be 8-byte, the other buffers 4-byte aligned%s");
+    const DeviceGuard device_guard(stream, pos_x);
+    ReturnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = *params; a.B = B; a.K = K; a.C = C; a.gamma = gamma;
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
+    a.act = act; a.ret = ret; a.indiv_ret = indiv_ret; a.steps = steps;
+    return returns_dispatch(a, N, (hipStream_t)stream);
+}
+
+int fg_describe_returns_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap) {
+    if (!text || cap < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_returns_launch: out buffer required%s");
+    text[0] = 0;
+    const int rc = returns_check(params, B, N, K, C, 1.0f);
+    if (rc || B == 0) return rc;                      // an empty batch: FG_OK and no launch to name
+    ReturnsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = *params; a.B = B; a.K = K; a.C = C; a.gamma = 1.0f;
+    const DescribeScope describing(text, cap);
+    return returns_dispatch(a, N, nullptr);
 }
 
 }  // extern "C"

@@ -305,6 +305,8 @@ SIGNATURES = {
                                   + [_I, _P]),
     "fg_describe_scenario_actor_launch": (_I, [_PP, ctypes.POINTER(FgScenario), ctypes.POINTER(FgActor), _P, _I, _I, _I, _I,
                                                ctypes.c_char_p, _I]),
+    "fg_rollout_hd_returns": (_I, [_PP, _I, _I, _I, _I, ctypes.c_float] + [_P] * 12),
+    "fg_describe_returns_launch": (_I, [_PP, _I, _I, _I, _I, ctypes.c_char_p, _I]),
 }
 
 _lib = None

@@ -171,7 +171,8 @@ class MultiAgentEnv(object):
 
     def rollout(self, action_seq, out=None, obs_every=1, obs_dtype=None):
         """K consecutive `step` calls in ONE launch (`fg_rollout_hd`): for policies that hand over a
-        whole action sequence (open-loop / pre-staged random policies, model-predictive candidates).
+        whole action sequence (open-loop / pre-staged random policies; for model-predictive candidates - the returns of C
+        sequences from the SAME state, the env left where it was - see `rollout_returns`).
         `action_seq` is a [K, B, N, 2] tensor of raw continuous actions.  Results are bit-identical to
         K calls of `step` (device auto-reset included, when `self.auto_reset` is set) and come back
         stacked along a leading step axis:
@@ -196,6 +197,12 @@ class MultiAgentEnv(object):
         if fmt and (len(action_seq) < 2 or self.obs_path(obs_dtype) == "cast"):
             return self._rollout_cast(obs_dtype, out, len(action_seq), int(obs_every), False,
                                       lambda o: self.rollout(action_seq, o, obs_every))
+        out, first = self._rollout_into(action_seq, out, obs_every, obs_dtype)
+        return self._rollout_result(out, rew=first)
+
+    def _rollout_into(self, action_seq, out, obs_every, obs_dtype=None):
+        """`rollout` up to its result: (the `out` the K steps were written to - obs, reward (shared), indiv, done -, the reward
+        `rollout` returns where it is not out's: a Scenario file's first_reward of the host-paced loop, else None)."""
         roll = getattr(self.scenario, "rollout_batch", None)
         if roll is None or self.post_step_callback is not None:
             # no multi-step launch (a reference-style Scenario file: its callbacks run on the host), or a post_step_callback
@@ -217,7 +224,140 @@ class MultiAgentEnv(object):
         out, own_buffers = self._rollout_out(want, out, K, obs_every, False, obs_dtype)
         self._run_rollout(("roll", act.data_ptr(), K), want, out, own_buffers, K, obs_every, obs_dtype,
                           getattr(self.scenario, "bind_rollout", None), roll, (act,))
-        return self._rollout_result(out)
+        return out, None
+
+    # ---- returns of candidate action sequences from the current state ------------------------------------------------------
+    RETURNS_FUSED_N = (3, 4, 8, 9, 16, 25, 27, 32)        # the agent counts returns_kernel is built for (fg_returns_kernel.hpp)
+
+    def returns_path(self):
+        """'fused' when `rollout_returns` runs as ONE launch that leaves the env untouched (`fg_rollout_hd_returns`), 'replay'
+        when it runs the same contract through the existing launches (snapshot, one `rollout` per candidate, restore).
+        'fused' needs a scenario with `bind_rollout_returns` (formation_hd_env), one of its agent counts (3, 4, 8, 9, 16, 25,
+        27, 32), no World options (walls, u_noise, max_speed, accel, per-agent properties, communication: the predicate of
+        `_resolve_actor`), silent agents, no scripted agents and no post_step_callback.  Decided without touching the device."""
+        sc = self.scenario
+        if getattr(sc, "bind_rollout_returns", None) is None or self.post_step_callback is not None \
+                or getattr(self, "_returns_replay_only", False):      # (the private switch: tests hold the replay to the fused bits)
+            return "replay"
+        if self.num_agents not in self.RETURNS_FUSED_N or self.world.any_non_silent():
+            return "replay"
+        try:
+            p = sc.params(self.world)
+        except NotImplementedError:                        # scripted agents: only the World API drives them
+            return "replay"
+        if p.num_walls > 0 or p.u_noise > 0 or p.max_speed > 0 or p.accel > 0 or p.agent_props or p.comm_state:
+            return "replay"
+        return "fused"
+
+    def _check_returns_actions(self, action_seqs):
+        """`rollout_returns`' candidates: [C, K] in front of `rollout`'s per-step shape in the env's action mode, C >= 1, K >= 1.
+        Returns (mode, the dtype the launches read)."""
+        B, N = self.num_envs, self.num_agents
+        mode = self._action_mode()
+        tail, dtype = {0: ((B, N, 2), torch.float32),
+                       _native.FG_ACT_ONEHOT5: ((B, N, 5), torch.float32),
+                       _native.FG_ACT_INDEX: ((B, N), torch.int32),
+                       _native.FG_ACT_ARGMAX: ((B, N, 2), torch.float32)}[mode]
+        if not torch.is_tensor(action_seqs) or action_seqs.dim() != len(tail) + 2 or tuple(action_seqs.shape[2:]) != tail \
+                or action_seqs.shape[0] < 1 or action_seqs.shape[1] < 1:
+            raise ValueError("action_seqs must be a tensor of shape [C, K%s] with C >= 1 and K >= 1"
+                             % "".join(", %d" % d for d in tail))
+        return mode, dtype
+
+    def _returns_actions(self, action_seqs):
+        """The checked candidates as raw u [C, K, B, N, 2], fp32 contiguous on the env's device.  In a discrete action mode they
+        are decoded in ONE `fg_decode_actions` launch over all C K B N entries (force_discrete_action: the caller's array is
+        rewritten as the one-hot, as `rollout` does)."""
+        mode, dtype = self._check_returns_actions(action_seqs)
+        B, N = self.num_envs, self.num_agents
+        dev = self._act.device
+        src = action_seqs
+        if src.dtype != dtype or src.device != dev or not src.is_contiguous():
+            src = src.to(device=dev, dtype=dtype).contiguous()
+        if not mode:
+            return src
+        C, K = int(src.shape[0]), int(src.shape[1])
+        u = torch.empty((C, K, B, N, 2), dtype=torch.float32, device=dev)
+        _native.check(_native.load().fg_decode_actions(mode, C * K * B * N, src.data_ptr(), u.data_ptr(),
+                                                       _native.current_stream(dev)))
+        if mode == _native.FG_ACT_ARGMAX and src is not action_seqs:
+            action_seqs.copy_(src)                     # the reference overwrites the caller's array (:213-215)
+        return u
+
+    def rollout_returns(self, action_seqs, gamma=1.0):
+        """Score C candidate action sequences from the CURRENT state and leave the env where it was: what a planner (random
+        shooting, CEM, MPPI) or a trainer that weighs alternatives asks of the simulator.  `action_seqs` is [C, K, B, N, 2]
+        (each `action_seqs[c]` a valid argument of `rollout`; in the discrete action modes `rollout`'s per-step shape behind
+        the leading C), converted to fp32 contiguous on the env's device like `rollout`'s.  For every candidate c and env b
+        the K steps are exactly those `rollout(action_seqs[c])` runs with `auto_reset` off, from env b's current state; with
+        their shared rewards, individual rewards and done flags r_k,
+            d_0 = 1, d_{k+1} = d_k * gamma;   R_k = R_{k-1} + d_k * r_k   for k < steps[b]          (R_{-1} = 0)
+        in fp32, every product and every sum rounded on its own.  A step counts while no earlier step of this call has set the
+        done flag: the step that sets it counts, nothing after it does, and no reset is drawn -
+        steps[b] = min(K, max(1, world_length - step_count[b])), the same for every candidate.
+        Returns (returns, info): returns [C, B, N] fp32, the recurrence on the shared reward when `shared_reward`, else on the
+        individual one (the choice `rollout` makes); info = {'individual_return': [C, B, N] fp32, 'steps': [B] int32}.  Fresh
+        tensors that alias nothing.
+        NOTHING OF THE ENV CHANGES: state, step counters, ideal shape and velocity, the RNG offset (or device counter),
+        `current_step`, `world.world_step`, `auto_reset`, the env-owned rollout buffers and their zero-primed registration.
+        `returns_path()` tells how.  'fused': ONE launch (`fg_rollout_hd_returns`) that reads the state and writes only the
+        results - a few floats per (candidate, env), no observation, no per-step reward.  'replay': `_snapshot()`, then per
+        candidate `_restore` and `rollout(action_seqs[c], out=False, obs_every=K)` with `auto_reset` off, the recurrence in
+        torch fp32 ops on its outputs, and in a `finally` `_restore` and the old `auto_reset` - every scenario, agent count and
+        World option, and on a fused shape the fused launch's bits.  With motor noise (`u_noise`) every candidate starts from the same RNG offset:
+        the candidates are compared under common random numbers.
+        ValueError: a wrong shape, C < 1 or K < 1, a `gamma` that is not a finite number in [0, 1]."""
+        if isinstance(gamma, bool) or not isinstance(gamma, numbers.Real) or not (0.0 <= float(gamma) <= 1.0):
+            raise ValueError("gamma must be a finite number in [0, 1]")
+        gamma = float(gamma)
+        if self.returns_path() == "replay":
+            return self._returns_by_replay(action_seqs, gamma)
+        act = self._returns_actions(action_seqs)
+        C, K = int(act.shape[0]), int(act.shape[1])
+        B, N = self.num_envs, self.num_agents
+        dev = self._act.device
+        out = dict(ret=torch.empty((C, B, N), dtype=torch.float32, device=dev),
+                   indiv=torch.empty((C, B, N), dtype=torch.float32, device=dev),
+                   steps=torch.empty((B,), dtype=torch.int32, device=dev))
+        # fresh results per call: nothing to key a cached binding on, so the launch is bound and made at once
+        self.scenario.bind_rollout_returns(self.world, act, out, gamma)(0)
+        return (out["ret"] if self.shared_reward else out["indiv"]), {"individual_return": out["indiv"], "steps": out["steps"]}
+
+    def _returns_by_replay(self, action_seqs, gamma):
+        """`rollout_returns` through the existing launches (see there)."""
+        self._check_returns_actions(action_seqs)
+        C, K = int(action_seqs.shape[0]), int(action_seqs.shape[1])
+        B, N = self.num_envs, self.num_agents
+        dev = self._act.device
+        ret = torch.empty((C, B, N), dtype=torch.float32, device=dev)
+        indiv = torch.empty((C, B, N), dtype=torch.float32, device=dev)
+        steps = torch.zeros((B,), dtype=torch.int32, device=dev)
+        g = torch.tensor(gamma, dtype=torch.float32, device=dev)
+        snap, auto_reset = self._snapshot(), self.auto_reset
+        self.auto_reset = False
+        try:
+            for c in range(C):
+                self._restore(snap)
+                # `rollout(action_seqs[c], out=False)` up to its out dict, which has the shared reward whatever `shared_reward`
+                # says; one observation block, at the last step
+                out = self._rollout_into(action_seqs[c], False, K)[0]
+                rew, own, done = out["reward"], out["indiv"], out["done"][:, :, 0].to(torch.int32)   # the done flag is the env's
+                counts = torch.cumsum(done, 0) - done == 0      # [K, B]: a step counts while no EARLIER step has set the flag
+                d = torch.ones((), dtype=torch.float32, device=dev)
+                r_sh = torch.zeros((B, N), dtype=torch.float32, device=dev)
+                r_own = torch.zeros((B, N), dtype=torch.float32, device=dev)
+                for k in range(K):
+                    m = counts[k][:, None]
+                    r_sh = torch.where(m, r_sh + d * rew[k], r_sh)
+                    r_own = torch.where(m, r_own + d * own[k], r_own)
+                    d = d * g
+                ret[c], indiv[c] = r_sh, r_own
+                if c == 0:
+                    steps.copy_(counts.sum(0).to(torch.int32))
+        finally:
+            self._restore(snap)
+            self.auto_reset = auto_reset
+        return (ret if self.shared_reward else indiv), {"individual_return": indiv, "steps": steps}
 
     # ---- the one path of the three K-step launches: rollout, rollout_policy, rollout_actor --------------------------------
     @staticmethod
@@ -326,7 +466,7 @@ class MultiAgentEnv(object):
 
     def _rollout_by_steps(self, action_seq, out, obs_every):
         """`rollout` as K calls of `step` (host-paced: one launch - and whatever the scenario / the post_step_callback does on
-        the host - per step), results stacked like `rollout`'s."""
+        the host - per step), results stacked like `rollout`'s, as `_rollout_into` returns them."""
         K, obs_every = self._check_steps(len(action_seq), obs_every)
         dev = self._act.device
         want = self._rollout_shapes(K, obs_every)
@@ -351,7 +491,7 @@ class MultiAgentEnv(object):
                 first[k].copy_(r[..., 0])
             if (k + 1) % obs_every == 0:
                 out["obs"][k // obs_every].copy_(o)
-        return self._rollout_result(out, rew=first)      # not shared: what `step` returned (a Scenario file's first_reward)
+        return out, first                                # not shared: what `step` returned (a Scenario file's first_reward)
 
     def _step_loop(self, K, obs_every, act_fn, after_step=None):
         """The host-paced closed loop, K x (act = act_fn(obs, k); obs, ... = step(act); after_step(done)), from the env's

@@ -452,6 +452,20 @@ class Scenario(BaseScenario):
             + self._out_ptrs(out) + (int(obs_every), _native.current_stream(world.device))
         return _native.bind_launch(fn, p, *args, keep=(act_seq, out))
 
+    def bind_rollout_returns(self, world, act_seqs, out, gamma=1.0):
+        """The discounted returns of C candidate action sequences from the current state (`fg_rollout_hd_returns`), every
+        pointer and the FgParams struct resolved once: returns `launch(rng_offset)` (the offset is ignored: the launch draws
+        nothing).  act_seqs [C,K,B,N,2] raw actions; out["ret"] / out["indiv"] [C,B,N] fp32 and out["steps"] [B] int32 receive
+        the shared and the individual return and the counted steps.  The launch reads the world's state and writes only `out`."""
+        lib = _native.load()
+        p = self.params(world)                            # no observation buffer: nothing of the zero-primed registry is touched
+        args = (world.num_envs, len(world.agents), int(act_seqs.shape[1]), int(act_seqs.shape[0]), float(gamma),
+                world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(), world.step_count.data_ptr(), act_seqs.data_ptr(),
+                out["ret"].data_ptr(), _native.ptr(out.get("indiv")), _native.ptr(out.get("steps")),
+                _native.current_stream(world.device))
+        return _native.bind_launch(lib.fg_rollout_hd_returns, p, *args, keep=(act_seqs, out))
+
     def upload_mt_streams(self, world):
         """Copy every env's legacy MT19937 state (RandomState(seed + 1000 b), at its CURRENT
         position) to the device; from here on `reset_mt` continues those streams on the GPU."""

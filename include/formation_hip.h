@@ -912,6 +912,32 @@ int fg_rollout_scenario_actor(const FgParams* params, const FgScenario* scenario
 int fg_describe_scenario_actor_launch(const FgParams* params, const FgScenario* scenario, const FgActor* actor,
                                       const float* log_std, int B, int N, int K, int obs_every, char* out, int out_len);
 
+/* Discounted returns of C candidate action sequences, each run for K steps from the CURRENT state of every env, in ONE launch
+ * (returns_kernel<N,G,T>): what a planner (random shooting, CEM, MPPI) needs from the simulator.  For every (candidate c, env b)
+ * the launch runs the K steps fg_rollout_hd runs on act[c] ([K][B][N][2]) with auto-reset off - the same World.step and reward,
+ * bit for bit - from env b's positions, velocities, ideal shape, ideal velocity and step counter, and keeps, per agent i,
+ *     d_0 = 1, d_{k+1} = d_k * gamma;   R_k = R_{k-1} + d_k * r_k   for k < steps[b],   R_{-1} = 0
+ * in fp32 with every product and every sum rounded on its own (no fused multiply-add): ret [C][B][N] with r = the shared
+ * reward (fg_rollout_hd's reward_seq), indiv_ret [C][B][N] (NULL: not written) with r = the individual one (indiv_seq).  A step
+ * counts while no earlier step of the launch has set the done flag; the step that sets it counts, nothing after it does:
+ *     steps[b] = min(K, max(1, world_length - step[b]))          ([B] int32, NULL: not written; the same for every candidate)
+ * EVERY STATE POINTER IS const AND NEVER WRITTEN: state, step counters, ideal shape and velocity stay as they are, no reset is
+ * drawn and no RNG counter is read or advanced.  params->auto_reset, rng_offset and rng_offset_dev are ignored.
+ * Buffers: fp32 / int32 in DEVICE memory; act, ideal_shape and ideal_vel 8-byte aligned, the others 4-byte aligned.
+ * Checks in this order, each with one fixed message: params (NULL, its values); FG_ERR_BAD_ARG for B < 0, K < 1 or C < 1, for a
+ * gamma that is not a finite number in [0, 1], and for World options, communication or per-agent properties in params (walls,
+ * u_noise, max_speed, accel, agent_props, comm_state: not supported, there is no fall-back inside the library);
+ * FG_ERR_UNSUPPORTED_N for an N other than 3, 4, 8, 9, 16, 25, 27, 32; FG_ERR_BAD_ARG for B * C >= 2^31; B == 0 returns FG_OK
+ * without a launch; then FG_ERR_BAD_ARG for a NULL required pointer and FG_ERR_ALIGNMENT. */
+int fg_rollout_hd_returns(const FgParams* params, int B, int N, int K, int C, float gamma,
+                          const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                          const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                          const float* act, float* ret, float* indiv_ret, int32_t* steps, void* stream);
+/* Dry run of fg_rollout_hd_returns: the same checks and status codes (those on the buffers and on gamma apart), then
+ * "returns_kernel<N,G,T> grid W block T lds L; " in `text` (cap bytes): G lanes per (candidate, env) pair, T / G pairs per
+ * workgroup, W = ceil(B C / (T / G)) workgroups.  B == 0: FG_OK and an empty text.  Touches no device. */
+int fg_describe_returns_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap);
+
 #ifdef __cplusplus
 }
 #endif
