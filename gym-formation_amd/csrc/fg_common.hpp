@@ -60,6 +60,11 @@ FG_DEV double hw_sqrt(double a) { return sqrt(a); }
 FG_DEV double hw_rcp(double a) { return 1.0 / a; }
 FG_DEV double hw_log(double a) { return log(a); }
 FG_DEV double hw_exp(double a) { return exp(a); }
+// a product / a sum rounded on its own: never contracted into an fma with a neighbouring operation (returns_kernel's recurrence)
+FG_DEV float mul_rn_(float a, float b) { return __fmul_rn(a, b); }
+FG_DEV float add_rn_(float a, float b) { return __fadd_rn(a, b); }
+FG_DEV double mul_rn_(double a, double b) { return __dmul_rn(a, b); }
+FG_DEV double add_rn_(double a, double b) { return __dadd_rn(a, b); }
 
 // World / scenario constants as the kernels read them: the C ABI's FgParams (fp32 fields), or the same names in fp64
 // for the parity build (0.1f is not the reference's 0.1)

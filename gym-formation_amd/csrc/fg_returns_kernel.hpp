@@ -1,5 +1,6 @@
 // fg_returns_kernel.hpp - Discounted returns of C candidate action sequences from the CURRENT state (fg_rollout_hd_returns).
-// Part of libformation_hip (gfx950); included by formation_hip.hip, one translation unit.
+// Part of libformation_hip (gfx950); included by formation_hip.hip, one translation unit - and, with real = double, by the
+// tests' parity build formation_hip_f64.hip (fg64_rollout_hd_returns: the same geometry per agent count).
 #ifndef FG_RETURNS_KERNEL_HPP_
 #define FG_RETURNS_KERNEL_HPP_
 
@@ -45,8 +46,15 @@ struct ReturnsArgs {
 // written for (rollout_kernel's small workgroups): the compiler then takes 66 ... 100 (3 / 4 agents 68 / 66, 8: 82, 9: 100,
 // 16: 88, 25 / 27 / 32: 80), which is 7 ... 4 resident waves per SIMD to cover one wave's chain.  Asking for more costs
 // scratch: a minimum of 6 spills 18 registers at 9 agents and 8 at 16, a budget of 64 (8 waves) 14 ... 28 in every instantiation.
+// The budget was sized for floats: the fp64 parity build (tests only) spills 45 ... 142 registers under it, so the attribute is
+// the product's alone and the doubles get what __launch_bounds__ allows.
+#if FG_F64
+#define FG_RETURNS_OCCUPANCY
+#else
+#define FG_RETURNS_OCCUPANCY __attribute__((amdgpu_waves_per_eu(4)))
+#endif
 template <int NC, int G, int T>
-__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4)))
+__global__ __launch_bounds__(T) FG_RETURNS_OCCUPANCY
 void returns_kernel(const ReturnsArgs a) {
     static_assert(G <= 64 && T % 64 == 0 && 64 % G == 0 && G >= npad(NC), "a pair lives in one wave");
     constexpr int N = NC, NP = npad(NC), PW = T / G;
@@ -96,7 +104,7 @@ void returns_kernel(const ReturnsArgs a) {
     if (valid) u_even = *act_next;
     act_next += a.K > 1 ? act_stride : 0;
 
-    real disc = 1.0f, ret_shared = 0.0f, ret_own = 0.0f;
+    real disc = (real)1, ret_shared = (real)0, ret_own = (real)0;
 
     // one step: World.step + reward of step k, then the recurrence.  The statements between the two marks are those of
     // rollout_kernel's `produce` (fg_rollout_kernels.hpp: contact force, action force, integration, reductions, reward pass,
@@ -143,10 +151,10 @@ void returns_kernel(const ReturnsArgs a) {
         // ---- end of rollout_kernel::produce's statements ----
         // R_k = R_{k-1} + d_k r_k, d_{k+1} = d_k gamma: every product and every sum rounded on its own (never an fma)
         if (k < nsteps) {
-            ret_shared = __fadd_rn(ret_shared, __fmul_rn(disc, shared));
-            ret_own = __fadd_rn(ret_own, __fmul_rn(disc, own));
+            ret_shared = add_rn_(ret_shared, mul_rn_(disc, shared));
+            ret_own = add_rn_(ret_own, mul_rn_(disc, own));
         }
-        disc = __fmul_rn(disc, a.gamma);
+        disc = mul_rn_(disc, a.gamma);
         if (valid) { QX[i] = p.x; QY[i] = p.y; }       // next step's partners
     };
 

@@ -13,6 +13,8 @@
 // fg64_rollout_scenario is the run-time-count kernel of the four landmark scenarios (fg_scn_kernel.hpp: scn_kernel<G, T> at every
 // lane-group width 4 ... 64 and every whole-workgroup size 128 ... 1024, both observation writers, the K-loop, per-agent tables and
 // walls), free-running on the 14 landmark fixtures (tests/test_gpu_f64_scenarios.py).
+// fg64_rollout_hd_returns is returns_kernel<N, G, 256> (fg_returns_kernel.hpp) at the product's lane group per agent count: the
+// discounted returns of candidate action sequences against float64 sums over the reference's steps (tests/test_gpu_f64_returns.py).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=on -DFG_F64=1 -fPIC -shared -Iinclude
 //         -o lib/libformation_hip_f64.so csrc/formation_hip_f64.hip          (no -fapprox-func: full-precision libm)
@@ -22,8 +24,21 @@
 #include "fg_step_kernel.hpp"
 #include "fg_rollout_kernels.hpp"
 #include "fg_scn_kernel.hpp"
+#include "fg_returns_kernel.hpp"
 
 namespace fg {
+
+// returns_kernel<N, G, 256> with real = double at the product's geometry (returns_dispatch, formation_hip.hip): the pair-per-wave
+// layout under test is the one that ships.  LDS is (256 / G) pairs x 6 NP doubles: 12 KB at most, inside the default limit.
+template <int NC, int G>
+static int launch_returns64(const ReturnsArgs& a, hipStream_t st) {
+    constexpr int T = 256, PW = T / G;
+    constexpr int lds = returns_lds_bytes<NC, G, T>();
+    static_assert(lds <= 64 * 1024, "the parity build stays inside the default LDS limit");
+    const unsigned grid = (unsigned)(((long long)a.B * a.C + PW - 1) / PW);
+    hipLaunchKernelGGL((returns_kernel<NC, G, T>), dim3(grid), dim3(T), lds, st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
 
 // The pipelined producer / writer rollout kernel (fg_rollout_kernels.hpp) with real = double: the SAME source as the product's
 // rollout_kernel<N, G, TP, TW, E, 0, 0, false> - producer waves, double-buffered LDS tables, the rows writer - so that the K-step
@@ -201,6 +216,34 @@ int fg64_rollout_hd(const Fg64Params* params, int B, int N, int K,
     const hipError_t err = N == 9 ? launch_roll64<9, 16, 64, 128, 4>(a, st) : N == 27 ? launch_roll64<27, 32, 128, 256, 4>(a, st)
                          : N == 81 ? launch_wide64<81, 2, 2, 128>(a, st) : launch_wide64<243, 4, 1, 256>(a, st);
     return err == hipSuccess ? 0 : -4;
+}
+
+// fg_rollout_hd_returns in fp64: the discounted returns of C candidate action sequences from the current state, ONE launch of
+// returns_kernel<N, G, 256> at the product's (N, G) table (returns_dispatch's FG_RETURNS list).  The state is read only.
+// act [C][K][B][N][2], ret / indiv_ret [C][B][N] (indiv_ret may be NULL), steps [B] (may be NULL).
+// Returns 0, -1 bad argument, -2 unsupported N, -4 HIP error; an empty batch is 0 without a launch.
+int fg64_rollout_hd_returns(const Fg64Params* params, int B, int N, int K, int C, double gamma,
+                            const double* pos_x, const double* pos_y, const double* vel_x, const double* vel_y,
+                            const double* ideal_shape, const double* ideal_vel, const int32_t* step,
+                            const double* act, double* ret, double* indiv_ret, int32_t* steps, void* stream) {
+    using namespace fg;
+    if (!params || B < 0 || K < 1 || C < 1 || !(gamma >= 0.0 && gamma <= 1.0) || (long long)B * C > 0x7fffffffLL) return -1;
+    if (N != 3 && N != 4 && N != 8 && N != 9 && N != 16 && N != 25 && N != 27 && N != 32) return -2;
+    if (B == 0) return 0;
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel || !step || !act || !ret) return -1;
+    ReturnsArgs a; memset(&a, 0, sizeof(a));
+    a.p.dt = params->dt; a.p.damping = params->damping; a.p.contact_force = params->contact_force;
+    a.p.contact_margin = params->contact_margin; a.p.sensitivity = params->sensitivity; a.p.mass = params->mass;
+    a.p.dist_min = params->dist_min; a.p.collide_thresh = params->collide_thresh; a.p.world_length = params->world_length;
+    a.B = B; a.K = K; a.C = C; a.gamma = gamma;
+    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
+    a.act = act; a.ret = ret; a.indiv_ret = indiv_ret; a.steps = steps;
+    hipStream_t st = (hipStream_t)stream;
+#define FG64_RETURNS(NN, G) if (N == NN) return launch_returns64<NN, G>(a, st);
+    FG64_RETURNS(3, 4) FG64_RETURNS(4, 4) FG64_RETURNS(8, 8) FG64_RETURNS(9, 16) FG64_RETURNS(16, 16)
+    FG64_RETURNS(25, 32) FG64_RETURNS(27, 32) FG64_RETURNS(32, 32)
+#undef FG64_RETURNS
+    return -2;
 }
 
 // The landmark scenarios' constants in double, field for field what FgScenario holds (kind: FG_SCN_BASIC ... FG_SCN_OBSTACLE)

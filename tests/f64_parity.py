@@ -56,6 +56,9 @@ def load():
         lib.fg64_rollout_scenario.restype = ctypes.c_int
         lib.fg64_rollout_scenario.argtypes = [ctypes.POINTER(Fg64Params), ctypes.POINTER(Fg64Scenario), ctypes.POINTER(Fg64Options)] + \
                                              [ctypes.c_int] * 6 + [ctypes.c_void_p] * 15
+        lib.fg64_rollout_hd_returns.restype = ctypes.c_int
+        lib.fg64_rollout_hd_returns.argtypes = [ctypes.POINTER(Fg64Params)] + [ctypes.c_int] * 4 + [ctypes.c_double] + \
+                                               [ctypes.c_void_p] * 12
         _lib = lib
     return _lib
 
@@ -306,3 +309,26 @@ def rollout64(g, params=None):
     torch.cuda.synchronize()
     return dict(pos=env.pos(), vel=env.vel(), obs=obs.cpu().numpy(), reward=rew.cpu().numpy(), indiv=indiv.cpu().numpy(),
                 done=done.cpu().numpy(), step=env.step_count.cpu().numpy())
+
+
+def returns64(pos, vel, ideal_shape, ideal_vel, step, acts, gamma, params=None):
+    """ONE launch of the fp64 build of returns_kernel (fg64_rollout_hd_returns: the product's geometry per agent count) over the
+    candidates acts [C,K,B,N,2] from the state pos, vel [B,N,2], ideal_shape [B,N,2], ideal_vel [B,2], step [B].  The outputs are
+    filled with NaN / -1 before the launch.  Returns dict(ret, indiv [C,B,N] float64, steps [B] int32)."""
+    f = dict(dtype=torch.float64, device="cuda")
+    acts = np.ascontiguousarray(np.asarray(acts, dtype=np.float64))
+    C, K, B, N = acts.shape[:4]
+    assert acts.shape == (C, K, B, N, 2)
+    env = Env64(pos, vel, ideal_shape, ideal_vel, step=step, params=params, indices=False)
+    assert (env.B, env.N) == (B, N)
+    act = torch.as_tensor(acts, **f)
+    ret = torch.full((C, B, N), float("nan"), **f)
+    indiv = torch.full((C, B, N), float("nan"), **f)
+    steps = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+    rc = load().fg64_rollout_hd_returns(env.params, B, N, K, C, float(gamma), env.px.data_ptr(), env.py.data_ptr(),
+                                        env.vx.data_ptr(), env.vy.data_ptr(), env.shape.data_ptr(), env.ivel.data_ptr(),
+                                        env.step_count.data_ptr(), act.data_ptr(), ret.data_ptr(), indiv.data_ptr(),
+                                        steps.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, "fg64_rollout_hd_returns returned %d" % rc
+    torch.cuda.synchronize()
+    return dict(ret=ret.cpu().numpy(), indiv=indiv.cpu().numpy(), steps=steps.cpu().numpy())

@@ -7,11 +7,13 @@ import os
 import re
 import types
 
+import numpy as np
 import pytest
 import torch
 
 from formation_gym import _native, load_scenario
 from formation_gym.environment import MultiAgentEnv
+from oracle import formation_oracle as O
 from tests import returns_testlib as rt
 from tests.actor_testlib import ROOT, params as _params
 
@@ -211,3 +213,120 @@ def test_the_phases_of_the_gpu_tests():
     ph = rt.phases(5, K, wl)
     assert rt.expected_steps(ph, K, wl).tolist() == [2, K, 1, K, K]
     assert rt.expected_steps(rt.phases(5, 1, wl), 1, wl).tolist() == [1] * 5
+
+
+# ---- the fp64 reference of the returns (rt.oracle_returns): held to the golden fixtures, then its teeth at the GPU tests' inputs ----
+ORACLE_FIXTURES = ["hd_n3", "hd_n3_done", "hd_n4", "hd_n9", "hd_n9_crowd", "hd_n16_crowd", "hd_n27_crowd"]
+
+
+@pytest.mark.parametrize("name", ORACLE_FIXTURES)
+def test_oracle_returns_sums_the_fixtures_recorded_rewards(golden, name):
+    """The fixture's own actions as the single candidate, gamma = 1: the plain sum of the reference's recorded shared and
+    individual rewards over the counted steps, to 1e-12 relative (the level at which tests/test_oracle_golden.py holds the oracle's
+    steps), and the counted steps are what the recorded done flags say - hd_n3_done's episode ends at step 100 of 102."""
+    g = golden(name)
+    T, B, N = g["acts"].shape[:3]
+    shared, indiv, steps, margin = rt.oracle_returns(rt.fixture_state(g), g["acts"][None], 1.0, rt.fixture_params(name, g))
+    want_steps, want_shared, want_indiv = rt.fixture_sums(g)
+    assert steps.dtype == np.int32 and steps.tolist() == want_steps.tolist()
+    if name == "hd_n3_done":
+        assert steps.tolist() == [100] and T == 102
+    else:
+        assert steps.tolist() == [T] * B
+    for got, want in ((shared[0], want_shared), (indiv[0], want_indiv)):
+        assert got.shape == (B, N)
+        assert (np.abs(got - want) <= 1e-12 * np.maximum(1.0, np.abs(want))).all(), np.abs(got - want).max()
+    assert margin.shape == (1, B) and (margin > 0).all()
+
+
+def _per_step(state, acts, P=None):
+    """(shared, indiv) [C,K,B,N] of every step of every candidate, by O.step_hd: what the mutants below accumulate wrongly"""
+    C, K, B, N = acts.shape[:4]
+    sh, ind = np.zeros((C, K, B, N)), np.zeros((C, K, B, N))
+    for c in range(C):
+        st = dict(state)
+        for k in range(K):
+            st, out = O.step_hd(st, acts[c, k], P)
+            sh[c, k], ind[c, k] = out["shared"][:, None], out["indiv"]
+    return sh, ind
+
+
+def _accumulate(r, steps, gamma, d0=1.0, on_sum=False):
+    """R [C,B,N] of the per-step rewards r [C,K,B,N]: R += d r, d *= gamma from d = d0 over the first steps[b] steps; on_sum:
+    R = gamma R + r instead."""
+    R = np.zeros(r[:, 0].shape)
+    d = d0
+    for k in range(r.shape[1]):
+        live = (k < steps)[None, :, None]
+        R = np.where(live, gamma * R + r[:, k] if on_sum else R + d * r[:, k], R)
+        d *= gamma
+    return R
+
+
+MUTANT_FACTOR = 100.0
+
+
+MUTANTS = ("discount starts at gamma", "done step not counted", "one step too many", "q decoded as c B + b",
+           "last action of an odd K repeated", "gamma on the sum")
+
+
+def mutant_factors(N, B, C, K):
+    """{mutant: (factor, values)} at the inputs of the fp64 GPU test of N agents.  A compared value is one shared or individual
+    return of a (candidate, env, agent) at one of the test's gammas (rt.F64_GAMMAS), wherever the mistake can show at all (the
+    gammas and envs are named per mutant below); it moves by |mutant - reference| / max(1, |reference|).  factor: what 90 % of
+    the values move by at least (their 10th percentile), in units of rt.F32_ORACLE_BOUND."""
+    state, acts = rt.oracle_state(B, N, K), rt.oracle_candidates(C, K, B, N)
+    sh, ind = _per_step(state, acts)
+    n = rt.oracle_returns(state, acts, 1.0)[2]
+    assert n.tolist() == [2, K, 1, K, K] and K % 2 == 1 and K > 1
+    ends = state["step"] + n >= O.HdParams.world_length                  # [B]: the episode's end is inside the counted steps
+    swapped = np.array(acts)
+    swapped[:, K - 1] = swapped[:, K - 2]
+    sh_sw, ind_sw = _per_step(state, swapped)
+    q = np.arange(B)[None, :] * C + np.arange(C)[:, None]                # [C,B]: the launch's pair index b C + c
+    cq, bq = q // B, q % B                                               # ... decoded the wrong way round
+    every = np.ones(B, dtype=bool)
+    moved = {name: [] for name in MUTANTS}
+    for gamma in rt.F64_GAMMAS:
+        ref = [rt.oracle_returns(state, acts, gamma)[i] for i in (0, 1)]
+        for r, want in zip((sh, ind), ref):
+            assert np.array_equal(_accumulate(r, n, gamma), want)       # the mutants below are mutants of the reference itself
+        mutants = {
+            # name: (its (shared, indiv), the envs [B] - or pairs [C,B] - in which it can show at this gamma)
+            MUTANTS[0]: ([_accumulate(r, n, gamma, d0=gamma) for r in (sh, ind)], every & (gamma < 1)),
+            MUTANTS[1]: ([_accumulate(r, n - ends, gamma) for r in (sh, ind)], ends & ((gamma > 0) | (n == 1))),
+            MUTANTS[2]: ([_accumulate(r, np.minimum(K, n + 1), gamma) for r in (sh, ind)], (n < K) & (gamma > 0)),
+            MUTANTS[3]: ([w[cq, bq] for w in ref], (cq != np.arange(C)[:, None]) | (bq != np.arange(B)[None, :])),
+            MUTANTS[4]: ([_accumulate(r, n, gamma) for r in (sh_sw, ind_sw)], (n == K) & (gamma > 0)),
+            MUTANTS[5]: ([_accumulate(r, n, gamma, on_sum=True) for r in (sh, ind)], (n > 1) & (gamma < 1)),
+        }
+        for name, (got, where) in mutants.items():
+            where = np.broadcast_to(where if where.ndim == 2 else where[None, :], (C, B))[None, :, :, None]
+            rel = np.stack([np.abs(g_ - w) / np.maximum(1.0, np.abs(w)) for g_, w in zip(got, ref)])
+            moved[name].append(rel[np.broadcast_to(where, rel.shape)])
+    out = {}
+    for name in MUTANTS:
+        values = np.concatenate(moved[name])
+        assert values.size >= 2 * C * N                                  # one env's values at least
+        out[name] = (float(np.percentile(values, 10, method="lower")) / rt.F32_ORACLE_BOUND, values.size)
+    return out
+
+
+@pytest.mark.parametrize("N,B,C,K", rt.F64_MAIN)
+def test_the_mutants_of_the_recurrence_move_the_reference(N, B, C, K):
+    """Six wrong returns kernels, each shown on the reference alone at the fp64 GPU test's inputs: at least 90 % of the compared
+    values move by 100 x the widest tolerance any GPU test of the returns uses (rt.F32_ORACLE_BOUND, relative to max(1, |R|); the
+    fp64 tests' 1e-9 is far inside it).  No tolerance of those tests can hide one of these.  (Measured: profiles/returns_parity.md)"""
+    for name, (factor, values) in mutant_factors(N, B, C, K).items():
+        print("N = %2d  %-34s 90 %% of %4d values move by >= %.3g x the bound" % (N, name, values, factor))
+        assert factor >= MUTANT_FACTOR, (N, name, factor)
+
+
+@pytest.mark.parametrize("N,B,C,K", rt.F64_MAIN + rt.F64_EDGES + [(N, 5, 7, 3) for N in rt.FUSED_N if N not in (3, 27)])
+def test_the_collision_counts_of_the_gpu_tests_are_off_their_thresholds(N, B, C, K):
+    """Every (candidate, env) pair of the fp64 GPU tests' inputs keeps its collision counts more than 1e-9 from flipping over the
+    counted steps - the fp64 check leaves nothing out - and at least 80 % keep 1e-4: what the fp32 check against the oracle
+    (tests/test_gpu_returns.py; K = 3 at every agent count) can compare."""
+    margin = rt.oracle_returns(rt.oracle_state(B, N, K), rt.oracle_candidates(C, K, B, N), 1.0)[3]
+    assert margin.shape == (C, B) and (margin > 1e-9).all(), margin.min()
+    assert (margin > 1e-4).mean() >= 0.8, (margin > 1e-4).mean()
