@@ -25,7 +25,8 @@
 // Source layout: fg_common.hpp (arguments, LDS layout, reductions, RNG, World options),
 // fg_pair_loops.hpp, fg_obs_writers.hpp, fg_step_kernel.hpp, fg_rollout_kernels.hpp,
 // fg_policy_kernels.hpp (the reference's demo controller), fg_aux_kernels.hpp (resets) with fg_scn_kernel.hpp (landmark
-// scenarios), fg_returns_kernel.hpp (returns of candidate action sequences from the current state); this file holds the host side: variant tables, dispatch and the extern "C" entry
+// scenarios), fg_returns_kernel.hpp (returns of candidate action sequences from the current state),
+// fg_planner_kernels.hpp (a sampling planner's candidates: drawn in that launch, as a tensor, MPPI's update); this file holds the host side: variant tables, dispatch and the extern "C" entry
 // points.  formation_hip_f64.hip builds the step, rollout and scenario kernels' source in double (tests only).
 
 #include <atomic>
@@ -46,6 +47,7 @@
 #include "fg_actor_rollout_kernel.hpp"
 #include "fg_scn_lane_actor_kernel.hpp"
 #include "fg_returns_kernel.hpp"
+#include "fg_planner_kernels.hpp"
 
 namespace fg {
 
@@ -1442,33 +1444,79 @@ static int scn_actor_dispatch(const ScnArgs& a, const FgActor& actor, float* act
 }
 
 // ---- discounted returns of C candidate action sequences from the current state (fg_returns_kernel.hpp) ----
-// the checks fg_rollout_hd_returns and its dry run share (no pointer, no device): FG_OK, or the status of the first that fails
-static int returns_check(const FgParams* params, int B, int N, int K, int C, float gamma) {
+// the checks fg_rollout_hd_returns (`who`; fg_rollout_hd_returns_sampled likewise) and its dry run share (no pointer, no
+// device): FG_OK, or the status of the first that fails
+static int returns_check(const FgParams* params, int B, int N, int K, int C, float gamma, const char* who = "fg_rollout_hd_returns") {
     const int rc = check_params(params);
     if (rc) return rc;
-    if (B < 0 || K < 1 || C < 1) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: B >= 0, K >= 1 and C >= 1 required%s");
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: gamma must be a finite number in [0, 1]%s");
+    if (B < 0 || K < 1 || C < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0, K >= 1 and C >= 1 required", who);
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(FG_ERR_BAD_ARG, "%s: gamma must be a finite number in [0, 1]", who);
     if (world_options_set(*params))
-        return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: World options, per-agent properties and communication are not supported%s");
-    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_returns: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");
-    if ((long long)B * C > 0x7fffffffLL) return fail(FG_ERR_BAD_ARG, "fg_rollout_hd_returns: B * C must be below 2^31%s");
+        return fail(FG_ERR_BAD_ARG, "%s: World options, per-agent properties and communication are not supported", who);
+    if (!actor_n_supported(N)) return fail(FG_ERR_UNSUPPORTED_N, "%s: N must be 3, 4, 8, 9, 16, 25, 27 or 32", who);
+    if ((long long)B * C > 0x7fffffffLL) return fail(FG_ERR_BAD_ARG, "%s: B * C must be below 2^31", who);
     return FG_OK;
 }
-// One geometry per agent count (fg_returns_kernel.hpp): the lane group of step_kernel and the rollout producers, 256 threads
-template <int NC, int G>
-static int launch_returns_v(const ReturnsArgs& a, hipStream_t st) {
+// ... and those on the buffers of the two entries, `src` being the one the actions come from (act / mean); fills `a`
+static int returns_args(const char* who, const char* aligned_fmt, ReturnsArgs* a, const FgParams* params, int B, int K, int C,
+                        float gamma, const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                        const float* ideal_shape, const float* ideal_vel, const int32_t* step, const float* src, float* ret,
+                        float* indiv_ret, int32_t* steps) {
+    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel || !step || !src || !ret) return null_pointer(who);
+    if ((((uintptr_t)src | (uintptr_t)ideal_shape | (uintptr_t)ideal_vel) & 7u) ||
+        (((uintptr_t)pos_x | (uintptr_t)pos_y | (uintptr_t)vel_x | (uintptr_t)vel_y | (uintptr_t)step | (uintptr_t)ret |
+          (uintptr_t)indiv_ret | (uintptr_t)steps) & 3u))
+        return fail(FG_ERR_ALIGNMENT, aligned_fmt, who);
+    memset(a, 0, sizeof(*a));
+    a->p = *params; a->B = B; a->K = K; a->C = C; a->gamma = gamma;
+    a->px = pos_x; a->py = pos_y; a->vx = vel_x; a->vy = vel_y; a->shape = ideal_shape; a->ivel = ideal_vel; a->step = step;
+    a->ret = ret; a->indiv_ret = indiv_ret; a->steps = steps;
+    return FG_OK;
+}
+// One geometry per agent count (fg_returns_kernel.hpp): the lane group of step_kernel and the rollout producers, 256 threads.
+// `A` is ReturnsArgs (returns_kernel: the actions read) or ReturnsSampledArgs (returns_sampled_kernel: the actions drawn,
+// fg_planner_kernels.hpp) - the same geometry for both.
+static const ReturnsArgs& returns_of(const ReturnsArgs& a) { return a; }
+static const ReturnsArgs& returns_of(const ReturnsSampledArgs& a) { return a.r; }
+template <int NC, int G, class A>
+static int launch_returns_v(const A& a, hipStream_t st) {
     constexpr int T = 256, PW = T / G;
     constexpr int lds = returns_lds_bytes<NC, G, T>();
-    const unsigned grid = (unsigned)(((long long)a.B * a.C + PW - 1) / PW);
-    if (describe("returns_kernel<%d,%d,%d> grid %u block %d lds %d; ", NC, G, T, grid, T, lds)) return FG_OK;
-    return launch<&returns_kernel<NC, G, T>>(grid, T, lds, st, "returns launch failed: %s", a);
+    constexpr bool sampled = std::is_same<A, ReturnsSampledArgs>::value;
+    const unsigned grid = (unsigned)(((long long)returns_of(a).B * returns_of(a).C + PW - 1) / PW);
+    if (describe("%s<%d,%d,%d> grid %u block %d lds %d; ", sampled ? "returns_sampled_kernel" : "returns_kernel", NC, G, T, grid, T, lds))
+        return FG_OK;
+    if constexpr (sampled) return launch<&returns_sampled_kernel<NC, G, T>>(grid, T, lds, st, "sampled returns launch failed: %s", a);
+    else return launch<&returns_kernel<NC, G, T>>(grid, T, lds, st, "returns launch failed: %s", a);
 }
-static int returns_dispatch(const ReturnsArgs& a, int N, hipStream_t st) {
+template <class A>
+static int returns_dispatch(const A& a, int N, hipStream_t st) {
 #define FG_RETURNS(NN, G) if (N == NN) return launch_returns_v<NN, G>(a, st);
     FG_RETURNS(3, 4) FG_RETURNS(4, 4) FG_RETURNS(8, 8) FG_RETURNS(9, 16) FG_RETURNS(16, 16)
     FG_RETURNS(25, 32) FG_RETURNS(27, 32) FG_RETURNS(32, 32)
 #undef FG_RETURNS
-    return fail(FG_ERR_UNSUPPORTED_N, "fg_rollout_hd_returns: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");   // (unreachable after returns_check)
+    return fail(FG_ERR_UNSUPPORTED_N, "returns launch: N must be 3, 4, 8, 9, 16, 25, 27 or 32%s");   // (unreachable after returns_check)
+}
+
+// ---- a sampling planner's candidates (fg_planner_kernels.hpp) ----
+// the scalars every planner entry shares, after its own check of params: FG_OK, or the status of the first that fails
+static int plan_check(const char* who, int B, int N, int K, int C, float sigma) {
+    if (B < 0 || K < 1 || C < 1) return fail(FG_ERR_BAD_ARG, "%s: B >= 0, K >= 1 and C >= 1 required", who);
+    if (N < 1 || N > FG_PLAN_MAX_N) return fail(FG_ERR_BAD_ARG, "%s: 1 <= N <= 2^12 required", who);
+    if (C > FG_PLAN_MAX_C) return fail(FG_ERR_BAD_ARG, "%s: C <= 2^17 required", who);
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return fail(FG_ERR_BAD_ARG, "%s: sigma must be a finite number >= 0", who);
+    return FG_OK;
+}
+static PlanDraw plan_draw_of(const FgParams* params, uint64_t noise_offset, float sigma, float clip) {
+    PlanDraw d;
+    d.seed = params->seed; d.noise_offset = noise_offset; d.env_index_base = (uint32_t)params->env_index_base;
+    d.sigma = sigma; d.clip = clip;
+    return d;
+}
+// one thread per element of an element-wise planner launch: the grid, or 0 when `count` threads are more than a launch holds
+static unsigned plan_grid(long long count) {
+    const long long grid = (count + 255) / 256;
+    return grid > 0x7fffffffLL ? 0u : (unsigned)grid;
 }
 
 extern "C" {
@@ -2528,18 +2576,13 @@ int fg_rollout_hd_returns(const FgParams* params, int B, int N, int K, int C, fl
     const int rc = returns_check(params, B, N, K, C, gamma);
     if (rc) return rc;
     if (B == 0) return FG_OK;                         // an empty batch: nothing to do
-    if (!pos_x || !pos_y || !vel_x || !vel_y || !ideal_shape || !ideal_vel || !step || !act || !ret)
-        return null_pointer("fg_rollout_hd_returns");
-    if ((((uintptr_t)act | (uintptr_t)ideal_shape | (uintptr_t)ideal_vel) & 7u) ||
-        (((uintptr_t)pos_x | (uintptr_t)pos_y | (uintptr_t)vel_x | (uintptr_t)vel_y | (uintptr_t)step | (uintptr_t)ret |
-          (uintptr_t)indiv_ret | (uintptr_t)steps) & 3u))
-        return fail(FG_ERR_ALIGNMENT, "fg_rollout_hd_returns: act/ideal_shape/ideal_vel must be 8-byte, the other buffers 4-byte aligned%s");
-    const DeviceGuard device_guard(stream, pos_x);
     ReturnsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.p = *params; a.B = B; a.K = K; a.C = C; a.gamma = gamma;
-    a.px = pos_x; a.py = pos_y; a.vx = vel_x; a.vy = vel_y; a.shape = ideal_shape; a.ivel = ideal_vel; a.step = step;
-    a.act = act; a.ret = ret; a.indiv_ret = indiv_ret; a.steps = steps;
+    if (const int rb = returns_args("fg_rollout_hd_returns", "%s: act/ideal_shape/ideal_vel must be 8-byte, the other buffers 4-byte aligned",
+                                    &a, params, B, K, C, gamma, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, act, ret,
+                                    indiv_ret, steps))
+        return rb;
+    a.act = act;
+    const DeviceGuard device_guard(stream, pos_x);
     return returns_dispatch(a, N, (hipStream_t)stream);
 }
 
@@ -2553,6 +2596,86 @@ int fg_describe_returns_launch(const FgParams* params, int B, int N, int K, int 
     a.p = *params; a.B = B; a.K = K; a.C = C; a.gamma = 1.0f;
     const DescribeScope describing(text, cap);
     return returns_dispatch(a, N, nullptr);
+}
+
+// ---- a sampling planner's candidates (fg_planner_kernels.hpp) ----
+int fg_rollout_hd_returns_sampled(const FgParams* params, int B, int N, int K, int C, float gamma, uint64_t noise_offset,
+                                  float sigma, float clip,
+                                  const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                                  const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                                  const float* mean, float* ret, float* indiv_ret, int32_t* steps, void* stream) {
+    const char* const who = "fg_rollout_hd_returns_sampled";
+    int rc = returns_check(params, B, N, K, C, gamma, who);
+    if (rc || (rc = plan_check(who, B, N, K, C, sigma))) return rc;
+    if (B == 0) return FG_OK;                         // an empty batch: nothing to do
+    ReturnsSampledArgs a;
+    if ((rc = returns_args(who, "%s: mean/ideal_shape/ideal_vel must be 8-byte, the other buffers 4-byte aligned", &a.r, params, B, K,
+                           C, gamma, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, mean, ret, indiv_ret, steps)))
+        return rc;
+    a.mean = mean;
+    a.d = plan_draw_of(params, noise_offset, sigma, clip);
+    const DeviceGuard device_guard(stream, pos_x);
+    return returns_dispatch(a, N, (hipStream_t)stream);
+}
+
+int fg_describe_returns_sampled_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap) {
+    if (!text || cap < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_returns_sampled_launch: out buffer required%s");
+    text[0] = 0;
+    int rc = returns_check(params, B, N, K, C, 1.0f, "fg_rollout_hd_returns_sampled");
+    if (rc || (rc = plan_check("fg_rollout_hd_returns_sampled", B, N, K, C, 0.0f)) || B == 0) return rc;
+    ReturnsSampledArgs a;
+    memset(&a, 0, sizeof(a));
+    a.r.p = *params; a.r.B = B; a.r.K = K; a.r.C = C; a.r.gamma = 1.0f;
+    const DescribeScope describing(text, cap);
+    return returns_dispatch(a, N, nullptr);
+}
+
+int fg_plan_candidates(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float sigma, float clip,
+                       const float* mean, float* act_out, void* stream) {
+    const char* const who = "fg_plan_candidates";
+    int rc = check_params(params);
+    if (rc || (rc = plan_check(who, B, N, K, C, sigma))) return rc;
+    if (B == 0) return FG_OK;
+    if (!act_out) return null_pointer(who);
+    if (((uintptr_t)mean | (uintptr_t)act_out) & 7u) return fail(FG_ERR_ALIGNMENT, "%s: mean and act_out must be 8-byte aligned", who);
+    const unsigned grid = plan_grid((long long)C * K * B * N);
+    if (!grid) return fail(FG_ERR_BAD_ARG, "%s: C * K * B * N must be below 2^39", who);
+    const DeviceGuard device_guard(stream, act_out);
+    return launch<&plan_candidates_kernel>(grid, 256, 0, (hipStream_t)stream, "plan candidates launch failed: %s",
+                                           plan_draw_of(params, noise_offset, sigma, clip), B, N, K, C,
+                                           reinterpret_cast<const float2*>(mean), reinterpret_cast<float2*>(act_out));
+}
+
+int fg_plan_mppi_update(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float sigma, float clip,
+                        float lambda, const float* ret, const float* mean_in, float* mean_out, float* act_out, int shift,
+                        void* stream) {
+    const char* const who = "fg_plan_mppi_update";
+    int rc = check_params(params);
+    if (rc || (rc = plan_check(who, B, N, K, C, sigma))) return rc;
+    if (!(lambda > 0.0f) || !std::isfinite(lambda)) return fail(FG_ERR_BAD_ARG, "%s: lambda must be a finite number > 0", who);
+    if (shift != 0 && shift != 1) return fail(FG_ERR_BAD_ARG, "%s: shift must be 0 or 1", who);
+    if (B == 0) return FG_OK;
+    if (!ret || !mean_in || !mean_out) return null_pointer(who);
+    if ((((uintptr_t)mean_in | (uintptr_t)mean_out | (uintptr_t)act_out) & 7u) || ((uintptr_t)ret & 3u))
+        return fail(FG_ERR_ALIGNMENT, "%s: mean_in, mean_out and act_out must be 8-byte, ret 4-byte aligned", who);
+    const unsigned grid = plan_grid((long long)K * B * N);
+    if (!grid) return fail(FG_ERR_BAD_ARG, "%s: K * B * N must be below 2^39", who);
+    // thread (k, b, i) writes row k - shift: another thread's input
+    const uintptr_t bytes = (uintptr_t)K * B * N * sizeof(float2), in = (uintptr_t)mean_in, out = (uintptr_t)mean_out;
+    if (in < out + bytes && out < in + bytes) return fail(FG_ERR_BAD_ARG, "%s: mean_out must not overlap mean_in", who);
+    // ... and the outputs are written while other threads still read `ret` and `mean_in`: each output apart from each input
+    // and from the other output
+    const uintptr_t ret_bytes = (uintptr_t)C * B * N * sizeof(float), rt = (uintptr_t)ret;
+    const uintptr_t act_bytes = (uintptr_t)B * N * sizeof(float2), ao = (uintptr_t)act_out;
+    const auto meet = [](uintptr_t x, uintptr_t nx, uintptr_t y, uintptr_t ny) { return x < y + ny && y < x + nx; };
+    if (meet(out, bytes, rt, ret_bytes) ||
+        (act_out && (meet(ao, act_bytes, in, bytes) || meet(ao, act_bytes, rt, ret_bytes) || meet(ao, act_bytes, out, bytes))))
+        return fail(FG_ERR_BAD_ARG, "%s: mean_out and act_out must not overlap ret, mean_in or each other", who);
+    const DeviceGuard device_guard(stream, mean_in);
+    return launch<&plan_mppi_update_kernel>(grid, 256, 0, (hipStream_t)stream, "plan update launch failed: %s",
+                                            plan_draw_of(params, noise_offset, sigma, clip), B, N, K, C, lambda, ret,
+                                            reinterpret_cast<const float2*>(mean_in), reinterpret_cast<float2*>(mean_out),
+                                            reinterpret_cast<float2*>(act_out), shift);
 }
 
 }  // extern "C"

@@ -20,9 +20,10 @@ from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
 from .actor_rollout import (CategoricalActor, GaussianActor, GumbelSoftmaxActor, InputBatchNorm, OUNoiseActor,  # noqa: F401
                             PerAgentActor, RecurrentActor)
+from .planner import MPPIPlanner  # noqa: F401
 
 __all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm",
-           "OUNoiseActor", "CategoricalActor", "GumbelSoftmaxActor"]
+           "OUNoiseActor", "CategoricalActor", "GumbelSoftmaxActor", "MPPIPlanner"]
 
 _counter = [0]
 

@@ -307,7 +307,14 @@ SIGNATURES = {
                                                ctypes.c_char_p, _I]),
     "fg_rollout_hd_returns": (_I, [_PP, _I, _I, _I, _I, ctypes.c_float] + [_P] * 12),
     "fg_describe_returns_launch": (_I, [_PP, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_rollout_hd_returns_sampled": (_I, [_PP, _I, _I, _I, _I, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, ctypes.c_float]
+                                      + [_P] * 12),
+    "fg_describe_returns_sampled_launch": (_I, [_PP, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_plan_candidates": (_I, [_PP, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
+    "fg_plan_mppi_update": (_I, [_PP, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 _P, _P, _P, _P, _I, _P]),
 }
+PLAN_MAX_N, PLAN_MAX_C = 1 << 12, 1 << 17         # a planner's agent and candidate counts (the stream code's fields)
 
 _lib = None
 

@@ -466,6 +466,28 @@ class Scenario(BaseScenario):
                 _native.current_stream(world.device))
         return _native.bind_launch(lib.fg_rollout_hd_returns, p, *args, keep=(act_seqs, out))
 
+    def bind_rollout_returns_sampled(self, world, mean, candidates, out, gamma=1.0):
+        """`bind_rollout_returns` with the candidates drawn inside the launch (`fg_rollout_hd_returns_sampled`): candidate c's
+        action at step k is clamp(mean[k] + sigma eps) with eps from the planner's counter stream, so no [C,K,B,N,2] tensor
+        exists.  mean [K,B,N,2] fp32 contiguous is read in place; `out` as for `bind_rollout_returns`.  Returns
+        `launch(noise_offset, sigma, clip)`: the planner's scalars as they are at the call.  The launch reads the world's state
+        and writes only `out`; the env's RNG offset is neither read nor moved."""
+        lib = _native.load()
+        p = self.params(world)
+        head = (world.num_envs, len(world.agents), int(mean.shape[0]), int(candidates), float(gamma))
+        tail = (world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(), world.step_count.data_ptr(), mean.data_ptr(),
+                out["ret"].data_ptr(), _native.ptr(out.get("indiv")), _native.ptr(out.get("steps")),
+                _native.current_stream(world.device))
+        keep = (mean, out)
+
+        def launch(noise_offset, sigma, clip):
+            rc = lib.fg_rollout_hd_returns_sampled(p, *head, int(noise_offset), float(sigma), float(clip), *tail)
+            if rc:
+                _native.check(rc)
+            return keep
+        return launch
+
     def upload_mt_streams(self, world):
         """Copy every env's legacy MT19937 state (RandomState(seed + 1000 b), at its CURRENT
         position) to the device; from here on `reset_mt` continues those streams on the GPU."""

@@ -938,6 +938,57 @@ int fg_rollout_hd_returns(const FgParams* params, int B, int N, int K, int C, fl
  * workgroup, W = ceil(B C / (T / G)) workgroups.  B == 0: FG_OK and an empty text.  Touches no device. */
 int fg_describe_returns_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap);
 
+/* ---- A sampling planner's candidates (MPPI, random shooting) without a candidate tensor ----
+ * Candidate c's action for agent i of env b at step k of a plan is
+ *     u = mean[k][b][i] + sigma * eps          (one rounded product, one rounded sum per component; never an fma)
+ *     u = min(max(u, -clip), clip)             where clip > 0; clip <= 0: no clamp
+ * with eps the unit normal pair of the planner's own counter stream: the Box-Muller (fp32, words 0 and 1, as the motor noise)
+ * of the Philox4x32-10 block with key params->seed and counter
+ *     {b + params->env_index_base, 0x40000000 | c << 12 | i, lo32(noise_offset + k), hi32(noise_offset + k)}.
+ * Stream code (counter word 1, top three bits): 010 - beside reset and landmarks 000, obstacles 001, Gumbel 011, motor noise
+ * 100, actor noise 101, communication 110, ideal velocity 111.  Limits: N <= 2^12 (i in bits 0-11), C <= 2^17 (c in bits
+ * 12-28); every planner entry returns FG_ERR_BAD_ARG beyond them.  noise_offset is the CALLER'S counter, passed by value
+ * (frozen when a launch is captured into a graph): params->rng_offset and rng_offset_dev are ignored, so planning never moves
+ * the env's RNG, and a caller that advances noise_offset by K per plan never draws a number twice.  The three entries below
+ * draw the same bits for the same (seed, env_index_base, noise_offset, c, k, b, i).
+ * Their common checks, after params: FG_ERR_BAD_ARG for B < 0, K < 1, C < 1, N outside 1 .. 2^12, C > 2^17 or a sigma that
+ * is not a finite number >= 0. */
+
+/* fg_rollout_hd_returns with the candidates drawn inside the launch (returns_sampled_kernel<N,G,T>: returns_kernel's
+ * geometry, step and recurrence - the results are, bit for bit, those of fg_rollout_hd_returns on the tensor
+ * fg_plan_candidates writes).  mean [K][B][N][2] (required, 8-byte aligned) is shared by an env's C candidates; every other
+ * buffer, check, status code and their order are fg_rollout_hd_returns' (under this entry's name), followed by the planner
+ * checks above, before the pointers. */
+int fg_rollout_hd_returns_sampled(const FgParams* params, int B, int N, int K, int C, float gamma, uint64_t noise_offset,
+                                  float sigma, float clip,
+                                  const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                                  const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                                  const float* mean, float* ret, float* indiv_ret, int32_t* steps, void* stream);
+/* Dry run of fg_rollout_hd_returns_sampled: fg_describe_returns_launch's checks and status codes, FG_ERR_BAD_ARG for
+ * C > 2^17, then "returns_sampled_kernel<N,G,T> grid W block T lds L; ".  Touches no device. */
+int fg_describe_returns_sampled_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap);
+
+/* The candidates as a tensor: act_out [C][K][B][N][2] (required, 8-byte aligned), one element-wise launch for any
+ * 1 <= N <= 2^12.  mean [K][B][N][2] or NULL = zeros; with mean NULL, sigma = 1 and clip = 0 act_out holds the unit draws
+ * themselves.  World options in params are not looked at.  B == 0 returns FG_OK without a launch. */
+int fg_plan_candidates(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float sigma, float clip,
+                       const float* mean, float* act_out, void* stream);
+
+/* MPPI's update without the candidate tensor.  For every (k, b, i), in fp32 and over c in ascending order:
+ *     m = max_c ret[c][b][i];   w_c = exp((ret[c][b][i] - m) / lambda);   new = (sum_c w_c u_c) / (sum_c w_c)
+ * with u_c the candidate action above, drawn again from mean_in [K][B][N][2].  new goes to mean_out[k - shift] for
+ * k >= shift; with shift = 1 step K - 1's value also goes to mean_out[K - 1] (the plan moves on one step, its last step
+ * repeated); step 0's value goes to act_out [B][N][2] (NULL: not written) - the action to take now.  ret [C][B][N] is what
+ * the returns entries write (4-byte aligned); mean_in, mean_out, act_out 8-byte aligned.
+ * After the common checks: FG_ERR_BAD_ARG for a lambda that is not a finite number > 0 and for a shift other than 0 or 1;
+ * B == 0 returns FG_OK; then FG_ERR_BAD_ARG for a NULL ret / mean_in / mean_out, FG_ERR_ALIGNMENT, and FG_ERR_BAD_ARG
+ * where the K B N float2 of mean_out overlap those of mean_in (a thread writes another thread's input row), and where
+ * mean_out or act_out overlaps ret, act_out overlaps mean_in, or the two outputs overlap each other (outputs are written
+ * while other threads still read the inputs). */
+int fg_plan_mppi_update(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float sigma, float clip,
+                        float lambda, const float* ret, const float* mean_in, float* mean_out, float* act_out, int shift,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
