@@ -1,7 +1,8 @@
-// fg_returns_body.inc - the body of returns_kernel and returns_sampled_kernel (fg_returns_kernel.hpp, fg_planner_kernels.hpp):
-// included inside each kernel, after `a` (const ReturnsArgs&) and the template parameters NC, G, T, with FG_RETURNS_SAMPLED
-// 0 (the actions are read from a.act) or 1 (they are drawn: `sa` is the kernel's ReturnsSampledArgs).  One `produce`, one
-// recurrence; the two kernels differ in where u comes from and in nothing else.  Included text and not a function: a
+// fg_returns_body.inc - the body of returns_kernel, returns_sampled_kernel and returns_sampled_std_kernel (fg_returns_kernel.hpp,
+// fg_planner_kernels.hpp): included inside each kernel, after `a` (const ReturnsArgs&) and the template parameters NC, G, T, with
+// FG_RETURNS_SAMPLED 0 (the actions are read from a.act), 1 (they are drawn: `sa` is the kernel's ReturnsSampledArgs) or 2 (drawn
+// with a sigma per element: `sa` is its ReturnsSampledStdArgs).  One `produce`, one recurrence; the kernels differ in where u
+// comes from and in nothing else.  Included text and not a function: a
 // call, even inlined, changes returns_kernel's instructions.
     static_assert(G <= 64 && T % 64 == 0 && 64 % G == 0 && G >= npad(NC), "a pair lives in one wave");
     constexpr int N = NC, NP = npad(NC), PW = T / G;
@@ -50,7 +51,14 @@
     // drawn from the plan's mean[k][b][i] - 8 N contiguous bytes per env and step, shared by the env's C candidates
     const size_t mean_stride = (size_t)a.B * N;                 // float2 units between consecutive steps
     const float2* mean_next = reinterpret_cast<const float2*>(sa.mean) + (size_t)(valid ? b : 0) * N + (valid ? i : 0);
+#if FG_RETURNS_SAMPLED == 2
+    // ... with the sigma of the same element, std[k][b][i], beside it
+    const float2* std_next = reinterpret_cast<const float2*>(sa.sd) + (size_t)(valid ? b : 0) * N + (valid ? i : 0);
+    if (valid) u_even = plan_draw_std(sa.d, *mean_next, *std_next, (uint32_t)b, (uint32_t)c, (uint32_t)i, 0u);
+    std_next += a.K > 1 ? mean_stride : 0;
+#else
     if (valid) u_even = plan_draw(sa.d, *mean_next, (uint32_t)b, (uint32_t)c, (uint32_t)i, 0u);
+#endif
     mean_next += a.K > 1 ? mean_stride : 0;
 #else
     // fetched from act[c][k][b][i]: a pair's step is 8 N contiguous bytes
@@ -75,7 +83,12 @@
             // one 8-byte load, ten Philox rounds, a log, a square root, a sine and a cosine: independent work beside the
             // pair loops below, where returns_kernel has its load in flight; nothing is drawn past the last step
             if (k + 1 < a.K) {
+#if FG_RETURNS_SAMPLED == 2
+                u_nxt = plan_draw_std(sa.d, *mean_next, *std_next, (uint32_t)b, (uint32_t)c, (uint32_t)i, (uint32_t)(k + 1));
+                std_next += mean_stride;
+#else
                 u_nxt = plan_draw(sa.d, *mean_next, (uint32_t)b, (uint32_t)c, (uint32_t)i, (uint32_t)(k + 1));
+#endif
                 mean_next += mean_stride;
             }
 #else

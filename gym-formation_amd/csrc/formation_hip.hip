@@ -1478,15 +1478,20 @@ static int returns_args(const char* who, const char* aligned_fmt, ReturnsArgs* a
 // fg_planner_kernels.hpp) - the same geometry for both.
 static const ReturnsArgs& returns_of(const ReturnsArgs& a) { return a; }
 static const ReturnsArgs& returns_of(const ReturnsSampledArgs& a) { return a.r; }
+static const ReturnsArgs& returns_of(const ReturnsSampledStdArgs& a) { return a.r; }
 template <int NC, int G, class A>
 static int launch_returns_v(const A& a, hipStream_t st) {
     constexpr int T = 256, PW = T / G;
     constexpr int lds = returns_lds_bytes<NC, G, T>();
     constexpr bool sampled = std::is_same<A, ReturnsSampledArgs>::value;
+    constexpr bool sampled_std = std::is_same<A, ReturnsSampledStdArgs>::value;     // (a sigma per element)
     const unsigned grid = (unsigned)(((long long)returns_of(a).B * returns_of(a).C + PW - 1) / PW);
-    if (describe("%s<%d,%d,%d> grid %u block %d lds %d; ", sampled ? "returns_sampled_kernel" : "returns_kernel", NC, G, T, grid, T, lds))
+    if (describe("%s<%d,%d,%d> grid %u block %d lds %d; ",
+                 sampled_std ? "returns_sampled_std_kernel" : sampled ? "returns_sampled_kernel" : "returns_kernel", NC, G, T, grid, T, lds))
         return FG_OK;
-    if constexpr (sampled) return launch<&returns_sampled_kernel<NC, G, T>>(grid, T, lds, st, "sampled returns launch failed: %s", a);
+    if constexpr (sampled_std)
+        return launch<&returns_sampled_std_kernel<NC, G, T>>(grid, T, lds, st, "sampled returns launch failed: %s", a);
+    else if constexpr (sampled) return launch<&returns_sampled_kernel<NC, G, T>>(grid, T, lds, st, "sampled returns launch failed: %s", a);
     else return launch<&returns_kernel<NC, G, T>>(grid, T, lds, st, "returns launch failed: %s", a);
 }
 template <class A>
@@ -1517,6 +1522,21 @@ static PlanDraw plan_draw_of(const FgParams* params, uint64_t noise_offset, floa
 static unsigned plan_grid(long long count) {
     const long long grid = (count + 255) / 256;
     return grid > 0x7fffffffLL ? 0u : (unsigned)grid;
+}
+// the dry run of a sampled scoring entry (`who`; `A` its kernel's arguments): that entry's checks before the buffers, then
+// its dispatch.  Touches no device.
+template <class A>
+static int describe_sampled(const char* name, const char* who, const FgParams* params, int B, int N, int K, int C, char* text,
+                            int cap) {
+    if (!text || cap < 2) return fail(FG_ERR_BAD_ARG, "%s: out buffer required", name);
+    text[0] = 0;
+    int rc = returns_check(params, B, N, K, C, 1.0f, who);
+    if (rc || (rc = plan_check(who, B, N, K, C, 0.0f)) || B == 0) return rc;
+    A a;
+    memset(&a, 0, sizeof(a));
+    a.r.p = *params; a.r.B = B; a.r.K = K; a.r.C = C; a.r.gamma = 1.0f;
+    const DescribeScope describing(text, cap);
+    return returns_dispatch(a, N, nullptr);
 }
 
 extern "C" {
@@ -2619,15 +2639,109 @@ int fg_rollout_hd_returns_sampled(const FgParams* params, int B, int N, int K, i
 }
 
 int fg_describe_returns_sampled_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap) {
-    if (!text || cap < 2) return fail(FG_ERR_BAD_ARG, "fg_describe_returns_sampled_launch: out buffer required%s");
-    text[0] = 0;
-    int rc = returns_check(params, B, N, K, C, 1.0f, "fg_rollout_hd_returns_sampled");
-    if (rc || (rc = plan_check("fg_rollout_hd_returns_sampled", B, N, K, C, 0.0f)) || B == 0) return rc;
-    ReturnsSampledArgs a;
-    memset(&a, 0, sizeof(a));
-    a.r.p = *params; a.r.B = B; a.r.K = K; a.r.C = C; a.r.gamma = 1.0f;
-    const DescribeScope describing(text, cap);
-    return returns_dispatch(a, N, nullptr);
+    return describe_sampled<ReturnsSampledArgs>("fg_describe_returns_sampled_launch", "fg_rollout_hd_returns_sampled", params, B, N, K,
+                                                C, text, cap);
+}
+
+// ---- ... with a sigma per step, env, agent and component: the cross-entropy method ----
+int fg_rollout_hd_returns_sampled_std(const FgParams* params, int B, int N, int K, int C, float gamma, uint64_t noise_offset,
+                                      float clip,
+                                      const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                                      const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                                      const float* mean, const float* sd, float* ret, float* indiv_ret, int32_t* steps,
+                                      void* stream) {
+    const char* const who = "fg_rollout_hd_returns_sampled_std";
+    const char* const aligned = "%s: mean/std/ideal_shape/ideal_vel must be 8-byte, the other buffers 4-byte aligned";
+    int rc = returns_check(params, B, N, K, C, gamma, who);
+    if (rc || (rc = plan_check(who, B, N, K, C, 0.0f))) return rc;
+    if (B == 0) return FG_OK;                         // an empty batch: nothing to do
+    ReturnsSampledStdArgs a;
+    if ((rc = returns_args(who, aligned, &a.r, params, B, K, C, gamma, pos_x, pos_y, vel_x, vel_y, ideal_shape, ideal_vel, step, mean,
+                           ret, indiv_ret, steps)))
+        return rc;
+    if (!sd) return null_pointer(who);
+    if ((uintptr_t)sd & 7u) return fail(FG_ERR_ALIGNMENT, aligned, who);
+    a.mean = mean;
+    a.sd = sd;
+    a.d = plan_draw_of(params, noise_offset, 0.0f, clip);
+    const DeviceGuard device_guard(stream, pos_x);
+    return returns_dispatch(a, N, (hipStream_t)stream);
+}
+
+int fg_describe_returns_sampled_std_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap) {
+    return describe_sampled<ReturnsSampledStdArgs>("fg_describe_returns_sampled_std_launch", "fg_rollout_hd_returns_sampled_std",
+                                                   params, B, N, K, C, text, cap);
+}
+
+int fg_plan_candidates_std(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float clip,
+                           const float* mean, const float* sd, float* act_out, void* stream) {
+    const char* const who = "fg_plan_candidates_std";
+    int rc = check_params(params);
+    if (rc || (rc = plan_check(who, B, N, K, C, 0.0f))) return rc;
+    if (B == 0) return FG_OK;
+    if (!sd || !act_out) return null_pointer(who);
+    if (((uintptr_t)mean | (uintptr_t)sd | (uintptr_t)act_out) & 7u)
+        return fail(FG_ERR_ALIGNMENT, "%s: mean, std and act_out must be 8-byte aligned", who);
+    const unsigned grid = plan_grid((long long)C * K * B * N);
+    if (!grid) return fail(FG_ERR_BAD_ARG, "%s: C * K * B * N must be below 2^39", who);
+    const DeviceGuard device_guard(stream, act_out);
+    return launch<&plan_candidates_std_kernel>(grid, 256, 0, (hipStream_t)stream, "plan candidates launch failed: %s",
+                                               plan_draw_of(params, noise_offset, 0.0f, clip), B, N, K, C,
+                                               reinterpret_cast<const float2*>(mean), reinterpret_cast<const float2*>(sd),
+                                               reinterpret_cast<float2*>(act_out));
+}
+
+int fg_plan_cem_update(const FgParams* params, int B, int N, int K, int C, int E, uint64_t noise_offset, float clip, float alpha,
+                       float sigma_min, const float* ret, const float* mean_in, const float* std_in, float* mean_out,
+                       float* std_out, float* act_out, int32_t* elite_idx, int shift, void* stream) {
+    const char* const who = "fg_plan_cem_update";
+    int rc = check_params(params);
+    if (rc || (rc = plan_check(who, B, N, K, C, 0.0f))) return rc;
+    if (E < 1 || E > C) return fail(FG_ERR_BAD_ARG, "%s: 1 <= E <= C required", who);
+    if (!(alpha > 0.0f && alpha <= 1.0f)) return fail(FG_ERR_BAD_ARG, "%s: alpha must be a finite number in (0, 1]", who);
+    if (!(sigma_min >= 0.0f) || !std::isfinite(sigma_min)) return fail(FG_ERR_BAD_ARG, "%s: sigma_min must be a finite number >= 0", who);
+    if (shift != 0 && shift != 1) return fail(FG_ERR_BAD_ARG, "%s: shift must be 0 or 1", who);
+    if (B == 0) return FG_OK;
+    if (!ret || !mean_in || !std_in || !mean_out || !std_out) return null_pointer(who);
+    if ((((uintptr_t)mean_in | (uintptr_t)std_in | (uintptr_t)mean_out | (uintptr_t)std_out | (uintptr_t)act_out) & 7u) ||
+        (((uintptr_t)ret | (uintptr_t)elite_idx) & 3u))
+        return fail(FG_ERR_ALIGNMENT, "%s: mean_in, std_in, mean_out, std_out and act_out must be 8-byte, ret and elite_idx 4-byte aligned", who);
+    const long long rows = (long long)B * N;
+    const long long grid = (rows + FG_CEM_ROWS - 1) / FG_CEM_ROWS;
+    if (grid > 0x7fffffffLL) return fail(FG_ERR_BAD_ARG, "%s: B * N must be below 2^33", who);
+    // a row's wave writes row k - shift of the outputs while other waves still read the inputs: every output apart from
+    // every input and from every other output (NULL: absent)
+    const uintptr_t plan_bytes = (uintptr_t)K * B * N * sizeof(float2);
+    struct Span { const void* p; uintptr_t n; };
+    const Span in[3] = {{ret, (uintptr_t)C * B * N * sizeof(float)}, {mean_in, plan_bytes}, {std_in, plan_bytes}};
+    const Span out[4] = {{mean_out, plan_bytes}, {std_out, plan_bytes}, {act_out, (uintptr_t)B * N * sizeof(float2)},
+                         {elite_idx, (uintptr_t)E * B * N * sizeof(int32_t)}};
+    const auto meet = [](const Span& x, const Span& y) {
+        return x.p && y.p && (uintptr_t)x.p < (uintptr_t)y.p + y.n && (uintptr_t)y.p < (uintptr_t)x.p + x.n;
+    };
+    for (int o = 0; o < 4; ++o) {
+        bool bad = false;
+        for (int j = 0; j < 3; ++j) bad = bad || meet(out[o], in[j]);
+        for (int j = 0; j < o; ++j) bad = bad || meet(out[o], out[j]);
+        if (bad)
+            return fail(FG_ERR_BAD_ARG, "%s: mean_out, std_out, act_out and elite_idx must not overlap ret, mean_in, std_in or each other", who);
+    }
+    CemArgs a;
+    a.d = plan_draw_of(params, noise_offset, 0.0f, clip);
+    a.B = B; a.N = N; a.K = K; a.C = C; a.E = E; a.shift = shift; a.alpha = alpha; a.sigma_min = sigma_min;
+    a.ret = ret;
+    a.mean_in = reinterpret_cast<const float2*>(mean_in); a.std_in = reinterpret_cast<const float2*>(std_in);
+    a.mean_out = reinterpret_cast<float2*>(mean_out); a.std_out = reinterpret_cast<float2*>(std_out);
+    a.act_out = reinterpret_cast<float2*>(act_out); a.elite_idx = elite_idx;
+    const DeviceGuard device_guard(stream, mean_in);
+    const hipStream_t st = (hipStream_t)stream;
+    const char* const failed = "plan cem update launch failed: %s";
+    constexpr int T = 64 * FG_CEM_ROWS;
+    // the keys of a row in 1, 8 or 64 registers per lane; beyond FG_CEM_REG_C candidates they are re-read
+    if (C <= 64) return launch<&plan_cem_update_kernel<1>>((unsigned)grid, T, 0, st, failed, a);
+    if (C <= 512) return launch<&plan_cem_update_kernel<8>>((unsigned)grid, T, 0, st, failed, a);
+    if (C <= FG_CEM_REG_C) return launch<&plan_cem_update_kernel<FG_CEM_REG_C / 64>>((unsigned)grid, T, 0, st, failed, a);
+    return launch<&plan_cem_update_kernel<0>>((unsigned)grid, T, 0, st, failed, a);
 }
 
 int fg_plan_candidates(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float sigma, float clip,

@@ -20,10 +20,10 @@ from .scenario import BaseScenario
 from .policy_bfs import ezpolicy, get_action_BFS  # noqa: F401
 from .actor_rollout import (CategoricalActor, GaussianActor, GumbelSoftmaxActor, InputBatchNorm, OUNoiseActor,  # noqa: F401
                             PerAgentActor, RecurrentActor)
-from .planner import MPPIPlanner  # noqa: F401
+from .planner import CEMPlanner, MPPIPlanner  # noqa: F401
 
 __all__ = ["make_env", "MultiAgentEnv", "ezpolicy", "get_action_BFS", "GaussianActor", "RecurrentActor", "InputBatchNorm",
-           "OUNoiseActor", "CategoricalActor", "GumbelSoftmaxActor", "MPPIPlanner"]
+           "OUNoiseActor", "CategoricalActor", "GumbelSoftmaxActor", "MPPIPlanner", "CEMPlanner"]
 
 _counter = [0]
 

@@ -313,8 +313,16 @@ SIGNATURES = {
     "fg_plan_candidates": (_I, [_PP, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
     "fg_plan_mppi_update": (_I, [_PP, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                  _P, _P, _P, _P, _I, _P]),
+    "fg_plan_candidates_std": (_I, [_PP, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, _P, _P, _P, _P]),
+    "fg_rollout_hd_returns_sampled_std": (_I, [_PP, _I, _I, _I, _I, ctypes.c_float, ctypes.c_uint64, ctypes.c_float] + [_P] * 13),
+    "fg_describe_returns_sampled_std_launch": (_I, [_PP, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "fg_plan_cem_update": (_I, [_PP, _I, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+                           + [_P] * 7 + [_I, _P]),
 }
 PLAN_MAX_N, PLAN_MAX_C = 1 << 12, 1 << 17         # a planner's agent and candidate counts (the stream code's fields)
+# fg_plan_cem_update's two thresholds (fg_planner_kernels.hpp: FG_CEM_REG_C, FG_CEM_ELITE_CAP): up to CEM_REG_C candidates a
+# row's keys stay in registers, up to CEM_ELITE_CAP elites a row's elite list is kept in LDS
+CEM_REG_C, CEM_ELITE_CAP = 4096, 1024
 
 _lib = None
 

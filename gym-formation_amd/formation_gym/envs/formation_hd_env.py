@@ -488,6 +488,25 @@ class Scenario(BaseScenario):
             return keep
         return launch
 
+    def bind_rollout_returns_sampled_std(self, world, mean, std, candidates, out):
+        """`bind_rollout_returns_sampled` with a sigma per element (`fg_rollout_hd_returns_sampled_std`): std [K,B,N,2] fp32
+        contiguous, finite and >= 0, read in place beside `mean`.  Returns `launch(noise_offset, gamma, clip)`."""
+        lib = _native.load()
+        p = self.params(world)
+        head = (world.num_envs, len(world.agents), int(mean.shape[0]), int(candidates))
+        tail = (world.pos_x.data_ptr(), world.pos_y.data_ptr(), world.vel_x.data_ptr(), world.vel_y.data_ptr(),
+                self.ideal_shape.data_ptr(), self.ideal_vel.data_ptr(), world.step_count.data_ptr(), mean.data_ptr(),
+                std.data_ptr(), out["ret"].data_ptr(), _native.ptr(out.get("indiv")), _native.ptr(out.get("steps")),
+                _native.current_stream(world.device))
+        keep = (mean, std, out)
+
+        def launch(noise_offset, gamma, clip):
+            rc = lib.fg_rollout_hd_returns_sampled_std(p, *head, float(gamma), int(noise_offset), float(clip), *tail)
+            if rc:
+                _native.check(rc)
+            return keep
+        return launch
+
     def upload_mt_streams(self, world):
         """Copy every env's legacy MT19937 state (RandomState(seed + 1000 b), at its CURRENT
         position) to the device; from here on `reset_mt` continues those streams on the GPU."""

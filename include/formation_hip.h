@@ -989,6 +989,52 @@ int fg_plan_mppi_update(const FgParams* params, int B, int N, int K, int C, uint
                         float lambda, const float* ret, const float* mean_in, float* mean_out, float* act_out, int shift,
                         void* stream);
 
+/* ---- ... with a sigma per step, env, agent and component: the cross-entropy method (CEM) ----
+ * The three entries below take std [K][B][N][2] (laid out like mean; required, 8-byte aligned) where the entries above take
+ * the scalar sigma:
+ *     u = mean[k][b][i] + std[k][b][i] * eps   per component (one rounded product, one rounded sum; never an fma), clamped
+ * with the same eps, stream code, noise_offset + k rule and limits.  A std filled with float32(sigma) gives the scalar
+ * entries' bits.  THE CALLER'S CONTRACT: every element of std is finite and >= 0 - the library cannot look into device
+ * memory.  Their common checks are those above without the one on sigma. */
+
+/* fg_plan_candidates with the sigma tensor.  mean NULL = zeros. */
+int fg_plan_candidates_std(const FgParams* params, int B, int N, int K, int C, uint64_t noise_offset, float clip,
+                           const float* mean, const float* std, float* act_out, void* stream);
+
+/* fg_rollout_hd_returns_sampled with the sigma tensor (returns_sampled_std_kernel<N,G,T>: the same geometry, step and
+ * recurrence, one more 8-byte load per drawn action): bit for bit fg_rollout_hd_returns on the tensor fg_plan_candidates_std
+ * writes.  Checks, status codes and their order: fg_rollout_hd_returns_sampled's, under this entry's name, then std. */
+int fg_rollout_hd_returns_sampled_std(const FgParams* params, int B, int N, int K, int C, float gamma, uint64_t noise_offset,
+                                      float clip,
+                                      const float* pos_x, const float* pos_y, const float* vel_x, const float* vel_y,
+                                      const float* ideal_shape, const float* ideal_vel, const int32_t* step,
+                                      const float* mean, const float* std, float* ret, float* indiv_ret, int32_t* steps,
+                                      void* stream);
+/* Dry run of fg_rollout_hd_returns_sampled_std: fg_describe_returns_sampled_launch's checks and status codes, then
+ * "returns_sampled_std_kernel<N,G,T> grid W block T lds L; ".  Touches no device. */
+int fg_describe_returns_sampled_std_launch(const FgParams* params, int B, int N, int K, int C, char* text, int cap);
+
+/* CEM's update without the candidate tensor (plan_cem_update_kernel: one 64-lane wave per (b, i) row).  For every row:
+ *   select  the E elites are the E largest of ret[c][b][i], c = 0 .. C-1, under the total order of
+ *               key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000)      (bits of the float, keys compared unsigned)
+ *           so -0 < +0, -inf below every finite value, and every bit pattern (NaN included) has a place; equal keys rank
+ *           the lower c first.  The selection is exact.
+ *   refit   for every step k and component, over the elites' actions u drawn again from (mean_in, std_in), in fp32:
+ *               m = mean of u;   v = sum (u - m)^2 / E  (two passes);
+ *               mean_new = (1 - alpha) mean_in + alpha m,   std_new = max(sigma_min, (1 - alpha) std_in + alpha sqrt(v))
+ *           (the mean is accumulated as mean_in + sum(u - mean_in) / E, so elites that all equal mean_in give it back
+ *           exactly).  Two launches on the same inputs give the same bits.
+ *   store   mean_new, std_new go to mean_out / std_out [k - shift] for k >= shift; with shift = 1 step K - 1's values also
+ *           go to row K - 1 (fg_plan_mppi_update's rule).  mean_new of step 0 goes to act_out [B][N][2] (NULL: not
+ *           written); the elites' candidate indices, ascending, to elite_idx [E][B][N] int32 (NULL: not written).
+ * After the common checks: FG_ERR_BAD_ARG unless 1 <= E <= C, for an alpha that is not a finite number in (0, 1], a sigma_min
+ * that is not a finite number >= 0 and a shift other than 0 or 1; B == 0 returns FG_OK; then FG_ERR_BAD_ARG for a NULL ret /
+ * mean_in / std_in / mean_out / std_out, FG_ERR_ALIGNMENT (ret and elite_idx 4-byte, the others 8-byte), and FG_ERR_BAD_ARG
+ * where any of mean_out, std_out, act_out, elite_idx overlaps ret, mean_in, std_in or another output. */
+int fg_plan_cem_update(const FgParams* params, int B, int N, int K, int C, int E, uint64_t noise_offset, float clip, float alpha,
+                       float sigma_min, const float* ret, const float* mean_in, const float* std_in, float* mean_out,
+                       float* std_out, float* act_out, int32_t* elite_idx, int shift, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
